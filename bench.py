@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """Throughput of the Ray3D lifting forward pass on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode windows|eval] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--mode windows|eval] [--batch B] [--full] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing else: set-up, warm-up (the clock settle below, then the W
+warm-up steps), the K timed steps, the outputs (--dump-outputs) and the JSON line.  --full adds every other measurement
+and check listed below (parity gate, roofline objects, the other workloads and precisions, the CPU baseline, the
+clip-sharded `eval_pass` under a process group); the --no-* options still leave single ones out of a --full run.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64; windows mode `poses`, eval mode `clip_rows`; `_rank<r>` appended under more than one rank), at most 64 MB in all
+(a larger output is written as a fixed, seeded sample of its rows).  The inputs are seeded: the same arguments give the
+same inputs on every run, so that two builds can be compared output for output.
 
 --mode windows (default; BASELINE.json configs[1]): synthetic 17-joint, 243-frame ray-encoded windows, batch 256 per
 GPU, forward only, pos + trj networks (C=256, latent 256, stage 3, camera embedding on), random-init (deterministic
@@ -24,7 +34,7 @@ the secondary objects `cfg4` and `cfg5`.
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks through
 torch.distributed.run (one process per GPU, RCCL) and fails loudly when fewer GPUs are visible.
 
-Prints ONE JSON line (rank 0).  Besides the driver's keys it carries
+Prints ONE JSON line (rank 0).  Under --full it carries, besides the driver's keys,
   roofline        the dominant kernel's rate against the gfx950 fp32-MFMA peak.  Per-launch HIP events on the launch
                   stream give every launch's duration; they are scaled so that their sum per step equals the step time
                   of the timed region (HIP events around it, same stream) - bracketing every launch slows the chip's
@@ -63,6 +73,30 @@ PARITY_ATOL = 1e-4              # north_star: fp32 3D joint positions within 1e-
 BATCH = 256
 ARCH = "3,3,3,3,3"
 EVAL_CLIPS = 240                # 2 subjects x 15 actions x 2 sub-actions x 4 cameras (cfg 3)
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all files of all ranks together, .npy headers included
+
+
+def dump_outputs(dirname, arrays, world=1, rank=0):
+    """--dump-outputs: {name: array} -> dirname/<name>.npy (float32 / float64 kept, anything else as float64), with
+    `_rank<r>` appended under more than one rank.  An array larger than its share of DUMP_LIMIT_BYTES is written as a
+    fixed sample of its rows (seed 0, sorted): the same rows on every run of the same shape."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (max(len(arrays), 1) * world) - 1024      # (1 KB per file for the .npy header)
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            rows = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(share // max(rows.shape[1] * a.itemsize, 1), 1)
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], min(keep, rows.shape[0]), replace=False))
+            a = a[idx]
+            if a.nbytes > share:                    # (one row alone is over the share: a flat sample)
+                flat = a.reshape(-1)
+                a = flat[np.sort(np.random.default_rng(0).choice(flat.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(dirname, (name if world == 1 else "%s_rank%d" % (name, rank)) + ".npy"), a)
 
 
 def build(device, arch=ARCH, bf16x3=False, **over):
@@ -404,11 +438,12 @@ def lanes_variant(lifter, dev, x, p, out_ref, steps, warmup, n):
                     "one weight image; throughput of back-to-back independent batches, not the headline's step" % (n, B, n)}
 
 
-def c1024_line(dev, steps, warmup, barrier, batches=(256,)):
+def c1024_line(dev, steps, warmup, barrier, batches=(256,), outs=None):
     """SURVEY 8 f4 / lib/model/rie.py:14: TemporalBlock's class default is channels = 1024 (no shipped cfg uses it: every cfg file
     sets 256).  Such models run the LEVEL-BY-LEVEL form - the single persistent launch holds tiles of at most 256 channels - so
     this object carries what that form costs: poses/s, the roofline of its dominant kernel (r3d_gemm_f32, twelve launches per
-    step), and the gaps between its launches (step time minus the sum of the kernels' own times)."""
+    step), and the gaps between its launches (step time minus the sum of the kernels' own times).  `outs`: a dict that receives
+    the last timed step's output of every batch size as `poses_b<B>` (--dump-outputs)."""
     import ray3d_amd
     from ray3d_amd import synth
     lifter, states = build(dev, CHANNELS=1024)
@@ -425,7 +460,9 @@ def c1024_line(dev, steps, warmup, barrier, batches=(256,)):
             run = lambda: lifter(x, p)
             assert torch.isfinite(run()).all()
             settle_clocks(run, dev, group=5, max_groups=20)
-            el, dev_s, _ = timed_steps(run, steps, warmup, barrier, dev)
+            el, dev_s, last = timed_steps(run, steps, warmup, barrier, dev)
+            if outs is not None:
+                outs["poses_b%d" % B] = last.cpu().numpy()
             rl = roofline(lifter, x, p, dev_s / steps * 1e3, batch=B, key="c1024_b%d" % B)
             kern = sum(rl["kernels_us_per_step"].values())
             res["b%d" % B] = {"value": round(B * steps / el, 1), "unit": "poses/s", "ms_per_step": round(el / steps * 1e3, 4), "steps": steps,
@@ -486,9 +523,10 @@ WORKLOADS = {
 }
 
 
-def uv_workload(name, dev, world, rank, steps, warmup, barrier, want_rays_delta=True):
+def uv_workload(name, dev, world, rank, steps, warmup, barrier, want_rays_delta=True, full=True, keep_out=False):
     """One of WORKLOADS on this rank: build the pair, synthesise pixel windows + per-window cameras, check against the
-    rays mode (bit-identical by construction: the same float64 encode), time UV mode and rays mode, roofline of UV mode."""
+    rays mode (bit-identical by construction: the same float64 encode), time UV mode and rays mode, roofline of UV mode.
+    `full` False: UV mode timed, nothing else.  `keep_out`: the last timed step's output under `_out` (--dump-outputs)."""
     from ray3d_amd import synth
     arch, J, total, camset, desc = WORKLOADS[name]
     B = max(total // world, 1)
@@ -508,16 +546,20 @@ def uv_workload(name, dev, world, rank, steps, warmup, barrier, want_rays_delta=
     uvd, rowsd, pard = torch.from_numpy(uv).to(dev), torch.from_numpy(rows).to(dev), torch.from_numpy(par).to(dev)
     run_uv = lambda: lifter.forward_uv(uvd, rowsd, pard)
     res = {"workload": desc, "batch_per_gpu": B, "receptive_field": rf, "joints": J, "cameras": len(cams),
-           "input": "uv (pixels) + per-window camera rows"}
+           "input": "uv (pixels) + per-window camera rows", "dtype": lifter.precision(dev)}
     with torch.no_grad():
         lifter.prepare([B], dev)
         out = run_uv()
         torch.cuda.synchronize()
         assert torch.isfinite(out).all()
         settle_clocks(run_uv, dev, group=10, max_groups=30)
-        el, dev_s, _ = timed_steps(run_uv, steps, warmup, barrier, dev)
+        el, dev_s, last = timed_steps(run_uv, steps, warmup, barrier, dev)
+        if keep_out:
+            res["_out"] = last.cpu().numpy()
         res.update({"value": round(world * B * steps / el, 1), "unit": "poses/s", "ms_per_step": round(el / steps * 1e3, 4),
                     "steps": steps})
+        if not full:
+            return res
         rl = roofline(lifter, uvd, pard, dev_s / steps * 1e3, fn=run_uv, batch=B, key=name)
         flops_step = rl["flops_per_launch"] * rl["launches_per_step"]
         # which roof binds: the GEMMs have M = B rows (MLPs are 95 % of the FLOPs at RF 9) - matrix-bound when the
@@ -584,7 +626,7 @@ def eval_summary(allrows):
 
 
 def eval_pass(lifter, dev, dist, world, rank, n_clips, steps, warmup, barrier, max_over_ranks, all_ranks, cross_check=True,
-              length_div=1, lift=None, lanes=0):
+              length_div=1, lift=None, lanes=0, keep_rows=False):
     """BASELINE configs[2] / north_star's multi-GPU split on this process group: the synthetic clip set sharded over the ranks as
     whole clips (longest first), every clip lifted with in-kernel sliding windows and reduced to one row on the device, ONE
     all_gather of the rows per pass (lib/train_val/trainer.py:399-403,473-477 reduce them per action).  Strong scaling: the
@@ -592,7 +634,8 @@ def eval_pass(lifter, dev, dist, world, rank, n_clips, steps, warmup, barrier, m
     `cross_check`: every rank also lifts the first clip of the NEXT rank's shard, and the row it computes must equal the
     gathered one bit for bit - what a clip's row is does not depend on which rank (or how many ranks) lifted it.
     `lift(clip, out_row)` replaces the HIP path (forward_clip + r3d_clip_metrics) and `length_div` shortens the clips: the CPU
-    test of this function's own sharding / rows / gather / cross-check / summary logic (tests/test_host.py, world size 8 over gloo)."""
+    test of this function's own sharding / rows / gather / cross-check / summary logic (tests/test_host.py, world size 8 over gloo).
+    `keep_rows`: the gathered rows of the last timed pass, copied, under `_rows` (--dump-outputs)."""
     from ray3d_amd import evaluate
     dev = torch.device(dev)
     on_gpu = dev.type == "cuda"
@@ -645,6 +688,7 @@ def eval_pass(lifter, dev, dist, world, rank, n_clips, steps, warmup, barrier, m
     with torch.no_grad():
         one_pass()                          # first touch: workspace allocation
         elapsed_own, dev_s, allrows = timed_steps(one_pass, steps, warmup, barrier, dev)
+        last_rows = allrows.clone() if keep_rows else None
         # this rank's own pass (its clips, no gather): what the shard costs without waiting for the others
         barrier()
         t1 = time.perf_counter()
@@ -703,6 +747,8 @@ def eval_pass(lifter, dev, dist, world, rank, n_clips, steps, warmup, barrier, m
         res["algorithmic_tflops"] = round(frames * steps / elapsed * 251.7e6 / 1e12, 2)
         res["frac_of_fp32_mfma_peak_all_gpus"] = round(res["algorithmic_tflops"] / (PEAK_FP32_MFMA_TFLOPS * world), 4)
     res["_mine"] = mine
+    if keep_rows:
+        res["_rows"] = last_rows
     return res
 
 
@@ -745,6 +791,12 @@ def main():
     ap.add_argument("--two-stream", action="store_true", help="also time Ray3DLifter.forward_overlapped (two half batches on two streams)")
     ap.add_argument("--half-chip-streams", action="store_true",
                     help="also time two independent forwards side by side on two CU-masked streams of 128 CUs (secondary object `half_chip_streams_variant`; `two_stream_variant` keeps its round-4 meaning: --two-stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate, the roofline objects, the shipped configurations, the 1024-channel model, "
+                         "bf16x3, the CPU baseline, the clock-ramp figure and (under a process group) `eval_pass`; off: set-up, warm-up, "
+                         "the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 50 if args.mode == "windows" else 3
@@ -805,7 +857,10 @@ def main():
     if args.mode == "windows" and args.workload != "cfg2":
         # ---- one of the shipped configurations as the run's workload (rocprofv3 recipes use this form)
         arch, J, total, camset, desc = WORKLOADS[args.workload]
-        res = uv_workload(args.workload, dev, world, rank, args.steps, args.warmup, barrier)
+        res = uv_workload(args.workload, dev, world, rank, args.steps, args.warmup, barrier, full=args.full,
+                          keep_out=args.dump_outputs is not None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"poses": res.pop("_out")}, world, rank)
         el = max_over_ranks(res["ms_per_step"])
         per_rank = all_ranks(res["ms_per_step"])
         if rank == 0:
@@ -813,20 +868,23 @@ def main():
             print(json.dumps({
                 "metric": "lifted poses/sec (%d-joint, %d-frame window)" % (J, res["receptive_field"]), "unit": "poses/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "vs_baseline": None,
-                "dtype": "f32" if "fp32" in res["roofline"]["peak_of"] else "bf16x3",
+                "dtype": res["dtype"],
                 "data": "synthetic", "value": round(world * B / (el * 1e-3), 1), "ms_per_step": el, "scaling": "weak",
                 "config": {"workload": desc, "batch_per_gpu": B, "receptive_field": res["receptive_field"], "joints": J,
                            "parallelism": "dp%d (independent window batches, no data-path collective)" % world,
                            "world_size_observed": world if dist is None else dist.get_world_size(),
                            "ms_per_step_per_rank": per_rank},
-                "roofline": res["roofline"], "rays_mode": res.get("rays_mode"), "uv_vs_rays_ms_delta": res.get("uv_vs_rays_ms_delta"),
+                "roofline": res.get("roofline"), "rays_mode": res.get("rays_mode"), "uv_vs_rays_ms_delta": res.get("uv_vs_rays_ms_delta"),
                 "uv_equals_rays_mode": res.get("uv_equals_rays_mode")}))
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
         return
     if args.mode == "windows" and args.c1024:
-        res = c1024_line(dev, args.steps, args.warmup, barrier, batches=(64, 256))
+        outs = {} if args.dump_outputs else None
+        res = c1024_line(dev, args.steps, args.warmup, barrier, batches=(64, 256), outs=outs)
+        if outs:
+            dump_outputs(args.dump_outputs, outs, world, rank)
         if rank == 0:
             print(json.dumps({"metric": "lifted poses/sec (17-joint, 243-frame window, CHANNELS 1024)", "unit": "poses/s", "n_gpus": world,
                               "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "vs_baseline": None, "dtype": "f32",
@@ -857,25 +915,29 @@ def main():
             prepare_ms = (time.perf_counter() - t0) * 1e3
             lifter(x, p)
             torch.cuda.synchronize()
-            # parity gate BEFORE the timed region (every rank: its own device runs its own copy of the weights)
-            parity_err, parity_ref = parity_gate(lifter, dev, args.batch)
-            # the literal command first - W warm-up steps, K timed steps, the GPU's clocks still ramping (a process starts in a
-            # low power state) - reported beside the sustained number, never instead of it
-            torch.cuda.synchronize()
-            time.sleep(0.2)
-            el_cold, _, _ = timed_steps(lambda: lifter(x, p), args.steps, args.warmup, barrier, dev)
+            if args.full:
+                # parity gate BEFORE the timed region (every rank: its own device runs its own copy of the weights)
+                parity_err, parity_ref = parity_gate(lifter, dev, args.batch)
+                # the literal command first - W warm-up steps, K timed steps, the GPU's clocks still ramping (a process starts in a
+                # low power state) - reported beside the sustained number, never instead of it
+                torch.cuda.synchronize()
+                time.sleep(0.2)
+                el_cold, _, _ = timed_steps(lambda: lifter(x, p), args.steps, args.warmup, barrier, dev)
             settle_steps = settle_clocks(lambda: lifter(x, p), dev)
             elapsed_own, dev_s, out = timed_steps(lambda: lifter(x, p), args.steps, args.warmup, barrier, dev)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"poses": out}, world, rank)
         elapsed = max_over_ranks(elapsed_own)
         per_rank_ms = all_ranks(elapsed_own / args.steps * 1e3)
-        parity_err = max_over_ranks(parity_err)
+        if args.full:
+            parity_err = max_over_ranks(parity_err)
         assert torch.isfinite(out).all()
         # With a process group (the driver's N > 1 command; any run under a launcher): north_star's multi-GPU split as a
         # SECONDARY object of the same line - one strong-scaling pass set over the 240-clip evaluation shape, clips sharded
         # over the ranks, ONE all_gather of the per-clip rows per pass.  The windows-mode `value` above has no collective on
         # its data path; without this object an N-GPU run of this command would say nothing about clip sharding.
         ev = None
-        if dist is not None and args.batch == BATCH and not args.no_eval_pass and lifter.precision(dev) == "f32":
+        if dist is not None and args.full and args.batch == BATCH and not args.no_eval_pass and lifter.precision(dev) == "f32":
             try:
                 ev = eval_pass(lifter, dev, dist, world, rank, args.clips, 2, 1, barrier, max_over_ranks, all_ranks)
                 ev.pop("_mine")
@@ -892,13 +954,16 @@ def main():
                            "parallelism": "dp%d (independent window batches, no data-path collective)" % world,
                            "schedule_build_ms": round(prepare_ms, 1),
                            "clock_settle_steps": settle_steps,
-                           "ms_per_step_before_clock_settle": round(el_cold / args.steps * 1e3, 4),   # the same K steps right after W warm-up steps from idle clocks
                            "world_size_observed": world if dist is None else dist.get_world_size(),
-                           "ms_per_step_per_rank": [round(v, 4) for v in per_rank_ms]},
-                "parity_max_abs_err": parity_err,
-                "parity": {"max_abs_err_m": parity_err, "bound_m": PARITY_ATOL, "ref_max_abs_m": round(parity_ref, 3),
-                           "against": "tests/golden/model_j17_rf243_s3.npz (reference PyTorch-CPU outputs for these weights), "
-                                      "tiled to the timed batch size; checked before the timed region, on every rank (max)"}})
+                           "ms_per_step_per_rank": [round(v, 4) for v in per_rank_ms]}})
+            if args.full:
+                # the same K steps right after W warm-up steps from idle clocks
+                line["config"]["ms_per_step_before_clock_settle"] = round(el_cold / args.steps * 1e3, 4)
+                line.update({
+                    "parity_max_abs_err": parity_err,
+                    "parity": {"max_abs_err_m": parity_err, "bound_m": PARITY_ATOL, "ref_max_abs_m": round(parity_ref, 3),
+                               "against": "tests/golden/model_j17_rf243_s3.npz (reference PyTorch-CPU outputs for these weights), "
+                                          "tiled to the timed batch size; checked before the timed region, on every rank (max)"}})
             # (the extras below must never cost the run its line: a failure in one of them is reported in its place)
             def guarded(key, fn):
                 try:
@@ -910,8 +975,9 @@ def main():
             def _roofline():
                 with torch.no_grad():
                     return roofline(lifter, x, p, dev_s / args.steps * 1e3)
-            guarded("roofline", _roofline)
-            if world == 1 and args.batch == BATCH and not args.no_b1024:
+            if args.full:
+                guarded("roofline", _roofline)
+            if args.full and world == 1 and args.batch == BATCH and not args.no_b1024:
                 # north_star quotes its roofline target at 1024 x 243 x 17: the same measurement at that batch
                 def _b1024():
                     xb = torch.from_numpy(synth.synth_rays(1024, cfg, seed=100)).to(dev)
@@ -926,16 +992,16 @@ def main():
                     rb.update({"batch": 1024, "value": round(1024 * nb / el_b, 1), "ms_per_step": round(el_b / nb * 1e3, 4), "steps": nb})
                     return rb
                 guarded("roofline_b1024", _b1024)
-            if world == 1 and args.batch == BATCH and not args.no_shipped_cfgs:
+            if args.full and world == 1 and args.batch == BATCH and not args.no_shipped_cfgs:
                 # the configurations the reference ships (every cfg file is RF 9): BASELINE configs[3] and configs[4]
                 nsh = max(args.steps // 2, 10)
                 guarded("cfg4", lambda: {"rf9": uv_workload("cfg4_rf9", dev, 1, 0, nsh, 3, barrier),
                                          "rf243": uv_workload("cfg4_rf243", dev, 1, 0, max(nsh // 2, 5), 2, barrier)})
                 guarded("cfg5", lambda: uv_workload("cfg5", dev, 1, 0, nsh, 3, barrier))
-            if world == 1 and args.batch == BATCH and not args.no_c1024:
+            if args.full and world == 1 and args.batch == BATCH and not args.no_c1024:
                 # the reference's class-default width (1024 channels): the level-by-level form's cost, with its roofline
                 guarded("c1024", lambda: c1024_line(dev, max(args.steps // 4, 5), 2, barrier))
-            if world == 1 and not args.no_bf16x3 and lifter.precision(dev) == "f32":
+            if args.full and world == 1 and not args.no_bf16x3 and lifter.precision(dev) == "f32":
                 # secondary line: the same workload with r3d_config.bf16x3 = 1 - every big GEMM on the bf16 matrix cores with exact
                 # three-term splits of both operands (fp32-equivalent results: tests/test_gpu_parity.py holds it to the
                 # fp32 path's own error against a float64 reference).  Not the headline: `dtype` above stays f32.
@@ -956,14 +1022,17 @@ def main():
                               "pass; strong scaling (the set is fixed): compare `value` / `ms_per_pass` across N, `mpjpe_mm` must not change"
                               % (ev.get("clips", 0), ev.get("frames", 0), world)) if "error" not in ev else ev.get("error")
                 line["eval_pass"] = ev
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 # (rank 0 only, at every N: the reference's CPU path timed on this host beside the GPU numbers)
                 guarded("cpu_baseline", lambda: cpu_baseline(states, x_np, p_np))
             print(json.dumps(line))
     else:
         # ---- clip-sharded evaluation (configs[2]): whole clips per rank, resident in HBM, one all_gather per pass
-        ev = eval_pass(lifter, dev, dist, world, rank, args.clips, args.steps, args.warmup, barrier, max_over_ranks, all_ranks)
+        ev = eval_pass(lifter, dev, dist, world, rank, args.clips, args.steps, args.warmup, barrier, max_over_ranks, all_ranks,
+                       keep_rows=args.dump_outputs is not None)
         mine = ev.pop("_mine")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"clip_rows": ev.pop("_rows")})     # (the gathered rows: the same on every rank)
         if rank == 0:
             frames = ev["frames"]
             line.update({
@@ -982,7 +1051,7 @@ def main():
             # the whole pass as a rate - and the roofline of its dominant kernel on ONE full chunk of the first clip
             line["algorithmic_tflops"] = ev["algorithmic_tflops"]
             line["frac_of_fp32_mfma_peak"] = round(ev["algorithmic_tflops"] / PEAK_FP32_MFMA_TFLOPS, 4)
-            if world == 1 and mine and lifter.precision(dev) == "f32":
+            if args.full and world == 1 and mine and lifter.precision(dev) == "f32":
                 def _clip_roofline():
                     nb = lifter.CLIP_CHUNK
                     c, padded, prow, _ = max(mine, key=lambda t: t[1].shape[0])

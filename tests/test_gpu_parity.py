@@ -1642,7 +1642,7 @@ def test_bench_under_the_drivers_launcher_with_one_rank(mode):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    extra = ["--no-cpu-baseline", "--no-bf16x3", "--no-shipped-cfgs", "--no-b1024", "--no-c1024"] if mode == "windows" else ["--mode", "eval", "--clips", "6"]
+    extra = ["--full", "--no-cpu-baseline", "--no-bf16x3", "--no-shipped-cfgs", "--no-b1024", "--no-c1024"] if mode == "windows" else ["--mode", "eval", "--clips", "6"]
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"] + extra,
                          env=env, capture_output=True, text=True, timeout=900)
@@ -1658,6 +1658,35 @@ def test_bench_under_the_drivers_launcher_with_one_rank(mode):
         assert ep["all_gather_ms"] >= 0 and ep["mpjpe_mm"]["checksum"] > 0 and ep["scaling"] == "strong"
     else:
         assert line["config"]["shard_imbalance"] == 1.0 and len(line["config"]["pass_ms_per_rank"]) == 1
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_output(tmp_path):
+    """bench.py --gpus 1 --steps K --warmup W (no --full): the headline line only - none of the --full objects - and
+    --dump-outputs writes the last timed step's poses, which equal those of a second run with the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    poses = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert line["higher_is_better"] is True and line["unit"] == "poses/s"
+        assert abs(line["value"] - 256 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+        for key in ("roofline", "roofline_b1024", "cfg4", "cfg5", "c1024", "bf16x3", "cpu_baseline", "parity", "eval_pass"):
+            assert key not in line, key
+        assert sorted(os.listdir(d)) == ["poses.npy"]
+        poses.append(np.load(d / "poses.npy"))
+    assert poses[0].shape == (256, 1, 17, 3) and poses[0].dtype == np.float32 and np.isfinite(poses[0]).all()
+    assert np.array_equal(poses[0], poses[1])
 
 
 def test_clip_sharded_eval_over_rccl_two_gpus():

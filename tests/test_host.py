@@ -122,10 +122,11 @@ def test_module_state_dict_contract():
     pos, trj = fac.get_pos_model(), fac.get_trj_model()
     assert pos.receptive_field() == 27 and trj.receptive_field() == 27
     (cp, sp), (ct, st) = synth_states(mc)
-    assert set(pos.state_dict().keys()) == set(sp.keys())
-    assert set(trj.state_dict().keys()) == set(st.keys())
+    pre = "module." if torch.cuda.is_available() else ""     # with a GPU the factory returns the reference's DataParallel face
+    assert set(pos.state_dict().keys()) == {pre + k for k in sp}
+    assert set(trj.state_dict().keys()) == {pre + k for k in st}
     for k, v in pos.state_dict().items():
-        assert tuple(v.shape) == tuple(np.asarray(sp[k]).shape), k
+        assert tuple(v.shape) == tuple(np.asarray(sp[k[len(pre):]]).shape), k
     sd = {k: torch.from_numpy(np.asarray(v)) for k, v in sp.items()}
     pos.load_state_dict(sd, strict=True)
     pos.load_state_dict({"module." + k: v for k, v in sd.items()}, strict=True)   # DataParallel checkpoint
@@ -500,6 +501,26 @@ def _gloo_eval_pass_worker(rank, world, port, q, n_clips, length_div):
         dist.destroy_process_group()
 
 
+def test_bench_dump_outputs_keeps_small_arrays_and_samples_large_ones_under_the_cap(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 kept as they are, other types as float64; an output beyond its share of the
+    64 MB budget becomes a fixed sample of its rows - the same rows on every run - and all files together stay within it."""
+    import bench
+    small = np.random.default_rng(1).random((256, 1, 17, 3)).astype(np.float32)
+    big = np.random.default_rng(2).random((600000, 1, 17, 3)).astype(np.float32)       # 122 MB
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"poses": small, "big": big, "ids": np.arange(10)})
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("poses", "big", "ids")}
+    assert np.array_equal(a["poses"], small) and a["ids"].dtype == np.float64 and np.array_equal(a["ids"], np.arange(10))
+    assert a["big"].dtype == np.float32 and a["big"].shape[1:] == big.shape[1:] and 0 < a["big"].shape[0] < big.shape[0]
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    idx = [int(np.flatnonzero(big[:, 0, 0, 0] == r[0, 0, 0])[0]) for r in a["big"][:100]]       # (the sample is rows of the output, in order)
+    assert idx == sorted(idx) and all(np.array_equal(big[i], r) for i, r in zip(idx, a["big"]))
+    bench.dump_outputs(str(tmp_path / "r"), {"poses": big}, world=2, rank=1)
+    assert [f.name for f in (tmp_path / "r").iterdir()] == ["poses_rank1.npy"]
+    assert (tmp_path / "r" / "poses_rank1.npy").stat().st_size <= bench.DUMP_LIMIT_BYTES // 2
+
+
 def test_bench_eval_pass_object_at_world_size_8_over_gloo():
     """bench.eval_pass - the object the driver's `bench.py --gpus N` line carries under a process group (north_star's split:
     whole clips sharded over the ranks, ONE all_gather of the per-clip rows) - run as the bench runs it, on eight CPU ranks
@@ -689,9 +710,10 @@ def test_checkpoint_file_in_the_trainers_format(tmp_path):
     rest = ray3d_amd.load_checkpoint(path, pos, trj)
     assert rest["epoch"] == 10 and "optimizer" not in rest and "model_pos" not in rest
     k = "GlobalInfo.fc_1.weight"
-    assert np.array_equal(pos.state_dict()[k].numpy(), np.asarray(sp[k]))
-    assert np.array_equal(trj.state_dict()["shrink.weight" if "shrink.weight" in st else next(iter(st))].numpy(),
-                          np.asarray(st["shrink.weight" if "shrink.weight" in st else next(iter(st))]))
+    pre = "module." if torch.cuda.is_available() else ""     # with a GPU the factory returns the reference's DataParallel face
+    assert np.array_equal(pos.state_dict()[pre + k].cpu().numpy(), np.asarray(sp[k]))
+    kt = "shrink.weight" if "shrink.weight" in st else next(iter(st))
+    assert np.array_equal(trj.state_dict()[pre + kt].cpu().numpy(), np.asarray(st[kt]))
     torch.save({"epoch": 1, "model_pos": as_dp(sp)}, path)
     with pytest.raises(KeyError, match="model_trj"):
         ray3d_amd.load_checkpoint(path, pos, trj)
@@ -1024,7 +1046,10 @@ def test_host_schedule_plan_and_model_code_under_asan_and_ubsan():
     r = subprocess.run(["make", "-C", csrc, "san", "ARCH=gfx950"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     san = os.path.join(ROOT, "ray3d_amd", "libray3d_hip_san.so")
-    env = dict(os.environ, R3D_HOOKS_LIB=san, LD_PRELOAD=rts[-1],
+    # the ASan runtime first; a preload the environment already has stays in the list behind it.  Host code only: the child
+    # sees no GPU (HIP_VISIBLE_DEVICES=-1), as on a machine without one - the HIP runtime is never started under the sanitizers
+    env = dict(os.environ, R3D_HOOKS_LIB=san, LD_PRELOAD=":".join([rts[-1]] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else [])),
+               HIP_VISIBLE_DEVICES="-1",
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0:exitcode=66",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=67")
     sel = ("schedule or plan or forward_check or dependency or single_launch or narrow or tiles or workspace or pairs or grammar or "

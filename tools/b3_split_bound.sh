@@ -22,7 +22,7 @@ from ray3d_amd import _capi
 _capi.LIB_PATH=os.path.abspath(os.environ["R3D_LIB"])
 import bench
 bench.parity_gate=lambda *a, **k: (0.0, 1.0)      # (the experiment builds compute wrong values on purpose)
-sys.argv=["bench.py","--batch","$B","--no-cpu-baseline","--no-b1024","--no-bf16x3","--no-shipped-cfgs","--steps","200","--warmup","20"]
+sys.argv=["bench.py","--full","--batch","$B","--no-cpu-baseline","--no-b1024","--no-bf16x3","--no-shipped-cfgs","--steps","200","--warmup","20"]
 buf=io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()

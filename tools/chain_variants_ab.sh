@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 run() {   # name, env...
   local name=$1; shift
   for B in 256 1024; do
-    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --batch $B --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 --steps 200 --warmup 10 2>/dev/null | python -c "
+    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --full --batch $B --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys,json
 t=sys.stdin.read().strip().splitlines()
 try:

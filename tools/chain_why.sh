@@ -17,7 +17,7 @@ cat $O/icache_counters.txt
 for ctr in $(cat $O/icache_counters.txt | head -12) SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INST_CYCLES_VMEM TCC_HIT_sum TCC_MISS_sum FETCH_SIZE TCP_TCC_READ_REQ_sum SQ_INSTS_SALU SQ_WAIT_INST_LDS; do
   for c in 1 0; do
     d=$O/pmc_${ctr}_c$c
-    R3D_USE_HOOKS_LIB=1 R3D_CHAIN=$c timeout 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $d -- python $R/bench.py --batch 256 --steps 3 --warmup 1 --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 > $d.log 2>&1
+    R3D_USE_HOOKS_LIB=1 R3D_CHAIN=$c timeout 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $d -- python $R/bench.py --full --batch 256 --steps 3 --warmup 1 --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 > $d.log 2>&1
     f=$(find $d -name "*counter_collection.csv" | head -1)
     if [ -n "$f" ]; then
       python - "$f" $ctr $c <<'PY'

@@ -8,7 +8,7 @@ for cfg in "$@"; do
   tag=$(echo "$cfg" | tr ' =' '__')
   O=$R/gpurun_out/traffic_$tag
   rm -rf $O; mkdir -p $O
-  ARGS="--batch $B --steps 3 --warmup 1 --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024"
+  ARGS="--full --batch $B --steps 3 --warmup 1 --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024"
   env R3D_USE_HOOKS_LIB=1 $cfg rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/p3 -- python $R/bench.py $ARGS > $O/p3.log 2>&1
   env R3D_USE_HOOKS_LIB=1 $cfg rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/p4 -- python $R/bench.py $ARGS > $O/p4.log 2>&1
   python - "$O" "$cfg" <<'PY'

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 one() {
   local name=$1; shift
   for B in 256 1024; do
-    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --batch $B --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 --steps 200 --warmup 10 2>/dev/null | python -c "
+    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --full --batch $B --no-cpu-baseline --no-bf16x3 --no-shipped-cfgs --no-b1024 --no-c1024 --steps 200 --warmup 10 2>/dev/null | python -c "
 import sys,json
 t=sys.stdin.read().strip().splitlines()
 try:
@@ -14,7 +14,7 @@ try:
 except Exception as e: print('$name', $B, 'FAILED', e, t[-1:])"
   done
   if [ "$EVAL" = "eval" ]; then
-    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --mode eval 2>/dev/null | python -c "
+    env R3D_USE_HOOKS_LIB=1 "$@" python bench.py --full --mode eval 2>/dev/null | python -c "
 import sys,json
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$name', 'eval', l['value'], l['ms_per_step'], l['roofline']['frac'])"
   fi

@@ -111,10 +111,26 @@ int r3d_finalize(r3d_model *m);
 
 #define R3D_INPUT_RAYS 0 /* x is what the reference feeds the model: ray-encoded keypoints  */
 #define R3D_INPUT_UV 1   /* x is pixel keypoints; rays are computed on the fly from `cam`   */
+/* x is RAW pixel keypoints of a distorted camera (CameraInfoPacket(..., undistort=True), the H36M / HumanEva loaders'
+ * default: lib/dataset/h36m_dataset.py:383-385).  A pre-pass kernel (r3d_undistort_rays_f64) computes in float64, per
+ * keypoint, what lib/camera/camera.py:412-441 does on the host - cv2.undistortPoints(uv, K, dist, P=K), i.e. five
+ * fixed-point iterations and the re-projection with K - then the ray encoding (:460-471), casts once to float32
+ * (lib/train_val/trainer.py:298) and writes the rays into the TAIL of the workspace (size it with
+ * r3d_input_workspace_bytes); the R3D_INPUT_RAYS forward then reads them.  Needs in_features == 3 and cam_dev; cam_stride
+ * is 0 (one camera) or >= 16.  Rows whose five coefficients are all 0 skip the iteration and the re-projection (the
+ * reference's undistort=False): the outputs are then bit-identical to R3D_INPUT_UV.  Layout of the rays: one per input
+ * frame (frame f with the row of window min(f / window_stride, B - 1)) for one camera or window_stride >= RF; windows
+ * that overlap AND have their own cameras get a materialised (B, RF, J, 3) copy.  The pre-pass is enqueued on the
+ * stream the forward runs on (with R3D_OPT_LANES: the lane's, after the relay - workspace and inputs belong to the lane
+ * until r3d_lanes_join as always), is captured with the forward into a hipGraph, and is a record of its own in
+ * r3d_profile_read.  PARITY UNPINNED against cv2 itself (OpenCV is not a dependency): the arithmetic restates OpenCV's
+ * documented algorithm and is pinned to the project's other restatements (ray3d_amd/camera.py, the CPU oracle, the
+ * fixture generator's five-iteration grid), INTEGRATION.md section 5. */
+#define R3D_INPUT_UV_DIST 2
 
 typedef struct {
-    int32_t mode;          /* R3D_INPUT_RAYS | R3D_INPUT_UV                                  */
-    const float *x_dev;    /* RAYS: float32 (frames, J, F);  UV: float32 (frames, J, 2)      */
+    int32_t mode;          /* R3D_INPUT_RAYS | R3D_INPUT_UV | R3D_INPUT_UV_DIST              */
+    const float *x_dev;    /* RAYS: float32 (frames, J, F);  UV, UV_DIST: float32 (frames, J, 2) */
     int64_t window_stride; /* frames between the starts of consecutive windows:
                               RF for a (B,RF,J,F) batch (lib/train_val/trainer.py:47-58 output),
                               1 to slide over an edge-padded clip in place (replaces
@@ -124,8 +140,10 @@ typedef struct {
     int64_t param_stride;  /* floats between consecutive windows' rows: extrinsic_dim for a
                               (B,E) tensor, 0 to broadcast one row to every window           */
     const double *cam_dev; /* UV mode only: float64 rows {fx, fy, cx, cy, cos(pitch),
-                              sin(pitch), 0, 0} (lib/camera/camera.py:423-471)               */
-    int64_t cam_stride;    /* doubles between consecutive windows' rows: 8, or 0 = broadcast */
+                              sin(pitch), 0, 0} (lib/camera/camera.py:423-471);
+                              UV_DIST: rows of 16 doubles {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0,
+                              k1, k2, p1, p2, k3, 0, 0, 0} (dist_coeff order of h36m_dataset.py:378-380) */
+    int64_t cam_stride;    /* doubles between consecutive windows' rows: 8 (UV_DIST: >= 16), or 0 = broadcast */
 } r3d_input;
 
 /* Bytes of scratch HBM that suffice for every forward of AT MOST B windows (either model may be NULL): the maximum over
@@ -137,6 +155,12 @@ typedef struct {
  * cached batch size; a forward that is being captured into a hipGraph keeps all of it inside the workspace instead, so
  * a graph's workspace must stay allocated, and untouched by other work while the graph runs, as any captured buffer.) */
 size_t r3d_workspace_bytes(const r3d_model *pos, const r3d_model *trj, int64_t B);
+
+/* ... for forwards of AT MOST B windows with inputs shaped as `in` (mode, window_stride and cam_stride are read; the pointers
+ * are not): r3d_workspace_bytes for R3D_INPUT_RAYS and R3D_INPUT_UV; for R3D_INPUT_UV_DIST that plus the ray buffer of the
+ * pre-pass, which starts at r3d_workspace_bytes(B) rounded up to 256 bytes.  A UV_DIST forward given less returns
+ * R3D_ERR_WORKSPACE.  0 on bad arguments (r3d_last_error says which). */
+size_t r3d_input_workspace_bytes(const r3d_model *pos, const r3d_model *trj, const r3d_input *in, int64_t B);
 
 /* Everything a forward of B windows needs besides its arguments - the launch plan of the pair and the tile schedule
  * of this batch size, uploaded - so that the forward itself only enqueues kernels (hipGraph capture, latency).
@@ -307,6 +331,11 @@ int r3d_debug_plan_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg,
  * runs every earlier problem that touches the same buffer columns is complete for the tile's windows.  Returns 0, 1 when
  * the plan of this batch size runs launch by launch (nothing to check), or a negative code. */
 int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int *tiles, int *counters);
+
+/* The per-keypoint routine of the R3D_INPUT_UV_DIST pre-pass, run on the host: `row16` one camera row of 16 doubles, `uv`
+ * n pixel pairs; out_uv (n, 2) the undistorted pixels, out_rays (n, 3) the float64 rays before the cast (either may be
+ * NULL).  Returns 0 or R3D_ERR_ARG. */
+int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -17,7 +17,8 @@ LIB_PATH = os.path.join(_HERE, "libray3d_hip.so")
 HOOKS_LIB_PATH = os.environ.get("R3D_HOOKS_LIB") or os.path.join(_HERE, "libray3d_hip_hooks.so")
 
 R3D_KIND_POS, R3D_KIND_TRJ = 0, 1
-R3D_INPUT_RAYS, R3D_INPUT_UV = 0, 1
+R3D_INPUT_RAYS, R3D_INPUT_UV, R3D_INPUT_UV_DIST = 0, 1, 2
+R3D_ERR_ARG, R3D_ERR_WORKSPACE = -1, -6
 R3D_ERR_ABORTED = -7
 R3D_OPT_STAGED, R3D_OPT_SPIN_TIMEOUT_MS, R3D_OPT_CU_LIMIT, R3D_OPT_LANES = 1, 2, 3, 4
 
@@ -27,9 +28,10 @@ EXPORTS = (
     "r3d_set_weight", "r3d_finalize", "r3d_workspace_bytes", "r3d_forward", "r3d_forward_pair",
     "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
-    "r3d_lane_stream", "r3d_lanes_join",
+    "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes",
 )
-HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check")   # libray3d_hip_hooks.so only
+HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
+                "r3d_debug_undistort_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -102,6 +104,8 @@ def load():
     lib.r3d_finalize.argtypes = [vp]
     lib.r3d_workspace_bytes.argtypes = [vp, vp, C.c_int64]
     lib.r3d_workspace_bytes.restype = C.c_size_t
+    lib.r3d_input_workspace_bytes.argtypes = [vp, vp, C.POINTER(Input), C.c_int64]
+    lib.r3d_input_workspace_bytes.restype = C.c_size_t
     lib.r3d_forward.argtypes = [vp, C.POINTER(Input), C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_forward_pair.argtypes = [vp, vp, C.POINTER(Input), C.c_int64, vp, vp, vp, C.c_size_t, vp]
     lib.r3d_prepare.argtypes = [vp, vp, C.c_int64]
@@ -117,6 +121,8 @@ def load():
     lib.r3d_clip_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
+    if _hooks:
+        lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
     for name in EXPORTS + (HOOK_EXPORTS if _hooks else ()):
         fn = getattr(lib, name)
         if fn.restype is C.c_int or fn.restype is None:
@@ -233,6 +239,15 @@ def _lib_of(*handles):
 
 def workspace_bytes(pos: Optional[Handle], trj: Optional[Handle], batch: int) -> int:
     return int(_lib_of(pos, trj).r3d_workspace_bytes(pos.ptr if pos else None, trj.ptr if trj else None, batch))
+
+
+def input_workspace_bytes(pos: Optional[Handle], trj: Optional[Handle], inp: Input, batch: int) -> int:
+    """r3d_input_workspace_bytes: the workspace of forwards of at most `batch` windows with inputs shaped as `inp` (for
+    R3D_INPUT_UV_DIST: r3d_workspace_bytes + the pre-pass's ray buffer).  Raises on bad arguments (the library returns 0)."""
+    n = int(_lib_of(pos, trj).r3d_input_workspace_bytes(pos.ptr if pos else None, trj.ptr if trj else None, C.byref(inp), batch))
+    if n == 0:
+        raise Ray3DHipError("r3d_input_workspace_bytes failed: %s" % _lib_of(pos, trj).r3d_last_error().decode())
+    return n
 
 
 def prepare(pos: Optional[Handle], trj: Optional[Handle], batch: int):

@@ -4,7 +4,8 @@ Counterpart of the parts of ``CameraInfoPacket`` that sit on the lifting path
 (lib/camera/camera.py:210-277 constructor, :308-316 pitch, :325-345 normalised frame,
 :390-410 world<->normalised, :423-471 uv -> ray).  Everything per-camera is a handful of float64
 numbers computed once on the host; everything per-keypoint happens on the GPU
-(`Ray3DLifter.forward_uv`: the first-level gather of r3d_gemm_f32 encodes the rays it stages), fed by :meth:`Camera.cam_row`.
+(`Ray3DLifter.forward_uv`: the first-level gather of r3d_gemm_f32 encodes the rays it stages - or, for raw pixels of a
+distorted camera, a pre-pass kernel undistorts and encodes them), fed by :meth:`Camera.cam_row`.
 
 "Normalised" follows the reference's meaning: the camera frame rotated about its
 x axis by the camera pitch and shifted by the camera height - NOT unit-length rays.
@@ -57,10 +58,16 @@ class Camera:
         """[camera height (m), pitch (rad)] float32 - lib/train_val/trainer.py:297."""
         return np.array([self.height, self.pitch], dtype=np.float32)
 
-    def cam_row(self) -> np.ndarray:
-        """float64 row for r3d_input.cam_dev: {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0}."""
-        return np.array([self.fx, self.fy, self.cx, self.cy, self.cos_p, self.sin_p, 0.0, 0.0],
-                        dtype=np.float64)
+    def cam_row(self, distortion: bool = False) -> np.ndarray:
+        """float64 row for r3d_input.cam_dev: {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0} (R3D_INPUT_UV).
+        distortion=True: the 16-double row of R3D_INPUT_UV_DIST, the same 8 followed by {k1, k2, p1, p2, k3, 0, 0, 0} -
+        zeros for a camera without dist_coeff or built with undistort=False (the device then skips the undistortion, as
+        the reference skips cv2).  Raw pixels of an undistort=True camera go through that row on the device."""
+        row = [self.fx, self.fy, self.cx, self.cy, self.cos_p, self.sin_p, 0.0, 0.0]
+        if distortion:
+            dist = self.dist_coeff if (self.undistort and self.dist_coeff is not None) else np.zeros(5)
+            row += [float(v) for v in dist] + [0.0, 0.0, 0.0]
+        return np.array(row, dtype=np.float64)
 
     # -- host-side equivalents (dataset-load time in the reference, lib/dataset/__init__.py:191-203)
     def undistort_points(self, uv: np.ndarray) -> np.ndarray:
@@ -101,7 +108,9 @@ class Camera:
 
     def pixels_for_encoding(self, uv: np.ndarray) -> np.ndarray:
         """What encode_uv_with_intrinsic (camera.py:423-441) subtracts the principal point from: the keypoints,
-        undistorted first when the camera was built with undistort=True.  Feed this to Ray3DLifter.forward_uv."""
+        undistorted first when the camera was built with undistort=True - a float64 pass on the host.  Feed this to
+        Ray3DLifter.forward_uv with cam_row() rows; or feed the RAW keypoints with cam_row(distortion=True) rows, and
+        the GPU undistorts them in front of the forward (R3D_INPUT_UV_DIST) - same arithmetic, no host pass."""
         return self.undistort_points(uv) if self.undistort else np.asarray(uv, dtype=np.float64)
 
     def rays_from_uv(self, uv: np.ndarray) -> np.ndarray:

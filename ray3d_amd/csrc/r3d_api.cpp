@@ -4,6 +4,7 @@
 #include <mutex>
 
 #include "r3d_internal.hpp"
+#include "r3d_undistort.hpp"
 
 namespace r3d {
 const char *last_error();
@@ -54,6 +55,38 @@ static size_t workspace_act_bytes(const Plan *pl, int64_t B) {
     return (act + 255) / 256 * 256;
 }
 static size_t workspace_need(const Plan *pl, int64_t B) { return workspace_act_bytes(pl, B) + fwd_ctrl_bytes(pl, B); }
+
+// r3d_workspace_bytes of a pair (a = pos or the single model, b = trj of a pair)
+static size_t workspace_bytes_pair(Model *a, Model *b, int64_t B) {
+    // monotonic in B: the plan kind switches with the window count and the less fused plans of small calls keep larger
+    // intermediates, so a call of fewer windows may need MORE bytes than one of B - the answer covers every size <= B
+    size_t need = workspace_need(plan_get(a, b, plan_kind(B)), B);
+    for (int64_t edge : plan_kind_edges())
+        if (edge < B) need = std::max(need, workspace_need(plan_get(a, b, plan_kind(edge)), edge));
+    return need;
+}
+
+// R3D_INPUT_UV_DIST: the pre-pass writes its rays behind r3d_workspace_bytes(B) of the call's own B (<= that of any larger
+// B, so a workspace sized for the largest call serves every smaller one).  Layout: one ray per input frame, in the input's
+// own window stride - unless windows overlap AND have their own cameras: a frame then has one ray per window that holds it,
+// and the windows are materialised as (B, RF, J, 3), read with window_stride = RF.
+static bool dist_materialised(const Model *a, const r3d_input *in) { return in->cam_stride != 0 && in->window_stride < a->RF; }
+static int64_t dist_ray_frames(const Model *a, const r3d_input *in, int64_t B) {
+    return dist_materialised(a, in) ? B * a->RF : (B - 1) * in->window_stride + a->RF;
+}
+static size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B) {
+    return ((size_t)dist_ray_frames(a, in, B) * (size_t)a->cfg.num_joints * 3 * sizeof(float) + 255) / 256 * 256;
+}
+static int dist_check(const Model *a, const r3d_input *in, bool need_cam) {
+    if (a->cfg.in_features != 3) { set_error("R3D_INPUT_UV_DIST needs in_features == 3 (got %d)", a->cfg.in_features); return R3D_ERR_ARG; }
+    if (need_cam && !in->cam_dev) { set_error("R3D_INPUT_UV_DIST needs cam_dev (rows of 16 doubles)"); return R3D_ERR_ARG; }
+    if (in->cam_stride != 0 && in->cam_stride < UNDIST_ROW_DOUBLES) {
+        set_error("R3D_INPUT_UV_DIST: cam_stride must be 0 or >= %d doubles (got %lld)", UNDIST_ROW_DOUBLES, (long long)in->cam_stride);
+        return R3D_ERR_ARG;
+    }
+    if (in->window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
 
 struct Recorder {
     Model *m;
@@ -316,17 +349,43 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
             return R3D_ERR_STATE;
         }
     if (b && !same_input_shape(a, b)) { set_error("pos and trj models disagree on J / F / levels / extrinsic_dim"); return R3D_ERR_ARG; }
-    if (in->mode != R3D_INPUT_RAYS && in->mode != R3D_INPUT_UV) { set_error("bad input mode %d", in->mode); return R3D_ERR_ARG; }
+    if (in->mode != R3D_INPUT_RAYS && in->mode != R3D_INPUT_UV && in->mode != R3D_INPUT_UV_DIST) { set_error("bad input mode %d", in->mode); return R3D_ERR_ARG; }
     if (in->mode == R3D_INPUT_UV && (a->cfg.in_features != 3 || !in->cam_dev)) {
         set_error("R3D_INPUT_UV needs in_features == 3 and cam_dev");
         return R3D_ERR_ARG;
     }
+    if (in->mode == R3D_INPUT_UV_DIST)
+        if (const int rc = dist_check(a, in, true); rc != R3D_OK) return rc;
     const bool needs_param = a->cfg.embed_dim > 0 || (b && b->cfg.embed_dim > 0);
     if (needs_param && !in->param_dev) { set_error("param_dev is required when the camera embedding is on"); return R3D_ERR_ARG; }
     if (in->window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
     if (((B - 1) * in->window_stride + a->RF) * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL || B * (int64_t)(a->RF / 3) >= 0x7fffffffLL) {
         set_error("B too large for one call (the raw input must stay below 2 GiB)");
         return R3D_ERR_ARG;
+    }
+    // R3D_INPUT_UV_DIST: the forward below is the R3D_INPUT_RAYS one, on the rays the pre-pass writes into the workspace's tail
+    const r3d_input *in_px = nullptr;      // (the caller's pixels and camera rows: what the pre-pass reads)
+    r3d_input in_rays;
+    size_t dist_off = 0;
+    if (in->mode == R3D_INPUT_UV_DIST) {
+        if (dist_materialised(a, in) && B * (int64_t)a->RF * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL) {
+            set_error("B too large for one call (the materialised rays of overlapping windows must stay below 2 GiB)");
+            return R3D_ERR_ARG;
+        }
+        dist_off = (workspace_bytes_pair(a, b, B) + 255) / 256 * 256;
+        const size_t need = dist_off + dist_ray_bytes(a, in, B);
+        if (!ws || ws_bytes < need) {
+            set_error("workspace too small for R3D_INPUT_UV_DIST (r3d_input_workspace_bytes): need %zu bytes, got %zu", need, ws_bytes);
+            return R3D_ERR_WORKSPACE;
+        }
+        in_px = in;
+        in_rays = *in;
+        in_rays.mode = R3D_INPUT_RAYS;
+        in_rays.x_dev = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ws) + dist_off);
+        in_rays.window_stride = dist_materialised(a, in) ? a->RF : in->window_stride;
+        in_rays.cam_dev = nullptr;
+        in_rays.cam_stride = 0;
+        in = &in_rays;
     }
 
     Plan *pl = plan_get(a, b, plan_kind(B));
@@ -376,6 +435,26 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
     // profiling: an empty bracket first - what two event records cost by themselves on this stream (stage -1)
     if ((e = rec.begin("r3d_event_pair", -1, 0, 0.0, 0.0)) != hipSuccess) return hip_fail(e, "hipEventRecord");
     if ((e = rec.end()) != hipSuccess) return hip_fail(e, "hipEventRecord");
+
+    // R3D_INPUT_UV_DIST: the pre-pass, on the stream the forward runs on (a relayed call: the lane's, behind the caller's work)
+    if (in_px) {
+        UndistArgs ua;
+        memset(&ua, 0, sizeof ua);
+        ua.uv = in_px->x_dev;
+        ua.cam = in_px->cam_dev;
+        ua.cam_stride = in_px->cam_stride;
+        ua.rays = const_cast<float *>(in->x_dev);
+        ua.J = a->cfg.num_joints;
+        ua.npts = (int)(dist_ray_frames(a, in_px, B) * a->cfg.num_joints);
+        ua.pts_per_window = dist_materialised(a, in_px) ? a->RF * a->cfg.num_joints : 0;
+        ua.window_stride = (int)in_px->window_stride;
+        ua.last_window = (int)(B - 1);
+        if ((e = rec.begin("r3d_undistort_rays_f64", stage_no, (ua.npts + 255) / 256, 0.0, (double)ua.npts * (2 + 3) * sizeof(float))) != hipSuccess)
+            return hip_fail(e, "hipEventRecord");
+        if ((e = launch_undistort(ua, stream)) != hipSuccess) return hip_fail(e, "launch r3d_undistort_rays_f64");
+        if ((e = rec.end()) != hipSuccess) return hip_fail(e, "hipEventRecord");
+        ++stage_no;
+    }
 
     // UV mode: the kernels read pixel keypoints (frames, J, 2) and encode the rays while gathering them
     const bool uv = in->mode == R3D_INPUT_UV;
@@ -832,12 +911,22 @@ size_t r3d_workspace_bytes(const r3d_model *pos, const r3d_model *trj, int64_t B
     Model *t = const_cast<Model *>(reinterpret_cast<const Model *>(trj));
     Model *a = p ? p : t, *b = p ? t : nullptr;
     if (!a || B <= 0) return 0;
-    // monotonic in B: the plan kind switches with the window count and the less fused plans of small calls keep larger
-    // intermediates, so a call of fewer windows may need MORE bytes than one of B - the answer covers every size <= B
-    size_t need = workspace_need(plan_get(a, b, plan_kind(B)), B);
-    for (int64_t edge : plan_kind_edges())
-        if (edge < B) need = std::max(need, workspace_need(plan_get(a, b, plan_kind(edge)), edge));
-    return need;
+    return workspace_bytes_pair(a, b, B);
+}
+
+size_t r3d_input_workspace_bytes(const r3d_model *pos, const r3d_model *trj, const r3d_input *in, int64_t B) {
+    Model *p = const_cast<Model *>(reinterpret_cast<const Model *>(pos));
+    Model *t = const_cast<Model *>(reinterpret_cast<const Model *>(trj));
+    Model *a = p ? p : t, *b = p ? t : nullptr;
+    if (!a || !in || B <= 0) { set_error("r3d_input_workspace_bytes: no model, no input or B <= 0"); return 0; }
+    switch (in->mode) {
+        case R3D_INPUT_RAYS:
+        case R3D_INPUT_UV: return workspace_bytes_pair(a, b, B);
+        case R3D_INPUT_UV_DIST:
+            if (dist_check(a, in, false) != R3D_OK) return 0;
+            return (workspace_bytes_pair(a, b, B) + 255) / 256 * 256 + dist_ray_bytes(a, in, B);
+        default: set_error("r3d_input_workspace_bytes: bad input mode %d", in->mode); return 0;
+    }
 }
 
 int r3d_prepare(r3d_model *pos, r3d_model *trj, int64_t B) {
@@ -1136,6 +1225,20 @@ int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int n
         for (int u = 0; u < (int)((batch * pl->probs[i].rows_per_window + 31) / 32); ++u)
             if (cnt[fw.cnt_base[i] + u] != (unsigned)gcols[i]) return -24;
     return 0;
+}
+
+// Test hook: the pre-pass's per-keypoint routine (r3d_undistort.hpp) on the host.
+int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays) {
+    if (!row16 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_undistort_host: bad argument"); return R3D_ERR_ARG; }
+    const UndistRow k = undist_row(row16);
+    for (int64_t i = 0; i < n; ++i) {
+        double uo, vo, r[3];
+        undistort_pixel(k, uv[2 * i], uv[2 * i + 1], uo, vo);
+        pixel_to_ray(k, uo, vo, r);
+        if (out_uv) { out_uv[2 * i] = uo; out_uv[2 * i + 1] = vo; }
+        if (out_rays) for (int c = 0; c < 3; ++c) out_rays[3 * i + c] = r[c];
+    }
+    return R3D_OK;
 }
 
 #endif  // R3D_TEST_HOOKS

@@ -128,6 +128,19 @@ struct BindArgs {
     long long arm_vec4;
 };
 
+// R3D_INPUT_UV_DIST pre-pass (r3d_k_undistort.hip): pixel keypoints of a distorted camera -> float32 rays in the workspace
+struct UndistArgs {
+    const float *uv;               // (frames, J, 2) raw pixels, the caller's input
+    const double *cam;             // rows of 16 doubles (r3d_undistort.hpp)
+    long long cam_stride;          // doubles between consecutive windows' rows, 0 = one camera
+    float *rays;                   // npts rays of 3 floats
+    int npts;                      // keypoints written
+    int J;
+    int pts_per_window;            // > 0: materialised (B, RF, J, 3), RF * J points per window; 0: one ray per input frame
+    int window_stride;             // frames between the starts of consecutive windows in the input
+    int last_window;               // B - 1
+};
+
 constexpr int MAX_DEC = 6;     // 5 body-part decoders + the trajectory decoder
 // Fused decoder tail: the last Linear (1024 -> 3*n_g) of every Integration block, the joint
 // reassembly (rie.py:415-432) and the trajectory add (trainer.py:353) in one pass.
@@ -507,6 +520,7 @@ hipError_t launch_forward(const FwdArgs &args, int nwg, int kind, bool uv, hipSt
 const char *forward_kernel_name(int kind, bool uv);
 int forward_resident_capacity(int kind, bool uv);      // workgroups of that kernel the current device holds at once (0: unknown)
 hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
+hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip)
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

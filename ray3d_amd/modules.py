@@ -456,10 +456,11 @@ class Ray3DLifter(nn.Module):
                         t.record_stream(caller)        # (allocated under the lane's stream, consumed on the caller's after join_lanes)
                 return res
             workspace = self._lane_ws[kk]
-        ws = (workspace or self._ws).get(_capi.workspace_bytes(hp, ht, B), dev)
         inp = _capi.make_input(mode, x.data_ptr(), window_stride,
                                param.data_ptr() if param is not None else None, param_stride,
                                cam.data_ptr() if cam is not None else None, cam_stride)
+        nbytes = _capi.input_workspace_bytes(hp, ht, inp, B) if mode == _capi.R3D_INPUT_UV_DIST else _capi.workspace_bytes(hp, ht, B)
+        ws = (workspace or self._ws).get(nbytes, dev)
         with torch.cuda.device(dev):
             _capi.forward_pair(hp, ht, inp, B, out.data_ptr(),
                                out_trj.data_ptr() if out_trj is not None else None,
@@ -602,7 +603,12 @@ class Ray3DLifter(nn.Module):
         uv (B,RF,J,2) float32 - or a frame sequence (T,J,2) with `window_stride` (1: slide over an edge-padded clip);
         window i covers frames [i*stride, i*stride + RF) and is encoded with ITS camera row, also where windows
         overlap (BASELINE configs[3]: mixed intrinsics per batch);
-        cam_rows (B,8) or (8,) float64 {fx,fy,cx,cy,cos(pitch),sin(pitch),0,0} (:meth:`Camera.cam_row`);
+        cam_rows (B,8) or (8,) float64 {fx,fy,cx,cy,cos(pitch),sin(pitch),0,0} (:meth:`Camera.cam_row`): pixels that
+        are already undistorted (a camera with undistort=False, or :meth:`Camera.pixels_for_encoding` on the host);
+        cam_rows (B,16) or (16,) - :meth:`Camera.cam_row` with distortion=True, the 8 followed by {k1,k2,p1,p2,k3,0,0,0}:
+        RAW pixels of a distorted camera (undistort=True, the H36M / HumanEva default), undistorted on the GPU by a
+        pre-pass kernel in float64 (cv2.undistortPoints' five iterations, lib/camera/camera.py:412-441) in front of the
+        forward (R3D_INPUT_UV_DIST); rows with zero coefficients give exactly the 8-wide result;
         param (B,E) or (E,) float32 [height, pitch]."""
         rf = self.receptive_field()
         uv = uv.detach().to(torch.float32).contiguous()
@@ -620,20 +626,22 @@ class Ray3DLifter(nn.Module):
                 raise RuntimeError("window_stride must be >= 1 and the sequence at least RF frames long")
             B = (uv.shape[0] - rf) // ws_ + 1
         cam = cam_rows.detach().to(uv.device, torch.float64).contiguous()
-        if cam.dim() == 2 and cam.shape != (B, 8) or cam.dim() == 1 and cam.shape != (8,):
-            raise RuntimeError("cam_rows must be (%d, 8) or (8,), got %s" % (B, tuple(cam.shape)))
+        width = cam.shape[-1] if cam.dim() in (1, 2) else 0
+        if width not in (8, 16) or cam.dim() == 2 and cam.shape[0] != B:
+            raise RuntimeError("cam_rows must be (%d, 8), (8,), (%d, 16) or (16,), got %s" % (B, B, tuple(cam.shape)))
+        mode = _capi.R3D_INPUT_UV if width == 8 else _capi.R3D_INPUT_UV_DIST
         p = param.detach().to(uv.device, torch.float32).contiguous() if self.pos.camera_embedding else None
         pstride = 0 if (p is None or p.dim() == 1) else self.pos.extrinsic_dim
-        cstride = 0 if cam.dim() == 1 else 8
+        cstride = 0 if cam.dim() == 1 else width
         if uv.dim() == 4:
-            return self._run(_capi.R3D_INPUT_UV, uv, ws_, B, p, pstride, cam, cstride)
+            return self._run(mode, uv, ws_, B, p, pstride, cam, cstride)
         # a frame sequence: every clip has its own length, and the library keeps one tile schedule per batch size - the
         # windows are lifted in the batch sizes of clip_batch_sizes (as forward_clip does), the surplus ones sliding over
         # repeated last frames with the last window's camera, their poses cut off
         sizes = self.clip_batch_sizes(B)
         total = sum(sizes)
         if total == B and len(sizes) == 1:
-            return self._run(_capi.R3D_INPUT_UV, uv, ws_, B, p, pstride, cam, cstride)
+            return self._run(mode, uv, ws_, B, p, pstride, cam, cstride)
         if total > B:
             uv = torch.cat([uv, uv[-1:].expand((total - B) * ws_, -1, -1)], dim=0)
             if cstride:
@@ -643,7 +651,7 @@ class Ray3DLifter(nn.Module):
         out = torch.empty((total, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=uv.device)
         start = 0
         for b in sizes:
-            self._run(_capi.R3D_INPUT_UV, uv[start * ws_:], ws_, b, p[start:] if pstride else p, pstride,
+            self._run(mode, uv[start * ws_:], ws_, b, p[start:] if pstride else p, pstride,
                       cam[start:] if cstride else cam, cstride, out=out[start:start + b])
             start += b
         return out[:B]

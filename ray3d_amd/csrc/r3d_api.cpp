@@ -228,13 +228,6 @@ int fill_prob(const Plan *pl, const ProbSpec &q, int64_t B, const Model *a, cons
         tg[13] = tg[14] = TA;
         g.K3 = L3.Kpad;
         g.slope3 = L3.slope;
-        // the register-chained form of the same three layers (r3d_chain.hpp): gathered rays, fp32 tiles - an experiment that only the
-        // hooks build switches on (R3D_CHAIN=1, at r3d_finalize AND here): faster stand-alone, slower inside the forward
-        if (L.chain_off != 0 && L.chain_l1 == q.layer2 && L.chain_l2 == q.layer3 && !cs.uv && !cs.shared && g.lut != nullptr &&
-            hook_on("R3D_CHAIN")) {
-            g.wchain = arena_ptr(L.chain_off);
-            tg[18] = TA;
-        }
     }
     if (tags) memcpy(tags, tg, sizeof tg);
     return R3D_OK;
@@ -626,8 +619,7 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
         fa.spin_ticks = (long long)std::max(a->spin_timeout_ms, 1) * 100000LL;          // 100 MHz wall clock
         if (const char *ft = hook_env("R3D_FAULT_TILE")) fa.fault_tile1 = atoi(ft) + 1;   // (hooks build only: see FwdArgs)
         const bool uv_launch = uv && fw.uses_gather;
-        int fwd_kernel = shared ? FWD_KERNEL_CLIP : fw.kernel;           // (shared: fw.kernel is FWD_KERNEL_F32 - `single` above)
-        if (fwd_kernel == FWD_KERNEL_F32 && !uv_launch && hook_on("R3D_CHAIN")) fwd_kernel = FWD_KERNEL_CHAIN;   // (experiment: fill_prob has set wchain)
+        const int fwd_kernel = shared ? FWD_KERNEL_CLIP : fw.kernel;           // (shared: fw.kernel is FWD_KERNEL_F32 - `single` above)
         if ((e = rec.begin(forward_kernel_name(fwd_kernel, uv_launch), stage_no, fw.grid, fw.flops, fw.bytes)) != hipSuccess)
             return hip_fail(e, "hipEventRecord");
 #ifdef R3D_TIMING

@@ -69,9 +69,6 @@ struct GemmProb {
     // ray = ((u-cx)/fx, c*y+s, -s*y+c), y = (v-cy)/fy, in float64 then cast (lib/camera/camera.py:423-471).
     const double *cam;        // rows {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0}
     long long cam_stride;     // doubles between consecutive windows' rows (0: one camera for all)
-    // --- the fused first level again as a register-chained tile (wchain != nullptr; r3d_chain.hpp): the three layers' weights as
-    // ONE stream of 16 KiB slabs in the order the tile multiplies them (r3d_model.cpp, pack_chain) ---
-    const float *wchain;
 };
 
 // Kernel argument of one persistent GEMM launch.  `tiles`/`wg_off` live in HBM (built once per
@@ -111,8 +108,8 @@ struct FwdArgs {
                               // its n-th GEMV tile neither stores nor reports (0: none; n + 1 stored)
     long long *dbg;
 };
-enum { FWD_KERNEL_F32 = 0, FWD_KERNEL_B3 = 1, FWD_KERNEL_LAT = 2, FWD_KERNEL_CLIP = 3, FWD_KERNEL_CHAIN = 4, FWD_KERNEL_COUNT = 5 };   // specialisations of the single-launch forward
-constexpr int BIND_NPTR = 19;  // pointer fields of a GemmProb, in the order r3d_bind_f32 walks them
+enum { FWD_KERNEL_F32 = 0, FWD_KERNEL_B3 = 1, FWD_KERNEL_LAT = 2, FWD_KERNEL_CLIP = 3, FWD_KERNEL_COUNT = 4 };   // specialisations of the single-launch forward
+constexpr int BIND_NPTR = 18;  // pointer fields of a GemmProb, in the order r3d_bind_f32 walks them
 enum { BIND_NULL = 0, BIND_WS, BIND_ARENA0, BIND_ARENA1, BIND_IARENA0, BIND_IARENA1, BIND_X, BIND_PARAM, BIND_CAM, BIND_NBASE };
 struct BindArgs {
     const GemmProb *rel;           // problems with byte OFFSETS in their pointer fields
@@ -230,10 +227,6 @@ struct Layer {
     // (shared_split = first current-frame column of the source layer), linear (slope 1), bias in E.
     int shared_of = -1;
     int shared_split = 0;
-    // expand_conv of a TemporalBlock whose fused first level can run as the register-chained tile (256 channels, K0 = 64):
-    // offset (floats) of the three layers' slab stream in the arena, (K0 / 16 + 64) slabs of 4096 floats; 0: none
-    size_t chain_off = 0;
-    int chain_l1 = -1, chain_l2 = -1;   // the level's 3-tap and 1x1 layers
 };
 
 struct Model {
@@ -513,7 +506,6 @@ FwdKernel fwd_kernel_f32(bool uv);        // r3d_forward_f32 / r3d_forward_uv_f3
 FwdKernel fwd_kernel_b3(bool uv);         // r3d_forward_b3 / r3d_forward_uv_b3         (r3d_k_fwd_b3.hip)
 FwdKernel fwd_kernel_lat(bool uv);        // r3d_forward_lat / r3d_forward_uv_lat       (r3d_k_fwd_lat.hip)
 FwdKernel fwd_kernel_clip(bool uv);       // r3d_forward_clip_f32 / _clip_uv_f32        (r3d_k_fwd_clip.hip)
-FwdKernel fwd_kernel_chain(bool uv);      // r3d_forward_chain_f32 (experiment, rays only) (r3d_k_fwd_chain.hip)
 hipError_t launch_gemm_stage(const LaunchArgs &args, int nwg, int kind, bool uv, hipStream_t stream);   // uv: the launch gathers pixel keypoints
 hipError_t launch_decode(const DecodeArgs &args, hipStream_t stream);
 hipError_t launch_forward(const FwdArgs &args, int nwg, int kind, bool uv, hipStream_t stream);

@@ -55,7 +55,7 @@ extern "C" __global__ __launch_bounds__(256) void r3d_bind_f32(const BindArgs b)
         fix(g.a[sgi], sgi);
     }
     fix(g.w, 4); fix(g.bias, 5); fix(g.res, 6); fix(g.c, 7); fix(g.w2, 8); fix(g.bias2, 9); fix(g.wb3, 10); fix(g.w2b3, 11);
-    fix(g.w3b3, 12); fix(g.w3, 13); fix(g.bias3, 14); fix(g.lut, 15); fix(g.x, 16); fix(g.cam, 17); fix(g.wchain, 18);
+    fix(g.w3b3, 12); fix(g.w3, 13); fix(g.bias3, 14); fix(g.lut, 15); fix(g.x, 16); fix(g.cam, 17);
     if (g.lut != nullptr) {
         g.enc_ws = b.enc_ws;
         g.enc_bytes = b.enc_bytes;
@@ -92,7 +92,6 @@ static FwdKernel forward_kernel(int kind, bool uv) {
         case FWD_KERNEL_B3: return fwd_kernel_b3(uv);
         case FWD_KERNEL_LAT: return fwd_kernel_lat(uv);
         case FWD_KERNEL_CLIP: return fwd_kernel_clip(uv);
-        case FWD_KERNEL_CHAIN: return fwd_kernel_chain(uv);
         default: return fwd_kernel_f32(uv);
     }
 }
@@ -101,7 +100,6 @@ const char *forward_kernel_name(int kind, bool uv) {
         case FWD_KERNEL_B3: return uv ? "r3d_forward_uv_b3" : "r3d_forward_b3";
         case FWD_KERNEL_LAT: return uv ? "r3d_forward_uv_lat" : "r3d_forward_lat";
         case FWD_KERNEL_CLIP: return uv ? "r3d_forward_clip_uv_f32" : "r3d_forward_clip_f32";
-        case FWD_KERNEL_CHAIN: return "r3d_forward_chain_f32";
         default: return uv ? "r3d_forward_uv_f32" : "r3d_forward_f32";
     }
 }

@@ -2455,8 +2455,6 @@ __device__ __forceinline__ void first_level_taps_b3(ProbRef P, const int4 *tile_
     }
 }
 
-#include "r3d_chain.hpp"
-
 // ------------------------------------------------------------------------------------ calls of a few windows: GEMV tiles
 //
 // A problem of M <= 4 rows (the MLPs and the top of the conv pyramid in calls of up to four windows) has nothing for a
@@ -2931,8 +2929,7 @@ __device__ __forceinline__ void gemv_run(FwdArgsPtr fargs, const int4 *tl, const
 // three specialisations - r3d_forward_f32 (neither: the fp32 throughput tiles only), r3d_forward_b3, r3d_forward_lat - picked
 // on the host by what the schedule's tile lists hold, so that the headline kernel pays neither registers nor scratch for
 // code it never runs and a trace names the mode.
-// CHAIN: the kernel carries the register-chained first-level tile (r3d_chain.hpp; GemmProb::wchain) - the fp32 kernels of gathered-rays calls.
-template <bool ENC, bool UV, bool DEP = false, bool B3 = true, bool NARROW = true, bool CLIP = !DEP, bool CHAIN = false>
+template <bool ENC, bool UV, bool DEP = false, bool B3 = true, bool NARROW = true, bool CLIP = !DEP>
 __device__ __forceinline__ void gemm_persistent(float *smem) {
     LaunchArgsPtr args = (LaunchArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     FwdArgsPtr fargs = (FwdArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();      // (DEP: the same segment holds a FwdArgs)
@@ -3021,7 +3018,7 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
             // critical path of a 256-window call thirteen times, and the weights' round trip now overlaps the counters' (-1.7 % at 256
             // windows, -0.2 % at 1024, six same-box rounds: profiles/r06_late_wait/).  First-level and gathered tiles have no producers;
             // the bf16x3 tiles and the timing build - whose "producers ready" stamp is taken here - keep the wait in front.
-            constexpr bool LATE = !B3 && !ENC && !CHAIN;      // (the chained-tile experiment's kernel as it was measured: its register budget has no room)
+            constexpr bool LATE = !B3 && !ENC;
 #else
             constexpr bool LATE = false;
 #endif
@@ -3074,8 +3071,6 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
                         else first_level_taps_b3<1, true, UV>(P, tl, TS, n, new_prob, smem, cnt, run_dbg);
                     }
                   }
-                } else if (CHAIN && P.wchain != nullptr && mi >= 2) {   // 64-row tiles of a body-part branch: register-chained
-                    if constexpr (CHAIN) first_level_chain<4>(P, tl, TS, n, new_prob, smem, cnt, run_dbg);
                 } else if (P.K <= 64) {
                     if (mi >= 2) first_level_taps<2, false, UV>(P, tl, TS, n, new_prob, smem, cnt, run_dbg);
                     else first_level_taps<1, false, UV>(P, tl, TS, n, new_prob, smem, cnt, run_dbg);
@@ -3210,5 +3205,14 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
     }
 #endif
 }
+
+// The whole forward in one launch: every level's tiles, ordered by ready counters (wait_deps).  One workgroup per CU, all of
+// them resident (grid <= CU count: a waiting workgroup can only wait for tiles of resident workgroups or of its own past).
+#define R3D_FORWARD_KERNEL(name, UV_, B3_, NARROW_, CLIP_)                                              \
+    extern "C" __global__ __launch_bounds__(GEMM_THREADS) void name(const FwdArgs args_) {             \
+        extern __shared__ __attribute__((aligned(16))) float smem[];                                    \
+        (void)args_;                                                                                    \
+        gemm_persistent<false, UV_, true, B3_, NARROW_, CLIP_>(smem);                                   \
+    }
 
 }  // namespace r3d

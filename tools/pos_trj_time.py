@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""A/B helper for the register-chained first-level tile: time the POS model alone (its first level is body-part
-tiles only - no 32-row trajectory tiles between them), the TRJ model alone and the pair, in one process, for the tile the
-environment selects (hooks build: R3D_USE_HOOKS_LIB=1 R3D_CHAIN=1|0).  usage: python tools/chain_pos_only.py [windows] [steps]"""
+"""Time the POS model alone (its first level is body-part tiles only - no 32-row trajectory tiles between them), the TRJ model
+alone and the pair, in one process, on the library the environment selects (R3D_USE_HOOKS_LIB=1, R3D_HOOKS_LIB=<variant>;
+tools/variant_time.sh).  usage: python tools/pos_trj_time.py [windows] [steps]"""
 import os
 import sys
 import torch
@@ -36,5 +36,5 @@ res = {"pos": timed(lambda: lifter.pos(x, p)), "trj": timed(lambda: lifter.trj(x
 with torch.no_grad():
     recs = lifter.profile_call(lambda: lifter.pos(x, p), dev)
 lifter.check_status()
-print("CHAIN=%s B=%d  pos alone %.4f ms  trj alone %.4f ms  pair %.4f ms  kernels(pos): %s" % (
-    os.environ.get("R3D_CHAIN", "-"), B, res["pos"], res["trj"], res["pair"], sorted(set(r["kernel"] for r in recs))))
+print("POS_TRJ B=%d  pos alone %.4f ms  trj alone %.4f ms  pair %.4f ms  kernels(pos): %s" % (
+    B, res["pos"], res["trj"], res["pair"], sorted(set(r["kernel"] for r in recs))))

@@ -7,7 +7,7 @@ R=$(cd $(dirname $0)/.. && pwd); C=$R/ray3d_amd/csrc; B=$C/build
 name=$1; fam=$2; flags=$3
 (cd $C && make -j8 >/dev/null)
 objs=""
-for f in r3d_kernels r3d_metrics r3d_k_gemm r3d_k_gemm_enc r3d_k_gemm_b3 r3d_k_fwd_f32 r3d_k_fwd_b3 r3d_k_fwd_lat r3d_k_fwd_clip r3d_k_fwd_chain; do
+for f in r3d_kernels r3d_metrics r3d_k_gemm r3d_k_gemm_enc r3d_k_gemm_b3 r3d_k_fwd_f32 r3d_k_fwd_b3 r3d_k_fwd_lat r3d_k_fwd_clip; do
   if [[ " $fam " == *" $f "* ]]; then
     (cd $C && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$R/include -I. -Wall -Wno-unused-result $flags -Rpass-analysis=kernel-resource-usage \
        -x hip -c -o $B/$f.$name.o $f.hip 2>&1 | grep -i "Function Name\|VGPRs Spill\|ScratchSize" | sed "s/^.*remark: [^ ]* *//" | paste - - - | sed "s/^/$name: /") &

@@ -301,6 +301,33 @@ int r3d_last_clock(r3d_model *m, void *hip_stream, double *ghz);
 int r3d_clip_metrics(const float *pred_dev, const float *gt_dev, int64_t n_frames, int32_t num_joints,
                      const double *rn2w, const double *tn2w, double *out_dev, void *stream);
 
+/* The same call (same arguments, checks and five sums in `out_dev`, bit for bit) that also keeps what those sums are made
+ * of.  It extends trainer.py:386-397 and loss.py:30-69; the reference has no counterpart - it reports the five clip means
+ * only - so the quantities below are this project's definition, all in the world frame, float64, metres:
+ *   frame_dev (optional, may be NULL): (n_frames, R3D_METRIC_COUNT) doubles, row f = the frame's MPJPE, P-MPJPE, N-MPJPE,
+ *     mean_j |first difference of the error| against frame f+1 (0.0 in the last row) and root-joint error, i.e. the
+ *     terms of the five sums (the velocity sum is the column's sum times n/(n-1)).
+ *   detail_dev: R3D_DETAIL_OUT_DOUBLES doubles; the first R3D_DETAIL_DOUBLES are the results, the rest is scratch for the
+ *     workgroups' partial rows.  Results: R3D_DETAIL_JOINT_ROWS rows of R3D_DETAIL_MAX_JOINTS columns (columns >=
+ *     num_joints are 0), each the sum over frames of a per-joint distance -
+ *       row 0: |pred_j - gt_j|
+ *       row 1: the same after the frame's similarity (Procrustes) fit: the per-joint term P-MPJPE averages
+ *       row 2: root-relative, |(pred_j - pred_0) - (gt_j - gt_0)|
+ *     then R3D_DETAIL_THRESHOLDS counts (exact integers stored as doubles): count[k] = the number of (frame, joint)
+ *     pairs with joint >= 1 whose root-relative distance is STRICTLY below 0.005 * k metres, k = 0..30 (0, 5, ..., 150 mm;
+ *     count[0] is 0).  The root joint - distance 0 by construction - is excluded: a caller that counts it adds n_frames
+ *     to every count with k >= 1.  PCK at a threshold is count / (n_frames * joints counted), PCK@150mm the last one (the
+ *     headline figure of MPI-INF-3DHP), AUC the mean of PCK over the R3D_DETAIL_THRESHOLDS thresholds.
+ * Deterministic (fixed summation order, integer counts); enqueued on `stream`, no synchronisation. */
+#define R3D_DETAIL_THRESHOLDS 31
+#define R3D_DETAIL_JOINT_ROWS 3
+#define R3D_DETAIL_MAX_JOINTS 17
+#define R3D_DETAIL_DOUBLES (R3D_DETAIL_JOINT_ROWS * R3D_DETAIL_MAX_JOINTS + R3D_DETAIL_THRESHOLDS)
+#define R3D_DETAIL_OUT_DOUBLES (R3D_DETAIL_DOUBLES * (1 + R3D_METRIC_MAX_BLOCKS))
+int r3d_clip_metrics_detail(const float *pred_dev, const float *gt_dev, int64_t n_frames, int32_t num_joints,
+                            const double *rn2w, const double *tn2w, double *out_dev, double *frame_dev, double *detail_dev,
+                            void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */

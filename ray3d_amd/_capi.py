@@ -26,7 +26,7 @@ R3D_OPT_STAGED, R3D_OPT_SPIN_TIMEOUT_MS, R3D_OPT_CU_LIMIT, R3D_OPT_LANES = 1, 2,
 EXPORTS = (
     "r3d_create", "r3d_destroy", "r3d_num_weights", "r3d_weight_key", "r3d_weight_shape",
     "r3d_set_weight", "r3d_finalize", "r3d_workspace_bytes", "r3d_forward", "r3d_forward_pair",
-    "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_last_error", "r3d_version",
+    "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes",
 )
@@ -35,6 +35,9 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
+DETAIL_THRESHOLDS, DETAIL_JOINT_ROWS, DETAIL_MAX_JOINTS = 31, 3, 17    # R3D_DETAIL_THRESHOLDS, _JOINT_ROWS, joint-row width
+DETAIL_DOUBLES = DETAIL_JOINT_ROWS * DETAIL_MAX_JOINTS + DETAIL_THRESHOLDS   # R3D_DETAIL_DOUBLES (82)
+DETAIL_OUT_DOUBLES = DETAIL_DOUBLES * (1 + 128)                         # R3D_DETAIL_OUT_DOUBLES
 
 
 class Config(C.Structure):
@@ -119,6 +122,7 @@ def load():
     lib.r3d_profile_enable.argtypes = [vp, C.c_int]
     lib.r3d_profile_read.argtypes = [vp, C.POINTER(LaunchRecord), C.c_int]
     lib.r3d_clip_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
+    lib.r3d_clip_metrics_detail.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
@@ -274,6 +278,16 @@ def clip_metrics(pred_ptr: int, gt_ptr: int, n_frames: int, num_joints: int, rn2
     r = (C.c_double * 9)(*[float(v) for row in rn2w for v in row])
     t = (C.c_double * 3)(*[float(v) for v in tn2w])
     check(load().r3d_clip_metrics(pred_ptr, gt_ptr, n_frames, num_joints, r, t, out_ptr, stream), "r3d_clip_metrics")
+
+
+def clip_metrics_detail(pred_ptr: int, gt_ptr: int, n_frames: int, num_joints: int, rn2w, tn2w, out_ptr: int,
+                        frame_ptr: Optional[int], detail_ptr: int, stream: int):
+    """r3d_clip_metrics_detail: clip_metrics plus `frame_ptr` ((n_frames, 5) float64 device memory, or None) and
+    `detail_ptr` (DETAIL_OUT_DOUBLES float64, the first DETAIL_DOUBLES are the results)."""
+    r = (C.c_double * 9)(*[float(v) for row in rn2w for v in row])
+    t = (C.c_double * 3)(*[float(v) for v in tn2w])
+    check(load().r3d_clip_metrics_detail(pred_ptr, gt_ptr, n_frames, num_joints, r, t, out_ptr, frame_ptr or None, detail_ptr,
+                                         stream), "r3d_clip_metrics_detail")
 
 
 def forward_pair(pos: Handle, trj: Handle, inp: Input, batch: int, out_ptr: int,

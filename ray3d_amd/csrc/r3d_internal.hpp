@@ -534,7 +534,8 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // with f in its two low bits (offsets are multiples of four).
 constexpr int ENC_INVALID = (int)0x80000000u;
 
+// frame / detail: the outputs of r3d_clip_metrics_detail, both null for r3d_clip_metrics
 int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, const double *Rn2w, const double *Tn2w,
-                        double *out, hipStream_t stream);
+                        double *out, double *frame, double *detail, hipStream_t stream);
 
 }  // namespace r3d

@@ -8,6 +8,13 @@
 // errors and the first-difference error against the next frame; a fixed-order tree adds a workgroup's frames up
 // and a second, one-wavefront launch adds the workgroups' partial sums in index order - no atomics, the same bits
 // on every run.
+//
+// r3d_clip_metrics_detail runs the same two kernels with MetricArgs::detail set: the frame's five terms go to a per-frame
+// table, and the per-joint distances (raw, after the frame's Procrustes fit, root-relative) and the PCK histogram of the
+// root-relative distances are added up next to the five sums - a wavefront adds a column over its 64 frames by a fixed
+// shuffle tree, its first lane keeps the running sums in LDS, the workgroup adds its four wavefronts in index order and the
+// second launch the workgroups.  The counts are integers (LDS integer atomics, exact in any order).  The code of the five
+// sums is the same in both modes: the detail is computed again from the poses and the fit, behind a uniform branch.
 #include <hip/hip_runtime.h>
 #include "r3d_internal.hpp"
 
@@ -17,6 +24,10 @@ namespace {
 
 constexpr int METRIC_THREADS = 256;
 constexpr int MAX_J = 17;
+constexpr int METRIC_WAVES = METRIC_THREADS / 64;
+constexpr int JOINT_COLS = R3D_DETAIL_JOINT_ROWS * MAX_J;     // per-joint columns of a detail row; the counts follow
+static_assert(R3D_DETAIL_DOUBLES == JOINT_COLS + R3D_DETAIL_THRESHOLDS, "layout of a detail row");
+constexpr double PCK_STEP = 0.005;                             // threshold k is PCK_STEP * k metres
 
 struct MetricArgs {
     const float *pred, *gt;      // (N, J, 3) each, normalised frame
@@ -24,7 +35,20 @@ struct MetricArgs {
     long long n;
     int J;
     double R[9], T[3];           // world = R @ p + T  (Rn2w, Tn2w: camera.py:258-259, :401-410)
+    double *detail;              // r3d_clip_metrics_detail only (null otherwise): R3D_DETAIL_DOUBLES results, then as many per workgroup
+    double *frame;               // ... and, optional, the (N, R3D_METRIC_COUNT) per-frame terms
 };
+
+// the similarity fit of one frame: aligned = a * (p Rm) + t
+struct Fit {
+    double a, Rm[3][3], t[3];
+};
+
+// the sum of v over the wavefront's 64 lanes, in lane 0: a fixed tree, the same bits on every run (all lanes active)
+__device__ inline double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
 
 __device__ inline void to_world(const MetricArgs &a, const float *src, double (*dst)[3]) {
     for (int j = 0; j < a.J; ++j) {
@@ -97,7 +121,7 @@ __device__ inline void svd3(double A[3][3], double U[3][3], double s[3], double 
 }
 
 // mean_j || a * (p_j R) + t - g_j || after the similarity alignment of loss.py:35-66 (target = g, predicted = p)
-__device__ inline double procrustes_error(const double (*p)[3], const double (*g)[3], int J) {
+__device__ inline double procrustes_error(const double (*p)[3], const double (*g)[3], int J, Fit &fit) {
     double mu_g[3] = {0, 0, 0}, mu_p[3] = {0, 0, 0};
     for (int j = 0; j < J; ++j)
         for (int r = 0; r < 3; ++r) { mu_g[r] += g[j][r]; mu_p[r] += p[j][r]; }
@@ -143,60 +167,145 @@ __device__ inline double procrustes_error(const double (*p)[3], const double (*g
         }
         e += sqrt(d2);
     }
+    fit.a = a;
+    for (int r = 0; r < 3; ++r) {
+        fit.t[r] = t[r];
+        for (int c = 0; c < 3; ++c) fit.Rm[r][c] = Rm[r][c];
+    }
     return e / J;
+}
+
+// The detail of one frame (a lane whose frame lies past the clip's end comes with live = false and adds zeros): every
+// per-joint distance is added over the wavefront and kept by lane 0 in `cols` (this wavefront's JOINT_COLS running sums);
+// the root-relative distances of joints >= 1 below 150 mm are counted in hist[k], k the first threshold above them.
+__device__ __noinline__ void frame_detail(const double (*p)[3], const double (*g)[3], int J, const Fit &fit, bool live,
+                                          double *cols, unsigned int *hist) {
+    const bool first = (threadIdx.x & 63) == 0;
+    for (int j = 0; j < J; ++j) {
+        double raw = 0, fitted = 0, rel = 0;
+        for (int c = 0; c < 3; ++c) {
+            const double d = p[j][c] - g[j][c];
+            raw += d * d;
+            const double v = fit.a * (p[j][0] * fit.Rm[0][c] + p[j][1] * fit.Rm[1][c] + p[j][2] * fit.Rm[2][c]) + fit.t[c] - g[j][c];
+            fitted += v * v;
+            const double w = (p[j][c] - p[0][c]) - (g[j][c] - g[0][c]);
+            rel += w * w;
+        }
+        raw = live ? sqrt(raw) : 0.0;
+        fitted = live ? sqrt(fitted) : 0.0;
+        rel = live ? sqrt(rel) : 0.0;
+        if (live && j >= 1 && rel < PCK_STEP * (R3D_DETAIL_THRESHOLDS - 1)) {
+            // the first k with rel < PCK_STEP * k, compared against the very products the thresholds are defined by
+            int k = (int)(rel / PCK_STEP);
+            k = k < 1 ? 1 : (k > R3D_DETAIL_THRESHOLDS - 1 ? R3D_DETAIL_THRESHOLDS - 1 : k);
+            while (k < R3D_DETAIL_THRESHOLDS - 1 && !(rel < PCK_STEP * k)) ++k;
+            while (k > 1 && rel < PCK_STEP * (k - 1)) --k;
+            atomicAdd(&hist[k], 1u);
+        }
+        raw = wave_sum(raw);
+        fitted = wave_sum(fitted);
+        rel = wave_sum(rel);
+        if (first) {
+            cols[j] += raw;
+            cols[MAX_J + j] += fitted;
+            cols[2 * MAX_J + j] += rel;
+        }
+    }
 }
 
 __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArgs a) {
     __shared__ double red[R3D_METRIC_COUNT][METRIC_THREADS];
+    __shared__ double cols[METRIC_WAVES][JOINT_COLS];
+    __shared__ unsigned int hist[R3D_DETAIL_THRESHOLDS + 1];
     double acc[R3D_METRIC_COUNT] = {0, 0, 0, 0, 0};
     const int J = a.J;
-    for (long long f = (long long)blockIdx.x * METRIC_THREADS + threadIdx.x; f < a.n; f += (long long)gridDim.x * METRIC_THREADS) {
+    const bool detail = a.detail != nullptr;
+    if (detail) {
+        for (int i = threadIdx.x; i < METRIC_WAVES * JOINT_COLS; i += METRIC_THREADS) (&cols[0][0])[i] = 0.0;
+        if (threadIdx.x <= R3D_DETAIL_THRESHOLDS) hist[threadIdx.x] = 0u;
+        __syncthreads();
+    }
+    // a wavefront walks the clip 64 frames at a time: its lanes stay together (the detail adds across them), a lane past
+    // the clip's end idles
+    const int lane = threadIdx.x & 63;
+    for (long long f0 = (long long)blockIdx.x * METRIC_THREADS + (threadIdx.x - lane); f0 < a.n; f0 += (long long)gridDim.x * METRIC_THREADS) {
+        const long long f = f0 + lane;
+        const bool live = f < a.n;
         double p[MAX_J][3], g[MAX_J][3];
-        to_world(a, a.pred + f * J * 3, p);
-        to_world(a, a.gt + f * J * 3, g);
-        // mpjpe (loss.py:17-18) and its root-joint restriction (trainer.py:387)
-        double e = 0, pp = 0, gp = 0;
-        for (int j = 0; j < J; ++j) {
-            double d2 = 0;
-            for (int r = 0; r < 3; ++r) {
-                const double d = p[j][r] - g[j][r];
-                d2 += d * d;
-                pp += p[j][r] * p[j][r];
-                gp += g[j][r] * p[j][r];
-            }
-            const double d = sqrt(d2);
-            e += d;
-            if (j == 0) acc[R3D_METRIC_ROOT] += d;
-        }
-        acc[R3D_METRIC_MPJPE] += e / J;
-        // n_mpjpe: scale = mean_j <g,p> / mean_j <p,p>   (loss.py:78-82)
-        const double sc = (gp / J) / (pp / J);
-        double en = 0;
-        for (int j = 0; j < J; ++j) {
-            double d2 = 0;
-            for (int r = 0; r < 3; ++r) {
-                const double d = sc * p[j][r] - g[j][r];
-                d2 += d * d;
-            }
-            en += sqrt(d2);
-        }
-        acc[R3D_METRIC_NMPJPE] += en / J;
-        acc[R3D_METRIC_PMPJPE] += procrustes_error(p, g, J);
-        // mean_velocity_error: first differences along the clip (loss.py:101-104)
-        if (f + 1 < a.n) {
-            double p1[MAX_J][3], g1[MAX_J][3];
-            to_world(a, a.pred + (f + 1) * J * 3, p1);
-            to_world(a, a.gt + (f + 1) * J * 3, g1);
-            double ev = 0;
+        Fit fit;
+        if (live) {
+            double term[R3D_METRIC_COUNT];
+            to_world(a, a.pred + f * J * 3, p);
+            to_world(a, a.gt + f * J * 3, g);
+            // mpjpe (loss.py:17-18) and its root-joint restriction (trainer.py:387)
+            double e = 0, pp = 0, gp = 0;
             for (int j = 0; j < J; ++j) {
                 double d2 = 0;
                 for (int r = 0; r < 3; ++r) {
-                    const double d = (p1[j][r] - p[j][r]) - (g1[j][r] - g[j][r]);
+                    const double d = p[j][r] - g[j][r];
+                    d2 += d * d;
+                    pp += p[j][r] * p[j][r];
+                    gp += g[j][r] * p[j][r];
+                }
+                const double d = sqrt(d2);
+                e += d;
+                if (j == 0) term[R3D_METRIC_ROOT] = d;
+            }
+            term[R3D_METRIC_MPJPE] = e / J;
+            // n_mpjpe: scale = mean_j <g,p> / mean_j <p,p>   (loss.py:78-82)
+            const double sc = (gp / J) / (pp / J);
+            double en = 0;
+            for (int j = 0; j < J; ++j) {
+                double d2 = 0;
+                for (int r = 0; r < 3; ++r) {
+                    const double d = sc * p[j][r] - g[j][r];
                     d2 += d * d;
                 }
-                ev += sqrt(d2);
+                en += sqrt(d2);
             }
-            acc[R3D_METRIC_VELOCITY] += ev / J;
+            term[R3D_METRIC_NMPJPE] = en / J;
+            term[R3D_METRIC_PMPJPE] = procrustes_error(p, g, J, fit);
+            // mean_velocity_error: first differences along the clip (loss.py:101-104)
+            term[R3D_METRIC_VELOCITY] = 0.0;
+            if (f + 1 < a.n) {
+                double p1[MAX_J][3], g1[MAX_J][3];
+                to_world(a, a.pred + (f + 1) * J * 3, p1);
+                to_world(a, a.gt + (f + 1) * J * 3, g1);
+                double ev = 0;
+                for (int j = 0; j < J; ++j) {
+                    double d2 = 0;
+                    for (int r = 0; r < 3; ++r) {
+                        const double d = (p1[j][r] - p[j][r]) - (g1[j][r] - g[j][r]);
+                        d2 += d * d;
+                    }
+                    ev += sqrt(d2);
+                }
+                term[R3D_METRIC_VELOCITY] = ev / J;
+            }
+            for (int k = 0; k < R3D_METRIC_COUNT; ++k) acc[k] += term[k];
+            if (a.frame)
+                for (int k = 0; k < R3D_METRIC_COUNT; ++k) a.frame[f * R3D_METRIC_COUNT + k] = term[k];
+        } else if (detail) {
+            for (int j = 0; j < J; ++j)
+                for (int r = 0; r < 3; ++r) p[j][r] = g[j][r] = 0.0;
+            fit = Fit{};
+        }
+        if (detail) frame_detail(p, g, J, fit, live, cols[threadIdx.x >> 6], hist);
+    }
+    if (detail) {
+        // the workgroup's detail row: its wavefronts' sums in index order, then the counts below each threshold
+        __syncthreads();
+        double *row = a.detail + R3D_DETAIL_DOUBLES * (1 + (long long)blockIdx.x);
+        for (int c = threadIdx.x; c < R3D_DETAIL_DOUBLES; c += METRIC_THREADS) {
+            double v = 0;
+            if (c < JOINT_COLS) {
+                for (int w = 0; w < METRIC_WAVES; ++w) v += cols[w][c];
+            } else {
+                unsigned long long below = 0;
+                for (int k = 1; k <= c - JOINT_COLS; ++k) below += hist[k];
+                v = (double)below;
+            }
+            row[c] = v;
         }
     }
     for (int k = 0; k < R3D_METRIC_COUNT; ++k) red[k][threadIdx.x] = acc[k];
@@ -210,25 +319,34 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
         for (int k = 0; k < R3D_METRIC_COUNT; ++k) a.out[R3D_METRIC_COUNT * (1 + blockIdx.x) + k] = red[k][0];
 }
 
-__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n) {
+__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail) {
     const int k = threadIdx.x;
-    if (k >= R3D_METRIC_COUNT) return;
-    double s = 0;
-    for (int b = 0; b < blocks; ++b) s += out[R3D_METRIC_COUNT * (1 + b) + k];
-    // n * mean over the n-1 differences (trainer.py:395 weights the clip's mean by its frame count); an empty mean
-    // is NaN in NumPy
-    if (k == R3D_METRIC_VELOCITY) s = n > 1 ? s * ((double)n / (double)(n - 1)) : nan("");
-    out[k] = s;
+    if (k < R3D_METRIC_COUNT) {
+        double s = 0;
+        for (int b = 0; b < blocks; ++b) s += out[R3D_METRIC_COUNT * (1 + b) + k];
+        // n * mean over the n-1 differences (trainer.py:395 weights the clip's mean by its frame count); an empty mean
+        // is NaN in NumPy
+        if (k == R3D_METRIC_VELOCITY) s = n > 1 ? s * ((double)n / (double)(n - 1)) : nan("");
+        out[k] = s;
+    }
+    if (detail)
+        for (int c = threadIdx.x; c < R3D_DETAIL_DOUBLES; c += 64) {
+            double s = 0;
+            for (int b = 0; b < blocks; ++b) s += detail[R3D_DETAIL_DOUBLES * (1 + b) + c];
+            detail[c] = s;
+        }
 }
 
 }  // namespace
 
 int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, const double *Rn2w, const double *Tn2w,
-                        double *out, hipStream_t stream) {
+                        double *out, double *frame, double *detail, hipStream_t stream) {
     MetricArgs a;
     a.pred = pred;
     a.gt = gt;
     a.out = out;
+    a.frame = frame;
+    a.detail = detail;
     a.n = n;
     a.J = J;
     for (int i = 0; i < 9; ++i) a.R[i] = Rn2w[i];
@@ -236,7 +354,7 @@ int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, 
     long long blocks = (n + METRIC_THREADS - 1) / METRIC_THREADS;
     blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
     hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n);
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n, detail);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

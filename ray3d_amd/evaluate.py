@@ -199,12 +199,12 @@ def shard_clips(lengths: Sequence[int], world_size: int) -> List[List[int]]:
     return bins
 
 
-def gather_partials(local_rows: torch.Tensor, counts: Sequence[int], group=None) -> torch.Tensor:
-    """The single exchange step: all_gather of per-clip rows, padded to the largest shard."""
+def gather_partials(local_rows: torch.Tensor, counts: Sequence[int], group=None, cols: int = PARTIAL_COLS) -> torch.Tensor:
+    """The single exchange step: all_gather of per-clip rows (`cols` wide), padded to the largest shard."""
     import torch.distributed as dist
     world = dist.get_world_size(group)
     kmax = max(max(counts), 1)
-    pad = torch.zeros((kmax, PARTIAL_COLS), dtype=torch.float64, device=local_rows.device)
+    pad = torch.zeros((kmax, cols), dtype=torch.float64, device=local_rows.device)
     pad[: local_rows.shape[0]] = local_rows
     bucket = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(bucket, pad, group=group)
@@ -238,6 +238,133 @@ def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
     per = reduce_partials(allrows)
     named = {actions[a]: v for a, v in per.items()}
     return named, action_average(per), allrows
+
+
+# ------------------------------------------------------------------------------------ per-joint / per-frame / PCK detail
+
+DETAIL_COLS = M.DETAIL_DOUBLES   # 3 rows of 17 per-joint sums (raw, Procrustes-fitted, root-relative), then 31 PCK counts
+PCK_THRESHOLDS_MM = tuple(5.0 * k for k in range(M.DETAIL_THRESHOLDS))
+
+
+def _clip_detail_hip(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor], frames: bool):
+    """(five sums, detail row, per-frame tensor or None) of one clip through r3d_clip_metrics_detail on the current stream."""
+    from . import _capi
+    dev = pred_norm.device
+    n = pred_norm.shape[0]
+    pred = pred_norm.reshape(n, -1, 3).contiguous().float()
+    if gt_dev is not None:
+        gt = gt_dev.to(dev, torch.float32).reshape(n, -1, 3).contiguous()
+    else:
+        gt = torch.from_numpy(np.ascontiguousarray(clip.gt_norm, dtype=np.float32)).to(dev, non_blocking=True).reshape(n, -1, 3)
+    assert gt.shape == pred.shape, "ground truth %s vs prediction %s" % (tuple(gt.shape), tuple(pred.shape))
+    sums = torch.empty(_capi.METRIC_OUT_DOUBLES, dtype=torch.float64, device=dev)
+    detail = torch.empty(_capi.DETAIL_OUT_DOUBLES, dtype=torch.float64, device=dev)
+    per_frame = torch.empty((n, 5), dtype=torch.float64, device=dev) if frames else None
+    _capi.clip_metrics_detail(pred.data_ptr(), gt.data_ptr(), n, pred.shape[1], np.asarray(clip.camera.Rn2w, dtype=np.float64),
+                              np.asarray(clip.camera.Tn2w, dtype=np.float64).reshape(3), sums.data_ptr(),
+                              per_frame.data_ptr() if frames else None, detail.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+    return sums[:5], detail[:_capi.DETAIL_DOUBLES], per_frame
+
+
+def clip_detail(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor] = None, frames: bool = False):
+    """The DETAIL_COLS-wide detail row of one clip (float64, on pred's device, metres / counts; layout:
+    :func:`ray3d_amd.metrics.clip_detail`), and with `frames` also the (N, 5) per-frame errors in R3D_METRIC_* order.
+    Predictions on a GPU go through the HIP kernel; CPU tensors (host-logic tests, a stand-in lifter) through torch."""
+    if pred_norm.is_cuda:
+        _, detail, per_frame = _clip_detail_hip(pred_norm, clip, gt_dev, frames)
+        return (detail, per_frame) if frames else detail
+    dev = pred_norm.device
+    n = pred_norm.shape[0]
+    R = torch.from_numpy(clip.camera.Rn2w.T.copy()).to(dev)
+    T = torch.from_numpy(clip.camera.Tn2w.T.copy()).to(dev)
+    gt = clip.gt_norm if gt_dev is None else gt_dev.detach().cpu().numpy()
+    pw = pred_norm.to(torch.float64).reshape(n, -1, 3) @ R + T
+    gw = torch.from_numpy(np.asarray(gt, dtype=np.float32)).to(dev).to(torch.float64).reshape(n, -1, 3) @ R + T
+    detail, per_frame = M.clip_detail(pw, gw)
+    return (detail, per_frame) if frames else detail
+
+
+def reduce_detail(rows: torch.Tensor, detail_rows: torch.Tensor, num_joints: int, include_root: bool = False) -> Dict:
+    """{action_id: table, "overall": table} from the per-clip partial rows and their detail rows (same row order), frame
+    weighted: table = {"mpjpe", "p_mpjpe", "root_rel": per-joint errors in mm (num_joints long), "pck": PCK in percent at
+    each of PCK_THRESHOLDS_MM, "pck150": its last entry, "auc": the mean over the thresholds}.  PCK counts the joints whose
+    root-relative distance is strictly below the threshold; `include_root` adds the root joint (distance 0 by construction)
+    to the count of every threshold above 0 and to the total.  Clips are added up in clip-id order, so the result does
+    not depend on how they were sharded."""
+    rows = rows.detach().to("cpu", torch.float64)
+    detail_rows = detail_rows.detach().to("cpu", torch.float64)
+    order = torch.argsort(rows[:, 0], stable=True)
+    rows, detail_rows = rows[order], detail_rows[order]
+    W, nj = M.DETAIL_MAX_JOINTS, M.DETAIL_JOINT_ROWS * M.DETAIL_MAX_JOINTS
+
+    def table(sel):
+        n = rows[sel, 2].sum()
+        d = detail_rows[sel].sum(dim=0)
+        counts, total = d[nj:].clone(), n * (num_joints - 1)
+        if include_root:
+            counts[1:] += n
+            total = n * num_joints
+        pck = (counts / total * 100.0).tolist()
+        out = {name: (d[r * W: r * W + num_joints] / n * 1000.0).tolist() for r, name in enumerate(("mpjpe", "p_mpjpe", "root_rel"))}
+        out.update(pck=pck, pck150=pck[-1], auc=float(np.mean(pck)))
+        return out
+
+    out = {a: table(rows[:, 1] == a) for a in sorted(set(int(v) for v in rows[:, 1].tolist()))}
+    out["overall"] = table(torch.ones(rows.shape[0], dtype=torch.bool))
+    return out
+
+
+def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
+                          kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
+                          rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
+                          joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                          include_root: bool = False):
+    """:func:`evaluate_clips` with the per-joint tables and PCK / AUC on top.  Every rank returns
+    (per_action, action-wise average, partial rows, detail) - the first three as evaluate_clips does, the rows in clip-id
+    order - with detail = {action name: table, "overall": table, "rows": the gathered detail rows} (tables:
+    :func:`reduce_detail`).  On a GPU one r3d_clip_metrics_detail call per clip yields both rows; with `world_size` > 1 the
+    detail rows travel in ONE additional all_gather."""
+    actions = sorted(set(c.action for c in clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
+    on_gpu = torch.device(device).type == "cuda"
+    local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], device)
+    dlocal = torch.zeros((len(shards[rank]), DETAIL_COLS), dtype=torch.float64, device=device)
+    for k, idx in enumerate(shards[rank]):
+        c = clips[idx]
+        pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right)
+        cc = Clip(c.camera, c.rays, c.gt_norm, c.action, idx)
+        if on_gpu and pred.is_cuda:
+            local[k, 3:8], dlocal[k], _ = _clip_detail_hip(pred, cc, None, False)
+        else:
+            local[k] = clip_partials(pred, cc, aid[c.action])
+            dlocal[k] = clip_detail(pred, cc)
+    if world_size > 1:
+        counts = [len(s) for s in shards]
+        allrows = gather_partials(local, counts, group)
+        alldetail = gather_partials(dlocal, counts, group, cols=DETAIL_COLS)
+    else:
+        allrows, alldetail = local, dlocal
+    order = torch.argsort(allrows[:, 0], stable=True)
+    allrows, alldetail = allrows[order], alldetail[order]
+    per = reduce_partials(allrows)
+    named = {actions[a]: v for a, v in per.items()}
+    tables = reduce_detail(allrows, alldetail, clips[0].gt_norm.shape[1] if len(clips) else 0, include_root)
+    detail = {(actions[a] if a != "overall" else a): t for a, t in tables.items()}
+    detail["rows"] = alldetail
+    return named, action_average(per), allrows, detail
+
+
+def format_detail_report(table: Dict, joint_names: Optional[Sequence[str]] = None) -> List[str]:
+    """Plain text for one table of :func:`reduce_detail`: one line per joint, then the PCK / AUC line."""
+    nj = len(table["mpjpe"])
+    names = list(joint_names) if joint_names is not None else ["joint %2d" % j for j in range(nj)]
+    assert len(names) == nj
+    lines = ["%s: MPJPE %.1f mm, P-MPJPE %.1f mm, root-relative %.1f mm"
+             % (names[j], table["mpjpe"][j], table["p_mpjpe"][j], table["root_rel"][j]) for j in range(nj)]
+    lines.append("PCK@150mm: %.1f %%, AUC: %.1f %%" % (table["pck150"], table["auc"]))
+    return lines
 
 
 def format_report(named: Dict[str, tuple], average: tuple) -> List[str]:

@@ -2,10 +2,11 @@
 
 Counterparts of lib/loss/loss.py: mpjpe (:12-18), n_mpjpe (:72-82), p_mpjpe (:30-69, NumPy SVD in
 the reference, batched torch.linalg.svd here so it can stay on the GPU), mean_velocity_error
-(:95-104).  All take (..., J, 3) tensors and return a 0-d tensor.
+(:95-104).  All take (..., J, 3) tensors and return a 0-d tensor.  clip_detail restates what r3d_clip_metrics_detail
+keeps of them: per-frame terms, per-joint sums and PCK counts.
 
 HOST-SIDE ONLY: the product path computes these on the device in float64 (r3d_clip_metrics, csrc/r3d_metrics.hip), which
-is what `evaluate.clip_partials` calls for every CUDA tensor.  This module serves CPU tensors - the host-logic tests that
+is what `evaluate.clip_partials` / `evaluate.clip_detail` call for every CUDA tensor.  This module serves CPU tensors - the host-logic tests that
 drive the evaluation loop with a stand-in lifter (tests/test_host.py) and callers without a GPU tensor in hand; it is
 never a fallback for the HIP kernels.
 """
@@ -27,8 +28,8 @@ def n_mpjpe(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return mpjpe(num / den * pred, target)
 
 
-def p_mpjpe(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """Procrustes-aligned MPJPE (similarity transform per frame)."""
+def procrustes_distances(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """(N, J) per-joint distances after the per-frame similarity (Procrustes) fit of pred onto target."""
     assert pred.shape == target.shape
     pred = pred.reshape(-1, pred.shape[-2], 3)
     target = target.reshape(-1, target.shape[-2], 3)
@@ -47,7 +48,12 @@ def p_mpjpe(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     R = V @ U.transpose(1, 2)
     a = s.sum(dim=1, keepdim=True).unsqueeze(2) * nt / np_
     t = mu_t - a * (mu_p @ R)
-    return torch.linalg.vector_norm(a * (pred @ R) + t - target, dim=-1).mean()
+    return torch.linalg.vector_norm(a * (pred @ R) + t - target, dim=-1)
+
+
+def p_mpjpe(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Procrustes-aligned MPJPE (similarity transform per frame)."""
+    return procrustes_distances(pred, target).mean()
 
 
 def mean_velocity_error(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -56,3 +62,45 @@ def mean_velocity_error(pred: torch.Tensor, target: torch.Tensor) -> torch.Tenso
     if pred.shape[0] < 2:
         return torch.full((), float("nan"), dtype=pred.dtype, device=pred.device)
     return torch.linalg.vector_norm(torch.diff(pred, dim=0) - torch.diff(target, dim=0), dim=-1).mean()
+
+
+# ---- per-joint, per-frame and PCK detail (the host restatement of r3d_clip_metrics_detail; the project's own definition -
+# the reference computes the five clip means only)
+
+DETAIL_THRESHOLDS = 31          # t_k = 0.005 * k metres, k = 0..30: 0, 5, ..., 150 mm
+DETAIL_JOINT_ROWS = 3           # raw, after the Procrustes fit, root-relative
+DETAIL_MAX_JOINTS = 17
+DETAIL_DOUBLES = DETAIL_JOINT_ROWS * DETAIL_MAX_JOINTS + DETAIL_THRESHOLDS
+
+
+def clip_detail(pred: torch.Tensor, target: torch.Tensor):
+    """(N, J, 3) float64 world-frame poses of one clip -> (detail (DETAIL_DOUBLES,), frames (N, 5)), float64:
+
+    * detail[r * 17 + j], r = 0, 1, 2: the sum over frames of joint j's distance |pred_j - gt_j|, of its distance after the
+      frame's Procrustes fit and of its root-relative distance |(pred_j - pred_0) - (gt_j - gt_0)|; columns j >= J are 0;
+    * detail[51 + k]: the number of (frame, joint >= 1) pairs whose root-relative distance is strictly below 0.005 * k m
+      (so detail[51] is 0; the root joint, whose distance is 0 by construction, is left to the caller);
+    * frames[f]: the frame's MPJPE, P-MPJPE, N-MPJPE, first-difference error against frame f + 1 (0.0 in the last row) and
+      root-joint error - the terms the five clip sums add up."""
+    assert pred.shape == target.shape and pred.dim() == 3 and pred.shape[-1] == 3
+    n, J = pred.shape[0], pred.shape[1]
+    assert 1 <= J <= DETAIL_MAX_JOINTS
+    pred, target = pred.to(torch.float64), target.to(torch.float64)
+    raw = torch.linalg.vector_norm(pred - target, dim=-1)
+    fit = procrustes_distances(pred, target)
+    rel = torch.linalg.vector_norm((pred - pred[:, :1]) - (target - target[:, :1]), dim=-1)
+    num = (target * pred).sum(dim=-1, keepdim=True).mean(dim=-2, keepdim=True)
+    den = (pred * pred).sum(dim=-1, keepdim=True).mean(dim=-2, keepdim=True)
+    frames = torch.zeros((n, 5), dtype=torch.float64, device=pred.device)
+    frames[:, 0] = raw.mean(dim=1)
+    frames[:, 1] = fit.mean(dim=1)
+    frames[:, 2] = torch.linalg.vector_norm(num / den * pred - target, dim=-1).mean(dim=1)
+    if n > 1:
+        frames[:-1, 3] = torch.linalg.vector_norm(torch.diff(pred, dim=0) - torch.diff(target, dim=0), dim=-1).mean(dim=1)
+    frames[:, 4] = raw[:, 0]
+    detail = torch.zeros(DETAIL_DOUBLES, dtype=torch.float64, device=pred.device)
+    for r, d in enumerate((raw, fit, rel)):
+        detail[r * DETAIL_MAX_JOINTS: r * DETAIL_MAX_JOINTS + J] = d.sum(dim=0)
+    thr = torch.tensor([0.005 * k for k in range(DETAIL_THRESHOLDS)], dtype=torch.float64, device=pred.device)
+    detail[DETAIL_JOINT_ROWS * DETAIL_MAX_JOINTS:] = (rel[:, 1:, None] < thr).sum(dim=(0, 1)).to(torch.float64)
+    return detail, frames

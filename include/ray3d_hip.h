@@ -127,10 +127,30 @@ int r3d_finalize(r3d_model *m);
  * documented algorithm and is pinned to the project's other restatements (ray3d_amd/camera.py, the CPU oracle, the
  * fixture generator's five-iteration grid), INTEGRATION.md section 5. */
 #define R3D_INPUT_UV_DIST 2
+/* The inputs of the 2-feature models (INPUT_DIM 2, RAY_ENCODING False: the cfg_rie_* baselines) from RAW pixel keypoints.
+ * The same pre-pass kernel (r3d_undistort_rays_f64, one launch, same record name in r3d_profile_read) writes 2 floats per
+ * keypoint into the workspace tail - size it with r3d_input_workspace_bytes - and the R3D_INPUT_RAYS forward reads them.
+ * Both need in_features == 2 and cam_dev rows of 16 doubles (cam_stride 0 or >= 16); layouts, stream / lane / hipGraph
+ * behaviour and the 2 GiB limits are those of R3D_INPUT_UV_DIST; r3d_forward (pos or trj alone) and r3d_forward_pair take
+ * them with every window_stride.  Rounding contract of both: the float32 pixels are promoted to float64, the expressions
+ * below are evaluated in float64 in the written operation order with IEEE division, and the result is cast ONCE to float32
+ * (lib/train_val/trainer.py:298).
+ *   R3D_INPUT_PX_INTRINSIC replaces CameraInfoPacket.encode_uv_with_intrinsic (lib/camera/camera.py:423-441, called at load
+ *     time from lib/dataset/__init__.py:180-189 when INTRINSIC_ENCODING is set): the undistortion of R3D_INPUT_UV_DIST
+ *     (skipped for rows whose five coefficients are 0: undistort=False), then ((u - cx) / fx, (v - cy) / fy).  Slots 4-7 of
+ *     the row are not read.
+ *   R3D_INPUT_PX_SCREEN replaces normalize_screen_coordinates (lib/camera/camera.py:11-18, called from
+ *     lib/dataset/__init__.py:167-178): no undistortion - the reference normalises raw pixels - and
+ *     (u / w * 2 - 1, v / w * 2 - h / w) with w = res_w, h = res_h from slots 6 / 7 of the row (both must be set; the
+ *     other slots are not read).  The reference evaluates `X / w * 2` in the dtype of the keypoint archive it loaded, so
+ *     its own result depends on whether that archive is float32 or float64; this mode is the float64 evaluation, i.e. it
+ *     equals the reference bit for bit (before the cast) for a float64 archive holding these pixels. */
+#define R3D_INPUT_PX_INTRINSIC 3
+#define R3D_INPUT_PX_SCREEN 4
 
 typedef struct {
-    int32_t mode;          /* R3D_INPUT_RAYS | R3D_INPUT_UV | R3D_INPUT_UV_DIST              */
-    const float *x_dev;    /* RAYS: float32 (frames, J, F);  UV, UV_DIST: float32 (frames, J, 2) */
+    int32_t mode;          /* R3D_INPUT_RAYS | R3D_INPUT_UV | R3D_INPUT_UV_DIST | R3D_INPUT_PX_INTRINSIC | R3D_INPUT_PX_SCREEN */
+    const float *x_dev;    /* RAYS: float32 (frames, J, F);  UV, UV_DIST, PX_*: float32 (frames, J, 2) pixels */
     int64_t window_stride; /* frames between the starts of consecutive windows:
                               RF for a (B,RF,J,F) batch (lib/train_val/trainer.py:47-58 output),
                               1 to slide over an edge-padded clip in place (replaces
@@ -142,8 +162,10 @@ typedef struct {
     const double *cam_dev; /* UV mode only: float64 rows {fx, fy, cx, cy, cos(pitch),
                               sin(pitch), 0, 0} (lib/camera/camera.py:423-471);
                               UV_DIST: rows of 16 doubles {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0,
-                              k1, k2, p1, p2, k3, 0, 0, 0} (dist_coeff order of h36m_dataset.py:378-380) */
-    int64_t cam_stride;    /* doubles between consecutive windows' rows: 8 (UV_DIST: >= 16), or 0 = broadcast */
+                              k1, k2, p1, p2, k3, 0, 0, 0} (dist_coeff order of h36m_dataset.py:378-380);
+                              PX_INTRINSIC, PX_SCREEN: the same 16 doubles with slots 6 / 7 = {res_w, res_h}, the
+                              image size in pixels (read by PX_SCREEN only; UV and UV_DIST never read them)      */
+    int64_t cam_stride;    /* doubles between consecutive windows' rows: 8 (UV_DIST, PX_*: >= 16), or 0 = broadcast */
 } r3d_input;
 
 /* Bytes of scratch HBM that suffice for every forward of AT MOST B windows (either model may be NULL): the maximum over
@@ -158,8 +180,9 @@ size_t r3d_workspace_bytes(const r3d_model *pos, const r3d_model *trj, int64_t B
 
 /* ... for forwards of AT MOST B windows with inputs shaped as `in` (mode, window_stride and cam_stride are read; the pointers
  * are not): r3d_workspace_bytes for R3D_INPUT_RAYS and R3D_INPUT_UV; for R3D_INPUT_UV_DIST that plus the ray buffer of the
- * pre-pass, which starts at r3d_workspace_bytes(B) rounded up to 256 bytes.  A UV_DIST forward given less returns
- * R3D_ERR_WORKSPACE.  0 on bad arguments (r3d_last_error says which). */
+ * pre-pass, which starts at r3d_workspace_bytes(B) rounded up to 256 bytes; for R3D_INPUT_PX_INTRINSIC / _SCREEN the same
+ * with 2 floats per point instead of 3.  A forward of these modes given less returns R3D_ERR_WORKSPACE.  0 on bad
+ * arguments (r3d_last_error says which). */
 size_t r3d_input_workspace_bytes(const r3d_model *pos, const r3d_model *trj, const r3d_input *in, int64_t B);
 
 /* Everything a forward of B windows needs besides its arguments - the launch plan of the pair and the tile schedule
@@ -363,6 +386,10 @@ int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int n
  * n pixel pairs; out_uv (n, 2) the undistorted pixels, out_rays (n, 3) the float64 rays before the cast (either may be
  * NULL).  Returns 0 or R3D_ERR_ARG. */
 int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays);
+
+/* ... and its two 2-float encodings (R3D_INPUT_PX_INTRINSIC: encoding 1, R3D_INPUT_PX_SCREEN: encoding 2): `out2` (n, 2) the
+ * float64 values before the cast.  Returns 0 or R3D_ERR_ARG (null pointer, any other encoding). */
+int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, int32_t encoding, double *out2);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

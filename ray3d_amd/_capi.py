@@ -18,6 +18,8 @@ HOOKS_LIB_PATH = os.environ.get("R3D_HOOKS_LIB") or os.path.join(_HERE, "libray3
 
 R3D_KIND_POS, R3D_KIND_TRJ = 0, 1
 R3D_INPUT_RAYS, R3D_INPUT_UV, R3D_INPUT_UV_DIST = 0, 1, 2
+R3D_INPUT_PX_INTRINSIC, R3D_INPUT_PX_SCREEN = 3, 4     # the 2-feature models' inputs from raw pixels (same pre-pass kernel)
+PX_MODES = (R3D_INPUT_UV_DIST, R3D_INPUT_PX_INTRINSIC, R3D_INPUT_PX_SCREEN)   # modes whose workspace carries the pre-pass's output
 R3D_ERR_ARG, R3D_ERR_WORKSPACE = -1, -6
 R3D_ERR_ABORTED = -7
 R3D_OPT_STAGED, R3D_OPT_SPIN_TIMEOUT_MS, R3D_OPT_CU_LIMIT, R3D_OPT_LANES = 1, 2, 3, 4
@@ -31,7 +33,7 @@ EXPORTS = (
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
-                "r3d_debug_undistort_host")
+                "r3d_debug_undistort_host", "r3d_debug_encode_px_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -127,6 +129,7 @@ def load():
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
         lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
+        lib.r3d_debug_encode_px_host.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
     for name in EXPORTS + (HOOK_EXPORTS if _hooks else ()):
         fn = getattr(lib, name)
         if fn.restype is C.c_int or fn.restype is None:
@@ -247,7 +250,8 @@ def workspace_bytes(pos: Optional[Handle], trj: Optional[Handle], batch: int) ->
 
 def input_workspace_bytes(pos: Optional[Handle], trj: Optional[Handle], inp: Input, batch: int) -> int:
     """r3d_input_workspace_bytes: the workspace of forwards of at most `batch` windows with inputs shaped as `inp` (for
-    R3D_INPUT_UV_DIST: r3d_workspace_bytes + the pre-pass's ray buffer).  Raises on bad arguments (the library returns 0)."""
+    R3D_INPUT_UV_DIST: r3d_workspace_bytes + the pre-pass's ray buffer; for R3D_INPUT_PX_INTRINSIC / _SCREEN the same with 2
+    floats per point).  Raises on bad arguments (the library returns 0)."""
     n = int(_lib_of(pos, trj).r3d_input_workspace_bytes(pos.ptr if pos else None, trj.ptr if trj else None, C.byref(inp), batch))
     if n == 0:
         raise Ray3DHipError("r3d_input_workspace_bytes failed: %s" % _lib_of(pos, trj).r3d_last_error().decode())

@@ -1,8 +1,8 @@
 """Per-camera constants of the ray-encoding front end (host side, float64).
 
 Counterpart of the parts of ``CameraInfoPacket`` that sit on the lifting path
-(lib/camera/camera.py:210-277 constructor, :308-316 pitch, :325-345 normalised frame,
-:390-410 world<->normalised, :423-471 uv -> ray).  Everything per-camera is a handful of float64
+(lib/camera/camera.py:210-277 constructor, :308-316 pitch, :325-345 normalised frame, :347-366 world<->camera,
+:390-410 world<->normalised, :423-471 uv -> ray, :11-18 the screen normalisation of the 2-feature baselines).  Everything per-camera is a handful of float64
 numbers computed once on the host; everything per-keypoint happens on the GPU
 (`Ray3DLifter.forward_uv`: the first-level gather of r3d_gemm_f32 encodes the rays it stages - or, for raw pixels of a
 distorted camera, a pre-pass kernel undistorts and encodes them), fed by :meth:`Camera.cam_row`.
@@ -19,10 +19,14 @@ import numpy as np
 
 
 class Camera:
-    def __init__(self, K, R, t, dist_coeff=None, undistort: bool = False, name: str = ""):
+    def __init__(self, K, R, t, dist_coeff=None, undistort: bool = False, name: str = "",
+                 res_w: Optional[float] = None, res_h: Optional[float] = None):
         """K (3,3) intrinsics, R (3,3) world->camera rotation, t (3,) or (3,1) translation in the
-        camera frame (metres), exactly the arguments of CameraInfoPacket(K=, R=, t=)."""
+        camera frame (metres), exactly the arguments of CameraInfoPacket(K=, R=, t=); res_w / res_h the image size
+        in pixels (CameraInfoPacket(res_w=, res_h=)), needed by the screen encoding only."""
         self.name = name
+        self.res_w = None if res_w is None else float(res_w)
+        self.res_h = None if res_h is None else float(res_h)
         self.K = np.asarray(K, dtype=np.float64).reshape(3, 3)
         self.Rw2c = np.asarray(R, dtype=np.float64).reshape(3, 3)
         self.Tw2c = np.asarray(t, dtype=np.float64).reshape(3, 1)
@@ -38,6 +42,8 @@ class Camera:
         self.cx, self.cy = self.K[0, 2], self.K[1, 2]
 
         rc2w = self.Rw2c.T
+        self.Rc2w = rc2w
+        self.Tc2w = -(rc2w @ self.Tw2c)                           # camera.py:248-249
         self.position_world = -(rc2w @ self.Tw2c)                 # camera centre in world coords
         self.height = float(self.position_world[2, 0])            # param[0]
         axis = rc2w[:, 2]                                         # optical axis in world coords
@@ -62,9 +68,13 @@ class Camera:
         """float64 row for r3d_input.cam_dev: {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0} (R3D_INPUT_UV).
         distortion=True: the 16-double row of R3D_INPUT_UV_DIST, the same 8 followed by {k1, k2, p1, p2, k3, 0, 0, 0} -
         zeros for a camera without dist_coeff or built with undistort=False (the device then skips the undistortion, as
-        the reference skips cv2).  Raw pixels of an undistort=True camera go through that row on the device."""
+        the reference skips cv2).  Raw pixels of an undistort=True camera go through that row on the device.  In the
+        16-double row slots 6 / 7 hold {res_w, res_h} when the camera knows its resolution (R3D_INPUT_PX_SCREEN reads
+        them; nothing else does) and stay 0 otherwise; the 8-double row is unchanged."""
         row = [self.fx, self.fy, self.cx, self.cy, self.cos_p, self.sin_p, 0.0, 0.0]
         if distortion:
+            if self.res_w is not None and self.res_h is not None:
+                row[6], row[7] = self.res_w, self.res_h
             dist = self.dist_coeff if (self.undistort and self.dist_coeff is not None) else np.zeros(5)
             row += [float(v) for v in dist] + [0.0, 0.0, 0.0]
         return np.array(row, dtype=np.float64)
@@ -119,6 +129,24 @@ class Camera:
         y = (uv[..., 1] - self.cy) / self.fy
         return np.stack([x, self.cos_p * y + self.sin_p, -self.sin_p * y + self.cos_p], axis=-1)
 
+    def intrinsic_from_uv(self, uv: np.ndarray) -> np.ndarray:
+        """The INTRINSIC_ENCODING input of the 2-feature models, float64 (..., 2): encode_uv_with_intrinsic
+        (camera.py:423-441) - the keypoints undistorted first for an undistort=True camera.  The host equivalent of
+        R3D_INPUT_PX_INTRINSIC."""
+        uv = self.pixels_for_encoding(uv)
+        return np.stack([(uv[..., 0] - self.cx) / self.fx, (uv[..., 1] - self.cy) / self.fy], axis=-1)
+
+    def screen_from_uv(self, uv: np.ndarray) -> np.ndarray:
+        """The plain input of the 2-feature models, float64 (..., 2): normalize_screen_coordinates (camera.py:11-18) of the
+        RAW keypoints, X / w * 2 - [1, h / w] - [0, w] goes to [-1, 1], the aspect ratio is kept.  Evaluated in float64
+        whatever the dtype of `uv` (the reference computes in the dtype of the archive it loaded).  The host equivalent of
+        R3D_INPUT_PX_SCREEN."""
+        if self.res_w is None or self.res_h is None:
+            raise ValueError("the screen encoding needs the camera's resolution (res_w, res_h)")
+        uv = np.asarray(uv, dtype=np.float64)
+        w, h = self.res_w, self.res_h
+        return np.stack([uv[..., 0] / w * 2 - 1, uv[..., 1] / w * 2 - h / w], axis=-1)
+
     def uv_from_rays(self, rays: np.ndarray) -> np.ndarray:
         pc = np.asarray(rays, dtype=np.float64) @ self.Rc2n          # rays @ Rn2c^T, Rn2c = Rc2n^T
         return np.stack([pc[..., 0] * self.fx + self.cx, pc[..., 1] * self.fy + self.cy], axis=-1)
@@ -128,6 +156,15 @@ class Camera:
 
     def normalized2world(self, pts):
         return np.asarray(pts, dtype=np.float64) @ self.Rn2w.T + self.Tn2w.T
+
+    def world2camera(self, pts):
+        """camera.py:358-366."""
+        return np.asarray(pts, dtype=np.float64) @ self.Rw2c.T + self.Tw2c.T
+
+    def camera2world(self, pts):
+        """camera.py:347-356: the world transform of the evaluation when the ground truth is in the camera frame
+        (RAY_ENCODING False with a trajectory model, lib/train_val/trainer.py:361-362)."""
+        return np.asarray(pts, dtype=np.float64) @ self.Rc2w.T + self.Tc2w.T
 
     def project(self, pts_world):
         """Pinhole projection of (...,3) world points to pixels (camera.py:485-504, no distortion)."""

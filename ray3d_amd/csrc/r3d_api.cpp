@@ -66,22 +66,31 @@ static size_t workspace_bytes_pair(Model *a, Model *b, int64_t B) {
     return need;
 }
 
-// R3D_INPUT_UV_DIST: the pre-pass writes its rays behind r3d_workspace_bytes(B) of the call's own B (<= that of any larger
-// B, so a workspace sized for the largest call serves every smaller one).  Layout: one ray per input frame, in the input's
-// own window stride - unless windows overlap AND have their own cameras: a frame then has one ray per window that holds it,
-// and the windows are materialised as (B, RF, J, 3), read with window_stride = RF.
+// R3D_INPUT_UV_DIST, R3D_INPUT_PX_INTRINSIC, R3D_INPUT_PX_SCREEN - the modes with a pixel pre-pass: it writes the model's
+// input (3-float rays, or 2 floats per point for the in_features == 2 models) behind r3d_workspace_bytes(B) of the call's
+// own B (<= that of any larger B, so a workspace sized for the largest call serves every smaller one).  Layout: one point
+// per input frame, in the input's own window stride - unless windows overlap AND have their own cameras: a frame then has
+// one point per window that holds it, and the windows are materialised as (B, RF, J, F), read with window_stride = RF.
+static bool px_mode(int mode) { return mode == R3D_INPUT_UV_DIST || mode == R3D_INPUT_PX_INTRINSIC || mode == R3D_INPUT_PX_SCREEN; }
+static int px_encoding(int mode) { return mode == R3D_INPUT_PX_INTRINSIC ? ENC_INTRINSIC : mode == R3D_INPUT_PX_SCREEN ? ENC_SCREEN : ENC_RAY; }
+static const char *px_name(int mode) {
+    return mode == R3D_INPUT_PX_INTRINSIC ? "R3D_INPUT_PX_INTRINSIC" : mode == R3D_INPUT_PX_SCREEN ? "R3D_INPUT_PX_SCREEN" : "R3D_INPUT_UV_DIST";
+}
 static bool dist_materialised(const Model *a, const r3d_input *in) { return in->cam_stride != 0 && in->window_stride < a->RF; }
 static int64_t dist_ray_frames(const Model *a, const r3d_input *in, int64_t B) {
     return dist_materialised(a, in) ? B * a->RF : (B - 1) * in->window_stride + a->RF;
 }
 static size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B) {
-    return ((size_t)dist_ray_frames(a, in, B) * (size_t)a->cfg.num_joints * 3 * sizeof(float) + 255) / 256 * 256;
+    const size_t F = (size_t)enc_floats(px_encoding(in->mode));
+    return ((size_t)dist_ray_frames(a, in, B) * (size_t)a->cfg.num_joints * F * sizeof(float) + 255) / 256 * 256;
 }
 static int dist_check(const Model *a, const r3d_input *in, bool need_cam) {
-    if (a->cfg.in_features != 3) { set_error("R3D_INPUT_UV_DIST needs in_features == 3 (got %d)", a->cfg.in_features); return R3D_ERR_ARG; }
-    if (need_cam && !in->cam_dev) { set_error("R3D_INPUT_UV_DIST needs cam_dev (rows of 16 doubles)"); return R3D_ERR_ARG; }
+    const char *name = px_name(in->mode);
+    const int F = enc_floats(px_encoding(in->mode));
+    if (a->cfg.in_features != F) { set_error("%s needs in_features == %d (got %d)", name, F, a->cfg.in_features); return R3D_ERR_ARG; }
+    if (need_cam && !in->cam_dev) { set_error("%s needs cam_dev (rows of 16 doubles)", name); return R3D_ERR_ARG; }
     if (in->cam_stride != 0 && in->cam_stride < UNDIST_ROW_DOUBLES) {
-        set_error("R3D_INPUT_UV_DIST: cam_stride must be 0 or >= %d doubles (got %lld)", UNDIST_ROW_DOUBLES, (long long)in->cam_stride);
+        set_error("%s: cam_stride must be 0 or >= %d doubles (got %lld)", name, UNDIST_ROW_DOUBLES, (long long)in->cam_stride);
         return R3D_ERR_ARG;
     }
     if (in->window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
@@ -336,13 +345,17 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
     Model *a = pos ? pos : trj, *b = pos ? trj : nullptr;
     if (!a) { set_error("forward: no model given"); return R3D_ERR_ARG; }
     if (!in || !in->x_dev || !out || B <= 0) { set_error("forward: null input/output or B <= 0"); return R3D_ERR_ARG; }
+    // the 2-feature pixel modes: what is wrong with the arguments themselves (they are judged against the configuration
+    // only) is reported whatever state the handle is in - a binding can validate its call before anything is uploaded
+    if (in->mode == R3D_INPUT_PX_INTRINSIC || in->mode == R3D_INPUT_PX_SCREEN)
+        if (const int rc = dist_check(a, in, true); rc != R3D_OK) return rc;
     for (Model *m : {a, b})
         if (m && (!m->finalized || m->dirty)) {
             set_error("forward called before r3d_finalize (or weights changed since)");
             return R3D_ERR_STATE;
         }
     if (b && !same_input_shape(a, b)) { set_error("pos and trj models disagree on J / F / levels / extrinsic_dim"); return R3D_ERR_ARG; }
-    if (in->mode != R3D_INPUT_RAYS && in->mode != R3D_INPUT_UV && in->mode != R3D_INPUT_UV_DIST) { set_error("bad input mode %d", in->mode); return R3D_ERR_ARG; }
+    if (in->mode != R3D_INPUT_RAYS && in->mode != R3D_INPUT_UV && !px_mode(in->mode)) { set_error("bad input mode %d", in->mode); return R3D_ERR_ARG; }
     if (in->mode == R3D_INPUT_UV && (a->cfg.in_features != 3 || !in->cam_dev)) {
         set_error("R3D_INPUT_UV needs in_features == 3 and cam_dev");
         return R3D_ERR_ARG;
@@ -356,11 +369,11 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
         set_error("B too large for one call (the raw input must stay below 2 GiB)");
         return R3D_ERR_ARG;
     }
-    // R3D_INPUT_UV_DIST: the forward below is the R3D_INPUT_RAYS one, on the rays the pre-pass writes into the workspace's tail
+    // the pixel modes: the forward below is the R3D_INPUT_RAYS one, on the input the pre-pass writes into the workspace's tail
     const r3d_input *in_px = nullptr;      // (the caller's pixels and camera rows: what the pre-pass reads)
     r3d_input in_rays;
     size_t dist_off = 0;
-    if (in->mode == R3D_INPUT_UV_DIST) {
+    if (px_mode(in->mode)) {
         if (dist_materialised(a, in) && B * (int64_t)a->RF * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL) {
             set_error("B too large for one call (the materialised rays of overlapping windows must stay below 2 GiB)");
             return R3D_ERR_ARG;
@@ -368,7 +381,7 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
         dist_off = (workspace_bytes_pair(a, b, B) + 255) / 256 * 256;
         const size_t need = dist_off + dist_ray_bytes(a, in, B);
         if (!ws || ws_bytes < need) {
-            set_error("workspace too small for R3D_INPUT_UV_DIST (r3d_input_workspace_bytes): need %zu bytes, got %zu", need, ws_bytes);
+            set_error("workspace too small for %s (r3d_input_workspace_bytes): need %zu bytes, got %zu", px_name(in->mode), need, ws_bytes);
             return R3D_ERR_WORKSPACE;
         }
         in_px = in;
@@ -429,7 +442,7 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
     if ((e = rec.begin("r3d_event_pair", -1, 0, 0.0, 0.0)) != hipSuccess) return hip_fail(e, "hipEventRecord");
     if ((e = rec.end()) != hipSuccess) return hip_fail(e, "hipEventRecord");
 
-    // R3D_INPUT_UV_DIST: the pre-pass, on the stream the forward runs on (a relayed call: the lane's, behind the caller's work)
+    // the pixel modes: the pre-pass, on the stream the forward runs on (a relayed call: the lane's, behind the caller's work)
     if (in_px) {
         UndistArgs ua;
         memset(&ua, 0, sizeof ua);
@@ -442,7 +455,9 @@ static int run(Model *pos, Model *trj, const r3d_input *in, int64_t B, float *ou
         ua.pts_per_window = dist_materialised(a, in_px) ? a->RF * a->cfg.num_joints : 0;
         ua.window_stride = (int)in_px->window_stride;
         ua.last_window = (int)(B - 1);
-        if ((e = rec.begin("r3d_undistort_rays_f64", stage_no, (ua.npts + 255) / 256, 0.0, (double)ua.npts * (2 + 3) * sizeof(float))) != hipSuccess)
+        ua.encoding = px_encoding(in_px->mode);
+        if ((e = rec.begin("r3d_undistort_rays_f64", stage_no, (ua.npts + 255) / 256, 0.0,
+                           (double)ua.npts * (2 + enc_floats(ua.encoding)) * sizeof(float))) != hipSuccess)
             return hip_fail(e, "hipEventRecord");
         if ((e = launch_undistort(ua, stream)) != hipSuccess) return hip_fail(e, "launch r3d_undistort_rays_f64");
         if ((e = rec.end()) != hipSuccess) return hip_fail(e, "hipEventRecord");
@@ -915,6 +930,8 @@ size_t r3d_input_workspace_bytes(const r3d_model *pos, const r3d_model *trj, con
         case R3D_INPUT_RAYS:
         case R3D_INPUT_UV: return workspace_bytes_pair(a, b, B);
         case R3D_INPUT_UV_DIST:
+        case R3D_INPUT_PX_INTRINSIC:
+        case R3D_INPUT_PX_SCREEN:
             if (dist_check(a, in, false) != R3D_OK) return 0;
             return (workspace_bytes_pair(a, b, B) + 255) / 256 * 256 + dist_ray_bytes(a, in, B);
         default: set_error("r3d_input_workspace_bytes: bad input mode %d", in->mode); return 0;
@@ -1230,6 +1247,17 @@ int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, d
         if (out_uv) { out_uv[2 * i] = uo; out_uv[2 * i + 1] = vo; }
         if (out_rays) for (int c = 0; c < 3; ++c) out_rays[3 * i + c] = r[c];
     }
+    return R3D_OK;
+}
+
+// Test hook: the 2-float encodings of the pre-pass (r3d_undistort.hpp) on the host.
+int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, int32_t encoding, double *out2) {
+    if (!row16 || !out2 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_encode_px_host: bad argument"); return R3D_ERR_ARG; }
+    if (encoding != ENC_INTRINSIC && encoding != ENC_SCREEN) {
+        set_error("r3d_debug_encode_px_host: encoding must be 1 (intrinsic) or 2 (screen), got %d", encoding);
+        return R3D_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) encode_pixel_2d(row16, encoding, uv[2 * i], uv[2 * i + 1], out2 + 2 * i);
     return R3D_OK;
 }
 

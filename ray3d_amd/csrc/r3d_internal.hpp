@@ -125,17 +125,19 @@ struct BindArgs {
     long long arm_vec4;
 };
 
-// R3D_INPUT_UV_DIST pre-pass (r3d_k_undistort.hip): pixel keypoints of a distorted camera -> float32 rays in the workspace
+// The pixel pre-pass (r3d_k_undistort.hip) of R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: raw pixel
+// keypoints -> the model's float32 input (3-float rays, or one of the two 2-float encodings) in the workspace
 struct UndistArgs {
     const float *uv;               // (frames, J, 2) raw pixels, the caller's input
     const double *cam;             // rows of 16 doubles (r3d_undistort.hpp)
     long long cam_stride;          // doubles between consecutive windows' rows, 0 = one camera
-    float *rays;                   // npts rays of 3 floats
+    float *rays;                   // npts encoded points of 3 (ENC_RAY) or 2 floats
     int npts;                      // keypoints written
     int J;
-    int pts_per_window;            // > 0: materialised (B, RF, J, 3), RF * J points per window; 0: one ray per input frame
+    int pts_per_window;            // > 0: materialised (B, RF, J, F), RF * J points per window; 0: one point per input frame
     int window_stride;             // frames between the starts of consecutive windows in the input
     int last_window;               // B - 1
+    int encoding;                  // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN (r3d_undistort.hpp), the same for every point
 };
 
 constexpr int MAX_DEC = 6;     // 5 body-part decoders + the trajectory decoder
@@ -512,7 +514,7 @@ hipError_t launch_forward(const FwdArgs &args, int nwg, int kind, bool uv, hipSt
 const char *forward_kernel_name(int kind, bool uv);
 int forward_resident_capacity(int kind, bool uv);      // workgroups of that kernel the current device holds at once (0: unknown)
 hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
-hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip)
+hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip): every encoding
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

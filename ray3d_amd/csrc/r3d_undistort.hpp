@@ -1,17 +1,30 @@
-// R3D_INPUT_UV_DIST: the per-keypoint arithmetic of the undistortion pre-pass (r3d_k_undistort.hip), __host__ __device__ so
-// that the hooks build runs the very same routine on the CPU (r3d_debug_undistort_host).  float64 throughout, in the
-// reference's order (lib/camera/camera.py:412-441): cv2.undistortPoints(uv, K, dist, P=K) - five fixed-point iterations of
-// OpenCV's documented algorithm for the 5-coefficient Brown-Conrady model, then re-projection with K - followed by the
-// ray encoding of get_cam_ray_given_uv (:460-471).  PARITY UNPINNED against cv2 itself (OpenCV is not a dependency of this
-// project); pinned against the restatements in ray3d_amd/camera.py, oracle.undistort_points and tests/golden/undistort.npz.
+// R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: the per-keypoint arithmetic of the pixel pre-pass
+// (r3d_k_undistort.hip), __host__ __device__ so that the hooks build runs the very same routines on the CPU
+// (r3d_debug_undistort_host, r3d_debug_encode_px_host).  float64 throughout, in the reference's order
+// (lib/camera/camera.py:412-441): cv2.undistortPoints(uv, K, dist, P=K) - five fixed-point iterations of OpenCV's
+// documented algorithm for the 5-coefficient Brown-Conrady model, then re-projection with K - followed by one of three
+// encodings: the ray of get_cam_ray_given_uv (:460-471), the two components of encode_uv_with_intrinsic (:438-439), or -
+// without the undistortion, the reference normalises raw pixels - normalize_screen_coordinates (:11-18).  PARITY UNPINNED
+// against cv2 itself (OpenCV is not a dependency of this project); pinned against the restatements in
+// ray3d_amd/camera.py, oracle.undistort_points and tests/golden/undistort.npz; the two 2-float encodings are pinned to the
+// reference's own values (tests/golden/px2d.npz).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace r3d {
 
-// A camera row of R3D_INPUT_UV_DIST: {fx, fy, cx, cy, cos(pitch), sin(pitch), 0, 0, k1, k2, p1, p2, k3, 0, 0, 0}
+// A camera row of the pre-pass: {fx, fy, cx, cy, cos(pitch), sin(pitch), res_w, res_h, k1, k2, p1, p2, k3, 0, 0, 0}.
+// Slots 6 / 7 (the image's width and height in pixels; 0 when unknown) are read by the screen encoding ONLY - the other two
+// never touch them; cos / sin are read by the ray encoding only.
 constexpr int UNDIST_ROW_DOUBLES = 16;
+constexpr int UNDIST_ROW_RES_W = 6, UNDIST_ROW_RES_H = 7;
+
+// What the pre-pass writes per keypoint (UndistArgs::encoding, uniform over a launch)
+constexpr int ENC_RAY = 0;        // 3 floats: the ray (R3D_INPUT_UV_DIST)
+constexpr int ENC_INTRINSIC = 1;  // 2 floats: ((u-cx)/fx, (v-cy)/fy) of the undistorted pixel (R3D_INPUT_PX_INTRINSIC)
+constexpr int ENC_SCREEN = 2;     // 2 floats: (u/w*2 - 1, v/w*2 - h/w) of the raw pixel (R3D_INPUT_PX_SCREEN)
+__host__ __device__ inline int enc_floats(int encoding) { return encoding == ENC_RAY ? 3 : 2; }
 
 struct UndistRow { double fx, fy, cx, cy, c, s, k1, k2, p1, p2, k3; };
 
@@ -42,14 +55,45 @@ __host__ __device__ inline void undistort_pixel(const UndistRow &k, double u, do
     vo = y * k.fy + k.cy;
 }
 
-// The ray of an (undistorted) pixel: ((u-cx)/fx, c*y+s, -s*y+c) with y = (v-cy)/fy - the expressions of uv_to_ray
+// The intrinsic encoding of an (undistorted) pixel: ((u-cx)/fx, (v-cy)/fy) - encode_uv_with_intrinsic's two components
+// (camera.py:438-439; pp_cam is the principal point), IEEE subtraction and division.
+__host__ __device__ inline void pixel_to_intrinsic(const UndistRow &k, double u, double v, double o[2]) {
+    o[0] = (u - k.cx) / k.fx;
+    o[1] = (v - k.cy) / k.fy;
+}
+
+// The ray of an (undistorted) pixel: (x, c*y+s, -s*y+c) with (x, y) the intrinsic encoding - the expressions of uv_to_ray
 // (r3d_tiles.hpp), so that zero coefficients give UV mode's values bit for bit.
-__host__ __device__ inline void pixel_to_ray(const UndistRow &k, double u, double v, double r[3]) {
-    const double tx = (u - k.cx) / k.fx;
-    const double t = (v - k.cy) / k.fy;
+__host__ __device__ inline void intrinsic_to_ray(const UndistRow &k, const double o[2], double r[3]) {
+    const double tx = o[0], t = o[1];
     r[0] = tx;
     r[1] = k.c * t + k.s;
     r[2] = -k.s * t + k.c;
+}
+__host__ __device__ inline void pixel_to_ray(const UndistRow &k, double u, double v, double r[3]) {
+    double o[2];
+    pixel_to_intrinsic(k, u, v, o);
+    intrinsic_to_ray(k, o, r);
+}
+
+// The screen encoding of a RAW pixel in a w x h image: X / w * 2 - [1, h / w] (normalize_screen_coordinates,
+// camera.py:11-18) in that operation order.  (A compiler may contract "x * 2 - c" into one fma: the product by 2 is exact,
+// so the fused and the two-step forms round the same exact value - the result does not depend on it.)
+__host__ __device__ inline void pixel_to_screen(double w, double h, double u, double v, double o[2]) {
+    o[0] = u / w * 2 - 1;
+    o[1] = v / w * 2 - h / w;
+}
+
+// One keypoint through the 2-float encodings (ENC_INTRINSIC / ENC_SCREEN) from its 16-double camera row
+__host__ __device__ inline void encode_pixel_2d(const double *row, int encoding, double u, double v, double o[2]) {
+    if (encoding == ENC_SCREEN) {
+        pixel_to_screen(row[UNDIST_ROW_RES_W], row[UNDIST_ROW_RES_H], u, v, o);
+        return;
+    }
+    const UndistRow k = undist_row(row);
+    double uo, vo;
+    undistort_pixel(k, u, v, uo, vo);
+    pixel_to_intrinsic(k, uo, vo, o);
 }
 
 }  // namespace r3d

@@ -11,7 +11,10 @@ path consumes:
   in the 3DHP ground-truth file, per-camera dicts with ``'positions_2d'`` - plus ``['metadata'].item()`` with
   ``keypoints_symmetry`` (``lib/dataset/__init__.py:112-122``);
 * per camera i of a subject: ground truth = ``camera.world2normalized(positions)`` (:94-108), model input =
-  ``camera.get_cam_ray_given_uv(keypoints)`` (:191-203), the 2D sequence cut to the mocap length (:205-231).
+  ``camera.get_cam_ray_given_uv(keypoints)`` (:191-203), the 2D sequence cut to the mocap length (:205-231);
+* for the 2-feature baselines (``RAY_ENCODING False``): ground truth = ``camera.world2camera(positions)`` (:79-94), model
+  input = ``normalize_screen_coordinates`` (:167-178) or, with ``INTRINSIC_ENCODING``, ``encode_uv_with_intrinsic``
+  (:180-189) - ``load_pose_data(..., encoding=, frame=)``.
 
 The calibration tables themselves (numbers in the reference's dataset modules) are not part of this package: hand
 them to :func:`cameras_from_tables` in the reference's own dict layout - e.g. ``h36m_cameras_extrinsic_params`` and
@@ -50,7 +53,8 @@ def cameras_from_tables(extrinsics: Mapping[str, Sequence[Mapping]], intrinsics:
     ``undistort=True``, ``'radial_distortion'`` (k1, k2, k3) and ``'tangential_distortion'`` (p1, p2).  Every number
     goes through float32 first, as the dataset classes do (``np.array(v, dtype='float32')``, h36m_dataset.py:355-359);
     H36M translations are in millimetres there: pass ``translation_divisor=1000`` (:361-363, divided in float32).
-    Entries without a translation are skipped (:369-370)."""
+    Entries without a translation are skipped (:369-370).  ``'res_w'`` / ``'res_h'``, where an entry holds them, become
+    the camera's resolution (:384; the screen encoding of the 2-feature models needs it)."""
     f32 = lambda v: np.array(v, dtype="float32")
     out: Dict[str, List[Camera]] = {}
     for subject, views in extrinsics.items():
@@ -70,7 +74,7 @@ def cameras_from_tables(extrinsics: Mapping[str, Sequence[Mapping]], intrinsics:
                 rad, tan = f32(cam["radial_distortion"]), f32(cam["tangential_distortion"])
                 dist = np.concatenate((rad[:2], tan, rad[2:])).astype(np.float32)      # (k1, k2, p1, p2, k3), :379-381
             cams.append(Camera(K, f32(cam["R"]), t, dist_coeff=dist, undistort=undistort,
-                               name="%s/%d" % (subject, i)))
+                               name="%s/%d" % (subject, i), res_w=cam.get("res_w"), res_h=cam.get("res_h")))
         out[subject] = cams
     return out
 
@@ -98,10 +102,10 @@ def cameras_from_json(camera_meta, subjects: Sequence[str] = H36M_AUG_SUBJECTS) 
         t = np.array(cam["translation"], dtype=np.float64).reshape(3, 1)
         dist = np.array(list(cam["radial_distortion"][:2]) + list(cam["tangential_distortion"]) +
                         list(cam["radial_distortion"][2:]), dtype=np.float64).reshape(5)
-        per_cam.append((K, R, t, dist))
+        per_cam.append((K, R, t, dist, cam.get("res_w"), cam.get("res_h")))
         ids.append(str(cam["id"]))
-    out = {s: [Camera(K, R, t, dist_coeff=d, undistort=False, name="%s/%s" % (s, cid))
-               for (K, R, t, d), cid in zip(per_cam, ids)] for s in subjects}
+    out = {s: [Camera(K, R, t, dist_coeff=d, undistort=False, name="%s/%s" % (s, cid), res_w=rw, res_h=rh)
+               for (K, R, t, d, rw, rh), cid in zip(per_cam, ids)] for s in subjects}
     return out, ids
 
 
@@ -141,7 +145,8 @@ def _per_camera_keypoints(entry) -> np.ndarray:
 def load_pose_data(path_3d: str, path_2d: str, cameras: Mapping[str, Sequence[Camera]], subjects: Sequence[str],
                    joints_3d: Optional[Sequence[int]] = None, joints_2d: Optional[Sequence[int]] = None,
                    action_filter: Optional[Sequence[str]] = None, downsample: int = 1,
-                   joints_symmetry: Optional[Tuple[Sequence[int], Sequence[int]]] = None) -> PoseData:
+                   joints_symmetry: Optional[Tuple[Sequence[int], Sequence[int]]] = None,
+                   encoding: str = "ray", frame: str = "normalized") -> PoseData:
     """Read the two archives and build one :class:`Clip` per (subject, action, camera) - the sequences
     ``Trainer.evaluate`` walks (lib/train_val/trainer.py:407-460), grouped by ``action.split(' ')[0]`` (:417).
 
@@ -152,8 +157,16 @@ def load_pose_data(path_3d: str, path_2d: str, cameras: Mapping[str, Sequence[Ca
     ``KeyError`` as the reference's ``fetch_via_action`` would); ``downsample`` is ``DOWNSAMPLE`` as
     ``fetch_via_action`` applies it (lib/dataset/__init__.py:342-348);
     ``joints_symmetry`` = the skeleton's (joints_left, joints_right) when it is neither the 17- nor the 14-joint one.
+    ``encoding`` is the model input the clips carry: ``"ray"`` (RAY_ENCODING, (N, J, 3)), or for the 2-feature models
+    ``"intrinsic"`` (INTRINSIC_ENCODING: :meth:`Camera.intrinsic_from_uv`) or ``"screen"`` (neither key set:
+    :meth:`Camera.screen_from_uv`, needs cameras with a resolution), both (N, J, 2); ``frame`` the frame of the ground
+    truth, ``"normalized"`` (RAY_ENCODING, :96-110) or ``"camera"`` (world2camera, :79-94) - the clips remember it.
     Raises on what ``sanity_check`` (:205-231) asserts: missing subject/action, fewer 2D frames than mocap frames,
     camera-count mismatch."""
+    if encoding not in ("ray", "intrinsic", "screen"):
+        raise ValueError("encoding must be 'ray', 'intrinsic' or 'screen' (got %r)" % (encoding,))
+    if frame not in ("normalized", "camera"):
+        raise ValueError("frame must be 'normalized' or 'camera' (got %r)" % (frame,))
     a3 = np.load(path_3d, allow_pickle=True)["positions_3d"].item()
     z2 = np.load(path_2d, allow_pickle=True)
     a2, meta = z2["positions_2d"].item(), z2["metadata"].item()
@@ -205,11 +218,12 @@ def load_pose_data(path_3d: str, path_2d: str, cameras: Mapping[str, Sequence[Ca
                 if kps.shape[1] != world.shape[1]:
                     raise ValueError("%s / %s: %d keypoints vs %d joints" % (subject, action, kps.shape[1], world.shape[1]))
                 n_joints = world.shape[1]
-                gt = cam.world2normalized(world)[::downsample]
-                rays = cam.rays_from_uv(kps)[::downsample]
+                gt = (cam.world2normalized(world) if frame == "normalized" else cam.world2camera(world))[::downsample]
+                encode = {"ray": cam.rays_from_uv, "intrinsic": cam.intrinsic_from_uv, "screen": cam.screen_from_uv}[encoding]
+                rays = encode(kps)[::downsample]
                 key = action.split(" ")[0]
                 cid = len(clips)
-                clips.append(Clip(cam, rays.astype(np.float32), gt.astype(np.float32), key, cid))
+                clips.append(Clip(cam, rays.astype(np.float32), gt.astype(np.float32), key, cid, frame))
                 groups.setdefault(key, []).append(cid)
                 cam_of_clip.append(ci)
     if joints_symmetry is not None:

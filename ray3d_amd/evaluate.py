@@ -9,7 +9,10 @@ Reproduces the behaviour of ``Trainer.evaluate_core`` / ``Trainer.evaluate``
 * the camera row [height, pitch] is shared by all windows of the clip (trainer.py:297,324);
 * prediction = pos + trj, optionally averaged with the mirrored pass (trainer.py:299-302,338-353);
 * prediction and ground truth go to world coordinates in float64 (trainer.py:355-364) and the five
-  per-clip errors are accumulated weighted by the number of frames (trainer.py:386-403).
+  per-clip errors are accumulated weighted by the number of frames (trainer.py:386-403);
+* the 2-feature baselines (RAY_ENCODING False): a clip whose ground truth is in the camera frame (``Clip.frame ==
+  "camera"``) goes to the world through camera2world (trainer.py:361-362); without a trajectory model
+  (``root_relative=True``) the ground truth is made root-relative and nothing is transformed (trainer.py:319-320, :382-384).
 
 Multi-GPU: whole clips are partitioned over ranks (one process per GPU), each rank evaluates its
 share with resident weights, and ONE all_gather of the fixed-size per-clip partial rows
@@ -33,10 +36,34 @@ PARTIAL_COLS = 8   # clip_id, action_id, n_frames, sum_mpjpe, sum_pmpjpe, sum_nm
 @dataclass
 class Clip:
     camera: Camera
-    rays: np.ndarray          # (N, J, F) float32 ray-encoded keypoints (model input space)
-    gt_norm: np.ndarray       # (N, J, 3) float32 ground truth in the normalised frame
+    rays: np.ndarray          # (N, J, F) float32 ray-encoded keypoints (model input space; F = 2: the 2-feature encodings)
+    gt_norm: np.ndarray       # (N, J, 3) float32 ground truth in the normalised frame (`frame` "camera": the camera frame)
     action: str = ""
     clip_id: int = 0
+    frame: str = "normalized"   # the frame of gt_norm and of the predictions: "normalized" | "camera"
+
+
+_IDENTITY_R, _IDENTITY_T = np.eye(3, dtype=np.float64), np.zeros((3, 1), dtype=np.float64)
+
+
+def clip_world_transform(clip: Clip, root_relative: bool = False):
+    """(R (3,3), T (3,1)) float64 taking the clip's predictions and ground truth to the frame the errors are measured in:
+    Rn2w / Tn2w (normalised frame), Rc2w / Tc2w (camera frame, trainer.py:361-362), identity for root-relative evaluation."""
+    if root_relative:
+        return _IDENTITY_R, _IDENTITY_T
+    if clip.frame == "camera":
+        return clip.camera.Rc2w, clip.camera.Tc2w
+    if clip.frame != "normalized":
+        raise ValueError("Clip.frame must be 'normalized' or 'camera' (got %r)" % (clip.frame,))
+    return clip.camera.Rn2w, clip.camera.Tn2w
+
+
+def root_relative_gt(gt: np.ndarray) -> np.ndarray:
+    """trainer.py:319-320 on (N, J, 3): every joint relative to the root, the root itself at the origin."""
+    gt = np.array(gt, dtype=np.float32, copy=True)
+    gt[:, 1:] -= gt[:, :1]
+    gt[:, 0] = 0
+    return gt
 
 
 def pad_clip(rays: np.ndarray, pad: int, causal_shift: int = 0) -> np.ndarray:
@@ -62,17 +89,45 @@ def mirror_output(pred: torch.Tensor, joints_left: Sequence[int], joints_right: 
     return out
 
 
+def mirror_pixels(camera: Camera, encoding: str, kps_left: Sequence[int], kps_right: Sequence[int]) -> Callable:
+    """`mirror` of :func:`predict_clip` for clips that hold RAW PIXELS (lifted through ``forward_uv(..., encoding=)``): the
+    reference mirrors the ENCODED input (trainer.py:299-302, x -> -x), and the pixels whose encoding that is are
+    u -> res_w - u ("screen": -(u/w*2 - 1) = (w - u)/w*2 - 1) or u -> 2 cx - u ("intrinsic"), computed in float64 and
+    rounded once to float32 - equal to the negated encoding up to that rounding of the pixel (<= 2^-24 of it).  Not for an
+    undistort=True camera: the tangential terms are not symmetric about the principal point."""
+    if encoding == "screen":
+        if camera.res_w is None:
+            raise ValueError("the screen encoding needs the camera's resolution (res_w, res_h)")
+        axis = camera.res_w
+    elif encoding == "intrinsic":
+        if camera.undistort:
+            raise ValueError("mirror_pixels: the pixels of an undistort=True camera have no exact mirror image; undistort on the host first")
+        axis = 2.0 * camera.cx
+    else:
+        raise ValueError("encoding must be 'intrinsic' or 'screen' (got %r)" % (encoding,))
+
+    def mirror(clip: torch.Tensor) -> torch.Tensor:
+        out = clip.clone()
+        out[..., 0] = (axis - clip[..., 0].to(torch.float64)).to(clip.dtype)
+        out[:, list(kps_left) + list(kps_right)] = out[:, list(kps_right) + list(kps_left)]
+        return out
+    return mirror
+
+
 def predict_clip(lift_clip: Callable, clip: Clip, rf: int, device, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), causal: bool = False,
-                 joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None) -> torch.Tensor:
+                 joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                 mirror: Optional[Callable] = None) -> torch.Tensor:
     """(N,1,J,3) absolute poses in the normalised frame for one clip.
-    `lift_clip(padded (N+RF-1,J,F) tensor, param_row (E,) tensor) -> (N,1,J,3)`."""
+    `lift_clip(padded (N+RF-1,J,F) tensor, param_row (E,) tensor) -> (N,1,J,3)`.
+    `mirror`: what makes the mirrored input of the flip pass from the padded one, when the clip does not hold the encoded
+    input itself (:func:`mirror_pixels`); default :func:`mirror_input`."""
     pad = (rf - 1) // 2
     padded = torch.from_numpy(pad_clip(np.asarray(clip.rays, dtype=np.float32), pad, pad if causal else 0)).to(device)
     prow = torch.from_numpy(clip.camera.param()).to(device)
     pred = lift_clip(padded, prow)
     if flip:
-        pred_m = lift_clip(mirror_input(padded, kps_left, kps_right), prow)
+        pred_m = lift_clip(mirror(padded) if mirror is not None else mirror_input(padded, kps_left, kps_right), prow)
         pred = 0.5 * (pred + mirror_output(pred_m, kps_left if joints_left is None else joints_left,
                                            kps_right if joints_right is None else joints_right))
     return pred
@@ -89,12 +144,15 @@ def partial_rows(headers: Sequence[tuple], device) -> torch.Tensor:
 
 
 def clip_partials_hip(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0,
-                      gt_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      gt_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      root_relative: bool = False) -> torch.Tensor:
     """clip_partials on the GPU through r3d_clip_metrics: world transform, the five error sums and the per-frame
     Procrustes fits in one float64 kernel on the current stream - no D2H copy of the predictions.
     `gt_dev`: the clip's ground truth already on the device (callers that keep a data set resident in HBM).
     `out`: a row of :func:`partial_rows` (header columns already on the device): only the five sums are written, by a
-    device copy - no host tensor, no host synchronisation per clip, whatever the number of ranks."""
+    device copy - no host tensor, no host synchronisation per clip, whatever the number of ranks.
+    The rigid transform is the clip's (:func:`clip_world_transform`); `root_relative`: the clip's ground truth is already
+    root-relative (the caller's job, :func:`root_relative_gt`) and the transform is the identity."""
     from . import _capi
     dev = pred_norm.device
     n = pred_norm.shape[0]
@@ -105,8 +163,9 @@ def clip_partials_hip(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0,
         gt = torch.from_numpy(np.ascontiguousarray(clip.gt_norm, dtype=np.float32)).to(dev, non_blocking=True).reshape(n, -1, 3)
     assert gt.shape == pred.shape, "ground truth %s vs prediction %s" % (tuple(gt.shape), tuple(pred.shape))
     sums = torch.empty(_capi.METRIC_OUT_DOUBLES, dtype=torch.float64, device=dev)
-    _capi.clip_metrics(pred.data_ptr(), gt.data_ptr(), n, pred.shape[1], np.asarray(clip.camera.Rn2w, dtype=np.float64),
-                       np.asarray(clip.camera.Tn2w, dtype=np.float64).reshape(3), sums.data_ptr(),
+    R, T = clip_world_transform(clip, root_relative)
+    _capi.clip_metrics(pred.data_ptr(), gt.data_ptr(), n, pred.shape[1], np.asarray(R, dtype=np.float64),
+                       np.asarray(T, dtype=np.float64).reshape(3), sums.data_ptr(),
                        torch.cuda.current_stream(dev).cuda_stream)
     if out is not None:
         assert out.shape == (PARTIAL_COLS,) and out.dtype == torch.float64 and out.device == dev
@@ -119,15 +178,16 @@ def clip_partials_hip(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0,
     return row
 
 
-def clip_partials(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0) -> torch.Tensor:
+def clip_partials(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0, root_relative: bool = False) -> torch.Tensor:
     """One PARTIAL_COLS row (float64, on pred's device): N-weighted error sums in metres.  Predictions on a GPU
     go through the HIP kernel; CPU tensors (host-logic tests with a stand-in lifter) through torch."""
     if pred_norm.is_cuda:
-        return clip_partials_hip(pred_norm, clip, action_id)
+        return clip_partials_hip(pred_norm, clip, action_id, root_relative=root_relative)
     dev = pred_norm.device
     n = pred_norm.shape[0]
-    R = torch.from_numpy(clip.camera.Rn2w.T.copy()).to(dev)
-    T = torch.from_numpy(clip.camera.Tn2w.T.copy()).to(dev)
+    Rm, Tm = clip_world_transform(clip, root_relative)
+    R = torch.from_numpy(Rm.T.copy()).to(dev)
+    T = torch.from_numpy(Tm.T.copy()).to(dev)
     pw = pred_norm.to(torch.float64).reshape(n, 1, -1, 3) @ R + T             # trainer.py:358
     gw = torch.from_numpy(np.asarray(clip.gt_norm, dtype=np.float32)).to(dev).to(torch.float64)
     gw = gw.reshape(n, 1, -1, 3) @ R + T                                        # trainer.py:359
@@ -214,10 +274,14 @@ def gather_partials(local_rows: torch.Tensor, counts: Sequence[int], group=None,
 def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
                    kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                    rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
-                   joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None):
+                   joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                   root_relative: bool = False, mirror: Optional[Callable] = None):
     """Evaluate `clips` (sharded over `world_size` ranks when > 1; `causal`: pad as main.py:85-89 does for
     CAUSAL models).  Every rank returns
-    (per_action {name: (e1,e2,e3,ev,er) mm}, action-wise average, gathered partial rows)."""
+    (per_action {name: (e1,e2,e3,ev,er) mm}, action-wise average, gathered partial rows).
+    Each clip is measured in the world frame through the transform of ITS frame (`Clip.frame`); `root_relative` (models
+    without a trajectory network, RAY_ENCODING False: trainer.py:315-320, :382-384): the ground truth is made
+    root-relative and compared with the predictions as they are.  `mirror`: see :func:`predict_clip` (clips of raw pixels)."""
     actions = sorted(set(c.action for c in clips))
     aid = {a: i for i, a in enumerate(actions)}
     shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
@@ -225,12 +289,12 @@ def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
     local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], device)
     for k, idx in enumerate(shards[rank]):
         c = clips[idx]
-        pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right)
-        cc = Clip(c.camera, c.rays, c.gt_norm, c.action, idx)
+        pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right, mirror)
+        cc = Clip(c.camera, c.rays, root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, c.action, idx, c.frame)
         if on_gpu and pred.is_cuda:
-            clip_partials_hip(pred, cc, aid[c.action], out=local[k])
+            clip_partials_hip(pred, cc, aid[c.action], out=local[k], root_relative=root_relative)
         else:
-            local[k] = clip_partials(pred, cc, aid[c.action])
+            local[k] = clip_partials(pred, cc, aid[c.action], root_relative)
     if world_size > 1:
         allrows = gather_partials(local, [len(s) for s in shards], group)
     else:
@@ -246,7 +310,8 @@ DETAIL_COLS = M.DETAIL_DOUBLES   # 3 rows of 17 per-joint sums (raw, Procrustes-
 PCK_THRESHOLDS_MM = tuple(5.0 * k for k in range(M.DETAIL_THRESHOLDS))
 
 
-def _clip_detail_hip(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor], frames: bool):
+def _clip_detail_hip(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor], frames: bool,
+                     root_relative: bool = False):
     """(five sums, detail row, per-frame tensor or None) of one clip through r3d_clip_metrics_detail on the current stream."""
     from . import _capi
     dev = pred_norm.device
@@ -260,24 +325,27 @@ def _clip_detail_hip(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch
     sums = torch.empty(_capi.METRIC_OUT_DOUBLES, dtype=torch.float64, device=dev)
     detail = torch.empty(_capi.DETAIL_OUT_DOUBLES, dtype=torch.float64, device=dev)
     per_frame = torch.empty((n, 5), dtype=torch.float64, device=dev) if frames else None
-    _capi.clip_metrics_detail(pred.data_ptr(), gt.data_ptr(), n, pred.shape[1], np.asarray(clip.camera.Rn2w, dtype=np.float64),
-                              np.asarray(clip.camera.Tn2w, dtype=np.float64).reshape(3), sums.data_ptr(),
+    R, T = clip_world_transform(clip, root_relative)
+    _capi.clip_metrics_detail(pred.data_ptr(), gt.data_ptr(), n, pred.shape[1], np.asarray(R, dtype=np.float64),
+                              np.asarray(T, dtype=np.float64).reshape(3), sums.data_ptr(),
                               per_frame.data_ptr() if frames else None, detail.data_ptr(),
                               torch.cuda.current_stream(dev).cuda_stream)
     return sums[:5], detail[:_capi.DETAIL_DOUBLES], per_frame
 
 
-def clip_detail(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor] = None, frames: bool = False):
+def clip_detail(pred_norm: torch.Tensor, clip: Clip, gt_dev: Optional[torch.Tensor] = None, frames: bool = False,
+                root_relative: bool = False):
     """The DETAIL_COLS-wide detail row of one clip (float64, on pred's device, metres / counts; layout:
     :func:`ray3d_amd.metrics.clip_detail`), and with `frames` also the (N, 5) per-frame errors in R3D_METRIC_* order.
     Predictions on a GPU go through the HIP kernel; CPU tensors (host-logic tests, a stand-in lifter) through torch."""
     if pred_norm.is_cuda:
-        _, detail, per_frame = _clip_detail_hip(pred_norm, clip, gt_dev, frames)
+        _, detail, per_frame = _clip_detail_hip(pred_norm, clip, gt_dev, frames, root_relative)
         return (detail, per_frame) if frames else detail
     dev = pred_norm.device
     n = pred_norm.shape[0]
-    R = torch.from_numpy(clip.camera.Rn2w.T.copy()).to(dev)
-    T = torch.from_numpy(clip.camera.Tn2w.T.copy()).to(dev)
+    Rm, Tm = clip_world_transform(clip, root_relative)
+    R = torch.from_numpy(Rm.T.copy()).to(dev)
+    T = torch.from_numpy(Tm.T.copy()).to(dev)
     gt = clip.gt_norm if gt_dev is None else gt_dev.detach().cpu().numpy()
     pw = pred_norm.to(torch.float64).reshape(n, -1, 3) @ R + T
     gw = torch.from_numpy(np.asarray(gt, dtype=np.float32)).to(dev).to(torch.float64).reshape(n, -1, 3) @ R + T
@@ -319,12 +387,12 @@ def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
                           kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                           rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
                           joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
-                          include_root: bool = False):
+                          include_root: bool = False, root_relative: bool = False, mirror: Optional[Callable] = None):
     """:func:`evaluate_clips` with the per-joint tables and PCK / AUC on top.  Every rank returns
     (per_action, action-wise average, partial rows, detail) - the first three as evaluate_clips does, the rows in clip-id
     order - with detail = {action name: table, "overall": table, "rows": the gathered detail rows} (tables:
     :func:`reduce_detail`).  On a GPU one r3d_clip_metrics_detail call per clip yields both rows; with `world_size` > 1 the
-    detail rows travel in ONE additional all_gather."""
+    detail rows travel in ONE additional all_gather.  `Clip.frame`, `root_relative` and `mirror` as in :func:`evaluate_clips`."""
     actions = sorted(set(c.action for c in clips))
     aid = {a: i for i, a in enumerate(actions)}
     shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
@@ -333,13 +401,13 @@ def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     dlocal = torch.zeros((len(shards[rank]), DETAIL_COLS), dtype=torch.float64, device=device)
     for k, idx in enumerate(shards[rank]):
         c = clips[idx]
-        pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right)
-        cc = Clip(c.camera, c.rays, c.gt_norm, c.action, idx)
+        pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right, mirror)
+        cc = Clip(c.camera, c.rays, root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, c.action, idx, c.frame)
         if on_gpu and pred.is_cuda:
-            local[k, 3:8], dlocal[k], _ = _clip_detail_hip(pred, cc, None, False)
+            local[k, 3:8], dlocal[k], _ = _clip_detail_hip(pred, cc, None, False, root_relative)
         else:
-            local[k] = clip_partials(pred, cc, aid[c.action])
-            dlocal[k] = clip_detail(pred, cc)
+            local[k] = clip_partials(pred, cc, aid[c.action], root_relative)
+            dlocal[k] = clip_detail(pred, cc, root_relative=root_relative)
     if world_size > 1:
         counts = [len(s) for s in shards]
         allrows = gather_partials(local, counts, group)

@@ -459,7 +459,7 @@ class Ray3DLifter(nn.Module):
         inp = _capi.make_input(mode, x.data_ptr(), window_stride,
                                param.data_ptr() if param is not None else None, param_stride,
                                cam.data_ptr() if cam is not None else None, cam_stride)
-        nbytes = _capi.input_workspace_bytes(hp, ht, inp, B) if mode == _capi.R3D_INPUT_UV_DIST else _capi.workspace_bytes(hp, ht, B)
+        nbytes = _capi.input_workspace_bytes(hp, ht, inp, B) if mode in _capi.PX_MODES else _capi.workspace_bytes(hp, ht, B)
         ws = (workspace or self._ws).get(nbytes, dev)
         with torch.cuda.device(dev):
             _capi.forward_pair(hp, ht, inp, B, out.data_ptr(),
@@ -597,7 +597,7 @@ class Ray3DLifter(nn.Module):
         self._prepared.clear()
 
     def forward_uv(self, uv: torch.Tensor, cam_rows: torch.Tensor, param: Optional[torch.Tensor] = None,
-                   window_stride: Optional[int] = None):
+                   window_stride: Optional[int] = None, encoding: Optional[str] = None):
         """Pixel keypoints in; the rays are computed inside the first layers' gathers (float64 then cast, as
         lib/camera/camera.py:423-471 + lib/train_val/trainer.py:298 do on the host) - no rays tensor exists.
         uv (B,RF,J,2) float32 - or a frame sequence (T,J,2) with `window_stride` (1: slide over an edge-padded clip);
@@ -609,11 +609,23 @@ class Ray3DLifter(nn.Module):
         RAW pixels of a distorted camera (undistort=True, the H36M / HumanEva default), undistorted on the GPU by a
         pre-pass kernel in float64 (cv2.undistortPoints' five iterations, lib/camera/camera.py:412-441) in front of the
         forward (R3D_INPUT_UV_DIST); rows with zero coefficients give exactly the 8-wide result;
-        param (B,E) or (E,) float32 [height, pitch]."""
+        param (B,E) or (E,) float32 [height, pitch].
+        `encoding`: for INPUT_DIM == 2 pairs (RAY_ENCODING False, the cfg_rie_* baselines) - required there, refused for
+        ray models - which input the same pre-pass builds from the RAW pixels, cam_rows (B,16) or (16,):
+        "intrinsic" = encode_uv_with_intrinsic (INTRINSIC_ENCODING True; the rows' coefficients undistort first,
+        R3D_INPUT_PX_INTRINSIC), "screen" = normalize_screen_coordinates (R3D_INPUT_PX_SCREEN; the rows must carry
+        res_w / res_h in slots 6 / 7: a Camera built with its resolution)."""
         rf = self.receptive_field()
         uv = uv.detach().to(torch.float32).contiguous()
-        if self.pos.in_features != 3:
-            raise RuntimeError("forward_uv needs INPUT_DIM == 3 models (the ray encoding has three components)")
+        if encoding is None:
+            if self.pos.in_features != 3:
+                raise RuntimeError("forward_uv needs INPUT_DIM == 3 models (the ray encoding has three components) - or, for "
+                                   "INPUT_DIM == 2 models, encoding='intrinsic' / 'screen'")
+        else:
+            if encoding not in ("intrinsic", "screen"):
+                raise RuntimeError("encoding must be 'intrinsic' or 'screen' (got %r)" % (encoding,))
+            if self.pos.in_features != 2:
+                raise RuntimeError("encoding=%r is the input of INPUT_DIM == 2 models; this pair takes rays" % (encoding,))
         if uv.dim() == 4:
             assert uv.shape[1] == rf and uv.shape[2] == self.pos.num_joints_in and uv.shape[3] == 2
             B, ws_ = uv.shape[0], rf
@@ -630,6 +642,14 @@ class Ray3DLifter(nn.Module):
         if width not in (8, 16) or cam.dim() == 2 and cam.shape[0] != B:
             raise RuntimeError("cam_rows must be (%d, 8), (8,), (%d, 16) or (16,), got %s" % (B, B, tuple(cam.shape)))
         mode = _capi.R3D_INPUT_UV if width == 8 else _capi.R3D_INPUT_UV_DIST
+        if encoding is not None:
+            if width != 16:
+                raise RuntimeError("cam_rows must be (%d, 16) or (16,) with encoding=%r, got %s" % (B, encoding, tuple(cam.shape)))
+            mode = _capi.R3D_INPUT_PX_INTRINSIC if encoding == "intrinsic" else _capi.R3D_INPUT_PX_SCREEN
+            # (checked where the caller's rows live - on the host for host rows - before anything is launched)
+            if encoding == "screen" and bool((cam_rows.detach()[..., 6:8] <= 0).any()):
+                raise RuntimeError("encoding='screen' needs res_w > 0 and res_h > 0 in slots 6 / 7 of every camera row "
+                                   "(Camera(..., res_w=, res_h=).cam_row(distortion=True))")
         p = param.detach().to(uv.device, torch.float32).contiguous() if self.pos.camera_embedding else None
         pstride = 0 if (p is None or p.dim() == 1) else self.pos.extrinsic_dim
         cstride = 0 if cam.dim() == 1 else width

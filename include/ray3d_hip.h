@@ -351,6 +351,69 @@ int r3d_clip_metrics_detail(const float *pred_dev, const float *gt_dev, int64_t 
                             const double *rn2w, const double *tn2w, double *out_dev, double *frame_dev, double *detail_dev,
                             void *stream);
 
+/* ---- per-clip validation losses: Trainer.test after the forwards ---- */
+
+/* lib/train_val/trainer.py:187-223 for one clip of n_frames frames, in the NORMALISED frame (no world transform): the
+ * terms of losses_3d_valid - the figure that selects best_epoch.bin and is stored as `best_performance` (:235) - and of
+ * the logged test_pos / test_trj / test_bone.  Device memory: pos_dev (n, J, 3) float32, the pos network's output;
+ * trj_dev (n, 3) float32 or NULL (configurations without a trajectory model); gt_dev (n, J, 3) float32, the ABSOLUTE
+ * ground truth in the frame of the predictions.  `parents` is a HOST array of J entries (parents[0] == -1, 0 <= parents[j]
+ * < j otherwise; it travels as a kernel argument, nothing is copied to the device): bone j-1 is joint parents[j] minus
+ * joint j, the column order of lib/skeleton/bone.py:51-68; NULL: no bone terms (they are 0).
+ *   out[R3D_VALID_LOSS]      = sum_f mean_j |P_abs - G|                           (:216, without trj :220)
+ *   out[R3D_VALID_POS]       = sum_f mean_j |pos - G_rel|                         (:200)
+ *   out[R3D_VALID_TRJ_W]     = sum_f w_f d_f,  w_f = |1 / gt_root_z|, d_f = |trj - gt_root|   (weighted_mpjpe,
+ *                              lib/loss/loss.py:21-27 with the weights of :119-120)
+ *   out[R3D_VALID_TRJ_WSUM]  = sum_f w_f       out[R3D_VALID_TRJ_DSUM] = sum_f d_f
+ *   out[R3D_VALID_BONE_LEN]  = sum_f mean_b | |bp| - |bg| |                       (bone.py:80-88,  :203-205)
+ *   out[R3D_VALID_BONE_DIR]  = sum_f mean_b | bp/|bp| - bg/|bg| |                 (bone.py:91-100, :207-209)
+ * then R3D_VALID_BONE_ROWS rows of R3D_VALID_MAX_BONES columns, out[R3D_VALID_COUNT + row * R3D_VALID_MAX_BONES + b], the
+ * sums over frames of bone b's |len_p - len_g|, len_p, len_p^2 and len_g (columns >= J-1 and, without `parents`, all of
+ * them are 0): per-bone error, mean lengths and the temporal deviation of a predicted bone's length.  Each sum is the
+ * clip's contribution to an epoch accumulator of :200-222 (mean times frame count), in metres.
+ * ROUNDING CONTRACT.  The reference takes its sums and differences in float32 before any norm; so does this call, with one
+ * float32 rounding each:
+ *   with trj_dev:            G_rel = fl32(gt_j - gt_0) with the root exactly 0 (:193-194), P_abs = fl32(pos + trj) (:215),
+ *                            G = gt;
+ *   R3D_VALID_POS_IS_SUM:    pos_dev holds what r3d_forward_pair writes (pos + trj): P_abs = pos_dev, and the
+ *                            root-relative prediction is recovered as fl32(pos_dev - trj) - which differs from the
+ *                            separately computed pos by at most one float32 rounding of the sum (2^-24 |pos + trj| per
+ *                            coordinate, and as much again for the rounding of the difference);
+ *   without trj_dev:         P_abs = pos, G = gt - or G_rel with R3D_VALID_GT_ROOT_RELATIVE (the models that are not fed
+ *                            rays, :195-197); POS equals LOSS and the three TRJ sums are 0;
+ *   bones:                   parent minus child, fl32, of `pos` and of G_rel as defined above (:203-204);
+ *   differences prediction - target (and trj - gt_root): fl32.
+ * Everything after these steps is float64: the values are promoted, norms, divisions (IEEE) and sums are float64.  A
+ * zero-length bone or a zero root depth gives Inf / NaN exactly as the reference does; so does the empty bone mean of a
+ * one-joint tree.
+ * THE test_trj QUIRK.  Trainer.test passes the weights with shape (B,1) against a norm of shape (B,1,1) (:217-218):
+ * broadcasting makes the product an outer product, so the figure it logs as test_trj is mean(w) * mean(d) of the clip, not
+ * mean(w * d).  TRJ_W is the elementwise definition of Trainer.train (:119-120); TRJ_WSUM * TRJ_DSUM / n_frames is the
+ * clip's contribution to the figure as logged.
+ * `out_dev`: R3D_VALID_OUT_DOUBLES doubles, the R3D_VALID_DOUBLES results first, the rest scratch for the workgroups'
+ * partial rows.  `frame_dev` (optional, may be NULL): (n_frames, R3D_VALID_COUNT) doubles, row f the frame's seven terms.
+ * The inputs are only read (the reference overwrites its own in place, :193-194, :215).  R3D_ERR_ARG: a null required
+ * pointer, n_frames < 1, num_joints outside 1..17, a bad parent table, unknown flags, POS_IS_SUM without trj_dev,
+ * GT_ROOT_RELATIVE together with trj_dev.  Deterministic (fixed summation order, no atomics); enqueued on `stream`, no
+ * synchronisation. */
+#define R3D_VALID_POS_IS_SUM 1        /* flags */
+#define R3D_VALID_GT_ROOT_RELATIVE 2
+#define R3D_VALID_LOSS 0
+#define R3D_VALID_POS 1
+#define R3D_VALID_TRJ_W 2
+#define R3D_VALID_TRJ_WSUM 3
+#define R3D_VALID_TRJ_DSUM 4
+#define R3D_VALID_BONE_LEN 5
+#define R3D_VALID_BONE_DIR 6
+#define R3D_VALID_COUNT 7
+#define R3D_VALID_MAX_BONES 16
+#define R3D_VALID_BONE_ROWS 4 /* per bone: sum |len_p - len_g|, sum len_p, sum len_p^2, sum len_g */
+#define R3D_VALID_DOUBLES (R3D_VALID_COUNT + R3D_VALID_BONE_ROWS * R3D_VALID_MAX_BONES)
+#define R3D_VALID_OUT_DOUBLES (R3D_VALID_DOUBLES * (1 + R3D_METRIC_MAX_BLOCKS))
+int r3d_clip_valid_losses(const float *pos_dev, const float *trj_dev, const float *gt_dev, int64_t n_frames,
+                          int32_t num_joints, const int32_t *parents, int32_t flags,
+                          double *out_dev, double *frame_dev, void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -390,6 +453,11 @@ int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, d
 /* ... and its two 2-float encodings (R3D_INPUT_PX_INTRINSIC: encoding 1, R3D_INPUT_PX_SCREEN: encoding 2): `out2` (n, 2) the
  * float64 values before the cast.  Returns 0 or R3D_ERR_ARG (null pointer, any other encoding). */
 int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, int32_t encoding, double *out2);
+
+/* The per-frame routines of r3d_clip_valid_losses run on the host (HOST pointers throughout, the same arguments and checks),
+ * the frames added up by a plain index-order sum: `out` R3D_VALID_DOUBLES doubles, `frame` (n, R3D_VALID_COUNT) or NULL. */
+int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t n_frames, int32_t num_joints,
+                                const int32_t *parents, int32_t flags, double *out, double *frame);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -28,18 +28,23 @@ R3D_OPT_STAGED, R3D_OPT_SPIN_TIMEOUT_MS, R3D_OPT_CU_LIMIT, R3D_OPT_LANES = 1, 2,
 EXPORTS = (
     "r3d_create", "r3d_destroy", "r3d_num_weights", "r3d_weight_key", "r3d_weight_shape",
     "r3d_set_weight", "r3d_finalize", "r3d_workspace_bytes", "r3d_forward", "r3d_forward_pair",
-    "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_last_error", "r3d_version",
+    "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_clip_valid_losses", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
-                "r3d_debug_undistort_host", "r3d_debug_encode_px_host")
+                "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
 DETAIL_THRESHOLDS, DETAIL_JOINT_ROWS, DETAIL_MAX_JOINTS = 31, 3, 17    # R3D_DETAIL_THRESHOLDS, _JOINT_ROWS, joint-row width
 DETAIL_DOUBLES = DETAIL_JOINT_ROWS * DETAIL_MAX_JOINTS + DETAIL_THRESHOLDS   # R3D_DETAIL_DOUBLES (82)
 DETAIL_OUT_DOUBLES = DETAIL_DOUBLES * (1 + 128)                         # R3D_DETAIL_OUT_DOUBLES
+R3D_VALID_POS_IS_SUM, R3D_VALID_GT_ROOT_RELATIVE = 1, 2                 # flags of r3d_clip_valid_losses
+VALID_NAMES = ("loss", "pos", "trj_w", "trj_wsum", "trj_dsum", "bone_len", "bone_dir")   # R3D_VALID_* order
+VALID_COUNT, VALID_MAX_BONES, VALID_BONE_ROWS = 7, 16, 4                # R3D_VALID_COUNT, _MAX_BONES, _BONE_ROWS
+VALID_DOUBLES = VALID_COUNT + VALID_BONE_ROWS * VALID_MAX_BONES         # R3D_VALID_DOUBLES (71)
+VALID_OUT_DOUBLES = VALID_DOUBLES * (1 + 128)                           # R3D_VALID_OUT_DOUBLES
 
 
 class Config(C.Structure):
@@ -125,11 +130,13 @@ def load():
     lib.r3d_profile_read.argtypes = [vp, C.POINTER(LaunchRecord), C.c_int]
     lib.r3d_clip_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
     lib.r3d_clip_metrics_detail.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp, vp]
+    lib.r3d_clip_valid_losses.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
         lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.r3d_debug_encode_px_host.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
+        lib.r3d_debug_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp]
     for name in EXPORTS + (HOOK_EXPORTS if _hooks else ()):
         fn = getattr(lib, name)
         if fn.restype is C.c_int or fn.restype is None:
@@ -292,6 +299,19 @@ def clip_metrics_detail(pred_ptr: int, gt_ptr: int, n_frames: int, num_joints: i
     t = (C.c_double * 3)(*[float(v) for v in tn2w])
     check(load().r3d_clip_metrics_detail(pred_ptr, gt_ptr, n_frames, num_joints, r, t, out_ptr, frame_ptr or None, detail_ptr,
                                          stream), "r3d_clip_metrics_detail")
+
+
+def _parent_table(parents):
+    return (C.c_int32 * len(parents))(*[int(v) for v in parents]) if parents is not None else None
+
+
+def clip_valid_losses(pos_ptr: int, trj_ptr: Optional[int], gt_ptr: int, n_frames: int, num_joints: int, parents,
+                      flags: int, out_ptr: int, frame_ptr: Optional[int], stream: int):
+    """r3d_clip_valid_losses: `parents` a host sequence of at least num_joints ints (or None: no bone terms), `out_ptr`
+    VALID_OUT_DOUBLES float64 of device memory (the first VALID_DOUBLES are the results), `frame_ptr` (n_frames, VALID_COUNT)
+    float64 or None; the rest device pointers."""
+    check(load().r3d_clip_valid_losses(pos_ptr, trj_ptr or None, gt_ptr, n_frames, num_joints, _parent_table(parents), flags,
+                                       out_ptr, frame_ptr or None, stream), "r3d_clip_valid_losses")
 
 
 def forward_pair(pos: Handle, trj: Handle, inp: Input, batch: int, out_ptr: int,

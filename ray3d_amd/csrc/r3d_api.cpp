@@ -5,6 +5,7 @@
 
 #include "r3d_internal.hpp"
 #include "r3d_undistort.hpp"
+#include "r3d_valid.hpp"
 
 namespace r3d {
 const char *last_error();
@@ -869,6 +870,29 @@ void lanes_destroy(Model *m) {
 
 using namespace r3d;
 
+// the argument rules of r3d_clip_valid_losses, shared with its host hook (`what`: the name in the message)
+static int valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t n, int32_t J,
+                            const int32_t *parents, int32_t flags, const double *out) {
+    if (!pos || !gt || !out) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (n < 1) { set_error("%s: n_frames must be >= 1 (got %lld)", what, (long long)n); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (flags & ~(R3D_VALID_POS_IS_SUM | R3D_VALID_GT_ROOT_RELATIVE)) { set_error("%s: unknown flags 0x%x", what, flags); return R3D_ERR_ARG; }
+    if ((flags & R3D_VALID_POS_IS_SUM) && !trj) { set_error("%s: R3D_VALID_POS_IS_SUM needs trj_dev", what); return R3D_ERR_ARG; }
+    if ((flags & R3D_VALID_GT_ROOT_RELATIVE) && trj) {
+        set_error("%s: R3D_VALID_GT_ROOT_RELATIVE is for calls without trj_dev (with it the ground truth must be absolute)", what);
+        return R3D_ERR_ARG;
+    }
+    if (parents) {
+        if (parents[0] != -1) { set_error("%s: bad parent table: parents[0] must be -1 (got %d)", what, parents[0]); return R3D_ERR_ARG; }
+        for (int j = 1; j < J; ++j)
+            if (parents[j] < 0 || parents[j] >= j) {
+                set_error("%s: bad parent table: parents[%d] must be in 0..%d (got %d)", what, j, j - 1, parents[j]);
+                return R3D_ERR_ARG;
+            }
+    }
+    return R3D_OK;
+}
+
 extern "C" {
 
 int r3d_create(const r3d_config *cfg, r3d_model **out) {
@@ -1261,7 +1285,57 @@ int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, i
     return R3D_OK;
 }
 
+// Test hook: the per-frame routines of r3d_clip_valid_losses (r3d_valid.hpp) on the host, frames added in index order.
+int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t n_frames, int32_t num_joints,
+                                const int32_t *parents, int32_t flags, double *out, double *frame) {
+    const int rc = valid_check_args("r3d_debug_valid_losses_host", pos, trj, gt, n_frames, num_joints, parents, flags, out);
+    if (rc != R3D_OK) return rc;
+    ValidIn a;
+    a.pos = pos;
+    a.trj = trj;
+    a.gt = gt;
+    a.J = num_joints;
+    a.flags = flags;
+    a.bones = parents != nullptr;
+    a.tree = parents ? valid_pack_tree(parents, num_joints) : ValidTree{{0ull, 0ull}};
+    const int nb = a.bones ? num_joints - 1 : 0;
+    for (int c = 0; c < R3D_VALID_DOUBLES; ++c) out[c] = 0.0;
+    for (int64_t f = 0; f < n_frames; ++f) {
+        double term[R3D_VALID_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+        valid_frame_terms(a, f, term);
+        double bl = 0, bd = 0;
+        for (int b = 0; b < nb; ++b) {
+            double v[R3D_VALID_BONE_ROWS], dir;
+            valid_frame_bone(a, f, b, v, dir);
+            bl += v[0];
+            bd += dir;
+            for (int r = 0; r < R3D_VALID_BONE_ROWS; ++r) out[R3D_VALID_COUNT + r * R3D_VALID_MAX_BONES + b] += v[r];
+        }
+        if (a.bones) {
+            term[R3D_VALID_BONE_LEN] = bl / (double)nb;
+            term[R3D_VALID_BONE_DIR] = bd / (double)nb;
+        }
+        for (int k = 0; k < R3D_VALID_COUNT; ++k) {
+            out[k] += term[k];
+            if (frame) frame[f * R3D_VALID_COUNT + k] = term[k];
+        }
+    }
+    return R3D_OK;
+}
+
 #endif  // R3D_TEST_HOOKS
+
+int r3d_clip_valid_losses(const float *pos_dev, const float *trj_dev, const float *gt_dev, int64_t n_frames,
+                          int32_t num_joints, const int32_t *parents, int32_t flags,
+                          double *out_dev, double *frame_dev, void *stream) {
+    const int rc = valid_check_args("r3d_clip_valid_losses", pos_dev, trj_dev, gt_dev, n_frames, num_joints, parents, flags, out_dev);
+    if (rc != R3D_OK) return rc;
+    if (r3d::launch_clip_valid(pos_dev, trj_dev, gt_dev, n_frames, num_joints, parents, flags, out_dev, frame_dev, (hipStream_t)stream)) {
+        r3d::set_error("r3d_clip_valid_losses: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
 
 int r3d_clip_metrics(const float *pred_dev, const float *gt_dev, int64_t n_frames, int32_t num_joints,
                      const double *rn2w, const double *tn2w, double *out_dev, void *stream) {

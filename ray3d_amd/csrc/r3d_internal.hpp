@@ -539,5 +539,8 @@ constexpr int ENC_INVALID = (int)0x80000000u;
 // frame / detail: the outputs of r3d_clip_metrics_detail, both null for r3d_clip_metrics
 int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, const double *Rn2w, const double *Tn2w,
                         double *out, double *frame, double *detail, hipStream_t stream);
+// r3d_clip_valid_losses (a mode of the clip-metrics kernels: r3d_metrics.hip, r3d_valid_dev.hpp); arguments already checked, parents a host array or null
+int launch_clip_valid(const float *pos, const float *trj, const float *gt, long long n, int J, const int32_t *parents,
+                      int flags, double *out, double *frame, hipStream_t stream);
 
 }  // namespace r3d

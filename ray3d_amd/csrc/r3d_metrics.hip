@@ -15,8 +15,13 @@
 // shuffle tree, its first lane keeps the running sums in LDS, the workgroup adds its four wavefronts in index order and the
 // second launch the workgroups.  The counts are integers (LDS integer atomics, exact in any order).  The code of the five
 // sums is the same in both modes: the detail is computed again from the poses and the fit, behind a uniform branch.
+//
+// r3d_clip_valid_losses (Trainer.test's validation losses; r3d_valid_dev.hpp, r3d_valid.hpp) runs on the same two kernels with
+// their ValidArgs argument set: a uniform branch at the top of each hands the launch to that mode's own workgroup body, which
+// borrows the LDS of the five sums' tree; nothing of the error sums' code runs then, and nothing of that mode otherwise.
 #include <hip/hip_runtime.h>
 #include "r3d_internal.hpp"
+#include "r3d_valid_dev.hpp"
 
 namespace r3d {
 
@@ -38,6 +43,8 @@ struct MetricArgs {
     double *detail;              // r3d_clip_metrics_detail only (null otherwise): R3D_DETAIL_DOUBLES results, then as many per workgroup
     double *frame;               // ... and, optional, the (N, R3D_METRIC_COUNT) per-frame terms
 };
+static_assert(METRIC_THREADS == VALID_THREADS && R3D_METRIC_COUNT * METRIC_THREADS >= VALID_WAVES * R3D_VALID_DOUBLES,
+              "the validation-loss mode runs in this kernel's workgroups and in the LDS of its five-sum tree");
 
 // the similarity fit of one frame: aligned = a * (p Rm) + t
 struct Fit {
@@ -213,10 +220,14 @@ __device__ __noinline__ void frame_detail(const double (*p)[3], const double (*g
     }
 }
 
-__global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArgs a) {
+__global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArgs a, ValidArgs valid) {
     __shared__ double red[R3D_METRIC_COUNT][METRIC_THREADS];
     __shared__ double cols[METRIC_WAVES][JOINT_COLS];
     __shared__ unsigned int hist[R3D_DETAIL_THRESHOLDS + 1];
+    if (valid.out) {             // uniform: the whole launch is a validation-loss one (r3d_clip_valid_losses), `a` is unused
+        valid_block(valid, &red[0][0]);
+        return;
+    }
     double acc[R3D_METRIC_COUNT] = {0, 0, 0, 0, 0};
     const int J = a.J;
     const bool detail = a.detail != nullptr;
@@ -319,7 +330,11 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
         for (int k = 0; k < R3D_METRIC_COUNT; ++k) a.out[R3D_METRIC_COUNT * (1 + blockIdx.x) + k] = red[k][0];
 }
 
-__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail) {
+__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail, double *valid) {
+    if (valid) {                 // the second launch of r3d_clip_valid_losses
+        valid_sum_rows(valid, blocks);
+        return;
+    }
     const int k = threadIdx.x;
     if (k < R3D_METRIC_COUNT) {
         double s = 0;
@@ -353,8 +368,29 @@ int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, 
     for (int i = 0; i < 3; ++i) a.T[i] = Tn2w[i];
     long long blocks = (n + METRIC_THREADS - 1) / METRIC_THREADS;
     blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
-    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n, detail);
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, ValidArgs{});
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n, detail, (double *)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_clip_valid(const float *pos, const float *trj, const float *gt, long long n, int J, const int32_t *parents,
+                      int flags, double *out, double *frame, hipStream_t stream) {
+    MetricArgs a = {};
+    ValidArgs v = {};
+    v.in.pos = pos;
+    v.in.trj = trj;
+    v.in.gt = gt;
+    v.in.J = J;
+    v.in.flags = flags;
+    v.in.bones = parents != nullptr;
+    v.in.tree = parents ? valid_pack_tree(parents, J) : ValidTree{{0ull, 0ull}};
+    v.out = out;
+    v.frame = frame;
+    v.n = n;
+    long long blocks = (n + VALID_THREADS - 1) / VALID_THREADS;
+    blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, v);
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, (double *)nullptr, (int)blocks, n, (double *)nullptr, out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

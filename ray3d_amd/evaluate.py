@@ -29,6 +29,7 @@ import torch
 
 from . import metrics as M
 from .camera import Camera
+from .skeleton import H36M_17_PARENTS, validate_parents
 
 PARTIAL_COLS = 8   # clip_id, action_id, n_frames, sum_mpjpe, sum_pmpjpe, sum_nmpjpe, sum_vel, sum_root
 
@@ -432,6 +433,147 @@ def format_detail_report(table: Dict, joint_names: Optional[Sequence[str]] = Non
     lines = ["%s: MPJPE %.1f mm, P-MPJPE %.1f mm, root-relative %.1f mm"
              % (names[j], table["mpjpe"][j], table["p_mpjpe"][j], table["root_rel"][j]) for j in range(nj)]
     lines.append("PCK@150mm: %.1f %%, AUC: %.1f %%" % (table["pck150"], table["auc"]))
+    return lines
+
+
+# ------------------------------------------------------------------------------------ validation losses (Trainer.test)
+
+VALID_COLS = 3 + M.VALID_DOUBLES   # clip_id, action_id, n_frames, then the R3D_VALID_DOUBLES sums of r3d_clip_valid_losses
+
+
+def clip_valid(pos_or_sum: torch.Tensor, trj: Optional[torch.Tensor], clip: Clip, parents=H36M_17_PARENTS,
+               pos_is_sum: bool = False, gt_dev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               gt_root_relative: bool = False, action_id: int = 0) -> torch.Tensor:
+    """One VALID_COLS row (float64, on the predictions' device) of the clip's validation-loss sums - what one batch adds to
+    the accumulators of Trainer.test (lib/train_val/trainer.py:187-223), in the normalised frame, metres; layout and rounding
+    contract: r3d_clip_valid_losses in include/ray3d_hip.h.
+    `pos_or_sum` (N,1,J,3) or (N,J,3): the pos network's output - or, with `pos_is_sum`, pos + trj as Ray3DLifter writes it;
+    `trj` (N,1,1,3) or (N,3), None for configurations without a trajectory model (then `gt_root_relative` makes the ground
+    truth root-relative first: the models that are not fed rays, :195-197).  `clip.gt_norm` (or `gt_dev`, already on the
+    device) is the ABSOLUTE ground truth.  `parents`: the joint tree of the bone terms (:mod:`ray3d_amd.skeleton`), None for
+    none.  `out`: a row of ``partial_rows(..., cols=VALID_COLS)`` whose header is already in place - only the sums are written.
+    GPU tensors go through the HIP kernel on the current stream (no copy to the host, no synchronisation); CPU tensors
+    (host-logic tests, a stand-in lifter) through the torch restatement in :mod:`ray3d_amd.metrics`.  Nothing is modified."""
+    dev = pos_or_sum.device
+    n = pos_or_sum.shape[0]
+    pos = pos_or_sum.detach().reshape(n, -1, 3).contiguous().float()
+    J = pos.shape[1]
+    t = trj.detach().to(dev).reshape(n, 3).contiguous().float() if trj is not None else None
+    tree = validate_parents(parents, J) if parents is not None else None
+    if pos_is_sum and t is None:
+        raise ValueError("pos_is_sum needs the trajectory")
+    if gt_root_relative and t is not None:
+        raise ValueError("gt_root_relative is for models without a trajectory: with one the ground truth must be absolute")
+    if gt_dev is not None:
+        gt = gt_dev.to(dev, torch.float32).reshape(n, -1, 3).contiguous()
+    else:
+        gt = torch.from_numpy(np.ascontiguousarray(clip.gt_norm, dtype=np.float32)).to(dev, non_blocking=True).reshape(n, -1, 3)
+    assert gt.shape == pos.shape, "ground truth %s vs prediction %s" % (tuple(gt.shape), tuple(pos.shape))
+    if pos.is_cuda:
+        from . import _capi
+        sums = torch.empty(_capi.VALID_OUT_DOUBLES, dtype=torch.float64, device=dev)
+        flags = (_capi.R3D_VALID_POS_IS_SUM if pos_is_sum else 0) | (_capi.R3D_VALID_GT_ROOT_RELATIVE if gt_root_relative else 0)
+        with torch.cuda.device(dev):
+            _capi.clip_valid_losses(pos.data_ptr(), t.data_ptr() if t is not None else None, gt.data_ptr(), n, J, tree, flags,
+                                    sums.data_ptr(), None, torch.cuda.current_stream(dev).cuda_stream)
+        sums = sums[:M.VALID_DOUBLES]
+    else:
+        sums, _ = M.clip_valid(pos, t, gt, tree, pos_is_sum, gt_root_relative)
+    if out is not None:
+        assert out.shape == (VALID_COLS,) and out.dtype == torch.float64 and out.device == dev
+        out[3:] = sums
+        return out
+    row = torch.empty(VALID_COLS, dtype=torch.float64, device=dev)
+    for c, v in enumerate((clip.clip_id, action_id, n)):
+        row[c].fill_(float(v))
+    row[3:] = sums
+    return row
+
+
+def validate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, parents=H36M_17_PARENTS, group=None,
+                   pos_is_sum: bool = True, gt_root_relative: bool = False, causal: bool = False,
+                   bone_pairs: Optional[Sequence[tuple]] = None):
+    """Trainer.test's pass over `clips` (trainer.py:174-225; no flip, no world transform): every clip is lifted and
+    :func:`clip_valid` fills its row.  `lift_clip(padded (N+RF-1,J,F), param_row)` returns (poses, trj) - with `pos_is_sum`
+    the poses are pos + trj, ``Ray3DLifter.forward_clip(..., return_trj=True)`` - or, for a configuration without a
+    trajectory model, the poses alone.  With torch.distributed initialised (`group`: the process group, None the default one)
+    whole clips are sharded over the ranks as in :func:`evaluate_clips` and the rows travel in ONE all_gather.
+    Every rank returns (:func:`reduce_valid` of all rows, the rows in clip-id order)."""
+    import torch.distributed as dist
+    distributed = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if distributed else (0, 1)
+    actions = sorted(set(c.action for c in clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    shards = shard_clips([c.rays.shape[0] for c in clips], world)
+    local = torch.zeros((len(shards[rank]), VALID_COLS), dtype=torch.float64)
+    if shards[rank]:
+        local[:, :3] = torch.tensor([[float(idx), float(aid[clips[idx].action]), float(clips[idx].rays.shape[0])]
+                                     for idx in shards[rank]], dtype=torch.float64)
+    local = local.to(device)
+    pad = (rf - 1) // 2
+    for k, idx in enumerate(shards[rank]):
+        c = clips[idx]
+        padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(device)
+        res = lift_clip(padded, torch.from_numpy(c.camera.param()).to(device))
+        poses, trj = res if isinstance(res, tuple) else (res, None)
+        clip_valid(poses, trj, c, parents, pos_is_sum and trj is not None, out=local[k], gt_root_relative=gt_root_relative)
+    allrows = gather_partials(local, [len(s) for s in shards], group, cols=VALID_COLS) if world > 1 else local
+    allrows = allrows[torch.argsort(allrows[:, 0], stable=True)]
+    num_joints = int(clips[0].gt_norm.shape[1]) if len(clips) else 1
+    return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
+
+
+def reduce_valid(rows: torch.Tensor, num_joints: int = 17, bone_pairs: Optional[Sequence[tuple]] = None) -> Dict:
+    """The figures of Trainer.test from the per-clip rows (:func:`clip_valid`), in the reference's units (its logs multiply
+    every figure by 1000), frame-weighted over all clips as trainer.py:222-225 does:
+
+    * ``valid_mm``: losses_3d_valid * 1000 - what a checkpoint stores as ``best_performance``; ``pos_mm``: test_pos;
+    * ``trj_mm``: the depth-weighted root error by the elementwise definition of Trainer.train (:119-120);
+      ``trj_mm_as_logged``: the figure Trainer.test logs as test_trj, mean(w) * mean(d) per clip (:217-218 broadcast the
+      weights to an outer product);
+    * ``bone_mm``: test_bone, length plus direction term; ``bone_len_mm`` and ``bone_dir`` (x 1000) its two parts;
+    * ``bones``: one dict per bone (bone b = joint b+1 and its parent) from the same per-bone sums: ``len_err_mm`` mean
+      |predicted - true length|, ``len_pred_mm`` / ``len_gt_mm`` the mean lengths, ``len_pred_std_mm`` the deviation of the
+      predicted length over all frames, sqrt(E[l^2] - E[l]^2);
+    * ``symmetry``: for every pair (a, b) of `bone_pairs` (mirror-image bones, e.g. skeleton.H36M_17_BONE_PAIRS) the
+      differences of the two mean lengths, ``(a, b, pred_diff_mm, gt_diff_mm)``.
+    Clips are added up in clip-id order: the result does not depend on how they were sharded."""
+    rows = rows.detach().to("cpu", torch.float64)
+    rows = rows[torch.argsort(rows[:, 0], stable=True)]
+    n = rows[:, 2].sum()
+    s = rows[:, 3:].sum(dim=0)
+    C, W = M.VALID_COUNT, M.VALID_MAX_BONES
+    logged = (rows[:, 3 + 3] * rows[:, 3 + 4] / rows[:, 2]).sum()
+    out = {"frames": int(n), "valid_mm": float(s[0] / n * 1000.0), "pos_mm": float(s[1] / n * 1000.0),
+           "trj_mm": float(s[2] / n * 1000.0), "trj_mm_as_logged": float(logged / n * 1000.0),
+           "bone_len_mm": float(s[5] / n * 1000.0), "bone_dir": float(s[6] / n * 1000.0),
+           "bone_mm": float((s[5] + s[6]) / n * 1000.0)}
+    per = s[C:].reshape(M.VALID_BONE_ROWS, W) / n
+    bones = []
+    for b in range(max(num_joints - 1, 0)):
+        var = float(per[2, b] - per[1, b] * per[1, b])
+        bones.append({"len_err_mm": float(per[0, b] * 1000.0), "len_pred_mm": float(per[1, b] * 1000.0),
+                      "len_gt_mm": float(per[3, b] * 1000.0), "len_pred_std_mm": float(np.sqrt(max(var, 0.0)) * 1000.0)})
+    out["bones"] = bones
+    out["symmetry"] = [(int(a), int(b), bones[a]["len_pred_mm"] - bones[b]["len_pred_mm"], bones[a]["len_gt_mm"] - bones[b]["len_gt_mm"])
+                       for a, b in (bone_pairs or ())]
+    return out
+
+
+def format_valid_report(table: Dict, bone_names: Optional[Sequence[str]] = None) -> List[str]:
+    """Plain text for the table of :func:`reduce_valid`: the four figures Trainer.test logs (trainer.py:275-278), the
+    elementwise trajectory figure, then one line per bone and per mirror-image pair."""
+    nb = len(table["bones"])
+    names = list(bone_names) if bone_names is not None else ["bone %2d" % b for b in range(nb)]
+    assert len(names) == nb
+    lines = ["test      (losses_3d_valid): %.3f mm over %d frames" % (table["valid_mm"], table["frames"]),
+             "test_pos  (root-relative):   %.3f mm" % table["pos_mm"],
+             "test_trj  (as logged):       %.3f   [elementwise, as in training: %.3f]" % (table["trj_mm_as_logged"], table["trj_mm"]),
+             "test_bone (length + direction): %.3f   [length %.3f mm]" % (table["bone_mm"], table["bone_len_mm"])]
+    lines += ["%s: length error %.1f mm, length %.1f mm (true %.1f mm), deviation over time %.1f mm"
+              % (names[b], t["len_err_mm"], t["len_pred_mm"], t["len_gt_mm"], t["len_pred_std_mm"]) for b, t in enumerate(table["bones"])]
+    lines += ["%s vs %s: predicted lengths differ by %.1f mm (true: %.1f mm)" % (names[a], names[b], dp, dg)
+              for a, b, dp, dg in table["symmetry"]]
     return lines
 
 

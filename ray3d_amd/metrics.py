@@ -4,6 +4,8 @@ Counterparts of lib/loss/loss.py: mpjpe (:12-18), n_mpjpe (:72-82), p_mpjpe (:30
 the reference, batched torch.linalg.svd here so it can stay on the GPU), mean_velocity_error
 (:95-104).  All take (..., J, 3) tensors and return a 0-d tensor.  clip_detail restates what r3d_clip_metrics_detail
 keeps of them: per-frame terms, per-joint sums and PCK counts.
+clip_valid restates r3d_clip_valid_losses: the validation losses of Trainer.test (mpjpe, weighted_mpjpe :21-27, and the
+bone terms of lib/skeleton/bone.py) in the reference's float32 / float64 rounding.
 
 HOST-SIDE ONLY: the product path computes these on the device in float64 (r3d_clip_metrics, csrc/r3d_metrics.hip), which
 is what `evaluate.clip_partials` / `evaluate.clip_detail` call for every CUDA tensor.  This module serves CPU tensors - the host-logic tests that
@@ -104,3 +106,59 @@ def clip_detail(pred: torch.Tensor, target: torch.Tensor):
     thr = torch.tensor([0.005 * k for k in range(DETAIL_THRESHOLDS)], dtype=torch.float64, device=pred.device)
     detail[DETAIL_JOINT_ROWS * DETAIL_MAX_JOINTS:] = (rel[:, 1:, None] < thr).sum(dim=(0, 1)).to(torch.float64)
     return detail, frames
+
+
+# ---- validation losses (the host restatement of r3d_clip_valid_losses: Trainer.test, lib/train_val/trainer.py:187-223)
+
+VALID_COUNT, VALID_MAX_BONES, VALID_BONE_ROWS = 7, 16, 4
+VALID_DOUBLES = VALID_COUNT + VALID_BONE_ROWS * VALID_MAX_BONES
+
+
+def clip_valid(pos: torch.Tensor, trj, gt: torch.Tensor, parents=None, pos_is_sum: bool = False,
+               gt_root_relative: bool = False):
+    """pos (N, J, 3), trj (N, 3) or None, gt (N, J, 3), float32 -> (row (VALID_DOUBLES,), frames (N, VALID_COUNT)), float64,
+    by the rounding contract of include/ray3d_hip.h: the reference's sums and differences in float32 (one rounding each),
+    everything from the norms on in float64.  Row layout: loss, pos, trj_w, trj_wsum, trj_dsum, bone_len, bone_dir, then
+    four rows of 16 per-bone sums (|len_p - len_g|, len_p, len_p^2, len_g).  The inputs are not modified."""
+    assert pos.shape == gt.shape and pos.dim() == 3 and pos.shape[-1] == 3
+    assert not (pos_is_sum and trj is None) and not (gt_root_relative and trj is not None)
+    n, J = pos.shape[0], pos.shape[1]
+    pos, gt = pos.to(torch.float32), gt.to(torch.float32)
+    f64 = torch.float64
+
+    def norm(v):                                  # float32 difference in, float64 norm out
+        return torch.sqrt((v.to(f64) ** 2).sum(dim=-1))
+
+    def rel(g):                                   # trainer.py:193-194
+        out = g - g[:, :1]
+        out[:, 0] = 0
+        return out
+
+    frames = torch.zeros((n, VALID_COUNT), dtype=f64, device=pos.device)
+    if trj is not None:
+        t = trj.to(torch.float32).reshape(n, 1, 3)
+        p_abs = pos if pos_is_sum else pos + t
+        p_rel = pos - t if pos_is_sum else pos
+        g_rel = rel(gt)
+        frames[:, 0] = norm(p_abs - gt).mean(dim=1)
+        frames[:, 1] = norm(p_rel - g_rel).mean(dim=1)
+        w = torch.abs(1.0 / gt[:, 0, 2].to(f64))
+        d = norm(t[:, 0] - gt[:, 0])
+        frames[:, 2], frames[:, 3], frames[:, 4] = w * d, w, d
+    else:
+        p_rel = pos
+        g_rel = rel(gt) if gt_root_relative else gt
+        frames[:, 0] = norm(pos - g_rel).mean(dim=1)
+        frames[:, 1] = frames[:, 0]
+    row = torch.zeros(VALID_DOUBLES, dtype=f64, device=pos.device)
+    if parents is not None:
+        par = [int(v) for v in parents[1:J]]
+        child = list(range(1, J))
+        bp, bg = p_rel[:, par] - p_rel[:, child], g_rel[:, par] - g_rel[:, child]       # float32, parent minus child
+        lp, lg = norm(bp), norm(bg)
+        frames[:, 5] = torch.abs(lp - lg).mean(dim=1)
+        frames[:, 6] = torch.sqrt(((bp.to(f64) / lp[..., None] - bg.to(f64) / lg[..., None]) ** 2).sum(dim=-1)).mean(dim=1)
+        for r, v in enumerate((torch.abs(lp - lg), lp, lp * lp, lg)):
+            row[VALID_COUNT + r * VALID_MAX_BONES: VALID_COUNT + r * VALID_MAX_BONES + J - 1] = v.sum(dim=0)
+    row[:VALID_COUNT] = frames.sum(dim=0)
+    return row, frames

@@ -546,10 +546,11 @@ class Ray3DLifter(nn.Module):
                 sizes.append(up)
         return sizes
 
-    def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None):
+    def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False):
         """clip (N + RF - 1, J, F): an edge-padded sequence; window i = frames [i, i+RF) is gathered
         in the kernels instead of materialising lib/train_val/trainer.py:47-58's copy.
-        param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3).
+        param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3) - with `return_trj` the pair
+        ((N,1,J,3) poses, (N,1,1,3) trajectory: the trj network's output, which the poses already contain).
 
         The library keeps one tile schedule per batch size, and every clip has its own length: the windows are
         lifted in the batch sizes of :meth:`clip_batch_sizes` (the surplus windows slide over repeated last frames
@@ -565,15 +566,21 @@ class Ray3DLifter(nn.Module):
         sizes = self.clip_batch_sizes(n)
         total = sum(sizes)
         if total == n and len(sizes) == 1:
-            return self._run(_capi.R3D_INPUT_RAYS, clip, 1, n, p, 0)
+            return self._run(_capi.R3D_INPUT_RAYS, clip, 1, n, p, 0, return_trj=return_trj)
         if total > n:
             clip = torch.cat([clip, clip[-1:].expand(total - n, -1, -1)], dim=0)
         out = torch.empty((total, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=clip.device)
+        trjs = []
         start = 0
         for b in sizes:
-            self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, out=out[start:start + b])
+            res = self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, return_trj=return_trj, out=out[start:start + b])
+            if return_trj:
+                trjs.append(res[1])
             start += b
-        return out[:n]
+        if not return_trj:
+            return out[:n]
+        self.join_lanes()      # (the pieces were written on the lanes' streams: the concatenation below runs on the caller's)
+        return out[:n], torch.cat(trjs, dim=0)[:n]
 
     def prepare(self, batch_sizes, device=None):
         """Build and upload the tile schedules of these batch sizes now (r3d_prepare) instead of inside the first

@@ -1,0 +1,309 @@
+// The r3d_debug_* exports of libray3d_hip_hooks.so: checkers that run on the host and never touch a device.
+#ifdef R3D_TEST_HOOKS      // (libray3d_hip_hooks.so only: the product library gets an empty translation unit)
+#include <algorithm>
+
+#include "r3d_internal.hpp"
+#include "r3d_undistort.hpp"
+#include "r3d_valid.hpp"
+
+using namespace r3d;
+
+extern "C" {
+
+// Test hook: build the static schedule of one launch on the host and verify
+// that its tiles cover every (32-row unit, 32-column granule) of every problem exactly once within the
+// kernel's tile-shape limits.  Returns 0 or a negative code naming the first violated rule.
+int r3d_debug_schedule_check(int nprob, const int *M, const int *N, const int *nk, const int *max_ks, const int *max_units,
+                             int nwg, int enc, int *out_grid, int *out_tiles, double *out_imbalance) {
+    std::vector<SchedProb> probs;
+    for (int i = 0; i < nprob; ++i) {
+        probs.push_back({M[i], N[i], nk[i], max_ks[i], max_units[i]});
+        // (as sched_prob_of marks the plan's wide plain layers: their single-unit tiles may be 4 .. 7 column blocks wide)
+        probs.back().nb_ok = !enc && N[i] % 32 == 0 && N[i] >= 512 && nk[i] >= 8 && max_units[i] == 0 && !hook_on("R3D_NO_NB");
+    }
+    std::vector<int4> tiles;
+    std::vector<int> wgoff;
+    StageSchedule ss{};
+    schedule_stage(probs, nwg, GEMM_SCHED_MAX_UNITS, tiles, wgoff, ss, enc != 0);
+    if (out_grid) *out_grid = ss.nwg;
+    if (out_tiles) *out_tiles = ss.ntiles;
+    if (out_imbalance) *out_imbalance = ss.imbalance;
+    if (ss.nwg < 1 || ss.nwg > nwg) return -1;
+    if ((int)wgoff.size() != ss.nwg + 1 || wgoff.front() != 0 || wgoff.back() != ss.ntiles || (int)tiles.size() != ss.ntiles) return -2;
+    for (size_t i = 1; i < wgoff.size(); ++i)
+        if (wgoff[i] <= wgoff[i - 1] && ss.ntiles > 0) return -3;          // empty or unordered chunk
+    std::vector<std::vector<int>> cover(nprob);
+    for (int i = 0; i < nprob; ++i) cover[i].assign((size_t)((M[i] + 31) / 32) * ((N[i] + COL_GRANULE - 1) / COL_GRANULE), 0);
+    for (const int4 &t : tiles) {
+        const int pi = t.x & 0xff, mi = t.x >> 8, ks = t.w;
+        if (pi >= nprob || mi < 1 || (ks != 1 && ks != 2 && ks != 4 && ks != 8 && ks != 16 && !(ks >= NB_CODE + 4 && ks <= NB_CODE + 7))) return -4;
+        if (ks < 8 && ks > max_ks[pi]) return -5;
+        if ((ks == 1 && mi > (max_units[pi] > 0 ? std::min(max_units[pi], GEMM_SCHED_MAX_UNITS) : GEMM_SCHED_MAX_UNITS)) || (ks == 2 && mi > 2) || (ks >= 4 && mi != 1)) return -6;
+        if (t.y % 32 || t.y < 0 || t.y >= M[pi] || t.z % (tile_is_nb(ks) ? 32 : tile_width(ks)) || t.z < 0 || t.z >= N[pi]) return -7;
+        if (tile_is_nb(ks) && t.z + tile_width(ks) > N[pi]) return -7;        // (narrow tiles cover whole blocks of existing columns)
+        if (ks > 1 && ks < 8 && (nk[pi] + ks - 1) / ks < 2) return -8;
+        const int gcols = (N[pi] + COL_GRANULE - 1) / COL_GRANULE;
+        for (int u = t.y / 32; u < t.y / 32 + mi; ++u) {
+            if (u * 32 >= M[pi]) return -9;
+            for (int g = t.z / COL_GRANULE; g < (t.z + tile_width(ks)) / COL_GRANULE && g < gcols; ++g) ++cover[pi][(size_t)u * gcols + g];
+        }
+    }
+    for (int i = 0; i < nprob; ++i)
+        for (int c : cover[i])
+            if (c != 1) return -10;
+    return 0;
+}
+
+// Test hook: the whole forward's tile lists for `batch` windows on `nwg` CUs, built on the host (no device needed):
+// every 32-row x 32-column cell of every problem must be computed exactly once over all launches, a problem's
+// tiles must sit in launches that list it, and a consumer's launch must come after all of its producers' tiles.
+// Returns 0, or a negative code; *spilled = rows of the first level that run one launch late.
+int r3d_debug_plan_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int *launches, int *spilled) {
+    const ModelPair mp = model_pair(pos, trj);
+    Model *a = mp.a, *b = mp.b;
+    if (!a) return -1;
+    Plan *pl = plan_get(a, b, plan_kind(batch));
+    if (!pl) return -2;
+    int spill_row0 = -1;
+    std::vector<int4> tiles;
+    std::vector<int> wgoff;
+    std::vector<StageSchedule> stages;
+    const std::vector<std::vector<int>> &levels = *schedule_build_host(pl, batch, nwg, spill_row0, tiles, wgoff, stages);
+    if (launches) *launches = (int)stages.size();
+    if (spilled) *spilled = 0;
+    const int np = (int)pl->probs.size();
+    std::vector<std::vector<int>> cover(np);
+    std::vector<int> last_launch(np, -1), first_launch(np, 1 << 30);
+    for (int i = 0; i < np; ++i) {
+        const ProbSpec &q = pl->probs[i];
+        const int M = (int)(batch * q.rows_per_window), N = pl->m[q.model]->layers[q.layer].N;
+        cover[i].assign((size_t)((M + 31) / 32) * ((N + COL_GRANULE - 1) / COL_GRANULE), 0);
+    }
+    for (size_t si = 0; si < stages.size(); ++si) {
+        const StageSchedule &ss = stages[si];
+        const auto &st = levels[si];
+        if (ss.nwg < 1 || ss.nwg > 2 * nwg) return -3;
+        {   // a launch runs ONE kernel: its problems are all r3d_gemm_enc_f32's or none is
+            int n_enc = 0;
+            for (int e : st) n_enc += pl->probs[e & ~STAGE_SPILL_IN].enc_kernel ? 1 : 0;
+            if (n_enc != 0 && n_enc != (int)st.size()) return -11;
+            if ((n_enc != 0) != (ss.kind == STAGE_ENC)) return -12;
+        }
+        for (int t = 0; t < ss.ntiles; ++t) {
+            const int4 &tl = tiles[ss.tiles_off + t];
+            const int slot = tl.x & 0xff, mi = tl.x >> 8, ks = tl.w;
+            if (slot >= (int)st.size() || mi < 1) return -4;
+            const int id = st[slot] & ~STAGE_SPILL_IN;
+            const ProbSpec &q = pl->probs[id];
+            const int M = (int)(batch * q.rows_per_window), N = pl->m[q.model]->layers[q.layer].N;
+            if (tl.y % 32 || tl.y < 0 || tl.y >= M || tl.z < 0 || tl.z >= N) return -5;
+            if (id == pl->spill_prob) {
+                const bool late = (st[slot] & STAGE_SPILL_IN) != 0;
+                if (spill_row0 < 0 ? late : (late != (tl.y >= spill_row0))) return -6;
+                if (late && spilled) *spilled += std::min(mi * 32, M - tl.y);
+            }
+            const int gcols = (N + COL_GRANULE - 1) / COL_GRANULE;
+            for (int u = tl.y / 32; u < tl.y / 32 + mi; ++u) {
+                if (u * 32 >= M) return -7;
+                for (int g = tl.z / COL_GRANULE; g < (tl.z + tile_width(ks)) / COL_GRANULE && g < gcols; ++g) ++cover[id][(size_t)u * gcols + g];
+            }
+            last_launch[id] = std::max(last_launch[id], (int)si);
+            first_launch[id] = std::min(first_launch[id], (int)si);
+        }
+    }
+    for (int i = 0; i < np; ++i) {
+        for (int c : cover[i])
+            if (c != 1) return -8;
+        for (int d : pl->probs[i].deps)
+            if (last_launch[d] >= first_launch[i]) return -9;
+    }
+    return 0;
+}
+
+// Test hook: the single-launch form of the forward for `batch` windows on `nwg` CUs, built and EXECUTED on the host as a
+// dependency machine: a workgroup's next tile runs when the ready counters it waits for are full; every tile must get to
+// run (no waiting cycle), every counter must end full, and - independently of the dependency ranges the scheduler wrote -
+// at the moment a tile runs, every earlier problem that writes what the tile reads, or reads / writes what the tile
+// writes (same buffer, overlapping columns), must be complete for the tile's windows.
+// Returns 0 (or 1: this plan runs launch by launch, nothing to check), or a negative code.  For the plan of calls of a few
+// windows also: every workspace element is written exactly once per call (what poll mode relies on).
+int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int *out_tiles, int *out_counters) {
+    const ModelPair mp = model_pair(pos, trj);
+    Model *a = mp.a, *b = mp.b;
+    if (!a) return -1;
+    Plan *pl = plan_get(a, b, plan_kind(batch));
+    int spill_row0 = -1;
+    std::vector<int4> tiles;
+    std::vector<int> wgoff;
+    std::vector<StageSchedule> stages;
+    const std::vector<std::vector<int>> &levels = *schedule_build_host(pl, batch, nwg, spill_row0, tiles, wgoff, stages);
+    Schedule::Fwd fw;
+    std::vector<int> ft, fo;
+    if (!schedule_build_fwd(pl, batch, nwg, levels, stages, tiles, wgoff, fw, ft, fo)) return 1;
+    if (out_tiles) *out_tiles = fw.ntiles;
+    if (out_counters) *out_counters = fw.ncnt;
+    const int np = (int)pl->probs.size(), TI = FWD_TILE_INT4 * 4;
+    std::vector<int> gcols(np);
+    for (int i = 0; i < np; ++i) gcols[i] = (pl->m[pl->probs[i].model]->layers[pl->probs[i].layer].N + COL_GRANULE - 1) / COL_GRANULE;
+    std::vector<unsigned> cnt(fw.ncnt, 0);
+    // column range a problem reads / writes in a workspace buffer
+    struct Acc { int buf, c0, c1; };
+    auto reads = [&](const ProbSpec &q) {
+        std::vector<Acc> v;
+        for (int sgi = 0; sgi < q.nseg; ++sgi)
+            if (pl->buffers[q.seg[sgi].buf].external == 0) v.push_back({q.seg[sgi].buf, q.seg[sgi].col, q.seg[sgi].col + q.seg[sgi].width});
+        if (q.res_buf >= 0) v.push_back({q.res_buf, q.res_col, q.res_col + pl->m[q.model]->layers[q.layer2 >= 0 && q.layer3 < 0 ? q.layer2 : q.layer].N});
+        return v;
+    };
+    auto writes = [&](const ProbSpec &q) {
+        const int N = pl->m[q.model]->layers[q.layer3 >= 0 ? q.layer3 : q.layer2 >= 0 ? q.layer2 : q.layer].N;
+        return Acc{q.c_buf, q.c_col, q.c_col + N};
+    };
+    auto overlap = [](const Acc &x, const Acc &y) { return x.buf == y.buf && x.c0 < y.c1 && y.c0 < x.c1; };
+    auto complete = [&](int prob, int w0, int w1) {           // every unit of `prob` that holds rows of windows [w0, w1)
+        const ProbSpec &q = pl->probs[prob];
+        const int M = (int)(batch * q.rows_per_window);
+        const int a0 = w0 * q.rows_per_window, a1 = std::min(w1 * q.rows_per_window, M);
+        for (int u = a0 / 32; u < (a1 + 31) / 32; ++u)
+            if (cnt[fw.cnt_base[prob] + u] != (unsigned)gcols[prob]) return false;
+        return true;
+    };
+    if (pl->kind == PLAN_SMALL) {
+        // Calls of a few windows may take data as its own ready flag (poll mode): no element of a workspace buffer may then
+        // be written twice in a call (a stale value would pass for data), and everything a problem reads from the workspace
+        // must be written by some problem (a sentinel nobody replaces would be waited for until the spins give up).
+        for (int i = 0; i < np; ++i)
+            for (int o = 0; o < i; ++o)
+                if (overlap(writes(pl->probs[i]), writes(pl->probs[o]))) return -25;
+        // (column-exact where reader and writer see the buffer with the same row geometry - the MLPs' concatenations; a
+        // pyramid level reads three of its producer's rows as one, there only "somebody writes this buffer" is checked)
+        for (int i = 0; i < np; ++i)
+            for (const Acc &rd : reads(pl->probs[i])) {
+                std::vector<char> covered(rd.c1 - rd.c0, 0);
+                bool any = false, same_rows = true;
+                for (int o = 0; o < np; ++o) {
+                    const Acc w = writes(pl->probs[o]);
+                    if (w.buf != rd.buf) continue;
+                    any = true;
+                    same_rows = same_rows && pl->probs[o].rows_per_window == pl->probs[i].rows_per_window;
+                    for (int c = std::max(w.c0, rd.c0); c < std::min(w.c1, rd.c1); ++c) covered[c - rd.c0] = 1;
+                }
+                if (!any) return -26;
+                if (same_rows)
+                    for (char c : covered)
+                        if (!c) return -26;
+            }
+    }
+    std::vector<int> next(fw.grid);
+    for (int w = 0; w < fw.grid; ++w) next[w] = fo[w];
+    int done = 0;
+    for (bool progress = true; progress;) {
+        progress = false;
+        for (int w = 0; w < fw.grid; ++w) {
+            while (next[w] < fo[w + 1]) {
+                const int *d = &ft[(size_t)next[w] * TI];
+                bool ready = true;
+                for (int k = 0; k < d[4] && ready; ++k) {
+                    const int base = d[8 + 2 * k], n = d[9 + 2 * k] & 0xffff;
+                    const unsigned need = (unsigned)d[9 + 2 * k] >> 16;
+                    for (int u = 0; u < n && ready; ++u) ready = cnt[base + u] >= need;
+                }
+                if (!ready) break;
+                const int id = d[0] & 0xff, mi = d[0] >> 8;
+                const ProbSpec &q = pl->probs[id];
+                const int M = (int)(batch * q.rows_per_window);
+                const int r1 = std::min(d[1] + mi * 32, M);
+                const int w0 = d[1] / q.rows_per_window, w1 = (r1 - 1) / q.rows_per_window + 1;
+                const Acc wr = writes(q);
+                for (int o = 0; o < id; ++o) {                 // (problems are created in the reference's execution order)
+                    const ProbSpec &oq = pl->probs[o];
+                    bool hazard = false;
+                    for (const Acc &rd : reads(q)) hazard = hazard || overlap(rd, writes(oq));        // read after write
+                    for (const Acc &rd : reads(oq)) hazard = hazard || overlap(rd, wr);               // write after read
+                    hazard = hazard || overlap(writes(oq), wr);                                      // write after write
+                    if (hazard && !complete(o, w0, w1)) return -20;
+                }
+                if (d[5] != fw.cnt_base[id] + d[1] / 32 || d[5] + mi > fw.ncnt) return -21;
+                for (int u = 0; u < mi; ++u) {
+                    cnt[d[5] + u] += (unsigned)d[6];
+                    if (cnt[d[5] + u] > (unsigned)gcols[id]) return -22;
+                }
+                ++next[w];
+                ++done;
+                progress = true;
+            }
+        }
+    }
+    if (done != fw.ntiles) return -23;                          // a waiting cycle
+    for (int i = 0; i < np; ++i)
+        for (int u = 0; u < (int)((batch * pl->probs[i].rows_per_window + 31) / 32); ++u)
+            if (cnt[fw.cnt_base[i] + u] != (unsigned)gcols[i]) return -24;
+    return 0;
+}
+
+// Test hook: the pre-pass's per-keypoint routine (r3d_undistort.hpp) on the host.
+int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays) {
+    if (!row16 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_undistort_host: bad argument"); return R3D_ERR_ARG; }
+    const UndistRow k = undist_row(row16);
+    for (int64_t i = 0; i < n; ++i) {
+        double uo, vo, r[3];
+        undistort_pixel(k, uv[2 * i], uv[2 * i + 1], uo, vo);
+        pixel_to_ray(k, uo, vo, r);
+        if (out_uv) { out_uv[2 * i] = uo; out_uv[2 * i + 1] = vo; }
+        if (out_rays) for (int c = 0; c < 3; ++c) out_rays[3 * i + c] = r[c];
+    }
+    return R3D_OK;
+}
+
+// Test hook: the 2-float encodings of the pre-pass (r3d_undistort.hpp) on the host.
+int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, int32_t encoding, double *out2) {
+    if (!row16 || !out2 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_encode_px_host: bad argument"); return R3D_ERR_ARG; }
+    if (encoding != ENC_INTRINSIC && encoding != ENC_SCREEN) {
+        set_error("r3d_debug_encode_px_host: encoding must be 1 (intrinsic) or 2 (screen), got %d", encoding);
+        return R3D_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) encode_pixel_2d(row16, encoding, uv[2 * i], uv[2 * i + 1], out2 + 2 * i);
+    return R3D_OK;
+}
+
+// Test hook: the per-frame routines of r3d_clip_valid_losses (r3d_valid.hpp) on the host, frames added in index order.
+int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t n_frames, int32_t num_joints,
+                                const int32_t *parents, int32_t flags, double *out, double *frame) {
+    const int rc = valid_check_args("r3d_debug_valid_losses_host", pos, trj, gt, n_frames, num_joints, parents, flags, out);
+    if (rc != R3D_OK) return rc;
+    ValidIn a;
+    a.pos = pos;
+    a.trj = trj;
+    a.gt = gt;
+    a.J = num_joints;
+    a.flags = flags;
+    a.bones = parents != nullptr;
+    a.tree = parents ? valid_pack_tree(parents, num_joints) : ValidTree{{0ull, 0ull}};
+    const int nb = a.bones ? num_joints - 1 : 0;
+    for (int c = 0; c < R3D_VALID_DOUBLES; ++c) out[c] = 0.0;
+    for (int64_t f = 0; f < n_frames; ++f) {
+        double term[R3D_VALID_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+        valid_frame_terms(a, f, term);
+        double bl = 0, bd = 0;
+        for (int b = 0; b < nb; ++b) {
+            double v[R3D_VALID_BONE_ROWS], dir;
+            valid_frame_bone(a, f, b, v, dir);
+            bl += v[0];
+            bd += dir;
+            for (int r = 0; r < R3D_VALID_BONE_ROWS; ++r) out[R3D_VALID_COUNT + r * R3D_VALID_MAX_BONES + b] += v[r];
+        }
+        if (a.bones) {
+            term[R3D_VALID_BONE_LEN] = bl / (double)nb;
+            term[R3D_VALID_BONE_DIR] = bd / (double)nb;
+        }
+        for (int k = 0; k < R3D_VALID_COUNT; ++k) {
+            out[k] += term[k];
+            if (frame) frame[f * R3D_VALID_COUNT + k] = term[k];
+        }
+    }
+    return R3D_OK;
+}
+
+}  // extern "C"
+
+#endif  // R3D_TEST_HOOKS

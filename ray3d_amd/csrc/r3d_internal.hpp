@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -340,6 +341,22 @@ struct StageSchedule {
     double makespan;       // modelled cycles of the longest chunk
 };
 
+// What a bound problem table was bound to: a call with the same key finds the schedule's own table valid (no r3d_bind_f32).
+// Host side only - built from the call, kept in Schedule::Fwd::Bound, compared as a whole.
+struct BoundKey {
+    int variant = 0;                              // which relative table: UV input + 2 * first levels on the per-frame buffer
+    const void *base[BIND_NBASE] = {nullptr};     // (BIND_WS: the workspace the caller passed)
+    long long enc_ws = 0, cam_stride = 0;
+    unsigned enc_bytes = 0;
+    int param_stride = 0;
+    bool operator==(const BoundKey &o) const {
+        bool same = variant == o.variant && enc_ws == o.enc_ws && cam_stride == o.cam_stride && enc_bytes == o.enc_bytes &&
+                    param_stride == o.param_stride;
+        for (int k = 0; same && k < BIND_NBASE; ++k) same = base[k] == o.base[k];
+        return same;
+    }
+};
+
 struct Schedule {
     int64_t B = 0;
     bool pinned = false;   // named in r3d_prepare: never evicted (a captured hipGraph holds its device pointers) until r3d_release
@@ -381,10 +398,7 @@ struct Schedule {
         struct Bound {
             bool valid = false;
             int bank = 0;
-            const void *base[BIND_NBASE] = {nullptr};
-            long long enc_ws = 0, cam_stride = 0;
-            unsigned enc_bytes = 0;
-            int param_stride = 0, uv = 0;
+            BoundKey key;
         } bound;
     } fwd;
     ~Schedule();
@@ -444,8 +458,44 @@ struct CallShape {
     long long frames = 0;
 };
 
+// floats per input frame of a call (UV mode: pixel keypoints, two per joint)
+inline int frame_floats(const Model *a, bool uv) { return a->cfg.num_joints * (uv ? 2 : a->cfg.in_features); }
+
+// (pos, trj) as the API takes them -> a = pos or the single model, b = trj of a pair
+struct ModelPair { Model *a, *b; };
+inline ModelPair model_pair(const r3d_model *pos, const r3d_model *trj) {
+    Model *p = const_cast<Model *>(reinterpret_cast<const Model *>(pos)), *t = const_cast<Model *>(reinterpret_cast<const Model *>(trj));
+    return {p ? p : t, p ? t : nullptr};
+}
+
+// r3d_forward.cpp: the forward driver and what the entry points share with it
 int fill_prob(const Plan *pl, const ProbSpec &q, int64_t B, const Model *a, const Bases &bs, const CallShape &cs, GemmProb &g,
-              unsigned char *tags);   // r3d_api.cpp
+              unsigned char *tags);
+bool same_input_shape(const Model *a, const Model *b);
+size_t workspace_bytes_pair(Model *a, Model *b, int64_t B);                    // r3d_workspace_bytes of a pair
+int dist_check(const Model *a, const r3d_input *in, bool need_cam);           // the pixel modes: argument rules, bytes of the pre-pass's output
+size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B);
+struct FwdKeys { int cu_limit, nwg, lane_key0, nlanes; };                      // lane keys lane_key0 .. lane_key0 + nlanes - 1 (schedule_key)
+FwdKeys forward_keys(const Model *a, const Model *b);
+int forward_run(Model *a, Model *b, const r3d_input *in, int64_t B, float *out, float *out_trj, void *ws, size_t ws_bytes, void *stream);
+
+// r3d_order.cpp: the process-wide ordering of single-launch forwards
+extern std::mutex g_fwd_launch_mu;
+hipError_t wait_behind(hipStream_t stream, hipStream_t other, hipEvent_t &ev);
+hipError_t order_single_launch(hipStream_t stream, bool before, bool masked = false);
+int lanes_create(Model *m, int n);  // R3D_OPT_LANES: the lanes' streams and events
+void lanes_destroy(Model *m);
+
+// the argument rules of r3d_clip_valid_losses, shared with its host hook (r3d_api.cpp)
+int valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t n, int32_t J,
+                     const int32_t *parents, int32_t flags, const double *out);
+
+#ifdef R3D_TIMING      // r3d_timing.cpp
+void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
+void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
+bool timing_arm_stage(size_t si, LaunchArgs &la, hipStream_t stream);          // true: launch `si` is timed
+void timing_report_stage(size_t si, const StageSchedule &ss, hipStream_t stream);
+#endif
 
 void set_error(const char *fmt, ...);
 const char *last_error();
@@ -459,7 +509,6 @@ int plan_kind(int64_t B);                       // the plan a call of B windows 
 std::vector<int64_t> plan_kind_edges();         // the largest window count of every plan kind that has one (r3d_workspace_bytes)
 Plan *plan_get(Model *a, Model *b, int kind);
 void plans_drop(const Model *m);   // delete every cached plan (and its schedules) that names `m`
-void lanes_destroy(Model *m);       // R3D_OPT_LANES: the lanes' streams and events (r3d_api.cpp)
 bool plans_pinned(const Model *m); // some schedule of a plan that names `m` is pinned (r3d_prepare: a captured graph may point into it)
 constexpr int STAGE_SPILL_IN = 1 << 30;   // flag on a Plan::stages entry: the spilled rows of that problem
 constexpr int GEMM_SCHED_MAX_UNITS = 6;   // widest tile of r3d_gemm_f32: 6 x 32 rows

@@ -589,7 +589,7 @@ static SchedProb sched_prob_of(const Plan *pl, const ProbSpec &q, int64_t B) {
         sp.gemv = M <= GEMV_ROWS && narrow_ok && !hook_on("R3D_NO_GEMV");
         // ... and of up to 32 rows (one unit): latency tiles on the matrix cores (not beside the bf16x3 tiles: B >= 96 there)
         sp.lat = !sp.gemv && M <= 32 && narrow_ok && !hook_on("R3D_NO_LAT");
-        const bool b3 = B >= b3_min_batch();               // (r3d_api.cpp passes the bf16x3 operands under the same condition)
+        const bool b3 = B >= b3_min_batch();               // (fill_prob passes the bf16x3 operands under the same condition)
         // single-unit tiles of 5 - 7 column blocks (gemm_tile_nb) for the wide plain fp32 layers: the FCBlocks' 1024-wide Linears
         sp.nb_ok = q.enc_lut < 0 && q.layer2 < 0 && !sp.gemv && !sp.lat && !(b3 && L.bf3) && L.N % 32 == 0 && L.N >= 512 &&
                    L.Kpad / BK >= 8 && !hook_on("R3D_NO_NB");
@@ -876,7 +876,7 @@ Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin, int lane) {
                 CallShape cs;
                 cs.uv = uv != 0;
                 cs.shared = shared != 0;
-                if (shared) {                              // (a clip call: window stride one frame - r3d_api.cpp, run)
+                if (shared) {                              // (a clip call: window stride one frame - r3d_forward.cpp)
                     cs.window_stride = 1;
                     cs.frames = B + a->RF - 1;
                 }

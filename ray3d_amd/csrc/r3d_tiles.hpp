@@ -1935,7 +1935,7 @@ __device__ __forceinline__ void first_level_taps(ProbRef P, const int4 *tile_lis
 // (lib/train_val/trainer.py:47-58).  expand_conv is linear in its operand, so the pre-activation of expand_conv row t of
 // window w is E[f] + V[c]: E of the row's first frame f = w * stride + 3 t, V of the window's current frame c (quirk Q1) -
 // two C-vectors per input FRAME that a launch of gathered GEMMs ahead of the forward left in the per-frame buffer
-// (r3d_api.cpp: Plan::frame_probs; row = frame, this branch's block [E | V] at P.x, P.enc_jf floats per row).  The 81
+// (r3d_forward.cpp: Plan::frame_probs; row = frame, this branch's block [E | V] at P.x, P.enc_jf floats per row).  The 81
 // windows that contain a frame share them: the tile neither gathers nor multiplies for expand_conv - every lane loads the
 // 16 (row, column) values of its accumulator registers straight into them (two 128-byte row segments per wavefront
 // instruction), one tap ahead of their use and behind the previous tap's matrix work; V once per tile.  The rest - the

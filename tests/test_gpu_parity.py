@@ -1737,7 +1737,7 @@ def test_forward_captured_in_a_hip_graph_after_prepare():
 def test_a_call_on_the_buffers_of_the_previous_one_skips_the_bind_kernel():
     """Eager calls keep their ready counters and bound problem table in a control region the schedule owns: a call whose
     input / parameter / workspace pointers are the previous call's runs WITHOUT r3d_bind_f32, on the counter bank the
-    previous launch zeroed (r3d_api.cpp).  Outputs must not depend on which path a call took: repeated calls, calls that
+    previous launch zeroed (r3d_forward.cpp).  Outputs must not depend on which path a call took: repeated calls, calls that
     alternate between two inputs (bind every time), new contents behind the same pointer, and eager calls around the
     replay of a captured graph - which binds inside the graph, in the caller's workspace - all give the same bits."""
     import ray3d_amd

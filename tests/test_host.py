@@ -618,7 +618,7 @@ def test_partial_rows_header_is_uploaded_once_and_kept():
 
 def _schedule_check(probs, nwg=256, enc=False):
     """probs: list of (M, N, nk, max_ks, max_units).  Calls the library's own checker
-    (r3d_debug_schedule_check, r3d_api.cpp): exact cover + tile-shape rules."""
+    (r3d_debug_schedule_check, r3d_hooks.cpp): exact cover + tile-shape rules."""
     import ctypes as C
     from ray3d_amd import _capi
     lib = hooks_library()

@@ -17,5 +17,5 @@ for f in r3d_kernels r3d_metrics r3d_k_gemm r3d_k_gemm_enc r3d_k_gemm_b3 r3d_k_f
   fi
 done
 wait
-/opt/rocm/bin/hipcc -fPIC --offload-arch=gfx950 -shared -o $R/tools/libray3d_hip_$name.so $objs $B/r3d_model.hooks.o $B/r3d_plan.hooks.o $B/r3d_schedule.hooks.o $B/r3d_api.hooks.o
+/opt/rocm/bin/hipcc -fPIC --offload-arch=gfx950 -shared -o $R/tools/libray3d_hip_$name.so $objs $B/r3d_model.hooks.o $B/r3d_plan.hooks.o $B/r3d_schedule.hooks.o $B/r3d_api.hooks.o $B/r3d_forward.hooks.o $B/r3d_order.hooks.o $B/r3d_hooks.hooks.o $B/r3d_timing.hooks.o
 ls -la $R/tools/libray3d_hip_$name.so

@@ -171,11 +171,21 @@ typedef struct {
 /* Bytes of scratch HBM that suffice for every forward of AT MOST B windows (either model may be NULL): the maximum over
  * the launch plans calls of 1..B windows can select (small calls run less fused plans with larger intermediates), so a
  * caller may size its workspace once for its largest batch.
- * The workspace is scratch: nothing in it has to survive between calls, and the caller may use it for something else
- * between them.  (What a forward needs ACROSS calls - the ready counters and the bound problem table of the single-launch
- * forward, and for calls of <= 16 windows two banks of activations - lives in device memory the library owns, per
- * cached batch size; a forward that is being captured into a hipGraph keeps all of it inside the workspace instead, so
- * a graph's workspace must stay allocated, and untouched by other work while the graph runs, as any captured buffer.) */
+ * Exactly this many bytes are enough: a forward reads and writes nothing past workspace_dev + workspace_bytes, and a
+ * call of B windows given fewer than r3d_workspace_bytes(B) bytes returns R3D_ERR_WORKSPACE before anything is launched.
+ * `workspace_dev` must be 256-byte aligned (the library rounds its regions to 256 bytes relative to that base).  The
+ * float pointers of a call - x_dev, param_dev, out_dev, out_trj_dev - need the 4-byte alignment of their type and no
+ * more (a slice x + k windows of a larger tensor is fine as it is: what reads them several floats at a time does so
+ * with buffer loads, which need dword alignment only); cam_dev the 8 bytes of a double.  Each buffer is
+ * read or written inside its stated extent only: x_dev the (B - 1) * window_stride + RF frames of the call, param_dev
+ * and cam_dev B rows (one row with stride 0), out_dev / out_trj_dev B rows.
+ * The workspace is scratch: nothing in it has to survive between calls, the caller may use it for something else
+ * between them, and what it holds when a call starts - zeros, NaN, anything - has no effect on the outputs.  (What a
+ * forward needs ACROSS calls - the ready counters and the bound problem table of the single-launch forward, and for
+ * calls of <= 16 windows two banks of activations - lives in device memory the library owns, per cached batch size.)
+ * A forward that is being captured into a hipGraph keeps all of that inside the workspace instead and sets it up
+ * inside the graph on every replay.  So a graph's workspace must exist, and be left alone by other work, WHILE the
+ * graph runs - as any captured buffer; BETWEEN replays it may hold anything, like the workspace of an eager call. */
 size_t r3d_workspace_bytes(const r3d_model *pos, const r3d_model *trj, int64_t B);
 
 /* ... for forwards of AT MOST B windows with inputs shaped as `in` (mode, window_stride and cam_stride are read; the pointers

@@ -269,6 +269,7 @@ struct Call {
     r3d_input in_rays;
     Plan *pl = nullptr;
     Schedule *sched = nullptr;
+    size_t ws_need = 0;                    // r3d_workspace_bytes(B), asked once per call (redirect_px, or pick_plan)
     long long frames = 0;
     int JF = 0;                            // floats per input frame of the call
     bool uv = false, shared = false, single = false;
@@ -338,7 +339,8 @@ int redirect_px(Call &c) {
         set_error("B too large for one call (the materialised rays of overlapping windows must stay below 2 GiB)");
         return R3D_ERR_ARG;
     }
-    const size_t dist_off = (workspace_bytes_pair(c.a, c.b, c.B) + 255) / 256 * 256;
+    c.ws_need = workspace_bytes_pair(c.a, c.b, c.B);
+    const size_t dist_off = (c.ws_need + 255) / 256 * 256;
     const size_t need = dist_off + dist_ray_bytes(a, in, c.B);
     if (!c.ws || c.ws_bytes < need) {
         set_error("workspace too small for %s (r3d_input_workspace_bytes): need %zu bytes, got %zu", px_name(in->mode), need, c.ws_bytes);
@@ -359,9 +361,11 @@ int redirect_px(Call &c) {
 int pick_plan(Call &c) {
     c.pl = plan_get(c.a, c.b, plan_kind(c.B));
     c.frames = (c.B - 1) * c.in->window_stride + c.a->RF;
-    const size_t need = workspace_need(c.pl, c.B);
+    // the bound is what r3d_workspace_bytes(B) answers - the size formula and this check are one function - which is
+    // >= workspace_need(c.pl, B): the plans of smaller calls may need more than this call's own (1025 windows: 1023's)
+    const size_t need = c.ws_need ? c.ws_need : (c.ws_need = workspace_bytes_pair(c.a, c.b, c.B));
     if (!c.ws || c.ws_bytes < need) {
-        set_error("workspace too small: need %zu bytes, got %zu", need, c.ws_bytes);
+        set_error("workspace too small: need %zu bytes (r3d_workspace_bytes), got %zu", need, c.ws_bytes);
         return R3D_ERR_WORKSPACE;
     }
     c.act_base = (float *)c.ws;

@@ -67,7 +67,7 @@ class _Workspace:
 
     def get(self, nbytes: int, device) -> torch.Tensor:
         if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
-            self.buf = torch.empty(int(nbytes * 1.0) + 256, dtype=torch.uint8, device=device)
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         return self.buf
 
 

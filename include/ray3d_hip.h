@@ -361,6 +361,57 @@ int r3d_clip_metrics_detail(const float *pred_dev, const float *gt_dev, int64_t 
                             const double *rn2w, const double *tn2w, double *out_dev, double *frame_dev, double *detail_dev,
                             void *stream);
 
+/* ---- a whole shard of clips in one call ---- */
+
+/* lib/train_val/trainer.py:355-403 for every clip of a shard at once: r3d_clip_metrics / r3d_clip_metrics_detail over a table of
+ * clips that lives in DEVICE memory (uploaded once per data set; the host never sees a descriptor during the call), in exactly
+ * two kernel launches on `stream` - no copy, no allocation, no synchronisation.  pred_dev and gt_dev are (total_frames, J, 3)
+ * float32; clip c is rows [first_frame, first_frame + n_frames) of both (and of frame_dev), measured through ITS rigid
+ * transform (rn2w row-major, tn2w: as r3d_clip_metrics takes them).  Clips may lie in the buffers in any order, with gaps;
+ * the velocity term never crosses a clip's end.
+ *   rows_dev:   clip c's five sums (R3D_METRIC_* order) at rows_dev + c * row_stride, row_stride >= R3D_METRIC_COUNT: a
+ *               pointer to column 3 of a (k, 8) matrix of partial rows and stride 8 fills columns 3..7 in place; nothing else
+ *               of the matrix is written.
+ *   detail_dev: optional (NULL: none): clip c's R3D_DETAIL_DOUBLES results at detail_dev + c * detail_stride,
+ *               detail_stride >= R3D_DETAIL_DOUBLES.
+ *   frame_dev:  optional (NULL: none): (total_frames, R3D_METRIC_COUNT) doubles, row first_frame + f the terms of the clip's
+ *               frame f; rows no valid clip covers are left untouched.
+ * BIT-FOR-BIT EQUALITY WITH THE PER-CLIP CALLS.  For every clip the five sums equal r3d_clip_metrics on that clip alone,
+ * the detail row and the clip's rows of frame_dev equal r3d_clip_metrics_detail on that clip alone, bit for bit - the NaN
+ * velocity of a one-frame clip and clips above R3D_METRIC_MAX_BLOCKS * 256 frames (where the per-clip call wraps around its
+ * workgroups) included: both run one and the same workgroup body with the same frame-to-workgroup assignment and add the
+ * partial rows in the same order.  A caller may switch between the two paths without its numbers moving.
+ * GRID.  max_frames is the caller's bound on any clip's length and sizes the grid: (min(ceil(max_frames / 256),
+ * R3D_METRIC_MAX_BLOCKS), num_clips) workgroups; a workgroup past its clip's own count returns at once.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A descriptor is invalid when n_frames < 1, n_frames > max_frames, or
+ * [first_frame, first_frame + n_frames) is not inside [0, total_frames).  The kernels never follow an invalid descriptor:
+ * nothing of that clip is read, its five sums and its detail row are all NaN, its rows of frame_dev are left untouched.
+ * Beyond the descriptors the kernels read pred_dev / gt_dev within total_frames * num_joints * 3 floats, the table within
+ * num_clips descriptors, and write the strided rows, frame_dev within total_frames rows and the scratch within
+ * r3d_clips_metrics_scratch_bytes: no input can make them touch memory outside these extents.
+ * SCRATCH.  The workgroups' partial rows: num_clips * min(ceil(max_frames / 256), R3D_METRIC_MAX_BLOCKS) *
+ * (R3D_METRIC_COUNT + (detail ? R3D_DETAIL_DOUBLES : 0)) doubles - r3d_clips_metrics_scratch_bytes returns exactly that
+ * (0 for num_clips < 1 or max_frames < 1), exactly that many bytes suffice, and what the scratch holds at entry has no effect
+ * on the outputs.  With less the call returns R3D_ERR_WORKSPACE before anything is launched.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (pred_dev, gt_dev, clips_dev, rows_dev,
+ * scratch_dev), num_clips outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, max_frames < 1, total_frames < 1,
+ * row_stride < R3D_METRIC_COUNT, detail_dev with detail_stride < R3D_DETAIL_DOUBLES, a table or scratch pointer that is
+ * not 8-byte aligned.  Deterministic (fixed summation order, integer counts). */
+typedef struct {
+    int64_t first_frame;  /* row of the clip's first frame in pred_dev / gt_dev / frame_dev */
+    int64_t n_frames;
+    double  rn2w[9];      /* row-major, as r3d_clip_metrics takes it */
+    double  tn2w[3];
+} r3d_clip_desc;          /* 112 bytes, 8-byte aligned; lives in DEVICE memory */
+#define R3D_CLIPS_MAX 65535 /* clips per call (the grid's second dimension) */
+size_t r3d_clips_metrics_scratch_bytes(int32_t num_clips, int64_t max_frames, int detail);
+int r3d_clips_metrics(const float *pred_dev, const float *gt_dev, int64_t total_frames, int32_t num_joints,
+                      const r3d_clip_desc *clips_dev, int32_t num_clips, int64_t max_frames,
+                      double *rows_dev, int64_t row_stride,          /* clip c: 5 sums at rows_dev + c*row_stride */
+                      double *detail_dev, int64_t detail_stride,     /* optional (NULL): R3D_DETAIL_DOUBLES per clip */
+                      double *frame_dev,                             /* optional (NULL): (total_frames, R3D_METRIC_COUNT) */
+                      void *scratch_dev, size_t scratch_bytes, void *stream);
+
 /* ---- per-clip validation losses: Trainer.test after the forwards ---- */
 
 /* lib/train_val/trainer.py:187-223 for one clip of n_frames frames, in the NORMALISED frame (no world transform): the

@@ -30,7 +30,7 @@ EXPORTS = (
     "r3d_set_weight", "r3d_finalize", "r3d_workspace_bytes", "r3d_forward", "r3d_forward_pair",
     "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_clip_valid_losses", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
-    "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes",
+    "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host")
@@ -45,6 +45,8 @@ VALID_NAMES = ("loss", "pos", "trj_w", "trj_wsum", "trj_dsum", "bone_len", "bone
 VALID_COUNT, VALID_MAX_BONES, VALID_BONE_ROWS = 7, 16, 4                # R3D_VALID_COUNT, _MAX_BONES, _BONE_ROWS
 VALID_DOUBLES = VALID_COUNT + VALID_BONE_ROWS * VALID_MAX_BONES         # R3D_VALID_DOUBLES (71)
 VALID_OUT_DOUBLES = VALID_DOUBLES * (1 + 128)                           # R3D_VALID_OUT_DOUBLES
+METRIC_COUNT, METRIC_MAX_BLOCKS, METRIC_THREADS = 5, 128, 256           # R3D_METRIC_COUNT, _MAX_BLOCKS; frames per workgroup
+CLIPS_MAX = 65535                                                       # R3D_CLIPS_MAX
 
 
 class Config(C.Structure):
@@ -57,6 +59,17 @@ class Input(C.Structure):
     _fields_ = [("mode", C.c_int32), ("x_dev", C.c_void_p), ("window_stride", C.c_int64),
                 ("param_dev", C.c_void_p), ("param_stride", C.c_int64),
                 ("cam_dev", C.c_void_p), ("cam_stride", C.c_int64)]
+
+
+class ClipDesc(C.Structure):
+    """r3d_clip_desc: one row of the device-side table r3d_clips_metrics reads (112 bytes)."""
+    _fields_ = [("first_frame", C.c_int64), ("n_frames", C.c_int64), ("rn2w", C.c_double * 9), ("tn2w", C.c_double * 3)]
+
+
+def clip_desc_dtype():
+    """The NumPy structured dtype with r3d_clip_desc's layout: an array of it, uploaded as bytes, is the table."""
+    import numpy as np
+    return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("rn2w", np.float64, (9,)), ("tn2w", np.float64, (3,))])
 
 
 class LaunchRecord(C.Structure):
@@ -131,6 +144,9 @@ def load():
     lib.r3d_clip_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]
     lib.r3d_clip_metrics_detail.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp, vp]
     lib.r3d_clip_valid_losses.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp, vp]
+    lib.r3d_clips_metrics_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int]
+    lib.r3d_clips_metrics_scratch_bytes.restype = C.c_size_t
+    lib.r3d_clips_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
@@ -299,6 +315,22 @@ def clip_metrics_detail(pred_ptr: int, gt_ptr: int, n_frames: int, num_joints: i
     t = (C.c_double * 3)(*[float(v) for v in tn2w])
     check(load().r3d_clip_metrics_detail(pred_ptr, gt_ptr, n_frames, num_joints, r, t, out_ptr, frame_ptr or None, detail_ptr,
                                          stream), "r3d_clip_metrics_detail")
+
+
+def clips_metrics_scratch_bytes(num_clips: int, max_frames: int, detail: bool) -> int:
+    """r3d_clips_metrics_scratch_bytes: the scratch one r3d_clips_metrics call over `num_clips` clips of at most `max_frames`
+    frames needs (0 for num_clips < 1 or max_frames < 1)."""
+    return int(load().r3d_clips_metrics_scratch_bytes(num_clips, max_frames, 1 if detail else 0))
+
+
+def clips_metrics(pred_ptr: int, gt_ptr: int, total_frames: int, num_joints: int, table_ptr: int, num_clips: int, max_frames: int,
+                  rows_ptr: int, row_stride: int, detail_ptr: Optional[int], detail_stride: int, frame_ptr: Optional[int],
+                  scratch_ptr: int, scratch_bytes: int, stream: int):
+    """r3d_clips_metrics: every pointer is device memory; `table_ptr` num_clips r3d_clip_desc (:func:`clip_desc_dtype`) back to
+    back; `detail_ptr` / `frame_ptr` may be None."""
+    check(load().r3d_clips_metrics(pred_ptr, gt_ptr, total_frames, num_joints, table_ptr, num_clips, max_frames, rows_ptr, row_stride,
+                                   detail_ptr or None, detail_stride, frame_ptr or None, scratch_ptr, scratch_bytes, stream),
+          "r3d_clips_metrics")
 
 
 def _parent_table(parents):

@@ -192,6 +192,42 @@ int r3d_clip_metrics_detail(const float *pred_dev, const float *gt_dev, int64_t 
     return 0;
 }
 
+size_t r3d_clips_metrics_scratch_bytes(int32_t num_clips, int64_t max_frames, int detail) {
+    if (num_clips < 1 || max_frames < 1) return 0;
+    return r3d::clips_metrics_scratch_bytes(num_clips, max_frames, detail != 0);
+}
+
+int r3d_clips_metrics(const float *pred_dev, const float *gt_dev, int64_t total_frames, int32_t num_joints,
+                      const r3d_clip_desc *clips_dev, int32_t num_clips, int64_t max_frames, double *rows_dev, int64_t row_stride,
+                      double *detail_dev, int64_t detail_stride, double *frame_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
+    // (every check on the host, before any HIP call)
+    if (!pred_dev || !gt_dev || !clips_dev || !rows_dev || !scratch_dev) { r3d::set_error("r3d_clips_metrics: null pointer"); return R3D_ERR_ARG; }
+    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { r3d::set_error("r3d_clips_metrics: num_clips must be in 1..%d (got %d)", R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (num_joints < 1 || num_joints > 17) { r3d::set_error("r3d_clips_metrics: num_joints must be in 1..17 (got %d)", num_joints); return R3D_ERR_ARG; }
+    if (max_frames < 1) { r3d::set_error("r3d_clips_metrics: max_frames must be >= 1 (got %lld)", (long long)max_frames); return R3D_ERR_ARG; }
+    if (total_frames < 1) { r3d::set_error("r3d_clips_metrics: total_frames must be >= 1 (got %lld)", (long long)total_frames); return R3D_ERR_ARG; }
+    if (row_stride < R3D_METRIC_COUNT) { r3d::set_error("r3d_clips_metrics: row_stride must be >= %d (got %lld)", R3D_METRIC_COUNT, (long long)row_stride); return R3D_ERR_ARG; }
+    if (detail_dev && detail_stride < R3D_DETAIL_DOUBLES) {
+        r3d::set_error("r3d_clips_metrics: detail_stride must be >= %d (got %lld)", R3D_DETAIL_DOUBLES, (long long)detail_stride);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(clips_dev) % 8 || reinterpret_cast<uintptr_t>(scratch_dev) % 8) {
+        r3d::set_error("r3d_clips_metrics: clips_dev and scratch_dev must be 8-byte aligned");
+        return R3D_ERR_ARG;
+    }
+    const size_t need = r3d::clips_metrics_scratch_bytes(num_clips, max_frames, detail_dev != nullptr);
+    if (scratch_bytes < need) {
+        r3d::set_error("r3d_clips_metrics: scratch of %zu bytes, %zu needed (r3d_clips_metrics_scratch_bytes)", scratch_bytes, need);
+        return R3D_ERR_WORKSPACE;
+    }
+    if (r3d::launch_clips_metrics(pred_dev, gt_dev, total_frames, num_joints, clips_dev, num_clips, max_frames, rows_dev, row_stride,
+                                  detail_dev, detail_stride, frame_dev, scratch_dev, (hipStream_t)stream)) {
+        r3d::set_error("r3d_clips_metrics: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
 int r3d_set_option(r3d_model *m, int32_t option, int64_t value) {
     Model *mm = reinterpret_cast<Model *>(m);
     if (!mm) { r3d::set_error("r3d_set_option: null model"); return R3D_ERR_ARG; }

@@ -591,5 +591,11 @@ int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, 
 // r3d_clip_valid_losses (a mode of the clip-metrics kernels: r3d_metrics.hip, r3d_valid_dev.hpp); arguments already checked, parents a host array or null
 int launch_clip_valid(const float *pos, const float *trj, const float *gt, long long n, int J, const int32_t *parents,
                       int flags, double *out, double *frame, hipStream_t stream);
+// r3d_clips_metrics (the same kernels, one grid row per clip of the device-side table); arguments already checked, `scratch` of at
+// least clips_metrics_scratch_bytes.  Two launches, nothing else.
+size_t clips_metrics_scratch_bytes(int num_clips, long long max_frames, bool detail);
+int launch_clips_metrics(const float *pred, const float *gt, long long total, int J, const r3d_clip_desc *table, int num_clips,
+                         long long max_frames, double *rows, long long row_stride, double *detail, long long detail_stride,
+                         double *frame, void *scratch, hipStream_t stream);
 
 }  // namespace r3d

@@ -19,6 +19,14 @@
 // r3d_clip_valid_losses (Trainer.test's validation losses; r3d_valid_dev.hpp, r3d_valid.hpp) runs on the same two kernels with
 // their ValidArgs argument set: a uniform branch at the top of each hands the launch to that mode's own workgroup body, which
 // borrows the LDS of the five sums' tree; nothing of the error sums' code runs then, and nothing of that mode otherwise.
+//
+// r3d_clips_metrics (a whole shard of clips in one launch pair) runs on the same two kernels as well, with their ClipsArgs
+// argument set: blockIdx.y names a clip, the workgroup builds its MetricArgs from the clip's descriptor in device memory and
+// runs metrics_block - the one workgroup body of the five-sum / detail mode, which the per-clip launch enters with
+// (blockIdx.x, gridDim.x) and this one with blockIdx.x and the clip's OWN workgroup count - on the clip's slice of the scratch.
+// The frame loop, the wave-of-64 detail sums and both reduction trees are therefore the same instructions for both calls: a
+// clip's results have the bits of the per-clip call by construction.  (A mode of the two documented kernels, as the detail and
+// the validation losses are: the library's kernel set stays what tests/test_host.py pins.)
 #include <hip/hip_runtime.h>
 #include "r3d_internal.hpp"
 #include "r3d_valid_dev.hpp"
@@ -45,6 +53,41 @@ struct MetricArgs {
 };
 static_assert(METRIC_THREADS == VALID_THREADS && R3D_METRIC_COUNT * METRIC_THREADS >= VALID_WAVES * R3D_VALID_DOUBLES,
               "the validation-loss mode runs in this kernel's workgroups and in the LDS of its five-sum tree");
+
+// r3d_clips_metrics: the table of clips and the shard's buffers (`table` null: not that mode)
+struct ClipsArgs {
+    const r3d_clip_desc *table;  // num_clips descriptors, device memory
+    const float *pred, *gt;      // (total, J, 3) each
+    long long total, max_frames;
+    int J, blocks;               // blocks = metric_blocks(max_frames): workgroups (and partial rows) per clip
+    double *rows, *detail;       // clip c: its five sums at rows + c * row_stride, its detail row (optional) at detail + c * detail_stride
+    long long row_stride, detail_stride;
+    double *frame;               // optional (total, R3D_METRIC_COUNT)
+    double *part, *dpart;        // scratch: (num_clips, blocks, R3D_METRIC_COUNT) partial sums, (num_clips, blocks, R3D_DETAIL_DOUBLES) partial detail rows
+};
+static_assert(sizeof(r3d_clip_desc) == 112 && alignof(r3d_clip_desc) == 8, "layout of r3d_clip_desc (include/ray3d_hip.h)");
+
+// the workgroups that share a clip of n frames
+__host__ __device__ inline long long metric_blocks(long long n) {
+    const long long b = (n + METRIC_THREADS - 1) / METRIC_THREADS;
+    return b < 1 ? 1 : (b > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : b);
+}
+
+// a descriptor is followed only when its frames lie inside the buffers and within the caller's bound (uniform per workgroup)
+__device__ inline bool clip_desc_valid(long long first, long long n, const ClipsArgs &c) {
+    return n >= 1 && n <= c.max_frames && first >= 0 && first <= c.total - n;
+}
+
+// a double every lane holds the same value of, moved to scalar registers
+__device__ inline double uniform(double v) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ inline long long uniform(long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 
 // the similarity fit of one frame: aligned = a * (p Rm) + t
 struct Fit {
@@ -220,14 +263,11 @@ __device__ __noinline__ void frame_detail(const double (*p)[3], const double (*g
     }
 }
 
-__global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArgs a, ValidArgs valid) {
-    __shared__ double red[R3D_METRIC_COUNT][METRIC_THREADS];
-    __shared__ double cols[METRIC_WAVES][JOINT_COLS];
-    __shared__ unsigned int hist[R3D_DETAIL_THRESHOLDS + 1];
-    if (valid.out) {             // uniform: the whole launch is a validation-loss one (r3d_clip_valid_losses), `a` is unused
-        valid_block(valid, &red[0][0]);
-        return;
-    }
+// The workgroup body of the five-sum / detail mode: workgroup `wg` of the `nwg` that share the clip `a` describes adds up its
+// frames - wg * 256 + k * nwg * 256 ... - and leaves its five partial sums in part[0..4] and, with a.detail, its detail row in
+// dpart[0..R3D_DETAIL_DOUBLES).  `wg`, `nwg` and every field of `a` are the same for the whole workgroup.
+__device__ __forceinline__ void metrics_block(const MetricArgs &a, const int wg, const int nwg, double *part, double *dpart,
+                                              double (*red)[METRIC_THREADS], double (*cols)[JOINT_COLS], unsigned int *hist) {
     double acc[R3D_METRIC_COUNT] = {0, 0, 0, 0, 0};
     const int J = a.J;
     const bool detail = a.detail != nullptr;
@@ -239,7 +279,7 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
     // a wavefront walks the clip 64 frames at a time: its lanes stay together (the detail adds across them), a lane past
     // the clip's end idles
     const int lane = threadIdx.x & 63;
-    for (long long f0 = (long long)blockIdx.x * METRIC_THREADS + (threadIdx.x - lane); f0 < a.n; f0 += (long long)gridDim.x * METRIC_THREADS) {
+    for (long long f0 = (long long)wg * METRIC_THREADS + (threadIdx.x - lane); f0 < a.n; f0 += (long long)nwg * METRIC_THREADS) {
         const long long f = f0 + lane;
         const bool live = f < a.n;
         double p[MAX_J][3], g[MAX_J][3];
@@ -306,7 +346,7 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
     if (detail) {
         // the workgroup's detail row: its wavefronts' sums in index order, then the counts below each threshold
         __syncthreads();
-        double *row = a.detail + R3D_DETAIL_DOUBLES * (1 + (long long)blockIdx.x);
+        double *row = dpart;
         for (int c = threadIdx.x; c < R3D_DETAIL_DOUBLES; c += METRIC_THREADS) {
             double v = 0;
             if (c < JOINT_COLS) {
@@ -327,18 +367,52 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
         __syncthreads();
     }
     if (threadIdx.x == 0)
-        for (int k = 0; k < R3D_METRIC_COUNT; ++k) a.out[R3D_METRIC_COUNT * (1 + blockIdx.x) + k] = red[k][0];
+        for (int k = 0; k < R3D_METRIC_COUNT; ++k) part[k] = red[k][0];
 }
 
-__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail, double *valid) {
-    if (valid) {                 // the second launch of r3d_clip_valid_losses
-        valid_sum_rows(valid, blocks);
+__global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArgs a, ValidArgs valid, ClipsArgs clips) {
+    __shared__ double red[R3D_METRIC_COUNT][METRIC_THREADS];
+    __shared__ double cols[METRIC_WAVES][JOINT_COLS];
+    __shared__ unsigned int hist[R3D_DETAIL_THRESHOLDS + 1];
+    if (valid.out) {             // uniform: the whole launch is a validation-loss one (r3d_clip_valid_losses), `a` is unused
+        valid_block(valid, &red[0][0]);
         return;
     }
+    // r3d_clip_metrics(_detail): the clip of the arguments, every workgroup of the grid on it, partial rows behind the results
+    int nwg = gridDim.x;
+    double *part = a.out + R3D_METRIC_COUNT * (1 + (long long)blockIdx.x);
+    double *dpart = a.detail ? a.detail + R3D_DETAIL_DOUBLES * (1 + (long long)blockIdx.x) : nullptr;
+    if (clips.table) {
+        // uniform: r3d_clips_metrics - clip blockIdx.y of the table; its descriptor is read once, by scalar loads (one address
+        // for the workgroup), and decided on before anything else: an invalid one is not followed, a workgroup past the clip's
+        // own count has nothing to do
+        const r3d_clip_desc *d = clips.table + blockIdx.y;
+        const long long first = uniform((long long)d->first_frame), n = uniform((long long)d->n_frames);
+        if (!clip_desc_valid(first, n, clips)) return;
+        nwg = (int)metric_blocks(n);
+        if ((int)blockIdx.x >= nwg) return;
+        a.pred = clips.pred + first * clips.J * 3;
+        a.gt = clips.gt + first * clips.J * 3;
+        a.n = n;
+        a.J = clips.J;
+        for (int i = 0; i < 9; ++i) a.R[i] = uniform(d->rn2w[i]);
+        for (int i = 0; i < 3; ++i) a.T[i] = uniform(d->tn2w[i]);
+        a.frame = clips.frame ? clips.frame + first * R3D_METRIC_COUNT : nullptr;
+        a.detail = clips.dpart;  // (non-null: the detail mode; the rows themselves go to dpart)
+        const long long slot = (long long)blockIdx.y * clips.blocks + blockIdx.x;
+        part = clips.part + slot * R3D_METRIC_COUNT;
+        dpart = clips.dpart ? clips.dpart + slot * R3D_DETAIL_DOUBLES : nullptr;
+    }
+    metrics_block(a, (int)blockIdx.x, nwg, part, dpart, red, cols, hist);
+}
+
+// One wavefront adds a clip's `blocks` partial rows (part: five sums each; dpart, optional: detail rows) in index order into
+// out[0..4] and detail[0..R3D_DETAIL_DOUBLES): the second launch of both calls.
+__device__ __forceinline__ void metrics_sum_rows(const double *part, const double *dpart, int blocks, long long n, double *out, double *detail) {
     const int k = threadIdx.x;
     if (k < R3D_METRIC_COUNT) {
         double s = 0;
-        for (int b = 0; b < blocks; ++b) s += out[R3D_METRIC_COUNT * (1 + b) + k];
+        for (int b = 0; b < blocks; ++b) s += part[R3D_METRIC_COUNT * b + k];
         // n * mean over the n-1 differences (trainer.py:395 weights the clip's mean by its frame count); an empty mean
         // is NaN in NumPy
         if (k == R3D_METRIC_VELOCITY) s = n > 1 ? s * ((double)n / (double)(n - 1)) : nan("");
@@ -347,9 +421,33 @@ __global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int 
     if (detail)
         for (int c = threadIdx.x; c < R3D_DETAIL_DOUBLES; c += 64) {
             double s = 0;
-            for (int b = 0; b < blocks; ++b) s += detail[R3D_DETAIL_DOUBLES * (1 + b) + c];
+            for (int b = 0; b < blocks; ++b) s += dpart[R3D_DETAIL_DOUBLES * b + c];
             detail[c] = s;
         }
+}
+
+__global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail, double *valid, ClipsArgs clips) {
+    if (valid) {                 // the second launch of r3d_clip_valid_losses
+        valid_sum_rows(valid, blocks);
+        return;
+    }
+    if (clips.table) {           // ... of r3d_clips_metrics: workgroup c is clip c's wavefront
+        const r3d_clip_desc *d = clips.table + blockIdx.x;
+        const long long first = uniform((long long)d->first_frame);
+        n = uniform((long long)d->n_frames);
+        out = clips.rows + (long long)blockIdx.x * clips.row_stride;
+        detail = clips.detail ? clips.detail + (long long)blockIdx.x * clips.detail_stride : nullptr;
+        if (!clip_desc_valid(first, n, clips)) {      // nothing of the clip was read: its results are NaN
+            if (threadIdx.x < R3D_METRIC_COUNT) out[threadIdx.x] = nan("");
+            if (detail)
+                for (int c = threadIdx.x; c < R3D_DETAIL_DOUBLES; c += 64) detail[c] = nan("");
+            return;
+        }
+        const long long slot = (long long)blockIdx.x * clips.blocks;
+        metrics_sum_rows(clips.part + slot * R3D_METRIC_COUNT, detail ? clips.dpart + slot * R3D_DETAIL_DOUBLES : nullptr, (int)metric_blocks(n), n, out, detail);
+        return;
+    }
+    metrics_sum_rows(out + R3D_METRIC_COUNT, detail ? detail + R3D_DETAIL_DOUBLES : nullptr, blocks, n, out, detail);
 }
 
 }  // namespace
@@ -366,10 +464,37 @@ int launch_clip_metrics(const float *pred, const float *gt, long long n, int J, 
     a.J = J;
     for (int i = 0; i < 9; ++i) a.R[i] = Rn2w[i];
     for (int i = 0; i < 3; ++i) a.T[i] = Tn2w[i];
-    long long blocks = (n + METRIC_THREADS - 1) / METRIC_THREADS;
-    blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
-    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, ValidArgs{});
-    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n, detail, (double *)nullptr);
+    const long long blocks = metric_blocks(n);
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, ValidArgs{}, ClipsArgs{});
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, out, (int)blocks, n, detail, (double *)nullptr, ClipsArgs{});
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+size_t clips_metrics_scratch_bytes(int num_clips, long long max_frames, bool detail) {
+    return (size_t)num_clips * (size_t)metric_blocks(max_frames) * (R3D_METRIC_COUNT + (detail ? R3D_DETAIL_DOUBLES : 0)) * sizeof(double);
+}
+
+int launch_clips_metrics(const float *pred, const float *gt, long long total, int J, const r3d_clip_desc *table, int num_clips,
+                         long long max_frames, double *rows, long long row_stride, double *detail, long long detail_stride,
+                         double *frame, void *scratch, hipStream_t stream) {
+    ClipsArgs c = {};
+    c.table = table;
+    c.pred = pred;
+    c.gt = gt;
+    c.total = total;
+    c.max_frames = max_frames;
+    c.J = J;
+    c.blocks = (int)metric_blocks(max_frames);
+    c.rows = rows;
+    c.row_stride = row_stride;
+    c.detail = detail;
+    c.detail_stride = detail_stride;
+    c.frame = frame;
+    c.part = static_cast<double *>(scratch);
+    c.dpart = detail ? c.part + (size_t)num_clips * c.blocks * R3D_METRIC_COUNT : nullptr;
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)c.blocks, (unsigned)num_clips), dim3(METRIC_THREADS), 0, stream, MetricArgs{}, ValidArgs{}, c);
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3((unsigned)num_clips), dim3(64), 0, stream, (double *)nullptr, 0, 0ll, (double *)nullptr,
+                       (double *)nullptr, c);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -389,8 +514,8 @@ int launch_clip_valid(const float *pos, const float *trj, const float *gt, long 
     v.n = n;
     long long blocks = (n + VALID_THREADS - 1) / VALID_THREADS;
     blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
-    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, v);
-    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, (double *)nullptr, (int)blocks, n, (double *)nullptr, out);
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, v, ClipsArgs{});
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, (double *)nullptr, (int)blocks, n, (double *)nullptr, out, ClipsArgs{});
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

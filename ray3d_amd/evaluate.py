@@ -425,6 +425,143 @@ def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     return named, action_average(per), allrows, detail
 
 
+# ------------------------------------------------------------------------------------ a whole shard in one metrics call
+
+def clip_table(clips: Sequence[Clip], root_relative: bool = False):
+    """(table, first_frames, total_frames, max_frames) of `clips` laid out back to back in the given order: `table` a NumPy
+    structured array of r3d_clip_desc rows (``_capi.clip_desc_dtype()``) - clip k's frames are rows [first_frames[k],
+    first_frames[k] + N_k) of the shard's prediction / ground-truth buffers, its transform is :func:`clip_world_transform`'s -
+    to be uploaded once per data set (``torch.from_numpy(table.view(np.uint8))``) and handed to :func:`shard_metrics_hip`."""
+    from . import _capi
+    table = np.zeros(len(clips), dtype=_capi.clip_desc_dtype())
+    first_frames, at, longest = [], 0, 0
+    for k, c in enumerate(clips):
+        n = int(np.asarray(c.rays).shape[0])
+        R, T = clip_world_transform(c, root_relative)
+        table[k]["first_frame"], table[k]["n_frames"] = at, n
+        table[k]["rn2w"] = np.asarray(R, dtype=np.float64).reshape(9)
+        table[k]["tn2w"] = np.asarray(T, dtype=np.float64).reshape(3)
+        first_frames.append(at)
+        at += n
+        longest = max(longest, n)
+    return table, first_frames, at, longest
+
+
+_shard_scratch: Dict = {}    # device -> grow-only scratch of shard_metrics_hip
+
+
+def shard_metrics_hip(pred_all: torch.Tensor, gt_all: torch.Tensor, table_dev: torch.Tensor, num_clips: int, total_frames: int,
+                      max_frames: int, rows: torch.Tensor, detail_rows: Optional[torch.Tensor] = None,
+                      frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE r3d_clips_metrics call on the current stream for every clip of a shard: `pred_all` / `gt_all` (total_frames, J, 3)
+    (or (total_frames, 1, J, 3)) float32, `table_dev` the uploaded bytes of :func:`clip_table`, `rows` the (num_clips,
+    PARTIAL_COLS) float64 matrix of :func:`partial_rows` whose columns 3..7 are written in place - with the bits
+    :func:`clip_partials_hip` gives clip by clip; optional `detail_rows` (num_clips, DETAIL_COLS) and `frames` (total_frames, 5).
+    No copy, no allocation (the scratch is a cached tensor per device), no synchronisation."""
+    from . import _capi
+    dev = pred_all.device
+    for t, name in ((pred_all, "pred_all"), (gt_all, "gt_all")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape[0] != total_frames or t.shape[-1] != 3:
+            raise ValueError("%s: a contiguous float32 (total_frames, J, 3) tensor on %s is needed" % (name, dev))
+    J = pred_all.numel() // (3 * total_frames)
+    if pred_all.numel() != gt_all.numel():
+        raise ValueError("ground truth %s vs prediction %s" % (tuple(gt_all.shape), tuple(pred_all.shape)))
+    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
+        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
+    if rows.dtype != torch.float64 or rows.device != dev or tuple(rows.shape) != (num_clips, PARTIAL_COLS) or not rows.is_contiguous():
+        raise ValueError("rows: the contiguous float64 (%d, %d) matrix of partial_rows on %s is needed" % (num_clips, PARTIAL_COLS, dev))
+    if detail_rows is not None and (detail_rows.dtype != torch.float64 or detail_rows.device != dev or not detail_rows.is_contiguous()
+                                    or tuple(detail_rows.shape) != (num_clips, DETAIL_COLS)):
+        raise ValueError("detail_rows: a contiguous float64 (%d, %d) tensor on %s is needed" % (num_clips, DETAIL_COLS, dev))
+    if frames is not None and (frames.dtype != torch.float64 or frames.device != dev or not frames.is_contiguous()
+                               or tuple(frames.shape) != (total_frames, 5)):
+        raise ValueError("frames: a contiguous float64 (%d, 5) tensor on %s is needed" % (total_frames, dev))
+    nbytes = _capi.clips_metrics_scratch_bytes(num_clips, max_frames, detail_rows is not None)
+    scratch = _shard_scratch.get(dev)
+    if scratch is None or scratch.numel() < nbytes:
+        scratch = _shard_scratch[dev] = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _capi.clips_metrics(pred_all.data_ptr(), gt_all.data_ptr(), total_frames, J, table_dev.data_ptr(), num_clips, max_frames,
+                            rows.data_ptr() + 3 * 8, PARTIAL_COLS,
+                            detail_rows.data_ptr() if detail_rows is not None else None, DETAIL_COLS,
+                            frames.data_ptr() if frames is not None else None,
+                            scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    return rows
+
+
+def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
+                           kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
+                           rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
+                           joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                           root_relative: bool = False, mirror: Optional[Callable] = None, detail: bool = False,
+                           include_root: bool = False):
+    """:func:`evaluate_clips` (with `detail`: :func:`evaluate_clips_detail`, `include_root` as there) with the measuring side in
+    ONE call per shard: the rank's clip table and ground truth are uploaded once, every clip is lifted into its slice of one
+    prediction buffer (``lift_clip(padded, param_row, out=slice)``: ``Ray3DLifter.forward_clip``; the flip average is written
+    into the slice), and one :func:`shard_metrics_hip` call fills the error columns of all rows - then the same gather and
+    reduction.  Same arguments, same return values, the same bits in every row.  GPU only.  When `lift_clip` is the bound
+    ``forward_clip`` of a lifter with lanes (``set_lanes``), the clips are dealt to the lanes and joined once, before the
+    metrics call."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
+    actions = sorted(set(c.action for c in clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
+    mine = [clips[idx] for idx in shards[rank]]
+    local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], dev)
+    dlocal = torch.zeros((len(mine), DETAIL_COLS), dtype=torch.float64, device=dev) if detail else None
+    if mine:
+        table, first, total, longest = clip_table(mine, root_relative)
+        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+        gt_all = torch.from_numpy(np.concatenate(
+            [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        J = gt_all.shape[1]
+        pred_all = torch.empty((total, 1, J, 3), dtype=torch.float32, device=dev)
+        lifter = getattr(lift_clip, "__self__", None)
+        lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
+        pad = (rf - 1) // 2
+        jl = kps_left if joints_left is None else joints_left
+        jr = kps_right if joints_right is None else joints_right
+
+        def lift_into(c, dst):
+            padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
+            prow = torch.from_numpy(c.camera.param()).to(dev)
+            lift_clip(padded, prow, out=dst)
+            if flip:
+                pred_m = lift_clip(mirror(padded) if mirror is not None else mirror_input(padded, kps_left, kps_right), prow)
+                torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as predict_clip rounds it
+                dst.mul_(0.5)
+
+        for k, c in enumerate(mine):
+            dst = pred_all[first[k]:first[k] + c.rays.shape[0]]
+            if lanes:
+                with lifter.lane():          # the clip's forwards and its flip average on the next lane's stream
+                    lift_into(c, dst)
+            else:
+                lift_into(c, dst)
+        if lanes:
+            lifter.join_lanes()
+        shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)
+    if world_size > 1:
+        counts = [len(s) for s in shards]
+        allrows = gather_partials(local, counts, group)
+        alldetail = gather_partials(dlocal, counts, group, cols=DETAIL_COLS) if detail else None
+    else:
+        allrows, alldetail = local, dlocal
+    if not detail:
+        per = reduce_partials(allrows)
+        return {actions[a]: v for a, v in per.items()}, action_average(per), allrows
+    order = torch.argsort(allrows[:, 0], stable=True)
+    allrows, alldetail = allrows[order], alldetail[order]
+    per = reduce_partials(allrows)
+    named = {actions[a]: v for a, v in per.items()}
+    tables = reduce_detail(allrows, alldetail, clips[0].gt_norm.shape[1] if len(clips) else 0, include_root)
+    out = {(actions[a] if a != "overall" else a): t for a, t in tables.items()}
+    out["rows"] = alldetail
+    return named, action_average(per), allrows, out
+
+
 def format_detail_report(table: Dict, joint_names: Optional[Sequence[str]] = None) -> List[str]:
     """Plain text for one table of :func:`reduce_detail`: one line per joint, then the PCK / AUC line."""
     nj = len(table["mpjpe"])

@@ -546,7 +546,8 @@ class Ray3DLifter(nn.Module):
                 sizes.append(up)
         return sizes
 
-    def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False):
+    def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False,
+                     out: Optional[torch.Tensor] = None):
         """clip (N + RF - 1, J, F): an edge-padded sequence; window i = frames [i, i+RF) is gathered
         in the kernels instead of materialising lib/train_val/trainer.py:47-58's copy.
         param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3) - with `return_trj` the pair
@@ -554,7 +555,12 @@ class Ray3DLifter(nn.Module):
 
         The library keeps one tile schedule per batch size, and every clip has its own length: the windows are
         lifted in the batch sizes of :meth:`clip_batch_sizes` (the surplus windows slide over repeated last frames
-        and their poses are cut off), so that a whole evaluation uses a handful of batch sizes."""
+        and their poses are cut off), so that a whole evaluation uses a handful of batch sizes.
+
+        `out`: a contiguous (N,1,J,3) float32 tensor on the clip's device - e.g. the clip's slice of a shard's prediction
+        buffer (evaluate.evaluate_clips_batched) - that the poses are written into and that is returned in place of a new
+        tensor; the same forwards of the same sizes run, so the poses have the bits of a call without it.  A call whose
+        rounded-up size reaches past the N rows goes through a scratch tensor and its first rows are copied in."""
         rf = self.receptive_field()
         assert clip.dim() == 3 and clip.shape[1] == self.pos.num_joints_in and clip.shape[2] == self.pos.in_features
         n = clip.shape[0] - rf + 1
@@ -565,6 +571,8 @@ class Ray3DLifter(nn.Module):
             if self.pos.camera_embedding else None
         sizes = self.clip_batch_sizes(n)
         total = sum(sizes)
+        if out is not None:
+            return self._forward_clip_into(clip, p, n, sizes, return_trj, out)
         if total == n and len(sizes) == 1:
             return self._run(_capi.R3D_INPUT_RAYS, clip, 1, n, p, 0, return_trj=return_trj)
         if total > n:
@@ -581,6 +589,32 @@ class Ray3DLifter(nn.Module):
             return out[:n]
         self.join_lanes()      # (the pieces were written on the lanes' streams: the concatenation below runs on the caller's)
         return out[:n], torch.cat(trjs, dim=0)[:n]
+
+    def _forward_clip_into(self, clip, p, n, sizes, return_trj, out):
+        """forward_clip(out=): the forwards of `sizes` written straight into `out` (n rows) where they fit."""
+        J = self.pos.num_joints_in
+        if tuple(out.shape) != (n, 1, J, 3) or out.dtype != torch.float32 or out.device != clip.device or not out.is_contiguous():
+            raise ValueError("forward_clip(out=): a contiguous float32 (%d, 1, %d, 3) tensor on %s is needed (got %s %s on %s)"
+                             % (n, J, clip.device, tuple(out.shape), out.dtype, out.device))
+        total = sum(sizes)
+        if total > n:
+            clip = torch.cat([clip, clip[-1:].expand(total - n, -1, -1)], dim=0)
+        trjs, tails = [], []
+        start = 0
+        for b in sizes:
+            fits = start + b <= n
+            dst = out[start:start + b] if fits else torch.empty((b, 1, J, 3), dtype=torch.float32, device=clip.device)
+            res = self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, return_trj=return_trj, out=dst)
+            if not fits and start < n:
+                tails.append((start, dst))
+            if return_trj:
+                trjs.append(res[1])
+            start += b
+        if (tails or return_trj) and self._lane_of_current_stream(clip.device) is None:
+            self.join_lanes()  # (forwards relayed to the lanes' streams: what follows runs on the caller's)
+        for at, piece in tails:
+            out[at:] = piece[:n - at]
+        return (out, torch.cat(trjs, dim=0)[:n]) if return_trj else out
 
     def prepare(self, batch_sizes, device=None):
         """Build and upload the tile schedules of these batch sizes now (r3d_prepare) instead of inside the first

@@ -412,6 +412,60 @@ int r3d_clips_metrics(const float *pred_dev, const float *gt_dev, int64_t total_
                       double *frame_dev,                             /* optional (NULL): (total_frames, R3D_METRIC_COUNT) */
                       void *scratch_dev, size_t scratch_bytes, void *stream);
 
+/* ---- a shard's model inputs from raw pixels: pad, encode and mirror every clip in one call ---- */
+
+/* The input side of a clip evaluation on the device - the counterpart of what the reference does once per data set at load
+ * time (lib/dataset/__init__.py:167-189: every sequence encoded) and per sequence in its generator
+ * (lib/dataloader/generators.py:213-216: np.pad(..., 'edge')).  ONE launch turns a shard's raw pixel archive px_dev
+ * (total_frames, J, 2) float32 into the edge-padded, encoded float32 inputs x_dev (out_rows, J, F) that a R3D_INPUT_RAYS
+ * forward with window_stride 1 reads (F = 3 for R3D_ENCODE_RAY, 2 for the other two), clip by clip over a table of
+ * descriptors in DEVICE memory.  Clip c writes output rows [out_first, out_first + pad_front + n_frames + pad_back); its
+ * row r is the encoding of source frame first_frame + clamp(r - pad_front, 0, n_frames - 1) through the clip's camera row
+ * `cam` (the 16 doubles of R3D_INPUT_UV_DIST / R3D_INPUT_PX_*).  pad_back may carry, on top of the receptive field's pad,
+ * the surplus rows of a rounded-up batch size.  Rows that no valid clip covers are left untouched.  Clips may lie in the
+ * buffers in any order, with gaps; overlapping OUTPUT ranges of two valid clips are the caller's error (either value may
+ * win, nothing leaves the extents).
+ *   x_mirror_dev / mirror_perm: both NULL, or both given: the flip pass's inputs (lib/train_val/trainer.py:299-302 on the
+ *               ENCODED input - also right for distorted cameras, whose pixels have no exact mirror image):
+ *               x_mirror_dev[row, j] = x_dev[row, mirror_perm[j]] with component 0 negated, same layout and extents as
+ *               x_dev.  mirror_perm is a HOST array of J entries, a permutation of 0..J-1; it travels as a kernel argument.
+ *   status_dev: num_clips int32 words, required: 0 for a clip that was followed, 1 for an invalid descriptor.
+ * BIT-FOR-BIT WITH THE PRE-PASS.  Every value is what the pre-pass of a R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC /
+ * R3D_INPUT_PX_SCREEN forward writes for that pixel and camera row: the same float64 routines, the same single cast to
+ * float32 (zero coefficients: R3D_INPUT_UV's values).  A padding row is encoded again from the frame it repeats and has its
+ * bits; the negation of the mirrored copy is exact.
+ * GRID.  max_rows is the caller's bound on any clip's pad_front + n_frames + pad_back and sizes the grid:
+ * (ceil(max_rows * num_joints / 256), num_clips) workgroups, one output point per thread; a workgroup past its clip's points
+ * returns at once.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A descriptor is invalid when n_frames < 1, a pad is < 0, pad_front +
+ * n_frames + pad_back > max_rows, [first_frame, first_frame + n_frames) is not inside [0, total_frames), or the output rows
+ * are not inside [0, out_rows).  The kernel never follows an invalid descriptor: nothing of that clip is read or written,
+ * status_dev[c] = 1.  Beyond the descriptors it reads px_dev within total_frames * num_joints * 2 floats and the table within
+ * num_clips descriptors, and writes x_dev / x_mirror_dev within out_rows * num_joints * F floats and status_dev within
+ * num_clips words: no input can make it touch memory outside these extents.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (px_dev, clips_dev, x_dev, status_dev),
+ * num_clips outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, an unknown encoding, max_rows, total_frames or out_rows < 1,
+ * max_rows * num_joints, total_frames or out_rows above R3D_ENCODE_MAX_POINTS (index arithmetic), exactly one of
+ * x_mirror_dev / mirror_perm, a mirror_perm that is not a permutation, a table pointer that is not 8-byte aligned.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+typedef struct {
+    int64_t first_frame;  /* row of the clip's first frame in px_dev                       */
+    int64_t n_frames;
+    int64_t out_first;    /* row of the clip's first OUTPUT row in x_dev / x_mirror_dev     */
+    int32_t pad_front;    /* output rows in front that repeat frame 0                       */
+    int32_t pad_back;     /* output rows behind that repeat frame n_frames - 1              */
+    double  cam[16];      /* the 16-double camera row of R3D_INPUT_UV_DIST / PX_*           */
+} r3d_clip_input_desc;    /* 160 bytes, 8-byte aligned; lives in DEVICE memory */
+#define R3D_ENCODE_RAY 0        /* 3 floats, as the R3D_INPUT_UV_DIST pre-pass writes them  */
+#define R3D_ENCODE_INTRINSIC 1  /* 2 floats, R3D_INPUT_PX_INTRINSIC                          */
+#define R3D_ENCODE_SCREEN 2     /* 2 floats, R3D_INPUT_PX_SCREEN                             */
+#define R3D_ENCODE_MAX_POINTS 2147483391 /* 2^31 - 257: max_rows * num_joints (the grid), total_frames, out_rows */
+int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                     const r3d_clip_input_desc *clips_dev, int32_t num_clips, int64_t max_rows,
+                     float *x_dev, int64_t out_rows,
+                     float *x_mirror_dev, const int32_t *mirror_perm,   /* both NULL: no mirrored copy */
+                     int32_t *status_dev, void *stream);
+
 /* ---- per-clip validation losses: Trainer.test after the forwards ---- */
 
 /* lib/train_val/trainer.py:187-223 for one clip of n_frames frames, in the NORMALISED frame (no world transform): the
@@ -519,6 +573,11 @@ int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, i
  * the frames added up by a plain index-order sum: `out` R3D_VALID_DOUBLES doubles, `frame` (n, R3D_VALID_COUNT) or NULL. */
 int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t n_frames, int32_t num_joints,
                                 const int32_t *parents, int32_t flags, double *out, double *frame);
+/* r3d_clips_encode on the host (HOST pointers throughout): the same argument checks, the same descriptor rules and
+ * row-to-source mapping, the same per-keypoint routines and cast, clips in table order. */
+int r3d_debug_clips_encode_host(const float *px, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                                const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
+                                float *x_mirror, const int32_t *mirror_perm, int32_t *status);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

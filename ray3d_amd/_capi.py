@@ -31,9 +31,11 @@ EXPORTS = (
     "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_clip_valid_losses", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
+    "r3d_clips_encode",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
-                "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host")
+                "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
+                "r3d_debug_clips_encode_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -47,6 +49,10 @@ VALID_DOUBLES = VALID_COUNT + VALID_BONE_ROWS * VALID_MAX_BONES         # R3D_VA
 VALID_OUT_DOUBLES = VALID_DOUBLES * (1 + 128)                           # R3D_VALID_OUT_DOUBLES
 METRIC_COUNT, METRIC_MAX_BLOCKS, METRIC_THREADS = 5, 128, 256           # R3D_METRIC_COUNT, _MAX_BLOCKS; frames per workgroup
 CLIPS_MAX = 65535                                                       # R3D_CLIPS_MAX
+R3D_ENCODE_RAY, R3D_ENCODE_INTRINSIC, R3D_ENCODE_SCREEN = 0, 1, 2       # `encoding` of r3d_clips_encode
+ENCODE_FLOATS = {R3D_ENCODE_RAY: 3, R3D_ENCODE_INTRINSIC: 2, R3D_ENCODE_SCREEN: 2}   # floats per encoded keypoint
+ENCODE_MAX_POINTS = 2 ** 31 - 257                                       # R3D_ENCODE_MAX_POINTS
+CLIP_INPUT_DESC_BYTES = 160                                             # sizeof(r3d_clip_input_desc)
 
 
 class Config(C.Structure):
@@ -70,6 +76,14 @@ def clip_desc_dtype():
     """The NumPy structured dtype with r3d_clip_desc's layout: an array of it, uploaded as bytes, is the table."""
     import numpy as np
     return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("rn2w", np.float64, (9,)), ("tn2w", np.float64, (3,))])
+
+
+def clip_input_desc_dtype():
+    """The NumPy structured dtype with r3d_clip_input_desc's layout (160 bytes): an array of it, uploaded as bytes, is the
+    table r3d_clips_encode reads."""
+    import numpy as np
+    return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("out_first", np.int64),
+                     ("pad_front", np.int32), ("pad_back", np.int32), ("cam", np.float64, (16,))])
 
 
 class LaunchRecord(C.Structure):
@@ -147,12 +161,16 @@ def load():
     lib.r3d_clips_metrics_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int]
     lib.r3d_clips_metrics_scratch_bytes.restype = C.c_size_t
     lib.r3d_clips_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_size_t, vp]
+    lib.r3d_clips_encode.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
+                                     C.POINTER(C.c_int32), vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
         lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.r3d_debug_encode_px_host.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
         lib.r3d_debug_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp]
+        lib.r3d_debug_clips_encode_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
+                                                    C.POINTER(C.c_int32), vp]
     for name in EXPORTS + (HOOK_EXPORTS if _hooks else ()):
         fn = getattr(lib, name)
         if fn.restype is C.c_int or fn.restype is None:
@@ -331,6 +349,18 @@ def clips_metrics(pred_ptr: int, gt_ptr: int, total_frames: int, num_joints: int
     check(load().r3d_clips_metrics(pred_ptr, gt_ptr, total_frames, num_joints, table_ptr, num_clips, max_frames, rows_ptr, row_stride,
                                    detail_ptr or None, detail_stride, frame_ptr or None, scratch_ptr, scratch_bytes, stream),
           "r3d_clips_metrics")
+
+
+def clips_encode(px_ptr: int, total_frames: int, num_joints: int, encoding: int, table_ptr: int, num_clips: int, max_rows: int,
+                 x_ptr: int, out_rows: int, x_mirror_ptr: Optional[int], mirror_perm, status_ptr: int, stream: int):
+    """r3d_clips_encode: every pointer is device memory; `table_ptr` num_clips r3d_clip_input_desc
+    (:func:`clip_input_desc_dtype`) back to back; `x_mirror_ptr` (or None) and `mirror_perm` (a host sequence of num_joints
+    ints, or None) go together; `status_ptr` num_clips int32."""
+    if mirror_perm is not None and len(mirror_perm) != num_joints:
+        raise Ray3DHipError("r3d_clips_encode: mirror_perm has %d entries, num_joints is %d" % (len(mirror_perm), num_joints))
+    perm = (C.c_int32 * len(mirror_perm))(*[int(v) for v in mirror_perm]) if mirror_perm is not None else None
+    check(load().r3d_clips_encode(px_ptr, total_frames, num_joints, encoding, table_ptr, num_clips, max_rows, x_ptr, out_rows,
+                                  x_mirror_ptr or None, perm, status_ptr, stream), "r3d_clips_encode")
 
 
 def _parent_table(parents):

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "r3d_internal.hpp"
+#include "r3d_undistort.hpp"
 
 using namespace r3d;
 
@@ -25,6 +26,45 @@ int r3d::valid_check_args(const char *what, const float *pos, const float *trj, 
                 return R3D_ERR_ARG;
             }
     }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_clips_encode, shared with its host hook (`what`: the name in the message)
+int r3d::clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
+                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
+                                 const float *x_mirror, const int32_t *mirror_perm, const int32_t *status) {
+    static_assert(sizeof(r3d_clip_input_desc) == 160, "r3d_clip_input_desc is documented as 160 bytes");
+    if (!px || !clips || !x || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (encoding != R3D_ENCODE_RAY && encoding != R3D_ENCODE_INTRINSIC && encoding != R3D_ENCODE_SCREEN) {
+        set_error("%s: unknown encoding %d", what, encoding);
+        return R3D_ERR_ARG;
+    }
+    if (max_rows < 1 || total_frames < 1 || out_rows < 1) {
+        set_error("%s: max_rows, total_frames and out_rows must be >= 1 (got %lld, %lld, %lld)", what, (long long)max_rows,
+                  (long long)total_frames, (long long)out_rows);
+        return R3D_ERR_ARG;
+    }
+    if (max_rows > R3D_ENCODE_MAX_POINTS / J || total_frames > R3D_ENCODE_MAX_POINTS || out_rows > R3D_ENCODE_MAX_POINTS) {
+        set_error("%s: max_rows * num_joints, total_frames and out_rows must not exceed %d", what, R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if ((x_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (mirror_perm) {
+        unsigned seen = 0;
+        for (int j = 0; j < J; ++j) {
+            if (mirror_perm[j] < 0 || mirror_perm[j] >= J || (seen >> mirror_perm[j] & 1u)) {
+                set_error("%s: mirror_perm must be a permutation of 0..%d (entry %d is %d)", what, J - 1, j, mirror_perm[j]);
+                return R3D_ERR_ARG;
+            }
+            seen |= 1u << mirror_perm[j];
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(clips) % 8) { set_error("%s: the clip table must be 8-byte aligned", what); return R3D_ERR_ARG; }
     return R3D_OK;
 }
 
@@ -187,6 +227,33 @@ int r3d_clip_metrics_detail(const float *pred_dev, const float *gt_dev, int64_t 
     if (num_joints < 1 || num_joints > 17) { r3d::set_error("r3d_clip_metrics_detail: num_joints must be in 1..17 (got %d)", num_joints); return R3D_ERR_ARG; }
     if (r3d::launch_clip_metrics(pred_dev, gt_dev, n_frames, num_joints, rn2w, tn2w, out_dev, frame_dev, detail_dev, (hipStream_t)stream)) {
         r3d::set_error("r3d_clip_metrics_detail: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                     const r3d_clip_input_desc *clips_dev, int32_t num_clips, int64_t max_rows, float *x_dev, int64_t out_rows,
+                     float *x_mirror_dev, const int32_t *mirror_perm, int32_t *status_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    const int rc = clips_encode_check_args("r3d_clips_encode", px_dev, total_frames, num_joints, encoding, clips_dev, num_clips, max_rows,
+                                           x_dev, out_rows, x_mirror_dev, mirror_perm, status_dev);
+    if (rc != R3D_OK) return rc;
+    r3d::ClipsEncArgs a = {};
+    a.table = clips_dev;
+    a.px = px_dev;
+    a.x = x_dev;
+    a.x_mirror = x_mirror_dev;
+    a.status = status_dev;
+    a.total_frames = total_frames;
+    a.out_rows = out_rows;
+    a.max_rows = max_rows;
+    if (mirror_perm) r3d::mirror_pack_inverse(mirror_perm, num_joints, a.mirror_inv);
+    a.J = num_joints;
+    a.encoding = encoding;
+    const hipError_t err = r3d::launch_clips_encode(a, num_clips, (hipStream_t)stream);   // (the launcher consumed the error: print what it returned)
+    if (err != hipSuccess) {
+        set_error("r3d_clips_encode: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -266,6 +266,39 @@ int r3d_debug_encode_px_host(const double *row16, const double *uv, int64_t n, i
     return R3D_OK;
 }
 
+// Test hook: r3d_clips_encode on the host - its argument rules (clips_encode_check_args), its descriptor rules and row mapping
+// and the pre-pass's per-keypoint routine (r3d_undistort.hpp), clip by clip in table order.
+int r3d_debug_clips_encode_host(const float *px, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                                const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
+                                float *x_mirror, const int32_t *mirror_perm, int32_t *status) {
+    const int rc = clips_encode_check_args("r3d_debug_clips_encode_host", px, total_frames, num_joints, encoding, clips, num_clips, max_rows,
+                                           x, out_rows, x_mirror, mirror_perm, status);
+    if (rc != R3D_OK) return rc;
+    unsigned long long inv[2] = {0ull, 0ull};
+    if (mirror_perm) mirror_pack_inverse(mirror_perm, num_joints, inv);
+    const int J = num_joints, F = enc_floats(encoding);
+    for (int32_t c = 0; c < num_clips; ++c) {
+        const r3d_clip_input_desc &d = clips[c];
+        const bool ok = clip_input_valid(d.first_frame, d.n_frames, d.out_first, d.pad_front, d.pad_back, total_frames, out_rows, max_rows);
+        status[c] = ok ? 0 : 1;
+        if (!ok) continue;
+        const long long rows = d.pad_front + d.n_frames + d.pad_back;
+        for (long long r = 0; r < rows; ++r)
+            for (int j = 0; j < J; ++j) {
+                const long long src = (d.first_frame + clip_input_source(r, d.pad_front, d.n_frames)) * J + j;
+                const long long row0 = (d.out_first + r) * J;
+                const EncodedPoint pt = encode_point_f32(d.cam, encoding, (double)px[2 * src], (double)px[2 * src + 1]);
+                const float e[3] = {pt.x, pt.y, pt.z};
+                for (int k = 0; k < F; ++k) x[F * (row0 + j) + k] = e[k];
+                if (x_mirror) {
+                    float *m = x_mirror + F * (row0 + mirror_dest(inv[0], inv[1], j));
+                    for (int k = 0; k < F; ++k) m[k] = k == 0 ? -e[k] : e[k];
+                }
+            }
+    }
+    return R3D_OK;
+}
+
 // Test hook: the per-frame routines of r3d_clip_valid_losses (r3d_valid.hpp) on the host, frames added in index order.
 int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t n_frames, int32_t num_joints,
                                 const int32_t *parents, int32_t flags, double *out, double *frame) {

@@ -141,6 +141,20 @@ struct UndistArgs {
     int encoding;                  // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN (r3d_undistort.hpp), the same for every point
 };
 
+// r3d_clips_encode: the second argument set of r3d_undistort_rays_f64 (table == nullptr: the forwards' pre-pass, UndistArgs).
+// blockIdx.y names a clip of the device-side table; one output point (row, joint) per thread.
+struct ClipsEncArgs {
+    const r3d_clip_input_desc *table;   // num_clips (= gridDim.y) descriptors in device memory
+    const float *px;                    // (total_frames, J, 2) raw pixels
+    float *x;                           // (out_rows, J, F) encoded inputs
+    float *x_mirror;                    // the flip pass's inputs, or nullptr
+    int32_t *status;                    // num_clips words: 0 followed, 1 invalid descriptor
+    long long total_frames, out_rows, max_rows;
+    unsigned long long mirror_inv[2];   // mirror_pack_inverse (r3d_undistort.hpp)
+    int J;
+    int encoding;                       // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN
+};
+
 constexpr int MAX_DEC = 6;     // 5 body-part decoders + the trajectory decoder
 // Fused decoder tail: the last Linear (1024 -> 3*n_g) of every Integration block, the joint
 // reassembly (rie.py:415-432) and the trajectory add (trainer.py:353) in one pass.
@@ -490,6 +504,11 @@ void lanes_destroy(Model *m);
 int valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t n, int32_t J,
                      const int32_t *parents, int32_t flags, const double *out);
 
+// the argument rules of r3d_clips_encode, shared with its host hook (r3d_api.cpp)
+int clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
+                            const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
+                            const float *x_mirror, const int32_t *mirror_perm, const int32_t *status);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -564,6 +583,7 @@ const char *forward_kernel_name(int kind, bool uv);
 int forward_resident_capacity(int kind, bool uv);      // workgroups of that kernel the current device holds at once (0: unknown)
 hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip): every encoding
+hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // the same kernel, one grid row per clip
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

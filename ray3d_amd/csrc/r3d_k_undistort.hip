@@ -9,12 +9,47 @@
 //   ENC_SCREEN     no undistortion: the 2 floats (u/w*2 - 1, v/w*2 - h/w) from the row's resolution slots.
 // Memory-streaming elementwise work: consecutive threads read consecutive 8-byte pixel pairs and write consecutive 12-
 // or 8-byte outputs; the camera rows (a few KiB for a batch) come from the caches.
+//
+// r3d_clips_encode (a shard's padded model inputs from its raw pixel archive, include/ray3d_hip.h) runs on the same kernel with
+// its ClipsEncArgs argument set: blockIdx.y names a clip of the device-side table, the workgroup reads the clip's descriptor -
+// and with it the camera row - once, by scalar loads (one address for the workgroup), decides on it before anything else, and
+// each thread then encodes one output point (row, joint) from the clamped source frame through encode_point_f32, the routine
+// the pre-pass itself writes with: the same bits, also in the padding rows.  (One kernel, two argument sets, as the clip
+// metrics are: the library's kernel set stays what tests/test_host.py pins.)
 #include "r3d_internal.hpp"
 #include "r3d_undistort.hpp"
 
 namespace r3d {
 
-extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a) {
+extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c) {
+    if (c.table) {                           // uniform: r3d_clips_encode - clip blockIdx.y of the table
+        const r3d_clip_input_desc *d = c.table + blockIdx.y;
+        const long long first = d->first_frame, n = d->n_frames, out_first = d->out_first;
+        const int pad_front = d->pad_front, pad_back = d->pad_back;
+        const bool ok = clip_input_valid(first, n, out_first, pad_front, pad_back, c.total_frames, c.out_rows, c.max_rows);
+        if (blockIdx.x == 0 && threadIdx.x == 0) c.status[blockIdx.y] = ok ? 0 : 1;
+        if (!ok) return;                     // an invalid descriptor is not followed: nothing of the clip is read or written
+        // (max_rows * J fits in 31 bits - checked on the host - and so do the clip's points and this launch's indices)
+        const int npts = (int)(pad_front + n + pad_back) * c.J;
+        const int p = blockIdx.x * blockDim.x + threadIdx.x;
+        if (p >= npts) return;               // also the workgroups past the clip's own count
+        const int r = p / c.J, j = p - r * c.J;
+        const long long src = (first + clip_input_source(r, pad_front, n)) * c.J + j;
+        const long long row0 = (out_first + r) * c.J;
+        const int F = enc_floats(c.encoding);
+        const EncodedPoint e = encode_point_f32(d->cam, c.encoding, (double)c.px[2 * src], (double)c.px[2 * src + 1]);
+        float *o = c.x + F * (row0 + j);
+        o[0] = e.x;
+        o[1] = e.y;
+        if (F == 3) o[2] = e.z;
+        if (c.x_mirror) {                    // trainer.py:299-302 on the encoded input: x -> -x (exact), left <-> right
+            float *m = c.x_mirror + F * (row0 + mirror_dest(c.mirror_inv[0], c.mirror_inv[1], j));
+            m[0] = -e.x;
+            m[1] = e.y;
+            if (F == 3) m[2] = e.z;
+        }
+        return;
+    }
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.npts) return;
     int src = p, w;
@@ -26,34 +61,24 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
     }
     const double *row = a.cam + (long long)w * a.cam_stride;
     const double u = (double)a.uv[2 * (long long)src], v = (double)a.uv[2 * (long long)src + 1];
-    if (a.encoding == ENC_SCREEN) {          // raw pixels and the image size: no undistortion, no intrinsics
-        double e[2];
-        pixel_to_screen(row[UNDIST_ROW_RES_W], row[UNDIST_ROW_RES_H], u, v, e);
-        float *o = a.rays + 2 * (long long)p;
-        o[0] = (float)e[0];
-        o[1] = (float)e[1];
-        return;
-    }
-    const UndistRow k = undist_row(row);
-    double uo, vo, e[2], r[3];
-    undistort_pixel(k, u, v, uo, vo);
-    pixel_to_intrinsic(k, uo, vo, e);        // (shared: the ray's first component and the argument of the other two)
-    if (a.encoding == ENC_INTRINSIC) {
-        float *o = a.rays + 2 * (long long)p;
-        o[0] = (float)e[0];
-        o[1] = (float)e[1];
-        return;
-    }
-    intrinsic_to_ray(k, e, r);
-    float *o = a.rays + 3 * (long long)p;
-    o[0] = (float)r[0];
-    o[1] = (float)r[1];
-    o[2] = (float)r[2];
+    const int F = enc_floats(a.encoding);
+    const EncodedPoint e = encode_point_f32(row, a.encoding, u, v);
+    float *o = a.rays + F * (long long)p;
+    o[0] = e.x;
+    o[1] = e.y;
+    if (F == 3) o[2] = e.z;
 }
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args);
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{});
+    return hipGetLastError();
+}
+
+// r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
+hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
+    const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args);
     return hipGetLastError();
 }
 

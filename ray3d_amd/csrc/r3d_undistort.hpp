@@ -1,6 +1,6 @@
 // R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: the per-keypoint arithmetic of the pixel pre-pass
 // (r3d_k_undistort.hip), __host__ __device__ so that the hooks build runs the very same routines on the CPU
-// (r3d_debug_undistort_host, r3d_debug_encode_px_host).  float64 throughout, in the reference's order
+// (r3d_debug_undistort_host, r3d_debug_encode_px_host, r3d_debug_clips_encode_host).  float64 throughout, in the reference's order
 // (lib/camera/camera.py:412-441): cv2.undistortPoints(uv, K, dist, P=K) - five fixed-point iterations of OpenCV's
 // documented algorithm for the 5-coefficient Brown-Conrady model, then re-projection with K - followed by one of three
 // encodings: the ray of get_cam_ray_given_uv (:460-471), the two components of encode_uv_with_intrinsic (:438-439), or -
@@ -11,6 +11,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
 
 namespace r3d {
 
@@ -94,6 +96,66 @@ __host__ __device__ inline void encode_pixel_2d(const double *row, int encoding,
     double uo, vo;
     undistort_pixel(k, u, v, uo, vo);
     pixel_to_intrinsic(k, uo, vo, o);
+}
+
+// One keypoint through the encoding `encoding` from its 16-double camera row, cast ONCE to float32 (z: ENC_RAY only, 0
+// otherwise): what r3d_undistort_rays_f64 writes per point, for both of its argument sets (the forwards' pre-pass and
+// r3d_clips_encode), and what the hooks' r3d_debug_clips_encode_host writes on the CPU.  `encoding` is uniform over a launch:
+// scalar branches.  (Values, not an output array: nothing of it lives in scratch memory.)
+struct EncodedPoint { float x, y, z; };
+__host__ __device__ __forceinline__ EncodedPoint encode_point_f32(const double *row, int encoding, double u, double v) {
+    double e[2], z = 0.0;
+    if (encoding == ENC_SCREEN) {            // raw pixels and the image size: no undistortion, no intrinsics
+        pixel_to_screen(row[UNDIST_ROW_RES_W], row[UNDIST_ROW_RES_H], u, v, e);
+    } else {
+        const UndistRow k = undist_row(row);
+        double uo, vo;
+        undistort_pixel(k, u, v, uo, vo);
+        pixel_to_intrinsic(k, uo, vo, e);    // (shared: the ray's first component and the argument of the other two)
+        if (encoding != ENC_INTRINSIC) {
+            double r[3];
+            intrinsic_to_ray(k, e, r);
+            e[0] = r[0];
+            e[1] = r[1];
+            z = r[2];
+        }
+    }
+    return EncodedPoint{(float)e[0], (float)e[1], (float)z};
+}
+
+// ---- r3d_clips_encode: the descriptor rules and the row-to-source mapping, shared by the kernel and the host hook ----
+
+// A descriptor the call follows (include/ray3d_hip.h: "invalid descriptors", written so that no sum can overflow): at least
+// one frame, no negative pad, pad_front + n + pad_back <= max_rows, the source frames inside [0, total_frames), the output
+// rows inside [0, out_rows).
+__host__ __device__ inline bool clip_input_valid(long long first, long long n, long long out_first, int pad_front, int pad_back,
+                                                 long long total_frames, long long out_rows, long long max_rows) {
+    if (n < 1 || pad_front < 0 || pad_back < 0 || n > max_rows) return false;
+    const long long pads = (long long)pad_front + pad_back;
+    if (pads > max_rows - n) return false;
+    if (first < 0 || n > total_frames || first > total_frames - n) return false;
+    const long long rows = n + pads;
+    return out_first >= 0 && rows <= out_rows && out_first <= out_rows - rows;
+}
+
+// Output row r of a clip repeats source frame clamp(r - pad_front, 0, n - 1): np.pad(..., 'edge') (generators.py:213-216)
+__host__ __device__ inline long long clip_input_source(long long r, int pad_front, long long n) {
+    const long long f = r - pad_front;
+    return f < 0 ? 0 : (f > n - 1 ? n - 1 : f);
+}
+
+// The mirrored copy writes point j of the plain buffer to point inv[j] (the inverse of mirror_perm), 5 bits per joint, 12
+// joints per word - kernel arguments, like the parent table of the validation losses.
+__host__ __device__ inline int mirror_dest(unsigned long long w0, unsigned long long w1, int j) {
+    return (int)((j < 12 ? w0 >> (5 * j) : w1 >> (5 * (j - 12))) & 31ull);
+}
+// mirror_perm (J entries, a permutation of 0..J-1: the caller checked) -> its packed inverse
+inline void mirror_pack_inverse(const int32_t *perm, int J, unsigned long long w[2]) {
+    w[0] = w[1] = 0ull;
+    for (int j = 0; j < J; ++j) {
+        const int src = perm[j];             // x_mirror[row, j] = x[row, src]: the thread of point src writes to j
+        w[src < 12 ? 0 : 1] |= (unsigned long long)j << (5 * (src < 12 ? src : src - 12));
+    }
 }
 
 }  // namespace r3d

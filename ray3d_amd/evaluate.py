@@ -489,22 +489,130 @@ def shard_metrics_hip(pred_all: torch.Tensor, gt_all: torch.Tensor, table_dev: t
     return rows
 
 
+# ------------------------------------------------------------------------------------ a whole shard's inputs in one encode call
+
+ENCODINGS = {"ray": 0, "intrinsic": 1, "screen": 2}     # R3D_ENCODE_*: what `encode=` / shard_encode_hip name
+
+
+def mirror_permutation(num_joints: int, kps_left: Sequence[int], kps_right: Sequence[int]) -> List[int]:
+    """`perm` with mirror_input(x)[:, j] == x[:, perm[j]] (component 0 negated): left and right keypoints trade places."""
+    perm = list(range(num_joints))
+    for a, b in zip(list(kps_left) + list(kps_right), list(kps_right) + list(kps_left)):
+        perm[a] = b
+    if sorted(perm) != list(range(num_joints)):
+        raise ValueError("kps_left / kps_right do not make a permutation of the %d keypoints" % num_joints)
+    return perm
+
+
+def clip_input_table(clips: Sequence[Clip], rf: int, causal: bool = False, surplus: Optional[Callable[[int], int]] = None):
+    """(table, out_first, out_rows, max_rows) for `clips` whose ``rays`` hold RAW PIXELS (N, J, 2), laid out back to back in the
+    given order in one pixel buffer: `table` a NumPy structured array of r3d_clip_input_desc rows
+    (``_capi.clip_input_desc_dtype()``) - clip k's frames are rows [first_frame, first_frame + N_k) of the pixel buffer, its
+    padded, encoded input rows [out_first[k], out_first[k] + pad_front + N_k + pad_back) of the output buffer of `out_rows`
+    rows, back to back as well.  pad_front = pad + shift and pad_back = pad - shift + surplus(N_k), with pad = (RF-1)//2 and
+    shift = pad for `causal` models - :func:`pad_clip`'s padding - and `surplus(n)` the rows the rounded-up batch sizes of an
+    n-window clip read past it (``sum(lifter.clip_batch_sizes(n)) - n``; None: 0), so that a clip's slice is what
+    ``Ray3DLifter.forward_clip(..., n_windows=N_k)`` takes.  Camera rows: ``Camera.cam_row(distortion=True)``.  `max_rows` is
+    the longest clip's output row count.  Uploaded once (``torch.from_numpy(table.view(np.uint8))``) and handed to
+    :func:`shard_encode_hip`."""
+    from . import _capi
+    pad = (rf - 1) // 2
+    shift = pad if causal else 0
+    table = np.zeros(len(clips), dtype=_capi.clip_input_desc_dtype())
+    out_first, src, at, longest = [], 0, 0, 0
+    for k, c in enumerate(clips):
+        n = int(np.asarray(c.rays).shape[0])
+        extra = int(surplus(n)) if surplus is not None else 0
+        if extra < 0:
+            raise ValueError("surplus(%d) is negative" % n)
+        table[k]["first_frame"], table[k]["n_frames"], table[k]["out_first"] = src, n, at
+        table[k]["pad_front"], table[k]["pad_back"] = pad + shift, pad - shift + extra
+        table[k]["cam"] = c.camera.cam_row(distortion=True)
+        out_first.append(at)
+        rows = 2 * pad + n + extra
+        src += n
+        at += rows
+        longest = max(longest, rows)
+    return table, out_first, at, longest
+
+
+def shard_encode_hip(px_all: torch.Tensor, table_dev: torch.Tensor, num_clips: int, out_rows: int, max_rows: int,
+                     encoding: str = "ray", mirror_perm: Optional[Sequence[int]] = None, x_all: Optional[torch.Tensor] = None,
+                     x_mirror_all: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """ONE r3d_clips_encode call on the current stream for every clip of a shard: `px_all` (total_frames, J, 2) float32 raw
+    pixels, `table_dev` the uploaded bytes of :func:`clip_input_table`, `encoding` "ray" | "intrinsic" | "screen"; with
+    `mirror_perm` (:func:`mirror_permutation`) the same launch writes the flip pass's inputs as well.  Returns
+    (x_all (out_rows, J, F) float32, x_mirror_all or None, status (num_clips,) int32: 0 = followed, 1 = invalid descriptor).
+    `x_all` / `x_mirror_all` / `status`: tensors to write into (contiguous, of exactly these shapes) instead of new ones -
+    needed under hipGraph capture; new buffers are NOT zeroed: rows no clip covers keep what they held.  No copy and no
+    synchronisation: the caller reads `status` when it wants to."""
+    from . import _capi
+    dev = px_all.device
+    if encoding not in ENCODINGS:
+        raise ValueError("encoding must be one of %s (got %r)" % (sorted(ENCODINGS), encoding))
+    enc = ENCODINGS[encoding]
+    F = _capi.ENCODE_FLOATS[enc]
+    if px_all.dtype != torch.float32 or not px_all.is_contiguous() or not px_all.is_cuda or px_all.dim() != 3 or px_all.shape[-1] != 2 \
+            or px_all.shape[0] < 1:
+        raise ValueError("px_all: a contiguous float32 (total_frames, J, 2) tensor on a GPU is needed")
+    total, J = int(px_all.shape[0]), int(px_all.shape[1])
+    if table_dev.device != dev or not table_dev.is_contiguous() \
+            or table_dev.numel() * table_dev.element_size() < num_clips * _capi.CLIP_INPUT_DESC_BYTES:
+        raise ValueError("table_dev: %d descriptors of %d bytes on %s are needed" % (num_clips, _capi.CLIP_INPUT_DESC_BYTES, dev))
+    if (x_mirror_all is not None) and mirror_perm is None:
+        raise ValueError("x_mirror_all without mirror_perm")
+    bufs = []
+    for t, name, want in ((x_all, "x_all", True), (x_mirror_all, "x_mirror_all", mirror_perm is not None)):
+        if t is None:
+            t = torch.empty((out_rows, J, F), dtype=torch.float32, device=dev) if want else None
+        elif t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != (out_rows, J, F):
+            raise ValueError("%s: a contiguous float32 (%d, %d, %d) tensor on %s is needed" % (name, out_rows, J, F, dev))
+        bufs.append(t)
+    x_all, x_mirror_all = bufs
+    if status is None:
+        status = torch.empty(num_clips, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or tuple(status.shape) != (num_clips,):
+        raise ValueError("status: a contiguous int32 (%d,) tensor on %s is needed" % (num_clips, dev))
+    with torch.cuda.device(dev):
+        _capi.clips_encode(px_all.data_ptr(), total, J, enc, table_dev.data_ptr(), num_clips, max_rows, x_all.data_ptr(), out_rows,
+                           x_mirror_all.data_ptr() if x_mirror_all is not None else None,
+                           [int(v) for v in mirror_perm] if mirror_perm is not None else None,
+                           status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return x_all, x_mirror_all, status
+
+
 def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
                            kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                            rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
                            joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
                            root_relative: bool = False, mirror: Optional[Callable] = None, detail: bool = False,
-                           include_root: bool = False):
+                           include_root: bool = False, encode: Optional[str] = None):
     """:func:`evaluate_clips` (with `detail`: :func:`evaluate_clips_detail`, `include_root` as there) with the measuring side in
     ONE call per shard: the rank's clip table and ground truth are uploaded once, every clip is lifted into its slice of one
     prediction buffer (``lift_clip(padded, param_row, out=slice)``: ``Ray3DLifter.forward_clip``; the flip average is written
     into the slice), and one :func:`shard_metrics_hip` call fills the error columns of all rows - then the same gather and
     reduction.  Same arguments, same return values, the same bits in every row.  GPU only.  When `lift_clip` is the bound
     ``forward_clip`` of a lifter with lanes (``set_lanes``), the clips are dealt to the lanes and joined once, before the
-    metrics call."""
+    metrics call.
+
+    `encode` ("ray" | "intrinsic" | "screen"): ``Clip.rays`` holds RAW PIXELS (N, J, 2) and the input side is one call per
+    shard as well - the rank's pixels are uploaded once as one buffer and ONE r3d_clips_encode call (:func:`shard_encode_hip`,
+    on the caller's stream, before the first forward) pads, encodes and - with `flip` - mirrors every clip; each clip is
+    then lifted from its slice, ``lift_clip(x_all[slice], param_row, out=dst, n_windows=N)``: no per-clip upload, pad or
+    concatenation.  `lift_clip` must be the bound ``forward_clip`` of a lifter (its ``clip_batch_sizes`` size the slices).
+    The flip pass mirrors the ENCODED input, as the reference does - also right for undistort=True cameras, which
+    :func:`mirror_pixels` refuses; `kps_left` / `kps_right` give the permutation and `mirror` must be None."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
+    lifter = getattr(lift_clip, "__self__", None)
+    if encode is not None:        # (decided before the shards are cut: every rank raises alike, also one with an empty shard)
+        if encode not in ENCODINGS:
+            raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
+        if mirror is not None:
+            raise ValueError("encode=: the flip pass mirrors the encoded input on the device; `mirror` must be None")
+        if lifter is None or not hasattr(lifter, "clip_batch_sizes"):
+            raise ValueError("encode=: lift_clip must be the bound forward_clip of a Ray3DLifter")
     actions = sorted(set(c.action for c in clips))
     aid = {a: i for i, a in enumerate(actions)}
     shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
@@ -518,13 +626,32 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
             [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
         J = gt_all.shape[1]
         pred_all = torch.empty((total, 1, J, 3), dtype=torch.float32, device=dev)
-        lifter = getattr(lift_clip, "__self__", None)
         lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
         pad = (rf - 1) // 2
         jl = kps_left if joints_left is None else joints_left
         jr = kps_right if joints_right is None else joints_right
 
-        def lift_into(c, dst):
+        if encode is not None:
+            itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(lifter.clip_batch_sizes(n)) - n)
+            px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
+            itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
+            perm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
+            x_all, xm_all, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode, perm)
+            bad = torch.nonzero(status).flatten().tolist()
+            if bad:
+                raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
+
+            def lift_encoded(k, c, dst):
+                n = c.rays.shape[0]
+                rows = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
+                prow = torch.from_numpy(c.camera.param()).to(dev)
+                lift_clip(x_all[rows], prow, out=dst, n_windows=n)
+                if flip:
+                    pred_m = lift_clip(xm_all[rows], prow, n_windows=n)
+                    torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as lift_into rounds it
+                    dst.mul_(0.5)
+
+        def lift_into(k, c, dst):
             padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
             prow = torch.from_numpy(c.camera.param()).to(dev)
             lift_clip(padded, prow, out=dst)
@@ -533,13 +660,14 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
                 torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as predict_clip rounds it
                 dst.mul_(0.5)
 
+        lift = lift_encoded if encode is not None else lift_into
         for k, c in enumerate(mine):
             dst = pred_all[first[k]:first[k] + c.rays.shape[0]]
             if lanes:
                 with lifter.lane():          # the clip's forwards and its flip average on the next lane's stream
-                    lift_into(c, dst)
+                    lift(k, c, dst)
             else:
-                lift_into(c, dst)
+                lift(k, c, dst)
         if lanes:
             lifter.join_lanes()
         shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)

@@ -547,7 +547,7 @@ class Ray3DLifter(nn.Module):
         return sizes
 
     def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False,
-                     out: Optional[torch.Tensor] = None):
+                     out: Optional[torch.Tensor] = None, n_windows: Optional[int] = None):
         """clip (N + RF - 1, J, F): an edge-padded sequence; window i = frames [i, i+RF) is gathered
         in the kernels instead of materialising lib/train_val/trainer.py:47-58's copy.
         param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3) - with `return_trj` the pair
@@ -560,10 +560,22 @@ class Ray3DLifter(nn.Module):
         `out`: a contiguous (N,1,J,3) float32 tensor on the clip's device - e.g. the clip's slice of a shard's prediction
         buffer (evaluate.evaluate_clips_batched) - that the poses are written into and that is returned in place of a new
         tensor; the same forwards of the same sizes run, so the poses have the bits of a call without it.  A call whose
-        rounded-up size reaches past the N rows goes through a scratch tensor and its first rows are copied in."""
+        rounded-up size reaches past the N rows goes through a scratch tensor and its first rows are copied in.
+
+        `n_windows`: the clip has N = n_windows windows and the tensor ALREADY carries the surplus rows of the rounded-up
+        batch sizes behind them - exactly ``sum(clip_batch_sizes(n_windows)) + RF - 1`` rows, e.g. a clip's slice of the
+        buffer r3d_clips_encode filled (evaluate.shard_encode_hip) - so nothing is concatenated; the same forwards run on
+        the same values.  Any other row count is a ValueError."""
         rf = self.receptive_field()
         assert clip.dim() == 3 and clip.shape[1] == self.pos.num_joints_in and clip.shape[2] == self.pos.in_features
-        n = clip.shape[0] - rf + 1
+        if n_windows is not None:
+            n = int(n_windows)
+            want = (sum(self.clip_batch_sizes(n)) if n >= 1 else 0) + rf - 1
+            if n < 1 or clip.shape[0] != want:
+                raise ValueError("forward_clip(n_windows=%d): the clip must have sum(clip_batch_sizes(%d)) + RF - 1 = %d rows (got %d)"
+                                 % (n, n, want, clip.shape[0]))
+        else:
+            n = clip.shape[0] - rf + 1
         if n <= 0:
             raise RuntimeError("clip shorter than the receptive field")
         clip = clip.detach().to(torch.float32).contiguous()
@@ -572,10 +584,10 @@ class Ray3DLifter(nn.Module):
         sizes = self.clip_batch_sizes(n)
         total = sum(sizes)
         if out is not None:
-            return self._forward_clip_into(clip, p, n, sizes, return_trj, out)
+            return self._forward_clip_into(clip, p, n, sizes, return_trj, out, n_windows is not None)
         if total == n and len(sizes) == 1:
             return self._run(_capi.R3D_INPUT_RAYS, clip, 1, n, p, 0, return_trj=return_trj)
-        if total > n:
+        if total > n and n_windows is None:
             clip = torch.cat([clip, clip[-1:].expand(total - n, -1, -1)], dim=0)
         out = torch.empty((total, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=clip.device)
         trjs = []
@@ -590,14 +602,15 @@ class Ray3DLifter(nn.Module):
         self.join_lanes()      # (the pieces were written on the lanes' streams: the concatenation below runs on the caller's)
         return out[:n], torch.cat(trjs, dim=0)[:n]
 
-    def _forward_clip_into(self, clip, p, n, sizes, return_trj, out):
-        """forward_clip(out=): the forwards of `sizes` written straight into `out` (n rows) where they fit."""
+    def _forward_clip_into(self, clip, p, n, sizes, return_trj, out, has_surplus=False):
+        """forward_clip(out=): the forwards of `sizes` written straight into `out` (n rows) where they fit; `has_surplus`: the
+        clip already carries the rows of the surplus windows (forward_clip(n_windows=))."""
         J = self.pos.num_joints_in
         if tuple(out.shape) != (n, 1, J, 3) or out.dtype != torch.float32 or out.device != clip.device or not out.is_contiguous():
             raise ValueError("forward_clip(out=): a contiguous float32 (%d, 1, %d, 3) tensor on %s is needed (got %s %s on %s)"
                              % (n, J, clip.device, tuple(out.shape), out.dtype, out.device))
         total = sum(sizes)
-        if total > n:
+        if total > n and not has_surplus:
             clip = torch.cat([clip, clip[-1:].expand(total - n, -1, -1)], dim=0)
         trjs, tails = [], []
         start = 0

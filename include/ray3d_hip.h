@@ -210,7 +210,12 @@ int r3d_release(r3d_model *pos, r3d_model *trj, int64_t B);   /* un-pins the siz
 
 /* One network, exactly the reference module's forward:
  *   pos: out_dev (B,1,J,3)   lib/model/rie.py:284-434
- *   trj: out_dev (B,1,1,3)   lib/model/rie.py:518-559 */
+ *   trj: out_dev (B,1,1,3)   lib/model/rie.py:518-559
+ * Non-finite input (a detector's NaN / Inf for a missed joint; any NaN payload, signalling ones included), in every input
+ * mode and for r3d_forward_pair alike: an element of x_dev, param_dev or a pixel coordinate that is NaN or +-Inf makes every
+ * output of the windows that read it NaN (non-finite at least) - as the reference's forward does - and leaves every other
+ * window's output bits exactly what they are without it.  It is not an error: nothing is reported through r3d_status, and
+ * the call takes no longer than on finite input (tests/test_gpu_nonfinite.py). */
 int r3d_forward(r3d_model *m, const r3d_input *in, int64_t B, float *out_dev,
                 void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 

@@ -597,6 +597,7 @@ int bind_if_needed(Call &c, const Single &s) {
     if (s.poll) {                 // both activation banks armed, bank 0's table
         ba.base[BIND_WS] = fw.d_act;
         ba.arm = fw.d_act;
+        ba.canon = 1;             // (every producer of a polled operand, the throughput tiles included: r3d_tiles.hpp, act_canon)
         ba.arm_vec4 = (long long)(2 * fw.act_bytes / 16);
     }
     hipError_t e;

@@ -63,7 +63,7 @@ struct GemmProb {
     int enc_step;             // frames between consecutive operand rows of a window: 3 (stride-3 expand_conv), 1 (dense ablation)
     unsigned enc_bytes;       // size of the raw input in bytes (buffer-descriptor bound)
     int res_tap;              // fused first level: which frame of a triple is the residual (1 centre, 2 causal)
-    int pad2_;
+    int canon;                // poll mode (set by r3d_bind_f32): stores into the activation banks write the canonical quiet NaN for ACT_SENTINEL's bits
     // --- UV input mode (cam != nullptr): x holds pixel keypoints (frames, J, 2), `lut` is the UV variant of the
     // tables (element byte offsets into that layout, the ray component 0/1/2 in the two low bits) and every gathered
     // value is encoded on its way into LDS with the camera row of the window its operand row belongs to:
@@ -122,6 +122,7 @@ struct BindArgs {
     long long enc_ws, cam_stride;  // per call: window stride in elements, doubles between camera rows
     unsigned enc_bytes;
     int param_stride;
+    int canon;                     // -> GemmProb::canon of every problem (poll mode: 1)
     void *arm;                     // activation bank(s) to fill with sentinels (poll mode; nullptr otherwise)
     long long arm_vec4;
 };

@@ -56,6 +56,7 @@ extern "C" __global__ __launch_bounds__(256) void r3d_bind_f32(const BindArgs b)
     }
     fix(g.w, 4); fix(g.bias, 5); fix(g.res, 6); fix(g.c, 7); fix(g.w2, 8); fix(g.bias2, 9); fix(g.wb3, 10); fix(g.w2b3, 11);
     fix(g.w3b3, 12); fix(g.w3, 13); fix(g.bias3, 14); fix(g.lut, 15); fix(g.x, 16); fix(g.cam, 17);
+    g.canon = b.canon;
     if (g.lut != nullptr) {
         g.enc_ws = b.enc_ws;
         g.enc_bytes = b.enc_bytes;

@@ -151,6 +151,14 @@ typedef const GemmProb __attribute__((address_space(4))) &ProbRef;
 // the residual read too.
 constexpr int EPI_LD = GEMM_BN + 4;       // 260 floats: the two 32-lane halves of a ds_write_b32 hit different banks
 
+// Poll mode (GemmProb::canon, calls of a few windows): ACT_SENTINEL's bit pattern means "not there yet" to the GEMV / latency
+// tiles that read this tile's output.  The matrix cores and the VALU hand a NaN operand's payload through, so an input
+// element that carries exactly that NaN would arrive here unchanged: it is stored as the canonical quiet NaN instead.
+constexpr unsigned ACT_SENTINEL_BITS = 0x7fc5a1e7u;
+__device__ __forceinline__ float act_canon(const float v) {
+    return __builtin_bit_cast(unsigned, v) == ACT_SENTINEL_BITS ? __builtin_bit_cast(float, 0x7fc00000u) : v;
+}
+
 template <int MI, int KS>
 __device__ __forceinline__ void store_tile(ProbRef P, const f32x16 (&acc)[MI], const int row0, const int col0, float *lds,
                                            const bool second = false) {
@@ -163,6 +171,7 @@ __device__ __forceinline__ void store_tile(ProbRef P, const f32x16 (&acc)[MI], c
     const int M = P.M, N = P.N;
     const float slope = second ? P.slope2 : P.slope;
     const float *res = P.res;
+    const bool canon = P.canon != 0;
     const int ldc = P.ldc, ldr = P.ldr;
     // (descriptors based at the tile's first element: per-lane offsets stay small and the accesses carry sc1)
     const __amdgpu_buffer_rsrc_t crs = act_rsrc(P.c + (size_t)row0 * ldc + col0);
@@ -193,12 +202,19 @@ __device__ __forceinline__ void store_tile(ProbRef P, const f32x16 (&acc)[MI], c
             const int lrow = mi * 32 + lr;
             if (vec) {
                 if (res) v += act_load4(rrs, (lrow * ldr + rd_c4) * 4);
+                if (canon) {                                        // (uniform)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = act_canon(v[e]);
+                }
                 // (write-through: the consumer is another workgroup, mostly on another XCD - no use for the line in this L2)
                 act_store4(crs, (lrow * ldc + rd_c4) * 4, v);
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (col + e < N) act_store1(crs, (lrow * ldc + rd_c4 + e) * 4, v[e] + (res ? act_load1(rrs, (lrow * ldr + rd_c4 + e) * 4) : 0.0f));
+                    if (col + e < N) {
+                        const float o = v[e] + (res ? act_load1(rrs, (lrow * ldr + rd_c4 + e) * 4) : 0.0f);
+                        act_store1(crs, (lrow * ldc + rd_c4 + e) * 4, canon ? act_canon(o) : o);
+                    }
             }
         }
     }
@@ -358,6 +374,18 @@ __device__ __forceinline__ void gemm_tile(ProbRef P, const int row0, const int c
         if (WD2) {
             issue_a(4 < last ? 4 : last, ra3);
             prep_seg(5 < last ? 5 : last);
+        }
+        // An operand narrower than one K tile (embedder.w1 on the caller's 2-wide [height, pitch] rows: its only K tile): the
+        // descriptor bounds the LAST row alone, so the floats behind a row's own are the next rows' - harmless times the zero
+        // weights of the padded K unless one of them is NaN or Inf (0 x NaN = NaN: a bad row would poison the 15 rows in front
+        // of it).  Zeroed here, once per tile.
+        if (P.kend[0] < BK) {                   // (uniform)
+            const int width = P.kend[0];
+#pragma unroll
+            for (int i = 0; i < NA; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (a_kq + e >= width) r0.a[i][e] = 0.0f;
         }
         commit_a(0, r0);
         commit_a(1, r1);
@@ -2475,12 +2503,15 @@ __device__ __forceinline__ float act_ld(const float *p) {
     return __builtin_bit_cast(float, __hip_atomic_load((gu32)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));   // 4-byte sc1 load
 }
 // Data as its own ready flag (calls of a few windows, FwdArgs::poll): the activation bank of the call was filled with
-// ACT_SENTINEL - a quiet NaN no arithmetic produces - before the launch, GEMV / latency tiles read their operands until
+// ACT_SENTINEL - a quiet NaN no arithmetic produces FROM FINITE OR INFINITE OPERANDS (a NaN operand's payload does pass through
+// the matrix cores and the VALU unchanged: measured, tests/test_gpu_nonfinite.py) - before the launch, GEMV / latency tiles read their operands until
 // no sentinel is left in them instead of waiting for ready counters first, and their producers' write-through stores need
 // no drain, counter update and counter poll in between: a dependency hop is one store -> load latency.  Every float is
 // its own flag, so no ordering between stores is assumed.  (A producer that computes exactly this NaN - only from an
-// input that carries it - stores the canonical quiet NaN instead.)
+// input that carries it - stores the canonical quiet NaN instead: act_st here, and store_tile under GemmProb::canon for
+// the throughput tiles whose outputs these tiles poll - the gathered first layers, embedder.w1, layers of more than 32 rows.)
 constexpr unsigned ACT_SENTINEL = 0x7fc5a1e7u;
+static_assert(ACT_SENTINEL == ACT_SENTINEL_BITS, "store_tile canonicalises the same pattern");
 __device__ __forceinline__ bool act_missing(float v) { return __builtin_bit_cast(unsigned, v) == ACT_SENTINEL; }
 __device__ __forceinline__ void act_st(float *p, float v) {
     unsigned u = __builtin_bit_cast(unsigned, v);

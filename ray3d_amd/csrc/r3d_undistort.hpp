@@ -103,6 +103,11 @@ __host__ __device__ inline void encode_pixel_2d(const double *row, int encoding,
 // r3d_clips_encode), and what the hooks' r3d_debug_clips_encode_host writes on the CPU.  `encoding` is uniform over a launch:
 // scalar branches.  (Values, not an output array: nothing of it lives in scratch memory.)
 struct EncodedPoint { float x, y, z; };
+// The one cast.  A NaN (a bad pixel coordinate) leaves as THE canonical quiet NaN: which operand's sign and payload a NaN result
+// carries differs between the GPU and a host CPU, and the kernel and the host hook are held to the same bits.
+__host__ __device__ __forceinline__ float encoded_f32(const double d) {
+    return d != d ? __builtin_bit_cast(float, 0x7fc00000u) : (float)d;
+}
 __host__ __device__ __forceinline__ EncodedPoint encode_point_f32(const double *row, int encoding, double u, double v) {
     double e[2], z = 0.0;
     if (encoding == ENC_SCREEN) {            // raw pixels and the image size: no undistortion, no intrinsics
@@ -120,7 +125,7 @@ __host__ __device__ __forceinline__ EncodedPoint encode_point_f32(const double *
             z = r[2];
         }
     }
-    return EncodedPoint{(float)e[0], (float)e[1], (float)z};
+    return EncodedPoint{encoded_f32(e[0]), encoded_f32(e[1]), encoded_f32(z)};
 }
 
 // ---- r3d_clips_encode: the descriptor rules and the row-to-source mapping, shared by the kernel and the host hook ----

@@ -534,6 +534,51 @@ int r3d_clip_valid_losses(const float *pos_dev, const float *trj_dev, const floa
                           int32_t num_joints, const int32_t *parents, int32_t flags,
                           double *out_dev, double *frame_dev, void *stream);
 
+/* lib/train_val/trainer.py:187-225 for every clip of a shard at once: what Trainer.test does per batch between its forwards and
+ * its epoch accumulators - root-relative ground truth, the losses of :200-222 - as r3d_clip_valid_losses over the table of clips
+ * r3d_clips_metrics reads (r3d_clip_desc, DEVICE memory; rn2w / tn2w are NOT read: the losses live in the normalised frame, so a
+ * caller that both evaluates and validates uploads one table), in exactly two kernel launches on `stream` - no copy, no
+ * allocation, no synchronisation (it can be captured into a hipGraph).  pos_dev and gt_dev are (total_frames, J, 3) float32,
+ * trj_dev (total_frames, 3) float32 or NULL; clip c is rows [first_frame, first_frame + n_frames) of all three (and of
+ * frame_dev).  Clips may lie in the buffers in any order, with gaps.  `parents` and `flags` are r3d_clip_valid_losses's, one tree
+ * and one flag set per call; the rounding contract is that call's.
+ *   rows_dev:   clip c's R3D_VALID_DOUBLES sums at rows_dev + c * row_stride, row_stride >= R3D_VALID_DOUBLES: a pointer to
+ *               column 3 of a (k, 3 + R3D_VALID_DOUBLES) matrix of partial rows and that stride fills columns 3.. in place;
+ *               nothing else of the matrix is written.
+ *   frame_dev:  optional (NULL: none): (total_frames, R3D_VALID_COUNT) doubles, row first_frame + f the seven terms of the
+ *               clip's frame f; rows no valid clip covers are left untouched.
+ * BIT-FOR-BIT EQUALITY WITH THE PER-CLIP CALL.  For every valid clip the R3D_VALID_DOUBLES results and the clip's rows of
+ * frame_dev equal r3d_clip_valid_losses on that clip alone, bit for bit - clips above R3D_METRIC_MAX_BLOCKS * 256 frames (where
+ * the per-clip call wraps around its workgroups) and the Inf / NaN of a zero root depth, a zero-length bone or a one-joint tree
+ * included: both run one and the same workgroup body, assign frames to workgroups from the clip's own n_frames and add the
+ * partial rows in the same order.  A caller may switch between the two paths without its numbers moving.
+ * GRID.  max_frames is the caller's bound on any clip's length and sizes the grid: (min(ceil(max_frames / 256),
+ * R3D_METRIC_MAX_BLOCKS), num_clips) workgroups, then num_clips wavefronts; a workgroup past its clip's own count returns at once.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  The rule of r3d_clips_metrics: a descriptor is invalid when n_frames < 1,
+ * n_frames > max_frames, or [first_frame, first_frame + n_frames) is not inside [0, total_frames).  The kernels never follow an
+ * invalid descriptor: nothing of that clip is read, its R3D_VALID_DOUBLES results are all NaN, its rows of frame_dev are left
+ * untouched.  Beyond the descriptors the kernels read pos_dev / gt_dev within total_frames * num_joints * 3 floats, trj_dev
+ * within total_frames * 3, the table within num_clips descriptors, and write the strided rows (R3D_VALID_DOUBLES doubles per
+ * clip, nothing between rows), frame_dev within total_frames rows and the scratch within r3d_clips_valid_scratch_bytes: no
+ * input can make them touch memory outside these extents.
+ * SCRATCH.  The workgroups' partial rows: num_clips * min(ceil(max_frames / 256), R3D_METRIC_MAX_BLOCKS) * R3D_VALID_DOUBLES
+ * doubles - r3d_clips_valid_scratch_bytes returns exactly that (0 for num_clips < 1 or max_frames < 1), exactly that many bytes
+ * suffice, and what the scratch holds at entry has no effect on the outputs.  With less the call returns R3D_ERR_WORKSPACE
+ * before anything is launched.
+ * R3D_ERR_ARG (checked on the host before any HIP call): what r3d_clip_valid_losses rejects - a null required pointer (pos_dev,
+ * gt_dev, rows_dev; here also clips_dev, scratch_dev), num_joints outside 1..17, a bad parent table, unknown flags, POS_IS_SUM
+ * without trj_dev, GT_ROOT_RELATIVE together with trj_dev - what r3d_clips_metrics rejects - num_clips outside
+ * 1..R3D_CLIPS_MAX, max_frames < 1, total_frames < 1, a table or scratch pointer that is not 8-byte aligned - and
+ * row_stride < R3D_VALID_DOUBLES.  Deterministic (fixed summation order, no atomics). */
+size_t r3d_clips_valid_scratch_bytes(int32_t num_clips, int64_t max_frames);
+int r3d_clips_valid_losses(const float *pos_dev, const float *trj_dev, const float *gt_dev,
+                           int64_t total_frames, int32_t num_joints,
+                           const int32_t *parents, int32_t flags,          /* as r3d_clip_valid_losses: one tree, one flag set per call */
+                           const r3d_clip_desc *clips_dev, int32_t num_clips, int64_t max_frames,
+                           double *rows_dev, int64_t row_stride,           /* clip c: R3D_VALID_DOUBLES sums at rows_dev + c*row_stride */
+                           double *frame_dev,                              /* optional (NULL): (total_frames, R3D_VALID_COUNT) */
+                           void *scratch_dev, size_t scratch_bytes, void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -583,6 +628,11 @@ int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float 
 int r3d_debug_clips_encode_host(const float *px, int64_t total_frames, int32_t num_joints, int32_t encoding,
                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
                                 float *x_mirror, const int32_t *mirror_perm, int32_t *status);
+/* r3d_clips_valid_losses on the host (HOST pointers throughout, no scratch): the same argument checks, the same descriptor rule,
+ * per valid clip exactly r3d_debug_valid_losses_host on the clip's slice; an invalid clip's row is NaN, its frame rows stay. */
+int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t num_joints,
+                                      const int32_t *parents, int32_t flags, const r3d_clip_desc *clips, int32_t num_clips,
+                                      int64_t max_frames, double *rows, int64_t row_stride, double *frame);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -31,11 +31,11 @@ EXPORTS = (
     "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_clip_valid_losses", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
-    "r3d_clips_encode",
+    "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
-                "r3d_debug_clips_encode_host")
+                "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -163,9 +163,15 @@ def load():
     lib.r3d_clips_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_clips_encode.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
                                      C.POINTER(C.c_int32), vp, vp]
+    lib.r3d_clips_valid_scratch_bytes.argtypes = [C.c_int32, C.c_int64]
+    lib.r3d_clips_valid_scratch_bytes.restype = C.c_size_t
+    lib.r3d_clips_valid_losses.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, C.c_int64,
+                                           vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_clips_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32,
+                                                          C.c_int64, vp, C.c_int64, vp]
         lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
         lib.r3d_debug_encode_px_host.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
         lib.r3d_debug_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp]
@@ -374,6 +380,23 @@ def clip_valid_losses(pos_ptr: int, trj_ptr: Optional[int], gt_ptr: int, n_frame
     float64 or None; the rest device pointers."""
     check(load().r3d_clip_valid_losses(pos_ptr, trj_ptr or None, gt_ptr, n_frames, num_joints, _parent_table(parents), flags,
                                        out_ptr, frame_ptr or None, stream), "r3d_clip_valid_losses")
+
+
+def clips_valid_scratch_bytes(num_clips: int, max_frames: int) -> int:
+    """r3d_clips_valid_scratch_bytes: the scratch one r3d_clips_valid_losses call over `num_clips` clips of at most `max_frames`
+    frames needs (0 for num_clips < 1 or max_frames < 1)."""
+    return int(load().r3d_clips_valid_scratch_bytes(num_clips, max_frames))
+
+
+def clips_valid_losses(pos_ptr: int, trj_ptr: Optional[int], gt_ptr: int, total_frames: int, num_joints: int, parents, flags: int,
+                       table_ptr: int, num_clips: int, max_frames: int, rows_ptr: int, row_stride: int, frame_ptr: Optional[int],
+                       scratch_ptr: int, scratch_bytes: int, stream: int):
+    """r3d_clips_valid_losses: every pointer but `parents` (a host sequence of at least num_joints ints, or None: no bone terms) is
+    device memory; `table_ptr` num_clips r3d_clip_desc (:func:`clip_desc_dtype`) back to back, their rn2w / tn2w unread;
+    `trj_ptr` / `frame_ptr` may be None."""
+    check(load().r3d_clips_valid_losses(pos_ptr, trj_ptr or None, gt_ptr, total_frames, num_joints, _parent_table(parents), flags,
+                                        table_ptr, num_clips, max_frames, rows_ptr, row_stride, frame_ptr or None, scratch_ptr,
+                                        scratch_bytes, stream), "r3d_clips_valid_losses")
 
 
 def forward_pair(pos: Handle, trj: Handle, inp: Input, batch: int, out_ptr: int,

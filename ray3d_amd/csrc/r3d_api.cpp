@@ -29,6 +29,25 @@ int r3d::valid_check_args(const char *what, const float *pos, const float *trj, 
     return R3D_OK;
 }
 
+// the argument rules of r3d_clips_valid_losses, shared with its host hook: r3d_clip_valid_losses's on the buffers, the tree and the
+// flags, r3d_clips_metrics's on the table and the bounds
+int r3d::clips_valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t J,
+                                const int32_t *parents, int32_t flags, const r3d_clip_desc *clips, int32_t num_clips, int64_t max_frames,
+                                const double *rows, int64_t row_stride, const void *scratch, bool scratch_checked) {
+    if (!clips || (scratch_checked && !scratch)) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (total_frames < 1) { set_error("%s: total_frames must be >= 1 (got %lld)", what, (long long)total_frames); return R3D_ERR_ARG; }
+    const int rc = valid_check_args(what, pos, trj, gt, total_frames, J, parents, flags, rows);
+    if (rc != R3D_OK) return rc;
+    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (max_frames < 1) { set_error("%s: max_frames must be >= 1 (got %lld)", what, (long long)max_frames); return R3D_ERR_ARG; }
+    if (row_stride < R3D_VALID_DOUBLES) { set_error("%s: row_stride must be >= %d (got %lld)", what, R3D_VALID_DOUBLES, (long long)row_stride); return R3D_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(clips) % 8 || (scratch_checked && reinterpret_cast<uintptr_t>(scratch) % 8)) {
+        set_error("%s: the clip table and the scratch must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    return R3D_OK;
+}
+
 // the argument rules of r3d_clips_encode, shared with its host hook (`what`: the name in the message)
 int r3d::clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
                                  const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
@@ -202,6 +221,31 @@ int r3d_clip_valid_losses(const float *pos_dev, const float *trj_dev, const floa
     if (rc != R3D_OK) return rc;
     if (r3d::launch_clip_valid(pos_dev, trj_dev, gt_dev, n_frames, num_joints, parents, flags, out_dev, frame_dev, (hipStream_t)stream)) {
         r3d::set_error("r3d_clip_valid_losses: launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+size_t r3d_clips_valid_scratch_bytes(int32_t num_clips, int64_t max_frames) {
+    if (num_clips < 1 || max_frames < 1) return 0;
+    return r3d::clips_valid_scratch_bytes(num_clips, max_frames);
+}
+
+int r3d_clips_valid_losses(const float *pos_dev, const float *trj_dev, const float *gt_dev, int64_t total_frames, int32_t num_joints,
+                           const int32_t *parents, int32_t flags, const r3d_clip_desc *clips_dev, int32_t num_clips, int64_t max_frames,
+                           double *rows_dev, int64_t row_stride, double *frame_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
+    // (every check on the host, before any HIP call)
+    const int rc = clips_valid_check_args("r3d_clips_valid_losses", pos_dev, trj_dev, gt_dev, total_frames, num_joints, parents, flags,
+                                          clips_dev, num_clips, max_frames, rows_dev, row_stride, scratch_dev, true);
+    if (rc != R3D_OK) return rc;
+    const size_t need = r3d::clips_valid_scratch_bytes(num_clips, max_frames);
+    if (scratch_bytes < need) {
+        r3d::set_error("r3d_clips_valid_losses: scratch of %zu bytes, %zu needed (r3d_clips_valid_scratch_bytes)", scratch_bytes, need);
+        return R3D_ERR_WORKSPACE;
+    }
+    if (r3d::launch_clips_valid(pos_dev, trj_dev, gt_dev, total_frames, num_joints, parents, flags, clips_dev, num_clips, max_frames,
+                                rows_dev, row_stride, frame_dev, scratch_dev, (hipStream_t)stream)) {
+        r3d::set_error("r3d_clips_valid_losses: launch failed: %s", hipGetErrorString(hipGetLastError()));
         return R3D_ERR_HIP;
     }
     return 0;

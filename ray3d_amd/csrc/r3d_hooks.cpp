@@ -337,6 +337,28 @@ int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float 
     return R3D_OK;
 }
 
+// Test hook: r3d_clips_valid_losses on the host - its argument rules (clips_valid_check_args), its descriptor rule
+// (clip_range_valid, the kernels' own) and, per valid clip, r3d_debug_valid_losses_host on the clip's slice, clips in table order.
+int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t num_joints,
+                                      const int32_t *parents, int32_t flags, const r3d_clip_desc *clips, int32_t num_clips,
+                                      int64_t max_frames, double *rows, int64_t row_stride, double *frame) {
+    const int rc = clips_valid_check_args("r3d_debug_clips_valid_losses_host", pos, trj, gt, total_frames, num_joints, parents, flags, clips,
+                                          num_clips, max_frames, rows, row_stride, nullptr, false);
+    if (rc != R3D_OK) return rc;
+    for (int32_t c = 0; c < num_clips; ++c) {
+        const long long first = clips[c].first_frame, n = clips[c].n_frames;
+        double *row = rows + (long long)c * row_stride;
+        if (!clip_range_valid(first, n, total_frames, max_frames)) {     // not followed: nothing of it is read, its frame rows stay
+            for (int k = 0; k < R3D_VALID_DOUBLES; ++k) row[k] = nan("");
+            continue;
+        }
+        const int rc1 = r3d_debug_valid_losses_host(pos + first * num_joints * 3, trj ? trj + first * 3 : nullptr, gt + first * num_joints * 3, n,
+                                                    num_joints, parents, flags, row, frame ? frame + first * R3D_VALID_COUNT : nullptr);
+        if (rc1 != R3D_OK) return rc1;
+    }
+    return R3D_OK;
+}
+
 }  // extern "C"
 
 #endif  // R3D_TEST_HOOKS

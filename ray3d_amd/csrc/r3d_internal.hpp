@@ -505,6 +505,12 @@ void lanes_destroy(Model *m);
 int valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t n, int32_t J,
                      const int32_t *parents, int32_t flags, const double *out);
 
+// the argument rules of r3d_clips_valid_losses, shared with its host hook (r3d_api.cpp): those of r3d_clip_valid_losses and those of
+// r3d_clips_metrics; `scratch_checked` false: the host hook, which has no scratch
+int clips_valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t J,
+                           const int32_t *parents, int32_t flags, const r3d_clip_desc *clips, int32_t num_clips, int64_t max_frames,
+                           const double *rows, int64_t row_stride, const void *scratch, bool scratch_checked);
+
 // the argument rules of r3d_clips_encode, shared with its host hook (r3d_api.cpp)
 int clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
                             const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
@@ -618,5 +624,11 @@ size_t clips_metrics_scratch_bytes(int num_clips, long long max_frames, bool det
 int launch_clips_metrics(const float *pred, const float *gt, long long total, int J, const r3d_clip_desc *table, int num_clips,
                          long long max_frames, double *rows, long long row_stride, double *detail, long long detail_stride,
                          double *frame, void *scratch, hipStream_t stream);
+// r3d_clips_valid_losses (the validation-loss mode over the table: both argument sets of the kernels); arguments already checked, parents
+// a host array or null, `scratch` of at least clips_valid_scratch_bytes.  Two launches, nothing else.
+size_t clips_valid_scratch_bytes(int num_clips, long long max_frames);
+int launch_clips_valid(const float *pos, const float *trj, const float *gt, long long total, int J, const int32_t *parents, int flags,
+                       const r3d_clip_desc *table, int num_clips, long long max_frames, double *rows, long long row_stride,
+                       double *frame, void *scratch, hipStream_t stream);
 
 }  // namespace r3d

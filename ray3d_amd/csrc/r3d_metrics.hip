@@ -27,6 +27,13 @@
 // The frame loop, the wave-of-64 detail sums and both reduction trees are therefore the same instructions for both calls: a
 // clip's results have the bits of the per-clip call by construction.  (A mode of the two documented kernels, as the detail and
 // the validation losses are: the library's kernel set stays what tests/test_host.py pins.)
+//
+// r3d_clips_valid_losses (a shard's validation losses in one launch pair) is the two modes combined: ValidArgs AND ClipsArgs set.
+// The validation-loss branch then takes its clip from the table by the rule of r3d_clips_metrics - descriptor read once, decided
+// on first - moves the shard's buffers to the clip's first frame and runs valid_block, the one workgroup body of that mode, with
+// blockIdx.x and the clip's OWN workgroup count on the clip's slice of the scratch; the second launch adds a clip's partial rows
+// with valid_sum_rows, one wavefront per clip.  The per-clip call enters the same two bodies with (blockIdx.x, gridDim.x) and the
+// rows behind its results: the same instructions, the same bits.
 #include <hip/hip_runtime.h>
 #include "r3d_internal.hpp"
 #include "r3d_valid_dev.hpp"
@@ -64,6 +71,8 @@ struct ClipsArgs {
     long long row_stride, detail_stride;
     double *frame;               // optional (total, R3D_METRIC_COUNT)
     double *part, *dpart;        // scratch: (num_clips, blocks, R3D_METRIC_COUNT) partial sums, (num_clips, blocks, R3D_DETAIL_DOUBLES) partial detail rows
+    // r3d_clips_valid_losses (ValidArgs::out set as well) reads table, total, max_frames, blocks, rows, row_stride and part - there
+    // (num_clips, blocks, R3D_VALID_DOUBLES) partial rows; the buffers and the frame table are ValidArgs's
 };
 static_assert(sizeof(r3d_clip_desc) == 112 && alignof(r3d_clip_desc) == 8, "layout of r3d_clip_desc (include/ray3d_hip.h)");
 
@@ -75,7 +84,7 @@ __host__ __device__ inline long long metric_blocks(long long n) {
 
 // a descriptor is followed only when its frames lie inside the buffers and within the caller's bound (uniform per workgroup)
 __device__ inline bool clip_desc_valid(long long first, long long n, const ClipsArgs &c) {
-    return n >= 1 && n <= c.max_frames && first >= 0 && first <= c.total - n;
+    return clip_range_valid(first, n, c.total, c.max_frames);
 }
 
 // a double every lane holds the same value of, moved to scalar registers
@@ -374,8 +383,26 @@ __global__ __launch_bounds__(METRIC_THREADS) void r3d_clip_metrics_f64(MetricArg
     __shared__ double red[R3D_METRIC_COUNT][METRIC_THREADS];
     __shared__ double cols[METRIC_WAVES][JOINT_COLS];
     __shared__ unsigned int hist[R3D_DETAIL_THRESHOLDS + 1];
-    if (valid.out) {             // uniform: the whole launch is a validation-loss one (r3d_clip_valid_losses), `a` is unused
-        valid_block(valid, &red[0][0]);
+    if (valid.out) {             // uniform: the whole launch is a validation-loss one, `a` is unused
+        // r3d_clip_valid_losses: the clip of the arguments, every workgroup of the grid on it, partial rows behind the results
+        int vwg = gridDim.x;
+        double *row = valid.out + R3D_VALID_DOUBLES * (1 + (long long)blockIdx.x);
+        if (clips.table) {
+            // uniform: r3d_clips_valid_losses - clip blockIdx.y of the table, by the rule of r3d_clips_metrics below (rn2w / tn2w
+            // are not read): the descriptor decides first, the shard's buffers are moved to the clip's first frame
+            const r3d_clip_desc *d = clips.table + blockIdx.y;
+            const long long first = uniform((long long)d->first_frame), n = uniform((long long)d->n_frames);
+            if (!clip_desc_valid(first, n, clips)) return;
+            vwg = (int)metric_blocks(n);
+            if ((int)blockIdx.x >= vwg) return;
+            valid.in.pos += first * valid.in.J * 3;
+            valid.in.gt += first * valid.in.J * 3;
+            if (valid.in.trj) valid.in.trj += first * 3;
+            if (valid.frame) valid.frame += first * R3D_VALID_COUNT;
+            valid.n = n;
+            row = clips.part + ((long long)blockIdx.y * clips.blocks + blockIdx.x) * R3D_VALID_DOUBLES;
+        }
+        valid_block(valid, (int)blockIdx.x, vwg, row, &red[0][0]);
         return;
     }
     // r3d_clip_metrics(_detail): the clip of the arguments, every workgroup of the grid on it, partial rows behind the results
@@ -428,7 +455,19 @@ __device__ __forceinline__ void metrics_sum_rows(const double *part, const doubl
 
 __global__ __launch_bounds__(64) void r3d_clip_metrics_sum_f64(double *out, int blocks, long long n, double *detail, double *valid, ClipsArgs clips) {
     if (valid) {                 // the second launch of r3d_clip_valid_losses
-        valid_sum_rows(valid, blocks);
+        if (clips.table) {       // ... of r3d_clips_valid_losses: workgroup c is clip c's wavefront
+            const r3d_clip_desc *d = clips.table + blockIdx.x;
+            const long long first = uniform((long long)d->first_frame);
+            n = uniform((long long)d->n_frames);
+            double *row = clips.rows + (long long)blockIdx.x * clips.row_stride;
+            if (!clip_desc_valid(first, n, clips)) {      // nothing of the clip was read: its results are NaN
+                for (int c = threadIdx.x; c < R3D_VALID_DOUBLES; c += 64) row[c] = nan("");
+                return;
+            }
+            valid_sum_rows(clips.part + (long long)blockIdx.x * clips.blocks * R3D_VALID_DOUBLES, (int)metric_blocks(n), row);
+            return;
+        }
+        valid_sum_rows(valid + R3D_VALID_DOUBLES, blocks, valid);
         return;
     }
     if (clips.table) {           // ... of r3d_clips_metrics: workgroup c is clip c's wavefront
@@ -516,6 +555,39 @@ int launch_clip_valid(const float *pos, const float *trj, const float *gt, long 
     blocks = blocks < 1 ? 1 : (blocks > R3D_METRIC_MAX_BLOCKS ? R3D_METRIC_MAX_BLOCKS : blocks);
     hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)blocks), dim3(METRIC_THREADS), 0, stream, a, v, ClipsArgs{});
     hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3(1), dim3(64), 0, stream, (double *)nullptr, (int)blocks, n, (double *)nullptr, out, ClipsArgs{});
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+size_t clips_valid_scratch_bytes(int num_clips, long long max_frames) {
+    return (size_t)num_clips * (size_t)metric_blocks(max_frames) * R3D_VALID_DOUBLES * sizeof(double);
+}
+
+int launch_clips_valid(const float *pos, const float *trj, const float *gt, long long total, int J, const int32_t *parents, int flags,
+                       const r3d_clip_desc *table, int num_clips, long long max_frames, double *rows, long long row_stride,
+                       double *frame, void *scratch, hipStream_t stream) {
+    // both argument sets: ValidArgs the shard's buffers, the tree and the flags, ClipsArgs the table, the bounds, the rows and the scratch
+    ValidArgs v = {};
+    v.in.pos = pos;
+    v.in.trj = trj;
+    v.in.gt = gt;
+    v.in.J = J;
+    v.in.flags = flags;
+    v.in.bones = parents != nullptr;
+    v.in.tree = parents ? valid_pack_tree(parents, J) : ValidTree{{0ull, 0ull}};
+    v.out = rows;
+    v.frame = frame;
+    ClipsArgs c = {};
+    c.table = table;
+    c.total = total;
+    c.max_frames = max_frames;
+    c.J = J;
+    c.blocks = (int)metric_blocks(max_frames);
+    c.rows = rows;
+    c.row_stride = row_stride;
+    c.part = static_cast<double *>(scratch);
+    hipLaunchKernelGGL(r3d_clip_metrics_f64, dim3((unsigned)c.blocks, (unsigned)num_clips), dim3(METRIC_THREADS), 0, stream, MetricArgs{}, v, c);
+    hipLaunchKernelGGL(r3d_clip_metrics_sum_f64, dim3((unsigned)num_clips), dim3(64), 0, stream, (double *)nullptr, 0, 0ll, (double *)nullptr,
+                       rows, c);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

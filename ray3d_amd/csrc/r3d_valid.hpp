@@ -41,6 +41,12 @@ struct ValidIn {
     ValidTree tree;
 };
 
+// r3d_clips_valid_losses: a descriptor is followed only when its frames lie inside the shard's buffers and within the caller's bound -
+// the rule of r3d_clips_metrics (r3d_metrics.hip: clip_desc_valid), shared by the kernels and the host hook
+__host__ __device__ inline bool clip_range_valid(long long first, long long n, long long total, long long max_frames) {
+    return n >= 1 && n <= max_frames && first >= 0 && first <= total - n;
+}
+
 __host__ __device__ inline double valid_norm3(float x, float y, float z) {
     const double a = (double)x, b = (double)y, c = (double)z;
     return sqrt(a * a + b * b + c * c);

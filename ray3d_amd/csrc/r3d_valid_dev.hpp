@@ -18,6 +18,9 @@ namespace r3d {
 constexpr int VALID_THREADS = 256;
 constexpr int VALID_WAVES = VALID_THREADS / 64;
 
+// r3d_clips_valid_losses (the kernels' ClipsArgs table set as well): in.pos / in.trj / in.gt and `frame` are the SHARD's buffers,
+// `out` the strided result rows (only its being set is read); a workgroup moves the buffers to its clip's first frame and takes
+// n from the descriptor
 struct ValidArgs {
     ValidIn in;
     double *out;       // R3D_VALID_DOUBLES results, then as many per workgroup; null: the launch is not a validation-loss one
@@ -31,15 +34,19 @@ __device__ inline double valid_wave_sum(double v) {
     return v;
 }
 
-// One workgroup of VALID_THREADS threads; `cols`: VALID_WAVES * R3D_VALID_DOUBLES doubles of LDS
-__device__ inline void valid_block(const ValidArgs &a, double *cols) {
+// One workgroup of VALID_THREADS threads - workgroup `wg` of the `nwg` that share the clip `a` describes: it adds up frames
+// wg * 256 + k * nwg * 256 ... and leaves its R3D_VALID_DOUBLES sums in `row`.  `cols`: VALID_WAVES * R3D_VALID_DOUBLES doubles
+// of LDS.  `wg`, `nwg`, `row` and every field of `a` are the same for the whole workgroup.  The per-clip launch enters with
+// (blockIdx.x, gridDim.x) and a row behind its results, r3d_clips_valid_losses with blockIdx.x, the clip's OWN workgroup count
+// and the clip's slice of the scratch: the same instructions, the same bits.
+__device__ inline void valid_block(const ValidArgs &a, const int wg, const int nwg, double *row, double *cols) {
     for (int i = threadIdx.x; i < VALID_WAVES * R3D_VALID_DOUBLES; i += VALID_THREADS) cols[i] = 0.0;
     __syncthreads();
     const int lane = threadIdx.x & 63, J = a.in.J, nb = a.in.bones ? J - 1 : 0;
     const bool first = lane == 0;
     double *mine = cols + (threadIdx.x >> 6) * R3D_VALID_DOUBLES;
     // the wavefront's lanes stay together (the columns are added across them); a lane past the clip's end adds zeros
-    for (long long f0 = (long long)blockIdx.x * VALID_THREADS + (threadIdx.x - lane); f0 < a.n; f0 += (long long)gridDim.x * VALID_THREADS) {
+    for (long long f0 = (long long)wg * VALID_THREADS + (threadIdx.x - lane); f0 < a.n; f0 += (long long)nwg * VALID_THREADS) {
         const long long f = f0 + lane;
         const bool live = f < a.n;
         double term[R3D_VALID_COUNT] = {0, 0, 0, 0, 0, 0, 0};
@@ -68,7 +75,6 @@ __device__ inline void valid_block(const ValidArgs &a, double *cols) {
         }
     }
     __syncthreads();
-    double *row = a.out + R3D_VALID_DOUBLES * (1 + (long long)blockIdx.x);
     for (int c = threadIdx.x; c < R3D_VALID_DOUBLES; c += VALID_THREADS) {
         double v = 0;
         for (int w = 0; w < VALID_WAVES; ++w) v += cols[w * R3D_VALID_DOUBLES + c];
@@ -76,11 +82,11 @@ __device__ inline void valid_block(const ValidArgs &a, double *cols) {
     }
 }
 
-// The second launch (one wavefront): the workgroups' rows added in index order
-__device__ inline void valid_sum_rows(double *out, int blocks) {
+// The second launch (one wavefront per clip): the clip's `blocks` partial rows at `part` added in index order into `out`
+__device__ inline void valid_sum_rows(const double *part, int blocks, double *out) {
     for (int c = threadIdx.x; c < R3D_VALID_DOUBLES; c += 64) {
         double s = 0;
-        for (int b = 0; b < blocks; ++b) s += out[R3D_VALID_DOUBLES * (1 + b) + c];
+        for (int b = 0; b < blocks; ++b) s += part[R3D_VALID_DOUBLES * b + c];
         out[c] = s;
     }
 }

@@ -788,6 +788,154 @@ def validate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
     return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
 
 
+def shard_valid_hip(pos_all: torch.Tensor, trj_all: Optional[torch.Tensor], gt_all: torch.Tensor, table_dev: torch.Tensor,
+                    num_clips: int, total_frames: int, max_frames: int, rows: torch.Tensor, parents=H36M_17_PARENTS, flags: int = 0,
+                    frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE r3d_clips_valid_losses call on the current stream for every clip of a shard: `pos_all` / `gt_all` (total_frames, J, 3)
+    (or (total_frames, 1, J, 3)) float32, `trj_all` (total_frames, 3) (or (total_frames, 1, 1, 3)) float32 or None, `table_dev` the
+    uploaded bytes of a table of r3d_clip_desc rows (:func:`clip_table`, or :func:`clip_frame_table`: the transforms are not
+    read), `rows` the (num_clips, VALID_COLS) float64 matrix of row headers whose columns 3.. are written in place - with the
+    bits :func:`clip_valid` gives clip by clip; `parents` the joint tree (None: no bone terms), `flags` R3D_VALID_*; optional
+    `frames` (total_frames, VALID_COUNT).  No copy, no allocation (the scratch is a cached tensor per device), no
+    synchronisation."""
+    from . import _capi
+    dev = pos_all.device
+    for t, name in ((pos_all, "pos_all"), (gt_all, "gt_all")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape[0] != total_frames or t.shape[-1] != 3:
+            raise ValueError("%s: a contiguous float32 (total_frames, J, 3) tensor on %s is needed" % (name, dev))
+    J = pos_all.numel() // (3 * total_frames)
+    if pos_all.numel() != gt_all.numel():
+        raise ValueError("ground truth %s vs prediction %s" % (tuple(gt_all.shape), tuple(pos_all.shape)))
+    if trj_all is not None and (trj_all.dtype != torch.float32 or not trj_all.is_contiguous() or trj_all.device != dev
+                                or trj_all.shape[0] != total_frames or trj_all.numel() != 3 * total_frames):
+        raise ValueError("trj_all: a contiguous float32 (total_frames, 3) tensor on %s is needed" % (dev,))
+    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
+        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
+    if rows.dtype != torch.float64 or rows.device != dev or tuple(rows.shape) != (num_clips, VALID_COLS) or not rows.is_contiguous():
+        raise ValueError("rows: a contiguous float64 (%d, %d) matrix of row headers on %s is needed" % (num_clips, VALID_COLS, dev))
+    if frames is not None and (frames.dtype != torch.float64 or frames.device != dev or not frames.is_contiguous()
+                               or tuple(frames.shape) != (total_frames, M.VALID_COUNT)):
+        raise ValueError("frames: a contiguous float64 (%d, %d) tensor on %s is needed" % (total_frames, M.VALID_COUNT, dev))
+    tree = validate_parents(parents, J) if parents is not None else None
+    nbytes = _capi.clips_valid_scratch_bytes(num_clips, max_frames)
+    scratch = _shard_scratch.get(dev)
+    if scratch is None or scratch.numel() < nbytes:
+        scratch = _shard_scratch[dev] = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _capi.clips_valid_losses(pos_all.data_ptr(), trj_all.data_ptr() if trj_all is not None else None, gt_all.data_ptr(), total_frames,
+                                 J, tree, flags, table_dev.data_ptr(), num_clips, max_frames, rows.data_ptr() + 3 * 8, VALID_COLS,
+                                 frames.data_ptr() if frames is not None else None,
+                                 scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    return rows
+
+
+def clip_frame_table(lengths: Sequence[int]):
+    """(table, first_frame, total_frames, longest) for clips of these frame counts laid out back to back: r3d_clip_desc rows
+    with the identity for a transform - what r3d_clips_valid_losses needs of a table (it reads first_frame / n_frames only; a
+    caller that also evaluates hands it :func:`clip_table`'s)."""
+    from . import _capi
+    table = np.zeros(len(lengths), dtype=_capi.clip_desc_dtype())
+    first, at, longest = [], 0, 0
+    for k, n in enumerate(lengths):
+        table[k]["first_frame"], table[k]["n_frames"] = at, int(n)
+        table[k]["rn2w"] = np.eye(3).reshape(9)
+        first.append(at)
+        at += int(n)
+        longest = max(longest, int(n))
+    return table, first, at, longest
+
+
+def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, parents=H36M_17_PARENTS, group=None,
+                           pos_is_sum: bool = True, gt_root_relative: bool = False, causal: bool = False,
+                           bone_pairs: Optional[Sequence[tuple]] = None, encode: Optional[str] = None):
+    """:func:`validate_clips` with the measuring side in ONE call per shard: the rank's clip table and ground truth are uploaded
+    once, every clip is lifted into its slice of one pose buffer and one trajectory buffer
+    (``lift_clip(padded, param_row, out=pose_slice, trj_out=trj_slice)``), and one :func:`shard_valid_hip` call fills the sums
+    of all rows - then the same gather and :func:`reduce_valid`.  Same return values, the same bits in every row.  GPU only.
+
+    `lift_clip` takes the two keywords and returns (poses, trj) - ``functools.partial(lifter.forward_clip, return_trj=True)``
+    - or, for a configuration without a trajectory model, ignores ``trj_out`` and returns the poses alone; every clip of a
+    pass must answer alike.  When it is (a partial of) the bound ``forward_clip`` of a lifter with lanes (``set_lanes``), the
+    clips are dealt to the lanes and joined once, before the metrics call.
+
+    `encode` ("ray" | "intrinsic" | "screen"): ``Clip.rays`` holds RAW PIXELS (N, J, 2) and the input side is one call per
+    shard as well, exactly as in :func:`evaluate_clips_batched` (no mirror): the rank's pixels are uploaded once, ONE
+    r3d_clips_encode call pads and encodes every clip, each clip is lifted from its slice with ``n_windows=``; a descriptor
+    the encode call refuses raises."""
+    import torch.distributed as dist
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("validate_clips_batched measures on the GPU (r3d_clips_valid_losses); on CPU tensors use validate_clips")
+    lifter = getattr(lift_clip, "__self__", None) or getattr(getattr(lift_clip, "func", None), "__self__", None)
+    if encode is not None:        # (decided before the shards are cut: every rank raises alike, also one with an empty shard)
+        if encode not in ENCODINGS:
+            raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
+        if lifter is None or not hasattr(lifter, "clip_batch_sizes"):
+            raise ValueError("encode=: lift_clip must be (a functools.partial of) the bound forward_clip of a Ray3DLifter")
+    distributed = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if distributed else (0, 1)
+    actions = sorted(set(c.action for c in clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    shards = shard_clips([c.rays.shape[0] for c in clips], world)
+    mine = [clips[idx] for idx in shards[rank]]
+    local = torch.zeros((len(mine), VALID_COLS), dtype=torch.float64)
+    if mine:
+        local[:, :3] = torch.tensor([[float(idx), float(aid[clips[idx].action]), float(clips[idx].rays.shape[0])]
+                                     for idx in shards[rank]], dtype=torch.float64)
+    local = local.to(dev)
+    if mine:
+        table, first, total, longest = clip_frame_table([c.rays.shape[0] for c in mine])
+        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+        gt_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        J = gt_all.shape[1]
+        pos_all = torch.empty((total, 1, J, 3), dtype=torch.float32, device=dev)
+        trj_all = torch.empty((total, 1, 1, 3), dtype=torch.float32, device=dev)
+        lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
+        pad = (rf - 1) // 2
+
+        if encode is not None:
+            itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(lifter.clip_batch_sizes(n)) - n)
+            px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
+            itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
+            x_all, _, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode)
+            bad = torch.nonzero(status).flatten().tolist()
+            if bad:
+                raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
+
+        def lift(k, c, dst, tdst):
+            n = c.rays.shape[0]
+            prow = torch.from_numpy(c.camera.param()).to(dev)
+            if encode is not None:
+                rows = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
+                return lift_clip(x_all[rows], prow, out=dst, trj_out=tdst, n_windows=n)
+            padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
+            return lift_clip(padded, prow, out=dst, trj_out=tdst)
+
+        with_trj = set()
+        for k, c in enumerate(mine):
+            rows = slice(first[k], first[k] + c.rays.shape[0])
+            if lanes:
+                with lifter.lane():          # the clip's forwards on the next lane's stream
+                    res = lift(k, c, pos_all[rows], trj_all[rows])
+            else:
+                res = lift(k, c, pos_all[rows], trj_all[rows])
+            with_trj.add(isinstance(res, tuple))
+        if len(with_trj) != 1:
+            raise RuntimeError("lift_clip returned a trajectory for some clips of the pass and none for others")
+        has_trj = with_trj.pop()
+        if lanes:
+            lifter.join_lanes()
+        if gt_root_relative and has_trj:
+            raise ValueError("gt_root_relative is for models without a trajectory: with one the ground truth must be absolute")
+        from . import _capi
+        flags = (_capi.R3D_VALID_POS_IS_SUM if pos_is_sum and has_trj else 0) | (_capi.R3D_VALID_GT_ROOT_RELATIVE if gt_root_relative else 0)
+        shard_valid_hip(pos_all, trj_all if has_trj else None, gt_all, table_dev, len(mine), total, longest, local, parents, flags)
+    allrows = gather_partials(local, [len(s) for s in shards], group, cols=VALID_COLS) if world > 1 else local
+    allrows = allrows[torch.argsort(allrows[:, 0], stable=True)]
+    num_joints = int(clips[0].gt_norm.shape[1]) if len(clips) else 1
+    return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
+
+
 def reduce_valid(rows: torch.Tensor, num_joints: int = 17, bone_pairs: Optional[Sequence[tuple]] = None) -> Dict:
     """The figures of Trainer.test from the per-clip rows (:func:`clip_valid`), in the reference's units (its logs multiply
     every figure by 1000), frame-weighted over all clips as trainer.py:222-225 does:

@@ -422,7 +422,7 @@ class Ray3DLifter(nn.Module):
         return out
 
     def _run(self, mode, x, window_stride, B, param, param_stride, cam=None, cam_stride=0,
-             return_trj=False, out=None, workspace=None):
+             return_trj=False, out=None, workspace=None, out_trj=None):
         dev = x.device
         if self.pos.training or self.trj.training:
             raise RuntimeError("ray3d_amd modules are inference-only: call .eval() first")
@@ -431,7 +431,10 @@ class Ray3DLifter(nn.Module):
         hp, ht = self.pos.handle(dev), self.trj.handle(dev)
         if out is None:
             out = torch.empty((B, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=dev)
-        out_trj = torch.empty((B, 1, 1, 3), dtype=torch.float32, device=dev) if return_trj else None
+        if not return_trj:
+            out_trj = None
+        elif out_trj is None:
+            out_trj = torch.empty((B, 1, 1, 3), dtype=torch.float32, device=dev)
         if workspace is None and self.num_lanes():
             # one workspace per lane (forwards of different lanes are in flight together); a forward on a stream that is no lane's
             # is run on the next lane here, exactly as the library would relay it - so that the workspace is that lane's
@@ -439,7 +442,7 @@ class Ray3DLifter(nn.Module):
             if kk is None:
                 caller = torch.cuda.current_stream(dev)
                 with self.lane() as k2:
-                    res = self._run(mode, x, window_stride, B, param, param_stride, cam, cam_stride, return_trj, out, self._lane_ws[k2])
+                    res = self._run(mode, x, window_stride, B, param, param_stride, cam, cam_stride, return_trj, out, self._lane_ws[k2], out_trj)
                     # the caller's tensors are read / written on the lane's stream: keep them alive until the lane is past this forward
                     # (a caller on a side stream that drops its input right after the call would otherwise get the block back from
                     # the caching allocator and overwrite it on its own stream while the lane still reads it).  Not record_stream on
@@ -450,7 +453,7 @@ class Ray3DLifter(nn.Module):
                     keep = self._lane_keep
                     while keep and keep[0][0].query():
                         keep.pop(0)
-                    keep.append((done, x, param, cam, out))
+                    keep.append((done, x, param, cam, out, out_trj))
                 for t in (res if isinstance(res, tuple) else (res,)):
                     if t is not None:
                         t.record_stream(caller)        # (allocated under the lane's stream, consumed on the caller's after join_lanes)
@@ -547,7 +550,7 @@ class Ray3DLifter(nn.Module):
         return sizes
 
     def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False,
-                     out: Optional[torch.Tensor] = None, n_windows: Optional[int] = None):
+                     out: Optional[torch.Tensor] = None, n_windows: Optional[int] = None, trj_out: Optional[torch.Tensor] = None):
         """clip (N + RF - 1, J, F): an edge-padded sequence; window i = frames [i, i+RF) is gathered
         in the kernels instead of materialising lib/train_val/trainer.py:47-58's copy.
         param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3) - with `return_trj` the pair
@@ -565,8 +568,16 @@ class Ray3DLifter(nn.Module):
         `n_windows`: the clip has N = n_windows windows and the tensor ALREADY carries the surplus rows of the rounded-up
         batch sizes behind them - exactly ``sum(clip_batch_sizes(n_windows)) + RF - 1`` rows, e.g. a clip's slice of the
         buffer r3d_clips_encode filled (evaluate.shard_encode_hip) - so nothing is concatenated; the same forwards run on
-        the same values.  Any other row count is a ValueError."""
+        the same values.  Any other row count is a ValueError.
+
+        `trj_out` (needs `return_trj`): a contiguous (N,1,1,3) float32 tensor on the clip's device - e.g. the clip's slice of a
+        shard's trajectory buffer (evaluate.validate_clips_batched) - that the trajectory is written into, by `out`'s rule:
+        every call writes straight into its rows where its rounded-up size fits, the tail call goes through a scratch tensor.
+        Nothing is concatenated; the same forwards run, so poses and trajectory have the bits of a call without it.  The pair
+        returned is (poses, trj_out)."""
         rf = self.receptive_field()
+        if trj_out is not None and not return_trj:
+            raise ValueError("forward_clip(trj_out=) needs return_trj=True")
         assert clip.dim() == 3 and clip.shape[1] == self.pos.num_joints_in and clip.shape[2] == self.pos.in_features
         if n_windows is not None:
             n = int(n_windows)
@@ -583,8 +594,10 @@ class Ray3DLifter(nn.Module):
             if self.pos.camera_embedding else None
         sizes = self.clip_batch_sizes(n)
         total = sum(sizes)
+        if out is None and trj_out is not None:
+            out = torch.empty((n, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=clip.device)
         if out is not None:
-            return self._forward_clip_into(clip, p, n, sizes, return_trj, out, n_windows is not None)
+            return self._forward_clip_into(clip, p, n, sizes, return_trj, out, n_windows is not None, trj_out)
         if total == n and len(sizes) == 1:
             return self._run(_capi.R3D_INPUT_RAYS, clip, 1, n, p, 0, return_trj=return_trj)
         if total > n and n_windows is None:
@@ -602,10 +615,14 @@ class Ray3DLifter(nn.Module):
         self.join_lanes()      # (the pieces were written on the lanes' streams: the concatenation below runs on the caller's)
         return out[:n], torch.cat(trjs, dim=0)[:n]
 
-    def _forward_clip_into(self, clip, p, n, sizes, return_trj, out, has_surplus=False):
+    def _forward_clip_into(self, clip, p, n, sizes, return_trj, out, has_surplus=False, trj_out=None):
         """forward_clip(out=): the forwards of `sizes` written straight into `out` (n rows) where they fit; `has_surplus`: the
-        clip already carries the rows of the surplus windows (forward_clip(n_windows=))."""
+        clip already carries the rows of the surplus windows (forward_clip(n_windows=)); `trj_out`: the trajectory likewise."""
         J = self.pos.num_joints_in
+        if trj_out is not None and (tuple(trj_out.shape) != (n, 1, 1, 3) or trj_out.dtype != torch.float32 or trj_out.device != clip.device
+                                    or not trj_out.is_contiguous()):
+            raise ValueError("forward_clip(trj_out=): a contiguous float32 (%d, 1, 1, 3) tensor on %s is needed (got %s %s on %s)"
+                             % (n, clip.device, tuple(trj_out.shape), trj_out.dtype, trj_out.device))
         if tuple(out.shape) != (n, 1, J, 3) or out.dtype != torch.float32 or out.device != clip.device or not out.is_contiguous():
             raise ValueError("forward_clip(out=): a contiguous float32 (%d, 1, %d, 3) tensor on %s is needed (got %s %s on %s)"
                              % (n, J, clip.device, tuple(out.shape), out.dtype, out.device))
@@ -617,17 +634,25 @@ class Ray3DLifter(nn.Module):
         for b in sizes:
             fits = start + b <= n
             dst = out[start:start + b] if fits else torch.empty((b, 1, J, 3), dtype=torch.float32, device=clip.device)
-            res = self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, return_trj=return_trj, out=dst)
+            tdst, extra = None, {}
+            if trj_out is not None:
+                tdst = trj_out[start:start + b] if fits else torch.empty((b, 1, 1, 3), dtype=torch.float32, device=clip.device)
+                extra = {"out_trj": tdst}
+            res = self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, return_trj=return_trj, out=dst, **extra)
             if not fits and start < n:
-                tails.append((start, dst))
-            if return_trj:
+                tails.append((start, dst, tdst))
+            if return_trj and trj_out is None:
                 trjs.append(res[1])
             start += b
-        if (tails or return_trj) and self._lane_of_current_stream(clip.device) is None:
+        if (tails or trjs) and self._lane_of_current_stream(clip.device) is None:
             self.join_lanes()  # (forwards relayed to the lanes' streams: what follows runs on the caller's)
-        for at, piece in tails:
+        for at, piece, tpiece in tails:
             out[at:] = piece[:n - at]
-        return (out, torch.cat(trjs, dim=0)[:n]) if return_trj else out
+            if tpiece is not None:
+                trj_out[at:] = tpiece[:n - at]
+        if not return_trj:
+            return out
+        return (out, trj_out) if trj_out is not None else (out, torch.cat(trjs, dim=0)[:n])
 
     def prepare(self, batch_sizes, device=None):
         """Build and upload the tile schedules of these batch sizes now (r3d_prepare) instead of inside the first

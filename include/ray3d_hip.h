@@ -579,6 +579,56 @@ int r3d_clips_valid_losses(const float *pos_dev, const float *trj_dev, const flo
                            double *frame_dev,                              /* optional (NULL): (total_frames, R3D_VALID_COUNT) */
                            void *scratch_dev, size_t scratch_bytes, void *stream);
 
+/* ---- a shard's finished poses: flip average and world coordinates of every clip in one call ---- */
+
+/* What lies between a shard's forwards and its measurement, on the device and in ONE launch: the flip average of
+ * lib/train_val/trainer.py:340-346 and - what the reference hands to its renderer, Trainer.render, trainer.py:505-526 through
+ * cam.normalized2world / cam.camera2world, lib/camera/camera.py:347-410 - the poses in world coordinates.  raw_dev and
+ * raw_mirror_dev are (raw_rows, J, 3) float32: what the forwards wrote, the straight pass and the pass over the mirrored input.
+ * Clip c is its row of the r3d_clip_desc table that r3d_clips_metrics reads (a caller uploads ONE table) and raw_first_dev[c], a
+ * device array of num_clips int64: it reads raw rows [raw_first, raw_first + n_frames) - the rows behind them, up to the clip's
+ * rounded-up call sizes, are surplus and are never read - and writes rows [first_frame, first_frame + n_frames) of pred_dev
+ * (total_frames, J, 3) float32 and world_dev (total_frames, J, 3) float64; either output may be NULL, not both.  Clips may lie in
+ * any order, with gaps, in both layouts.  A trajectory buffer (rows, 3) is the J = 1 case with mirror_perm = {0}.
+ *   raw_mirror_dev / mirror_perm: both NULL, or both given.  mirror_perm is a HOST array of J entries, a permutation of 0..J-1
+ *               (left and right joints trade places); it travels as a kernel argument.
+ *   status_dev: num_clips int32 words, required: 0 for a clip that was followed, 1 for an invalid descriptor.
+ * ROUNDING CONTRACT.  Per output point (frame, joint j), p its three float32 components:
+ *   without raw_mirror_dev: p is the raw value, bits copied (NaN payloads included);
+ *   with raw_mirror_dev:    m = raw_mirror[row, mirror_perm[j]] with component 0 negated (exact), p = fl32(fl32(raw + m) * 0.5f):
+ *                           one float32 rounding each, in that operand order - the bits of
+ *                           torch.add(dst, mirror_output(pred_m)); dst.mul_(0.5), the per-clip sequence it replaces;
+ *   pred_dev receives p;
+ *   world_dev is computed from that same p promoted to float64, whether or not pred_dev is given: component r is
+ *                           ((R[3r] * x + R[3r+1] * y) + R[3r+2] * z) + T[r] with R = rn2w, T = tn2w of the clip's descriptor,
+ *                           every product and every sum rounded once (no fused multiply-add: the one routine the kernel and the
+ *                           host hook share is compiled with floating-point contraction off, so the two agree bit for bit).
+ * A NaN that the arithmetic produces is stored as the canonical quiet NaN (float32 0x7fc00000, float64 0x7ff8000000000000).
+ * NON-FINITE VALUES.  A NaN or Inf in a raw element makes exactly the output point(s) that read it non-finite - all three world
+ * components of that point included - and every other output keeps the bits it would have had without it.  Not an error.
+ * GRID.  max_frames is the caller's bound on any clip's length and sizes the grid: (ceil(max_frames * num_joints / 256),
+ * num_clips) workgroups, one output point per thread; a workgroup past its clip's points returns at once.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A descriptor is invalid when n_frames < 1, n_frames > max_frames,
+ * [first_frame, first_frame + n_frames) is not inside [0, total_frames), raw_first < 0, or raw_first + n_frames > raw_rows.  The
+ * kernel never follows an invalid descriptor: nothing of that clip is read or written, status_dev[c] = 1.  Rows no valid clip
+ * covers are left untouched.  Beyond the descriptors it reads raw_dev / raw_mirror_dev within raw_rows * num_joints * 3 floats,
+ * the table within num_clips descriptors and raw_first_dev within num_clips words, and writes pred_dev / world_dev within
+ * total_frames * num_joints * 3 elements and status_dev within num_clips words: no input can make it touch memory outside these
+ * extents.  Overlapping output rows of two valid clips are the caller's error (either value may win, nothing leaves the extents).
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (raw_dev, clips_dev, raw_first_dev,
+ * status_dev), both outputs null, exactly one of raw_mirror_dev / mirror_perm, a mirror_perm that is not a permutation,
+ * num_clips outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, max_frames, total_frames or raw_rows < 1, max_frames *
+ * num_joints, total_frames or raw_rows above R3D_ENCODE_MAX_POINTS (index arithmetic), a table, raw_first_dev or world_dev
+ * pointer that is not 8-byte aligned, an output extent (pred_dev, world_dev) that overlaps the extent of raw_dev or
+ * raw_mirror_dev - compared as address ranges: in-place use is refused rather than given rules.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
+ * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t raw_rows, int32_t num_joints,
+                    const int32_t *mirror_perm,                 /* HOST, J entries; given exactly when raw_mirror_dev is */
+                    const r3d_clip_desc *clips_dev, const int64_t *raw_first_dev, int32_t num_clips, int64_t max_frames,
+                    float *pred_dev, double *world_dev, int64_t total_frames,   /* either may be NULL, not both */
+                    int32_t *status_dev, void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -633,6 +683,11 @@ int r3d_debug_clips_encode_host(const float *px, int64_t total_frames, int32_t n
 int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t num_joints,
                                       const int32_t *parents, int32_t flags, const r3d_clip_desc *clips, int32_t num_clips,
                                       int64_t max_frames, double *rows, int64_t row_stride, double *frame);
+/* r3d_clips_poses on the host (HOST pointers throughout, no stream): the same argument checks, the same descriptor rule and the
+ * same per-point routines, clips in table order. */
+int r3d_debug_clips_poses_host(const float *raw, const float *raw_mirror, int64_t raw_rows, int32_t num_joints,
+                               const int32_t *mirror_perm, const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips,
+                               int64_t max_frames, float *pred, double *world, int64_t total_frames, int32_t *status);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

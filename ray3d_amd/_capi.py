@@ -31,11 +31,11 @@ EXPORTS = (
     "r3d_profile_enable", "r3d_profile_read", "r3d_clip_metrics", "r3d_clip_metrics_detail", "r3d_clip_valid_losses", "r3d_last_error", "r3d_version",
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
-    "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes",
+    "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
-                "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host")
+                "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -167,9 +167,13 @@ def load():
     lib.r3d_clips_valid_scratch_bytes.restype = C.c_size_t
     lib.r3d_clips_valid_losses.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, C.c_int64,
                                            vp, C.c_int64, vp, vp, C.c_size_t, vp]
+    lib.r3d_clips_poses.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_int64,
+                                    vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_clips_poses_host.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp,
+                                                   C.c_int64, vp]
         lib.r3d_debug_clips_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32,
                                                           C.c_int64, vp, C.c_int64, vp]
         lib.r3d_debug_undistort_host.argtypes = [vp, vp, C.c_int64, vp, vp]
@@ -367,6 +371,35 @@ def clips_encode(px_ptr: int, total_frames: int, num_joints: int, encoding: int,
     perm = (C.c_int32 * len(mirror_perm))(*[int(v) for v in mirror_perm]) if mirror_perm is not None else None
     check(load().r3d_clips_encode(px_ptr, total_frames, num_joints, encoding, table_ptr, num_clips, max_rows, x_ptr, out_rows,
                                   x_mirror_ptr or None, perm, status_ptr, stream), "r3d_clips_encode")
+
+
+def _mirror_table(what: str, mirror_perm, num_joints: int):
+    if mirror_perm is None:
+        return None
+    if len(mirror_perm) != num_joints:
+        raise Ray3DHipError("%s: mirror_perm has %d entries, num_joints is %d" % (what, len(mirror_perm), num_joints))
+    return (C.c_int32 * len(mirror_perm))(*[int(v) for v in mirror_perm])
+
+
+def clips_poses(raw_ptr: int, raw_mirror_ptr: Optional[int], raw_rows: int, num_joints: int, mirror_perm, table_ptr: int,
+                raw_first_ptr: int, num_clips: int, max_frames: int, pred_ptr: Optional[int], world_ptr: Optional[int],
+                total_frames: int, status_ptr: int, stream: int):
+    """r3d_clips_poses: every pointer is device memory; `table_ptr` num_clips r3d_clip_desc (:func:`clip_desc_dtype`) back to
+    back, `raw_first_ptr` num_clips int64; `raw_mirror_ptr` (or None) and `mirror_perm` (a host sequence of num_joints ints, or
+    None) go together; `pred_ptr` / `world_ptr`: either may be None, not both; `status_ptr` num_clips int32."""
+    perm = _mirror_table("r3d_clips_poses", mirror_perm, num_joints)
+    check(load().r3d_clips_poses(raw_ptr, raw_mirror_ptr or None, raw_rows, num_joints, perm, table_ptr, raw_first_ptr, num_clips,
+                                 max_frames, pred_ptr or None, world_ptr or None, total_frames, status_ptr, stream), "r3d_clips_poses")
+
+
+def debug_clips_poses_host(raw_ptr: int, raw_mirror_ptr: Optional[int], raw_rows: int, num_joints: int, mirror_perm, table_ptr: int,
+                           raw_first_ptr: int, num_clips: int, max_frames: int, pred_ptr: Optional[int], world_ptr: Optional[int],
+                           total_frames: int, status_ptr: int) -> int:
+    """r3d_debug_clips_poses_host (hooks library only: use_hooks(True)): r3d_clips_poses on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    perm = _mirror_table("r3d_debug_clips_poses_host", mirror_perm, num_joints)
+    return int(load().r3d_debug_clips_poses_host(raw_ptr, raw_mirror_ptr or None, raw_rows, num_joints, perm, table_ptr, raw_first_ptr,
+                                                 num_clips, max_frames, pred_ptr or None, world_ptr or None, total_frames, status_ptr))
 
 
 def _parent_table(parents):

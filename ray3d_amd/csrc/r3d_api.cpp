@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "r3d_internal.hpp"
+#include "r3d_poses.hpp"
 #include "r3d_undistort.hpp"
 
 using namespace r3d;
@@ -84,6 +85,55 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
         }
     }
     if (reinterpret_cast<uintptr_t>(clips) % 8) { set_error("%s: the clip table must be 8-byte aligned", what); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_clips_poses, shared with its host hook (`what`: the name in the message)
+int r3d::clips_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int64_t raw_rows, int32_t J,
+                                const int32_t *mirror_perm, const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips,
+                                int64_t max_frames, const float *pred, const double *world, int64_t total_frames, const int32_t *status) {
+    if (!raw || !clips || !raw_first || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (!pred && !world) { set_error("%s: pred_dev and world_dev are both null: nothing to write", what); return R3D_ERR_ARG; }
+    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (max_frames < 1 || total_frames < 1 || raw_rows < 1) {
+        set_error("%s: max_frames, total_frames and raw_rows must be >= 1 (got %lld, %lld, %lld)", what, (long long)max_frames,
+                  (long long)total_frames, (long long)raw_rows);
+        return R3D_ERR_ARG;
+    }
+    if (max_frames > R3D_ENCODE_MAX_POINTS / J || total_frames > R3D_ENCODE_MAX_POINTS || raw_rows > R3D_ENCODE_MAX_POINTS) {
+        set_error("%s: max_frames * num_joints, total_frames and raw_rows must not exceed %d", what, R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if ((raw_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: raw_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (mirror_perm) {
+        unsigned seen = 0;
+        for (int j = 0; j < J; ++j) {
+            if (mirror_perm[j] < 0 || mirror_perm[j] >= J || (seen >> mirror_perm[j] & 1u)) {
+                set_error("%s: mirror_perm must be a permutation of 0..%d (entry %d is %d)", what, J - 1, j, mirror_perm[j]);
+                return R3D_ERR_ARG;
+            }
+            seen |= 1u << mirror_perm[j];
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(clips) % 8 || reinterpret_cast<uintptr_t>(raw_first) % 8 || reinterpret_cast<uintptr_t>(world) % 8) {
+        set_error("%s: the clip table, raw_first_dev and world_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    // in-place use is refused: an output extent may not overlap an input extent (address ranges; the sizes fit in 64 bits)
+    const uintptr_t in_bytes = (uintptr_t)raw_rows * J * 3 * sizeof(float);
+    const uintptr_t out_bytes[2] = {(uintptr_t)total_frames * J * 3 * sizeof(float), (uintptr_t)total_frames * J * 3 * sizeof(double)};
+    const uintptr_t outs[2] = {reinterpret_cast<uintptr_t>(pred), reinterpret_cast<uintptr_t>(world)};
+    const uintptr_t ins[2] = {reinterpret_cast<uintptr_t>(raw), reinterpret_cast<uintptr_t>(raw_mirror)};
+    for (int o = 0; o < 2; ++o)
+        for (int i = 0; i < 2; ++i)
+            if (outs[o] && ins[i] && outs[o] < ins[i] + in_bytes && ins[i] < outs[o] + out_bytes[o]) {
+                set_error("%s: %s overlaps %s: the call does not work in place", what, o ? "world_dev" : "pred_dev", i ? "raw_mirror_dev" : "raw_dev");
+                return R3D_ERR_ARG;
+            }
     return R3D_OK;
 }
 
@@ -298,6 +348,34 @@ int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_join
     const hipError_t err = r3d::launch_clips_encode(a, num_clips, (hipStream_t)stream);   // (the launcher consumed the error: print what it returned)
     if (err != hipSuccess) {
         set_error("r3d_clips_encode: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t raw_rows, int32_t num_joints, const int32_t *mirror_perm,
+                    const r3d_clip_desc *clips_dev, const int64_t *raw_first_dev, int32_t num_clips, int64_t max_frames,
+                    float *pred_dev, double *world_dev, int64_t total_frames, int32_t *status_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    const int rc = clips_poses_check_args("r3d_clips_poses", raw_dev, raw_mirror_dev, raw_rows, num_joints, mirror_perm, clips_dev,
+                                          raw_first_dev, num_clips, max_frames, pred_dev, world_dev, total_frames, status_dev);
+    if (rc != R3D_OK) return rc;
+    r3d::ClipsPosesArgs a = {};
+    a.table = clips_dev;
+    a.raw_first = reinterpret_cast<const long long *>(raw_first_dev);
+    a.raw = raw_dev;
+    a.raw_mirror = raw_mirror_dev;
+    a.pred = pred_dev;
+    a.world = world_dev;
+    a.status = status_dev;
+    a.raw_rows = raw_rows;
+    a.total_frames = total_frames;
+    a.max_frames = max_frames;
+    if (mirror_perm) r3d::pose_pack_perm(mirror_perm, num_joints, a.mirror_perm);
+    a.J = num_joints;
+    const hipError_t err = r3d::launch_clips_poses(a, num_clips, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_clips_poses: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "r3d_internal.hpp"
+#include "r3d_poses.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
 
@@ -355,6 +356,36 @@ int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const 
         const int rc1 = r3d_debug_valid_losses_host(pos + first * num_joints * 3, trj ? trj + first * 3 : nullptr, gt + first * num_joints * 3, n,
                                                     num_joints, parents, flags, row, frame ? frame + first * R3D_VALID_COUNT : nullptr);
         if (rc1 != R3D_OK) return rc1;
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_clips_poses on the host - its argument rules (clips_poses_check_args), its descriptor rule (clip_pose_valid) and the
+// per-point routines of r3d_poses.hpp, clip by clip in table order.
+int r3d_debug_clips_poses_host(const float *raw, const float *raw_mirror, int64_t raw_rows, int32_t num_joints, const int32_t *mirror_perm,
+                               const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips, int64_t max_frames,
+                               float *pred, double *world, int64_t total_frames, int32_t *status) {
+    const int rc = clips_poses_check_args("r3d_debug_clips_poses_host", raw, raw_mirror, raw_rows, num_joints, mirror_perm, clips, raw_first,
+                                          num_clips, max_frames, pred, world, total_frames, status);
+    if (rc != R3D_OK) return rc;
+    unsigned long long perm[2] = {0ull, 0ull};
+    if (mirror_perm) pose_pack_perm(mirror_perm, num_joints, perm);
+    const int J = num_joints;
+    for (int32_t c = 0; c < num_clips; ++c) {
+        const long long first = clips[c].first_frame, n = clips[c].n_frames, rf = raw_first[c];
+        const bool ok = clip_pose_valid(first, n, rf, total_frames, max_frames, raw_rows);
+        status[c] = ok ? 0 : 1;
+        if (!ok) continue;
+        for (long long f = 0; f < n; ++f)
+            for (int j = 0; j < J; ++j) {
+                const long long src_row = (rf + f) * J;
+                const float *mir = raw_mirror ? raw_mirror + 3 * (src_row + pose_mirror_source(perm[0], perm[1], j)) : nullptr;
+                float p[3];
+                pose_finish(raw + 3 * (src_row + j), mir, p);
+                const long long dst = 3 * ((first + f) * J + j);
+                if (pred) memcpy(pred + dst, p, sizeof(p));
+                if (world) pose_world(clips[c].rn2w, clips[c].tn2w, p, world + dst);
+            }
     }
     return R3D_OK;
 }

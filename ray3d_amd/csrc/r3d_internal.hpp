@@ -156,6 +156,20 @@ struct ClipsEncArgs {
     int encoding;                       // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN
 };
 
+// r3d_clips_poses: the third argument set of r3d_undistort_rays_f64 (table == nullptr: not that mode).  blockIdx.y names a clip of
+// the device-side table; one output point (frame, joint) per thread (r3d_poses.hpp).
+struct ClipsPosesArgs {
+    const r3d_clip_desc *table;         // num_clips (= gridDim.y) descriptors in device memory
+    const long long *raw_first;         // num_clips: the clip's first row in raw / raw_mirror
+    const float *raw, *raw_mirror;      // (raw_rows, J, 3): what the forwards wrote; raw_mirror nullptr: no flip pass
+    float *pred;                        // (total_frames, J, 3) or nullptr
+    double *world;                      // (total_frames, J, 3) or nullptr
+    int32_t *status;                    // num_clips words: 0 followed, 1 invalid descriptor
+    long long raw_rows, total_frames, max_frames;
+    unsigned long long mirror_perm[2];  // pose_pack_perm (r3d_poses.hpp)
+    int J;
+};
+
 constexpr int MAX_DEC = 6;     // 5 body-part decoders + the trajectory decoder
 // Fused decoder tail: the last Linear (1024 -> 3*n_g) of every Integration block, the joint
 // reassembly (rie.py:415-432) and the trajectory add (trainer.py:353) in one pass.
@@ -516,6 +530,11 @@ int clips_encode_check_args(const char *what, const float *px, int64_t total_fra
                             const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
                             const float *x_mirror, const int32_t *mirror_perm, const int32_t *status);
 
+// the argument rules of r3d_clips_poses, shared with its host hook (r3d_api.cpp)
+int clips_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int64_t raw_rows, int32_t J,
+                           const int32_t *mirror_perm, const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips,
+                           int64_t max_frames, const float *pred, const double *world, int64_t total_frames, const int32_t *status);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -591,6 +610,7 @@ int forward_resident_capacity(int kind, bool uv);      // workgroups of that ker
 hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip): every encoding
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // the same kernel, one grid row per clip
+hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_poses
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -16,12 +16,54 @@
 // each thread then encodes one output point (row, joint) from the clamped source frame through encode_point_f32, the routine
 // the pre-pass itself writes with: the same bits, also in the padding rows.  (One kernel, two argument sets, as the clip
 // metrics are: the library's kernel set stays what tests/test_host.py pins.)
+//
+// r3d_clips_poses (a shard's finished poses from what its forwards wrote, include/ray3d_hip.h) is the kernel's third argument set,
+// ClipsPosesArgs, for the same reason and of the same shape: blockIdx.y names a clip of the r3d_clip_desc table, the workgroup reads
+// the descriptor and the clip's raw_first by scalar loads and decides on them before anything else, and each thread finishes one
+// output point (frame, joint) through pose_finish / pose_world of r3d_poses.hpp - the routines the host hook runs.  It is the
+// elementwise end of a clip pass as r3d_clips_encode is its elementwise start: 12 or 24 bytes read and 12 and / or 24 written per
+// thread, consecutive threads at consecutive addresses (the mirrored read is a permutation inside the row's J * 12 bytes).
 #include "r3d_internal.hpp"
+#include "r3d_poses.hpp"
 #include "r3d_undistort.hpp"
 
 namespace r3d {
 
-extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c) {
+__device__ __forceinline__ void clips_poses_body(const ClipsPosesArgs &q) {
+    const r3d_clip_desc *d = q.table + blockIdx.y;
+    const long long first = d->first_frame, n = d->n_frames, raw_first = q.raw_first[blockIdx.y];
+    const bool ok = clip_pose_valid(first, n, raw_first, q.total_frames, q.max_frames, q.raw_rows);
+    if (blockIdx.x == 0 && threadIdx.x == 0) q.status[blockIdx.y] = ok ? 0 : 1;
+    if (!ok) return;                         // an invalid descriptor is not followed: nothing of the clip is read or written
+    // (max_frames * J fits in 31 bits - checked on the host - and so do the clip's points and this launch's indices)
+    const int npts = (int)n * q.J;
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= npts) return;                  // also the workgroups past the clip's own count
+    const int f = pt / q.J, j = pt - f * q.J;
+    const long long src_row = (raw_first + f) * q.J;
+    const float *mir = q.raw_mirror ? q.raw_mirror + 3 * (src_row + pose_mirror_source(q.mirror_perm[0], q.mirror_perm[1], j)) : nullptr;
+    float p[3];
+    pose_finish(q.raw + 3 * (src_row + j), mir, p);
+    const long long dst = 3 * ((first + f) * q.J + j);
+    if (q.pred) {
+        q.pred[dst] = p[0];
+        q.pred[dst + 1] = p[1];
+        q.pred[dst + 2] = p[2];
+    }
+    if (q.world) {
+        double w[3];
+        pose_world(d->rn2w, d->tn2w, p, w);
+        q.world[dst] = w[0];
+        q.world[dst + 1] = w[1];
+        q.world[dst + 2] = w[2];
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q) {
+    if (q.table) {                           // uniform: r3d_clips_poses - clip blockIdx.y of the table
+        clips_poses_body(q);
+        return;
+    }
     if (c.table) {                           // uniform: r3d_clips_encode - clip blockIdx.y of the table
         const r3d_clip_input_desc *d = c.table + blockIdx.y;
         const long long first = d->first_frame, n = d->n_frames, out_first = d->out_first;
@@ -71,14 +113,21 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{});
+    return hipGetLastError();
+}
+
+// r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
+hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
+    const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args);
     return hipGetLastError();
 }
 

@@ -581,12 +581,177 @@ def shard_encode_hip(px_all: torch.Tensor, table_dev: torch.Tensor, num_clips: i
     return x_all, x_mirror_all, status
 
 
+# ------------------------------------------------------------------------------------ a whole shard's finished poses in one call
+
+def clip_raw_table(lengths: Sequence[int], sizes_of: Callable[[int], Sequence[int]]):
+    """(raw_first, raw_rows) for clips of these frame counts whose forwards write into ONE raw buffer back to back: clip k owns rows
+    [raw_first[k], raw_first[k] + sum(sizes_of(N_k))) - what ``Ray3DLifter.forward_clip(..., raw_out=)`` takes, `sizes_of` the
+    lifter's ``clip_batch_sizes`` - of which the first N_k are its poses and the rest the surplus windows' that
+    r3d_clips_poses never reads.  `raw_first` goes to the device as int64 (:func:`shard_poses_hip`)."""
+    raw_first, at = [], 0
+    for n in lengths:
+        raw_first.append(at)
+        at += int(sum(sizes_of(int(n))))
+    return raw_first, at
+
+
+def shard_poses_hip(raw_all: torch.Tensor, table_dev: torch.Tensor, raw_first_dev: torch.Tensor, num_clips: int, total_frames: int,
+                    max_frames: int, raw_mirror_all: Optional[torch.Tensor] = None, mirror_perm: Optional[Sequence[int]] = None,
+                    pred: bool = True, world: bool = False, pred_all: Optional[torch.Tensor] = None,
+                    world_all: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """ONE r3d_clips_poses call on the current stream for every clip of a shard: `raw_all` (raw_rows, J, 3) (or (raw_rows, 1, J, 3))
+    float32, what the forwards wrote (``forward_clip(raw_out=)``); `raw_mirror_all` the same from the pass over the mirrored
+    input, with `mirror_perm` (:func:`mirror_permutation` of the OUTPUT joints); `table_dev` the uploaded bytes of
+    :func:`clip_table` (the one :func:`shard_metrics_hip` reads), `raw_first_dev` (num_clips,) int64 (:func:`clip_raw_table`).
+    Returns (pred_all (total_frames, J, 3) float32 or None, world_all (total_frames, J, 3) float64 or None, status (num_clips,)
+    int32: 0 = followed, 1 = invalid descriptor) - `pred` / `world` say which outputs are wanted.  `pred_all` / `world_all` /
+    `status`: tensors to write into (contiguous, total_frames rows of J * 3 elements; (num_clips,)) instead of new ones - needed
+    under hipGraph capture; new buffers are NOT zeroed: rows no clip covers keep what they held.  No copy and no
+    synchronisation: the caller reads `status` when it wants to."""
+    from . import _capi
+    dev = raw_all.device
+    if raw_all.dtype != torch.float32 or not raw_all.is_contiguous() or not raw_all.is_cuda or raw_all.dim() not in (3, 4) \
+            or raw_all.shape[-1] != 3 or raw_all.shape[0] < 1 or (raw_all.dim() == 4 and raw_all.shape[1] != 1):
+        raise ValueError("raw_all: a contiguous float32 (raw_rows, J, 3) tensor on a GPU is needed")
+    raw_rows, J = int(raw_all.shape[0]), int(raw_all.shape[-2])
+    if (raw_mirror_all is None) != (mirror_perm is None):
+        raise ValueError("raw_mirror_all and mirror_perm go together")
+    if raw_mirror_all is not None and (raw_mirror_all.dtype != torch.float32 or raw_mirror_all.device != dev
+                                       or not raw_mirror_all.is_contiguous() or raw_mirror_all.shape[0] != raw_rows
+                                       or raw_mirror_all.numel() != raw_all.numel()):
+        raise ValueError("raw_mirror_all: a contiguous float32 (%d, %d, 3) tensor on %s is needed" % (raw_rows, J, dev))
+    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
+        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
+    if raw_first_dev.dtype != torch.int64 or raw_first_dev.device != dev or not raw_first_dev.is_contiguous() \
+            or tuple(raw_first_dev.shape) != (num_clips,):
+        raise ValueError("raw_first_dev: a contiguous int64 (%d,) tensor on %s is needed" % (num_clips, dev))
+    pred = pred or pred_all is not None
+    world = world or world_all is not None
+    if not pred and not world:
+        raise ValueError("neither pred nor world is wanted: nothing to write")
+    bufs = []
+    for t, name, want, dtype in ((pred_all, "pred_all", pred, torch.float32), (world_all, "world_all", world, torch.float64)):
+        if t is None:
+            t = torch.empty((total_frames, J, 3), dtype=dtype, device=dev) if want else None
+        elif t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.dim() < 2 or t.shape[0] != total_frames \
+                or t.numel() != total_frames * J * 3:
+            raise ValueError("%s: a contiguous %s (%d, %d, 3) tensor on %s is needed" % (name, dtype, total_frames, J, dev))
+        bufs.append(t)
+    pred_all, world_all = bufs
+    if status is None:
+        status = torch.empty(num_clips, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or tuple(status.shape) != (num_clips,):
+        raise ValueError("status: a contiguous int32 (%d,) tensor on %s is needed" % (num_clips, dev))
+    with torch.cuda.device(dev):
+        _capi.clips_poses(raw_all.data_ptr(), raw_mirror_all.data_ptr() if raw_mirror_all is not None else None, raw_rows, J,
+                          [int(v) for v in mirror_perm] if mirror_perm is not None else None, table_dev.data_ptr(),
+                          raw_first_dev.data_ptr(), num_clips, max_frames, pred_all.data_ptr() if pred_all is not None else None,
+                          world_all.data_ptr() if world_all is not None else None, total_frames, status.data_ptr(),
+                          torch.cuda.current_stream(dev).cuda_stream)
+    return pred_all, world_all, status
+
+
+def _lifter_of(lift_clip: Callable, what: str):
+    """The Ray3DLifter whose bound ``forward_clip`` `lift_clip` is, or a ValueError (decided before any shard is cut)."""
+    lifter = getattr(lift_clip, "__self__", None)
+    if lifter is None or getattr(lift_clip, "__name__", "") != "forward_clip" or not hasattr(lifter, "clip_batch_sizes"):
+        raise ValueError("%s: lift_clip must be the bound forward_clip of a Ray3DLifter (its raw_out= and clip_batch_sizes are used)" % what)
+    return lifter
+
+
+def _finished_shard(lift_clip: Callable, lifter, mine: Sequence[Clip], rf: int, dev, flip: bool, kps_left, kps_right, causal: bool,
+                    joints_left, joints_right, mirror: Optional[Callable], encode: Optional[str], table_dev: torch.Tensor,
+                    total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool):
+    """The lifting side of ``evaluate_clips_batched(finish=True)`` and :func:`predict_clips_batched`: every clip of `mine` lifted
+    with ``raw_out=`` into ONE raw buffer (with `flip`, the mirrored pass into a second one; with lanes the clips are dealt to the
+    lanes and joined ONCE), then ONE :func:`shard_poses_hip` call over `table_dev` (:func:`clip_table` of `mine`).  `encode` as in
+    :func:`evaluate_clips_batched`.  Reads the status once; a refused descriptor raises.  -> (pred_all, world_all or None)."""
+    J = lifter.pos.num_joints_in
+    sizes_of = lifter.clip_batch_sizes
+    raw_first, raw_rows = clip_raw_table([c.rays.shape[0] for c in mine], sizes_of)
+    raw_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev)
+    raw_m_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev) if flip else None
+    raw_first_dev = torch.tensor(raw_first, dtype=torch.int64).to(dev)
+    lanes = getattr(lifter, "num_lanes", lambda: 0)() > 0
+    pad = (rf - 1) // 2
+    jl = kps_left if joints_left is None else joints_left
+    jr = kps_right if joints_right is None else joints_right
+    if encode is not None:
+        itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(sizes_of(n)) - n)
+        px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
+        iperm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
+        x_all, xm_all, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode, iperm)
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
+
+    def lift(k, c):
+        n = c.rays.shape[0]
+        rows = slice(raw_first[k], raw_first[k] + sum(sizes_of(n)))
+        prow = torch.from_numpy(c.camera.param()).to(dev)
+        if encode is not None:
+            xr = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
+            lift_clip(x_all[xr], prow, raw_out=raw_all[rows], n_windows=n)
+            if flip:
+                lift_clip(xm_all[xr], prow, raw_out=raw_m_all[rows], n_windows=n)
+            return
+        padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
+        lift_clip(padded, prow, raw_out=raw_all[rows])
+        if flip:
+            lift_clip(mirror(padded) if mirror is not None else mirror_input(padded, kps_left, kps_right), prow, raw_out=raw_m_all[rows])
+
+    for k, c in enumerate(mine):
+        if lanes:
+            with lifter.lane():          # the clip's forwards on the next lane's stream
+                lift(k, c)
+        else:
+            lift(k, c)
+    if lanes:
+        lifter.join_lanes()              # the one join of the pass
+    perm = mirror_permutation(J, jl, jr) if flip else None
+    pred_all, world_all, status = shard_poses_hip(raw_all, table_dev, raw_first_dev, len(mine), total, longest, raw_m_all, perm,
+                                                  pred=True, world=world, pred_all=pred_all)
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        raise RuntimeError("r3d_clips_poses refused the descriptors of clips %s of this rank's shard" % bad)
+    return pred_all, world_all
+
+
+def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
+                          kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
+                          joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                          causal: bool = False, encode: Optional[str] = None, world: bool = True, root_relative: bool = False):
+    """:func:`predict_clip` for many clips, with the poses in world coordinates on top - the numerical core of the reference's
+    Trainer.render (lib/train_val/trainer.py:505-526: cam.normalized2world / cam.camera2world on the flip-averaged poses) without
+    its height rebase and its animation.  Every clip is lifted with ``raw_out=`` into one raw buffer and ONE r3d_clips_poses call
+    finishes them all (the lifting code of ``evaluate_clips_batched(finish=True)``).  Returns, per clip in the given order,
+    (poses (N, J, 3) float32 - the bits of :func:`predict_clip` - , world (N, J, 3) float64 or None without `world`): views of the
+    two shard buffers.  The transform is :func:`clip_world_transform`'s: a ``frame="camera"`` clip goes through Rc2w / Tc2w,
+    `root_relative` is the identity.  `lift_clip` must be the bound ``forward_clip`` of a lifter; `encode` as in
+    :func:`evaluate_clips_batched`.  Single rank, GPU only.  No ground truth is needed: ``Clip.gt_norm`` may be an empty array."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("predict_clips_batched finishes the poses on the GPU (r3d_clips_poses); on CPU tensors use predict_clip")
+    lifter = _lifter_of(lift_clip, "predict_clips_batched")
+    if encode is not None and encode not in ENCODINGS:
+        raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
+    if not clips:
+        return []
+    table, first, total, longest = clip_table(clips, root_relative)
+    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    pred_all, world_all = _finished_shard(lift_clip, lifter, clips, rf, dev, flip, kps_left, kps_right, causal, joints_left,
+                                          joints_right, None, encode, table_dev, total, longest, None, world)
+    return [(pred_all[first[k]:first[k] + c.rays.shape[0]],
+             world_all[first[k]:first[k] + c.rays.shape[0]] if world_all is not None else None) for k, c in enumerate(clips)]
+
+
 def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
                            kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                            rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
                            joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
                            root_relative: bool = False, mirror: Optional[Callable] = None, detail: bool = False,
-                           include_root: bool = False, encode: Optional[str] = None):
+                           include_root: bool = False, encode: Optional[str] = None, finish: bool = False):
     """:func:`evaluate_clips` (with `detail`: :func:`evaluate_clips_detail`, `include_root` as there) with the measuring side in
     ONE call per shard: the rank's clip table and ground truth are uploaded once, every clip is lifted into its slice of one
     prediction buffer (``lift_clip(padded, param_row, out=slice)``: ``Ray3DLifter.forward_clip``; the flip average is written
@@ -601,7 +766,13 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     then lifted from its slice, ``lift_clip(x_all[slice], param_row, out=dst, n_windows=N)``: no per-clip upload, pad or
     concatenation.  `lift_clip` must be the bound ``forward_clip`` of a lifter (its ``clip_batch_sizes`` size the slices).
     The flip pass mirrors the ENCODED input, as the reference does - also right for undistort=True cameras, which
-    :func:`mirror_pixels` refuses; `kps_left` / `kps_right` give the permutation and `mirror` must be None."""
+    :func:`mirror_pixels` refuses; `kps_left` / `kps_right` give the permutation and `mirror` must be None.
+
+    `finish`: the step between the forwards and the measurement is one call per shard as well - every clip is lifted with
+    ``raw_out=`` into one raw buffer (with `flip` the mirrored pass into a second one; with lanes ONE join in all, also for clips
+    with tails), ONE r3d_clips_poses call (:func:`shard_poses_hip`) writes the prediction buffer - flip average included - and the
+    one metrics call runs as before.  `lift_clip` must be the bound ``forward_clip`` of a lifter.  Same return values, the same
+    bits in every row."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
@@ -613,13 +784,24 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
             raise ValueError("encode=: the flip pass mirrors the encoded input on the device; `mirror` must be None")
         if lifter is None or not hasattr(lifter, "clip_batch_sizes"):
             raise ValueError("encode=: lift_clip must be the bound forward_clip of a Ray3DLifter")
+    if finish:
+        lifter = _lifter_of(lift_clip, "finish=True")
     actions = sorted(set(c.action for c in clips))
     aid = {a: i for i, a in enumerate(actions)}
     shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
     mine = [clips[idx] for idx in shards[rank]]
     local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], dev)
     dlocal = torch.zeros((len(mine), DETAIL_COLS), dtype=torch.float64, device=dev) if detail else None
-    if mine:
+    if mine and finish:
+        table, first, total, longest = clip_table(mine, root_relative)
+        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+        gt_all = torch.from_numpy(np.concatenate(
+            [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        pred_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
+        _finished_shard(lift_clip, lifter, mine, rf, dev, flip, kps_left, kps_right, causal, joints_left, joints_right, mirror, encode,
+                        table_dev, total, longest, pred_all, False)
+        shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)
+    elif mine:
         table, first, total, longest = clip_table(mine, root_relative)
         table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
         gt_all = torch.from_numpy(np.concatenate(

@@ -550,7 +550,8 @@ class Ray3DLifter(nn.Module):
         return sizes
 
     def forward_clip(self, clip: torch.Tensor, param_row: Optional[torch.Tensor] = None, return_trj: bool = False,
-                     out: Optional[torch.Tensor] = None, n_windows: Optional[int] = None, trj_out: Optional[torch.Tensor] = None):
+                     out: Optional[torch.Tensor] = None, n_windows: Optional[int] = None, trj_out: Optional[torch.Tensor] = None,
+                     raw_out: Optional[torch.Tensor] = None, raw_trj_out: Optional[torch.Tensor] = None):
         """clip (N + RF - 1, J, F): an edge-padded sequence; window i = frames [i, i+RF) is gathered
         in the kernels instead of materialising lib/train_val/trainer.py:47-58's copy.
         param_row (E,) is broadcast to every window (trainer.py:324).  Returns (N,1,J,3) - with `return_trj` the pair
@@ -574,10 +575,25 @@ class Ray3DLifter(nn.Module):
         shard's trajectory buffer (evaluate.validate_clips_batched) - that the trajectory is written into, by `out`'s rule:
         every call writes straight into its rows where its rounded-up size fits, the tail call goes through a scratch tensor.
         Nothing is concatenated; the same forwards run, so poses and trajectory have the bits of a call without it.  The pair
-        returned is (poses, trj_out)."""
+        returned is (poses, trj_out).
+
+        `raw_out`: a contiguous float32 ``(sum(clip_batch_sizes(N)), 1, J, 3)`` tensor on the clip's device - e.g. the clip's
+        slice of a shard's raw buffer (evaluate.clip_raw_table) - that EVERY forward writes straight into, surplus rows
+        included: no scratch tensor, no tail copy, no join, no concatenation.  The same forwards of the same sizes run, so rows
+        [0, N) have the bits `out=` gives; the rows behind them are the surplus windows' poses, for r3d_clips_poses
+        (evaluate.shard_poses_hip) to leave unread.  `raw_trj_out` (needs `return_trj`): the same for the trajectory,
+        ``(..., 1, 1, 3)``.  Returned: raw_out, or with `return_trj` the pair (raw_out, raw trajectory) - with lanes the
+        caller joins before it reads them.  Not together with `out` / `trj_out`; any other shape, dtype or device is a
+        ValueError."""
         rf = self.receptive_field()
         if trj_out is not None and not return_trj:
             raise ValueError("forward_clip(trj_out=) needs return_trj=True")
+        raw = raw_out is not None or raw_trj_out is not None
+        if raw and (out is not None or trj_out is not None):
+            raise ValueError("forward_clip: raw_out= / raw_trj_out= (every call's rows, surplus included) and out= / trj_out= (the "
+                             "clip's N rows) are two destinations for the same forwards: give one kind")
+        if raw_trj_out is not None and not return_trj:
+            raise ValueError("forward_clip(raw_trj_out=) needs return_trj=True")
         assert clip.dim() == 3 and clip.shape[1] == self.pos.num_joints_in and clip.shape[2] == self.pos.in_features
         if n_windows is not None:
             n = int(n_windows)
@@ -594,6 +610,8 @@ class Ray3DLifter(nn.Module):
             if self.pos.camera_embedding else None
         sizes = self.clip_batch_sizes(n)
         total = sum(sizes)
+        if raw:
+            return self._forward_clip_raw(clip, p, n, sizes, return_trj, raw_out, raw_trj_out, n_windows is not None)
         if out is None and trj_out is not None:
             out = torch.empty((n, 1, self.pos.num_joints_in, 3), dtype=torch.float32, device=clip.device)
         if out is not None:
@@ -653,6 +671,28 @@ class Ray3DLifter(nn.Module):
         if not return_trj:
             return out
         return (out, trj_out) if trj_out is not None else (out, torch.cat(trjs, dim=0)[:n])
+
+    def _forward_clip_raw(self, clip, p, n, sizes, return_trj, raw_out, raw_trj_out, has_surplus=False):
+        """forward_clip(raw_out=): the forwards of `sizes`, each written straight into its rows of the sum(sizes)-row
+        destinations; `has_surplus`: the clip already carries the rows of the surplus windows (forward_clip(n_windows=))."""
+        J, total = self.pos.num_joints_in, sum(sizes)
+        for t, name, cols in ((raw_out, "raw_out", J), (raw_trj_out, "raw_trj_out", 1)):
+            if t is not None and (tuple(t.shape) != (total, 1, cols, 3) or t.dtype != torch.float32 or t.device != clip.device
+                                  or not t.is_contiguous()):
+                raise ValueError("forward_clip(%s=): a contiguous float32 (%d, 1, %d, 3) tensor on %s is needed - sum(clip_batch_sizes(%d)) "
+                                 "rows (got %s %s on %s)" % (name, total, cols, clip.device, n, tuple(t.shape), t.dtype, t.device))
+        if raw_out is None:
+            raw_out = torch.empty((total, 1, J, 3), dtype=torch.float32, device=clip.device)
+        if return_trj and raw_trj_out is None:
+            raw_trj_out = torch.empty((total, 1, 1, 3), dtype=torch.float32, device=clip.device)
+        if total > n and not has_surplus:
+            clip = torch.cat([clip, clip[-1:].expand(total - n, -1, -1)], dim=0)
+        start = 0
+        for b in sizes:
+            extra = {"out_trj": raw_trj_out[start:start + b]} if return_trj else {}
+            self._run(_capi.R3D_INPUT_RAYS, clip[start:], 1, b, p, 0, return_trj=return_trj, out=raw_out[start:start + b], **extra)
+            start += b
+        return (raw_out, raw_trj_out) if return_trj else raw_out
 
     def prepare(self, batch_sizes, device=None):
         """Build and upload the tile schedules of these batch sizes now (r3d_prepare) instead of inside the first

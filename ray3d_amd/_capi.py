@@ -78,6 +78,9 @@ def clip_desc_dtype():
     return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("rn2w", np.float64, (9,)), ("tn2w", np.float64, (3,))])
 
 
+CLIP_DESC_BYTES = clip_desc_dtype().itemsize                            # sizeof(r3d_clip_desc)
+
+
 def clip_input_desc_dtype():
     """The NumPy structured dtype with r3d_clip_input_desc's layout (160 bytes): an array of it, uploaded as bytes, is the
     table r3d_clips_encode reads."""

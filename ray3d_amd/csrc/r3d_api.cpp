@@ -7,6 +7,46 @@
 
 using namespace r3d;
 
+// the ranges every call over a shard of clips allows: num_clips, then num_joints
+static int clips_range_check(const char *what, int32_t num_clips, int32_t J) {
+    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
+
+// mirror_perm (null: no flip pass) must be a permutation of the J joints
+static int mirror_perm_check(const char *what, const int32_t *mirror_perm, int32_t J) {
+    unsigned seen = 0;
+    for (int j = 0; mirror_perm && j < J; ++j) {
+        if (mirror_perm[j] < 0 || mirror_perm[j] >= J || (seen >> mirror_perm[j] & 1u)) {
+            set_error("%s: mirror_perm must be a permutation of 0..%d (entry %d is %d)", what, J - 1, j, mirror_perm[j]);
+            return R3D_ERR_ARG;
+        }
+        seen |= 1u << mirror_perm[j];
+    }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_clips_metrics (every check on the host, before any HIP call)
+static int clips_metrics_check_args(const char *what, const float *pred, const float *gt, int64_t total_frames, int32_t J,
+                                    const r3d_clip_desc *clips, int32_t num_clips, int64_t max_frames, const double *rows,
+                                    int64_t row_stride, const double *detail, int64_t detail_stride, const void *scratch) {
+    if (!pred || !gt || !clips || !rows || !scratch) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (const int rc = clips_range_check(what, num_clips, J)) return rc;
+    if (max_frames < 1) { set_error("%s: max_frames must be >= 1 (got %lld)", what, (long long)max_frames); return R3D_ERR_ARG; }
+    if (total_frames < 1) { set_error("%s: total_frames must be >= 1 (got %lld)", what, (long long)total_frames); return R3D_ERR_ARG; }
+    if (row_stride < R3D_METRIC_COUNT) { set_error("%s: row_stride must be >= %d (got %lld)", what, R3D_METRIC_COUNT, (long long)row_stride); return R3D_ERR_ARG; }
+    if (detail && detail_stride < R3D_DETAIL_DOUBLES) {
+        set_error("%s: detail_stride must be >= %d (got %lld)", what, R3D_DETAIL_DOUBLES, (long long)detail_stride);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(clips) % 8 || reinterpret_cast<uintptr_t>(scratch) % 8) {
+        set_error("%s: clips_dev and scratch_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    return R3D_OK;
+}
+
 // the argument rules of r3d_clip_valid_losses, shared with its host hook (`what`: the name in the message)
 int r3d::valid_check_args(const char *what, const float *pos, const float *trj, const float *gt, int64_t n, int32_t J,
                           const int32_t *parents, int32_t flags, const double *out) {
@@ -39,7 +79,7 @@ int r3d::clips_valid_check_args(const char *what, const float *pos, const float 
     if (total_frames < 1) { set_error("%s: total_frames must be >= 1 (got %lld)", what, (long long)total_frames); return R3D_ERR_ARG; }
     const int rc = valid_check_args(what, pos, trj, gt, total_frames, J, parents, flags, rows);
     if (rc != R3D_OK) return rc;
-    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
+    if (const int rc2 = clips_range_check(what, num_clips, J)) return rc2;      // (num_joints passed valid_check_args above)
     if (max_frames < 1) { set_error("%s: max_frames must be >= 1 (got %lld)", what, (long long)max_frames); return R3D_ERR_ARG; }
     if (row_stride < R3D_VALID_DOUBLES) { set_error("%s: row_stride must be >= %d (got %lld)", what, R3D_VALID_DOUBLES, (long long)row_stride); return R3D_ERR_ARG; }
     if (reinterpret_cast<uintptr_t>(clips) % 8 || (scratch_checked && reinterpret_cast<uintptr_t>(scratch) % 8)) {
@@ -55,8 +95,7 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
                                  const float *x_mirror, const int32_t *mirror_perm, const int32_t *status) {
     static_assert(sizeof(r3d_clip_input_desc) == 160, "r3d_clip_input_desc is documented as 160 bytes");
     if (!px || !clips || !x || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
-    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
-    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (const int rc = clips_range_check(what, num_clips, J)) return rc;
     if (encoding != R3D_ENCODE_RAY && encoding != R3D_ENCODE_INTRINSIC && encoding != R3D_ENCODE_SCREEN) {
         set_error("%s: unknown encoding %d", what, encoding);
         return R3D_ERR_ARG;
@@ -74,16 +113,7 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
         set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
         return R3D_ERR_ARG;
     }
-    if (mirror_perm) {
-        unsigned seen = 0;
-        for (int j = 0; j < J; ++j) {
-            if (mirror_perm[j] < 0 || mirror_perm[j] >= J || (seen >> mirror_perm[j] & 1u)) {
-                set_error("%s: mirror_perm must be a permutation of 0..%d (entry %d is %d)", what, J - 1, j, mirror_perm[j]);
-                return R3D_ERR_ARG;
-            }
-            seen |= 1u << mirror_perm[j];
-        }
-    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
     if (reinterpret_cast<uintptr_t>(clips) % 8) { set_error("%s: the clip table must be 8-byte aligned", what); return R3D_ERR_ARG; }
     return R3D_OK;
 }
@@ -94,8 +124,7 @@ int r3d::clips_poses_check_args(const char *what, const float *raw, const float 
                                 int64_t max_frames, const float *pred, const double *world, int64_t total_frames, const int32_t *status) {
     if (!raw || !clips || !raw_first || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
     if (!pred && !world) { set_error("%s: pred_dev and world_dev are both null: nothing to write", what); return R3D_ERR_ARG; }
-    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { set_error("%s: num_clips must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
-    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (const int rc = clips_range_check(what, num_clips, J)) return rc;
     if (max_frames < 1 || total_frames < 1 || raw_rows < 1) {
         set_error("%s: max_frames, total_frames and raw_rows must be >= 1 (got %lld, %lld, %lld)", what, (long long)max_frames,
                   (long long)total_frames, (long long)raw_rows);
@@ -109,16 +138,7 @@ int r3d::clips_poses_check_args(const char *what, const float *raw, const float 
         set_error("%s: raw_mirror_dev and mirror_perm go together (both or neither)", what);
         return R3D_ERR_ARG;
     }
-    if (mirror_perm) {
-        unsigned seen = 0;
-        for (int j = 0; j < J; ++j) {
-            if (mirror_perm[j] < 0 || mirror_perm[j] >= J || (seen >> mirror_perm[j] & 1u)) {
-                set_error("%s: mirror_perm must be a permutation of 0..%d (entry %d is %d)", what, J - 1, j, mirror_perm[j]);
-                return R3D_ERR_ARG;
-            }
-            seen |= 1u << mirror_perm[j];
-        }
-    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
     if (reinterpret_cast<uintptr_t>(clips) % 8 || reinterpret_cast<uintptr_t>(raw_first) % 8 || reinterpret_cast<uintptr_t>(world) % 8) {
         set_error("%s: the clip table, raw_first_dev and world_dev must be 8-byte aligned", what);
         return R3D_ERR_ARG;
@@ -389,21 +409,9 @@ size_t r3d_clips_metrics_scratch_bytes(int32_t num_clips, int64_t max_frames, in
 int r3d_clips_metrics(const float *pred_dev, const float *gt_dev, int64_t total_frames, int32_t num_joints,
                       const r3d_clip_desc *clips_dev, int32_t num_clips, int64_t max_frames, double *rows_dev, int64_t row_stride,
                       double *detail_dev, int64_t detail_stride, double *frame_dev, void *scratch_dev, size_t scratch_bytes, void *stream) {
-    // (every check on the host, before any HIP call)
-    if (!pred_dev || !gt_dev || !clips_dev || !rows_dev || !scratch_dev) { r3d::set_error("r3d_clips_metrics: null pointer"); return R3D_ERR_ARG; }
-    if (num_clips < 1 || num_clips > R3D_CLIPS_MAX) { r3d::set_error("r3d_clips_metrics: num_clips must be in 1..%d (got %d)", R3D_CLIPS_MAX, num_clips); return R3D_ERR_ARG; }
-    if (num_joints < 1 || num_joints > 17) { r3d::set_error("r3d_clips_metrics: num_joints must be in 1..17 (got %d)", num_joints); return R3D_ERR_ARG; }
-    if (max_frames < 1) { r3d::set_error("r3d_clips_metrics: max_frames must be >= 1 (got %lld)", (long long)max_frames); return R3D_ERR_ARG; }
-    if (total_frames < 1) { r3d::set_error("r3d_clips_metrics: total_frames must be >= 1 (got %lld)", (long long)total_frames); return R3D_ERR_ARG; }
-    if (row_stride < R3D_METRIC_COUNT) { r3d::set_error("r3d_clips_metrics: row_stride must be >= %d (got %lld)", R3D_METRIC_COUNT, (long long)row_stride); return R3D_ERR_ARG; }
-    if (detail_dev && detail_stride < R3D_DETAIL_DOUBLES) {
-        r3d::set_error("r3d_clips_metrics: detail_stride must be >= %d (got %lld)", R3D_DETAIL_DOUBLES, (long long)detail_stride);
-        return R3D_ERR_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(clips_dev) % 8 || reinterpret_cast<uintptr_t>(scratch_dev) % 8) {
-        r3d::set_error("r3d_clips_metrics: clips_dev and scratch_dev must be 8-byte aligned");
-        return R3D_ERR_ARG;
-    }
+    const int rc = clips_metrics_check_args("r3d_clips_metrics", pred_dev, gt_dev, total_frames, num_joints, clips_dev, num_clips, max_frames,
+                                            rows_dev, row_stride, detail_dev, detail_stride, scratch_dev);
+    if (rc != R3D_OK) return rc;
     const size_t need = r3d::clips_metrics_scratch_bytes(num_clips, max_frames, detail_dev != nullptr);
     if (scratch_bytes < need) {
         r3d::set_error("r3d_clips_metrics: scratch of %zu bytes, %zu needed (r3d_clips_metrics_scratch_bytes)", scratch_bytes, need);

@@ -134,14 +134,20 @@ def predict_clip(lift_clip: Callable, clip: Clip, rf: int, device, flip: bool = 
     return pred
 
 
+def _header_rows(headers: Sequence[tuple], cols: int, device) -> torch.Tensor:
+    """A (k, cols) float64 matrix of per-clip rows with the host-known columns - clip id, action id, frame count - filled in
+    and the rest zero, made on the host and moved in ONE host-to-device copy."""
+    rows = torch.zeros((len(headers), cols), dtype=torch.float64)
+    if headers:
+        rows[:, :3] = torch.tensor([[float(v) for v in h] for h in headers], dtype=torch.float64)
+    return rows.to(device)
+
+
 def partial_rows(headers: Sequence[tuple], device) -> torch.Tensor:
     """The (k, PARTIAL_COLS) float64 matrix of a rank's per-clip rows with the host-known columns - clip id, action id,
     frame count - filled in: ONE host-to-device copy per evaluation instead of one per clip (the error columns are written
     on the device by :func:`clip_partials_hip`)."""
-    rows = torch.zeros((len(headers), PARTIAL_COLS), dtype=torch.float64)
-    if headers:
-        rows[:, :3] = torch.tensor([[float(v) for v in h] for h in headers], dtype=torch.float64)
-    return rows.to(device)
+    return _header_rows(headers, PARTIAL_COLS, device)
 
 
 def clip_partials_hip(pred_norm: torch.Tensor, clip: Clip, action_id: int = 0,
@@ -272,6 +278,42 @@ def gather_partials(local_rows: torch.Tensor, counts: Sequence[int], group=None,
     return torch.cat([bucket[r][: counts[r]] for r in range(world)], dim=0)
 
 
+def _shard_plan(clips: Sequence[Clip], rank: int, world_size: int):
+    """(actions, aid, shards, mine): the sorted action names, their ids, every rank's clip indices (:func:`shard_clips`) and
+    this rank's clips in the order of its shard."""
+    actions = sorted(set(c.action for c in clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
+    return actions, aid, shards, [clips[idx] for idx in shards[rank]]
+
+
+def _shard_rows(clips: Sequence[Clip], aid: Dict[str, int], shard: Sequence[int], cols: int, device) -> torch.Tensor:
+    """The `cols`-wide rows of the clips of `shard` (indices into `clips`) with their headers in place (:func:`_header_rows`)."""
+    return _header_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shard], cols, device)
+
+
+def _gather(local: torch.Tensor, shards: Sequence[Sequence[int]], group, cols: int) -> torch.Tensor:
+    """The rows of all ranks (:func:`gather_partials`); with one rank they are `local` itself and nothing is exchanged."""
+    return gather_partials(local, [len(s) for s in shards], group, cols=cols) if len(shards) > 1 else local
+
+
+def _report(allrows: torch.Tensor, alldetail: Optional[torch.Tensor], actions: Sequence[str], clips: Sequence[Clip],
+            include_root: bool = False):
+    """What the evaluations return from the gathered rows: (per_action, action-wise average, rows as gathered) - or, with the
+    gathered detail rows, both sorted by clip id and (per_action, average, rows, detail) as :func:`evaluate_clips_detail` describes."""
+    if alldetail is not None:
+        order = torch.argsort(allrows[:, 0], stable=True)
+        allrows, alldetail = allrows[order], alldetail[order]
+    per = reduce_partials(allrows)
+    named = {actions[a]: v for a, v in per.items()}
+    if alldetail is None:
+        return named, action_average(per), allrows
+    tables = reduce_detail(allrows, alldetail, clips[0].gt_norm.shape[1] if len(clips) else 0, include_root)
+    detail = {(actions[a] if a != "overall" else a): t for a, t in tables.items()}
+    detail["rows"] = alldetail
+    return named, action_average(per), allrows, detail
+
+
 def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
                    kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                    rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
@@ -283,11 +325,9 @@ def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
     Each clip is measured in the world frame through the transform of ITS frame (`Clip.frame`); `root_relative` (models
     without a trajectory network, RAY_ENCODING False: trainer.py:315-320, :382-384): the ground truth is made
     root-relative and compared with the predictions as they are.  `mirror`: see :func:`predict_clip` (clips of raw pixels)."""
-    actions = sorted(set(c.action for c in clips))
-    aid = {a: i for i, a in enumerate(actions)}
-    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
+    actions, aid, shards, _ = _shard_plan(clips, rank, world_size)
     on_gpu = torch.device(device).type == "cuda"
-    local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], device)
+    local = _shard_rows(clips, aid, shards[rank], PARTIAL_COLS, device)
     for k, idx in enumerate(shards[rank]):
         c = clips[idx]
         pred = predict_clip(lift_clip, c, rf, device, flip, kps_left, kps_right, causal, joints_left, joints_right, mirror)
@@ -296,13 +336,7 @@ def evaluate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
             clip_partials_hip(pred, cc, aid[c.action], out=local[k], root_relative=root_relative)
         else:
             local[k] = clip_partials(pred, cc, aid[c.action], root_relative)
-    if world_size > 1:
-        allrows = gather_partials(local, [len(s) for s in shards], group)
-    else:
-        allrows = local
-    per = reduce_partials(allrows)
-    named = {actions[a]: v for a, v in per.items()}
-    return named, action_average(per), allrows
+    return _report(_gather(local, shards, group, PARTIAL_COLS), None, actions, clips)
 
 
 # ------------------------------------------------------------------------------------ per-joint / per-frame / PCK detail
@@ -394,11 +428,9 @@ def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     order - with detail = {action name: table, "overall": table, "rows": the gathered detail rows} (tables:
     :func:`reduce_detail`).  On a GPU one r3d_clip_metrics_detail call per clip yields both rows; with `world_size` > 1 the
     detail rows travel in ONE additional all_gather.  `Clip.frame`, `root_relative` and `mirror` as in :func:`evaluate_clips`."""
-    actions = sorted(set(c.action for c in clips))
-    aid = {a: i for i, a in enumerate(actions)}
-    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
+    actions, aid, shards, _ = _shard_plan(clips, rank, world_size)
     on_gpu = torch.device(device).type == "cuda"
-    local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], device)
+    local = _shard_rows(clips, aid, shards[rank], PARTIAL_COLS, device)
     dlocal = torch.zeros((len(shards[rank]), DETAIL_COLS), dtype=torch.float64, device=device)
     for k, idx in enumerate(shards[rank]):
         c = clips[idx]
@@ -409,35 +441,82 @@ def evaluate_clips_detail(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
         else:
             local[k] = clip_partials(pred, cc, aid[c.action], root_relative)
             dlocal[k] = clip_detail(pred, cc, root_relative=root_relative)
-    if world_size > 1:
-        counts = [len(s) for s in shards]
-        allrows = gather_partials(local, counts, group)
-        alldetail = gather_partials(dlocal, counts, group, cols=DETAIL_COLS)
+    return _report(_gather(local, shards, group, PARTIAL_COLS), _gather(dlocal, shards, group, DETAIL_COLS), actions, clips, include_root)
+
+
+# ------------------------------------------------------------------------------------ the pieces of the calls over a whole shard
+
+def _need(t: torch.Tensor, name: str, dtype, dev, shape=None, rows=None, numel=None, last=None):
+    """ValueError unless `t` is a contiguous `dtype` tensor on `dev` of exactly `shape` - or, where two layouts are taken
+    ((N, J, 3) and (N, 1, J, 3)), of `rows` leading rows, `numel` elements and a last dimension of `last`, whichever are given."""
+    if t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.dim() < 1 \
+            or (shape is not None and tuple(t.shape) != tuple(shape)) or (rows is not None and t.shape[0] != rows) \
+            or (numel is not None and t.numel() != numel) or (last is not None and t.shape[-1] != last):
+        size = "shape %s" % (tuple(shape),) if shape is not None else \
+            ", ".join("%s %d" % (k, v) for k, v in (("rows", rows), ("elements", numel), ("last dimension", last)) if v is not None)
+        raise ValueError("%s: a contiguous %s tensor (%s) on %s is needed" % (name, dtype, size, dev))
+
+
+def _need_table(table_dev: torch.Tensor, num_clips: int, desc_bytes: int, dev):
+    """ValueError unless `table_dev` holds `num_clips` descriptors of `desc_bytes` bytes (``_capi.CLIP_DESC_BYTES`` /
+    ``_capi.CLIP_INPUT_DESC_BYTES``), contiguous, on `dev`."""
+    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * desc_bytes:
+        raise ValueError("table_dev: %d descriptors of %d bytes on %s are needed" % (num_clips, desc_bytes, dev))
+
+
+_scratch_of: Dict = {}    # device -> the scratch of the shard calls
+
+
+def _shard_scratch(dev, nbytes: int) -> torch.Tensor:
+    """The cached per-device scratch of the shard calls, grown (never shrunk) to `nbytes`."""
+    scratch = _scratch_of.get(dev)
+    if scratch is None or scratch.numel() < nbytes:
+        scratch = _scratch_of[dev] = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    return scratch
+
+
+def _out_buffer(t: Optional[torch.Tensor], name: str, want: bool, dtype, dev, shape: tuple, exact: bool = True):
+    """The caller's output buffer `t` if given - of exactly `shape`, or without `exact` of shape[0] rows and as many elements -
+    else a new (not zeroed) one of `shape` if `want`, else None."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev) if want else None
+    if exact:
+        _need(t, name, dtype, dev, shape=shape)
     else:
-        allrows, alldetail = local, dlocal
-    order = torch.argsort(allrows[:, 0], stable=True)
-    allrows, alldetail = allrows[order], alldetail[order]
-    per = reduce_partials(allrows)
-    named = {actions[a]: v for a, v in per.items()}
-    tables = reduce_detail(allrows, alldetail, clips[0].gt_norm.shape[1] if len(clips) else 0, include_root)
-    detail = {(actions[a] if a != "overall" else a): t for a, t in tables.items()}
-    detail["rows"] = alldetail
-    return named, action_average(per), allrows, detail
+        _need(t, name, dtype, dev, rows=shape[0], numel=int(np.prod(shape)))
+    return t
 
 
-# ------------------------------------------------------------------------------------ a whole shard in one metrics call
+def _status_buffer(status: Optional[torch.Tensor], num_clips: int, dev) -> torch.Tensor:
+    """The caller's int32 (num_clips,) status buffer, or a new one."""
+    return _out_buffer(status, "status", True, torch.int32, dev, (num_clips,))
 
-def clip_table(clips: Sequence[Clip], root_relative: bool = False):
-    """(table, first_frames, total_frames, max_frames) of `clips` laid out back to back in the given order: `table` a NumPy
-    structured array of r3d_clip_desc rows (``_capi.clip_desc_dtype()``) - clip k's frames are rows [first_frames[k],
-    first_frames[k] + N_k) of the shard's prediction / ground-truth buffers, its transform is :func:`clip_world_transform`'s -
-    to be uploaded once per data set (``torch.from_numpy(table.view(np.uint8))``) and handed to :func:`shard_metrics_hip`."""
+
+def _raise_if_refused(status: torch.Tensor, call: str):
+    """Reads the status of a shard call (a device-to-host copy: the one synchronisation of the input / finishing side)."""
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        raise RuntimeError("%s refused the descriptors of clips %s of this rank's shard" % (call, bad))
+
+
+def _to_device_bytes(table: np.ndarray, dev) -> torch.Tensor:
+    """A descriptor table's bytes on `dev`: the one upload of the table."""
+    return torch.from_numpy(table.view(np.uint8)).to(dev)
+
+
+def _ground_truth(mine: Sequence[Clip], dev, root_relative: bool = False) -> torch.Tensor:
+    """The shard's ground truth back to back, (total_frames, J, 3) float32 on `dev` in one upload (`root_relative`: made so first)."""
+    return torch.from_numpy(np.concatenate(
+        [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
+
+
+def _desc_table(lengths: Sequence[int], transforms: Sequence[tuple]):
+    """(table of r3d_clip_desc rows, first_frames, total_frames, max_frames) of clips of these frame counts and (R, T) laid out
+    back to back."""
     from . import _capi
-    table = np.zeros(len(clips), dtype=_capi.clip_desc_dtype())
+    table = np.zeros(len(lengths), dtype=_capi.clip_desc_dtype())
     first_frames, at, longest = [], 0, 0
-    for k, c in enumerate(clips):
-        n = int(np.asarray(c.rays).shape[0])
-        R, T = clip_world_transform(c, root_relative)
+    for k, (n, (R, T)) in enumerate(zip(lengths, transforms)):
         table[k]["first_frame"], table[k]["n_frames"] = at, n
         table[k]["rn2w"] = np.asarray(R, dtype=np.float64).reshape(9)
         table[k]["tn2w"] = np.asarray(T, dtype=np.float64).reshape(3)
@@ -447,7 +526,86 @@ def clip_table(clips: Sequence[Clip], root_relative: bool = False):
     return table, first_frames, at, longest
 
 
-_shard_scratch: Dict = {}    # device -> grow-only scratch of shard_metrics_hip
+def _lifter_of(lift_clip: Callable, partial_ok: bool = False, need: Optional[str] = None, by_name: bool = False):
+    """The object whose bound method `lift_clip` is - with `partial_ok` also through a ``functools.partial`` of one - or None.
+    `need` (the option that needs a Ray3DLifter, named in the message): a ValueError unless it has ``clip_batch_sizes`` and, with
+    `by_name`, `lift_clip` is its ``forward_clip`` itself (``raw_out=`` is used).  Decided before any shard is cut."""
+    lifter = getattr(lift_clip, "__self__", None) or (getattr(getattr(lift_clip, "func", None), "__self__", None) if partial_ok else None)
+    if need is not None and (lifter is None or not hasattr(lifter, "clip_batch_sizes")
+                             or (by_name and getattr(lift_clip, "__name__", "") != "forward_clip")):
+        raise ValueError("%s: lift_clip must be %sthe bound forward_clip of a Ray3DLifter (its clip_batch_sizes%s are used)"
+                         % (need, "(a functools.partial of) " if partial_ok else "", " and raw_out=" if by_name else ""))
+    return lifter
+
+
+def _encoding_id(encoding, arg: str = "encode") -> int:
+    """R3D_ENCODE_* of the encoding's name; a ValueError names the argument `arg`."""
+    if encoding not in ENCODINGS:
+        raise ValueError("%s must be one of %s (got %r)" % (arg, sorted(ENCODINGS), encoding))
+    return ENCODINGS[encoding]
+
+
+class _ShardInputs:
+    """What the clips `mine` of a shard are lifted from.  ``inputs(k)`` -> (input of clip k, its mirrored input or None without
+    `flip`, the clip's camera parameter row on `dev`, extra keywords of ``lift_clip``):
+
+    * `encode` None: ``Clip.rays`` is the model input - the clip is edge-padded (:func:`pad_clip`) and uploaded when asked for,
+      the mirrored input is `mirror`'s or :func:`mirror_input`'s;
+    * `encode` given: ``Clip.rays`` holds raw pixels - here, once, the shard's pixels and its :func:`clip_input_table` are
+      uploaded, ONE :func:`shard_encode_hip` call on the current stream pads, encodes and - with `flip` - mirrors every clip and
+      its status is read (a refused descriptor raises); a clip's inputs are its slices of the two buffers, lifted with
+      ``n_windows=``.  `lifter`'s ``clip_batch_sizes`` size the slices."""
+
+    def __init__(self, mine: Sequence[Clip], rf: int, dev, causal: bool, encode: Optional[str], lifter, flip: bool = False,
+                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None):
+        self.mine, self.dev, self.flip, self.encode = mine, dev, flip, encode
+        self.pad, self.shift = (rf - 1) // 2, ((rf - 1) // 2 if causal else 0)
+        self.mirror = mirror if mirror is not None else (lambda x: mirror_input(x, kps_left, kps_right))
+        if encode is None:
+            return
+        sizes_of = lifter.clip_batch_sizes
+        itable, self.first, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(sizes_of(n)) - n)
+        self.rows = [int(d["pad_front"]) + int(d["n_frames"]) + int(d["pad_back"]) for d in itable]
+        px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        perm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
+        self.x_all, self.xm_all, status = shard_encode_hip(px_all, _to_device_bytes(itable, dev), len(mine), out_rows, max_rows, encode, perm)
+        _raise_if_refused(status, "r3d_clips_encode")
+
+    def __call__(self, k: int):
+        c = self.mine[k]
+        if self.encode is None:
+            x = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), self.pad, self.shift)).to(self.dev)
+            xm, kw = (self.mirror(x) if self.flip else None), {}
+        else:
+            rows = slice(self.first[k], self.first[k] + self.rows[k])
+            x, xm, kw = self.x_all[rows], (self.xm_all[rows] if self.flip else None), {"n_windows": c.rays.shape[0]}
+        return x, xm, torch.from_numpy(c.camera.param()).to(self.dev), kw
+
+
+def _deal(lifter, count: int, lift: Callable[[int], object]) -> list:
+    """``lift(k)`` for k in 0..count-1 - when `lifter` has lanes (``set_lanes``), each on the next lane's stream, and the ONE
+    join of the pass after the last.  -> what the calls returned."""
+    lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
+    out = []
+    for k in range(count):
+        if lanes:
+            with lifter.lane():          # the clip's upload, its forwards and what follows them on the next lane's stream
+                out.append(lift(k))
+        else:
+            out.append(lift(k))
+    if lanes:
+        lifter.join_lanes()
+    return out
+
+
+# ------------------------------------------------------------------------------------ a whole shard in one metrics call
+
+def clip_table(clips: Sequence[Clip], root_relative: bool = False):
+    """(table, first_frames, total_frames, max_frames) of `clips` laid out back to back in the given order: `table` a NumPy
+    structured array of r3d_clip_desc rows (``_capi.clip_desc_dtype()``) - clip k's frames are rows [first_frames[k],
+    first_frames[k] + N_k) of the shard's prediction / ground-truth buffers, its transform is :func:`clip_world_transform`'s -
+    to be uploaded once per data set (``torch.from_numpy(table.view(np.uint8))``) and handed to :func:`shard_metrics_hip`."""
+    return _desc_table([int(np.asarray(c.rays).shape[0]) for c in clips], [clip_world_transform(c, root_relative) for c in clips])
 
 
 def shard_metrics_hip(pred_all: torch.Tensor, gt_all: torch.Tensor, table_dev: torch.Tensor, num_clips: int, total_frames: int,
@@ -460,26 +618,18 @@ def shard_metrics_hip(pred_all: torch.Tensor, gt_all: torch.Tensor, table_dev: t
     No copy, no allocation (the scratch is a cached tensor per device), no synchronisation."""
     from . import _capi
     dev = pred_all.device
-    for t, name in ((pred_all, "pred_all"), (gt_all, "gt_all")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape[0] != total_frames or t.shape[-1] != 3:
-            raise ValueError("%s: a contiguous float32 (total_frames, J, 3) tensor on %s is needed" % (name, dev))
+    _need(pred_all, "pred_all", torch.float32, dev, rows=total_frames, last=3)
+    _need(gt_all, "gt_all", torch.float32, dev, rows=total_frames, last=3)
     J = pred_all.numel() // (3 * total_frames)
     if pred_all.numel() != gt_all.numel():
         raise ValueError("ground truth %s vs prediction %s" % (tuple(gt_all.shape), tuple(pred_all.shape)))
-    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
-        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
-    if rows.dtype != torch.float64 or rows.device != dev or tuple(rows.shape) != (num_clips, PARTIAL_COLS) or not rows.is_contiguous():
-        raise ValueError("rows: the contiguous float64 (%d, %d) matrix of partial_rows on %s is needed" % (num_clips, PARTIAL_COLS, dev))
-    if detail_rows is not None and (detail_rows.dtype != torch.float64 or detail_rows.device != dev or not detail_rows.is_contiguous()
-                                    or tuple(detail_rows.shape) != (num_clips, DETAIL_COLS)):
-        raise ValueError("detail_rows: a contiguous float64 (%d, %d) tensor on %s is needed" % (num_clips, DETAIL_COLS, dev))
-    if frames is not None and (frames.dtype != torch.float64 or frames.device != dev or not frames.is_contiguous()
-                               or tuple(frames.shape) != (total_frames, 5)):
-        raise ValueError("frames: a contiguous float64 (%d, 5) tensor on %s is needed" % (total_frames, dev))
-    nbytes = _capi.clips_metrics_scratch_bytes(num_clips, max_frames, detail_rows is not None)
-    scratch = _shard_scratch.get(dev)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _shard_scratch[dev] = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    _need_table(table_dev, num_clips, _capi.CLIP_DESC_BYTES, dev)
+    _need(rows, "rows (the matrix of partial_rows)", torch.float64, dev, shape=(num_clips, PARTIAL_COLS))
+    if detail_rows is not None:
+        _need(detail_rows, "detail_rows", torch.float64, dev, shape=(num_clips, DETAIL_COLS))
+    if frames is not None:
+        _need(frames, "frames", torch.float64, dev, shape=(total_frames, 5))
+    scratch = _shard_scratch(dev, _capi.clips_metrics_scratch_bytes(num_clips, max_frames, detail_rows is not None))
     with torch.cuda.device(dev):
         _capi.clips_metrics(pred_all.data_ptr(), gt_all.data_ptr(), total_frames, J, table_dev.data_ptr(), num_clips, max_frames,
                             rows.data_ptr() + 3 * 8, PARTIAL_COLS,
@@ -548,31 +698,18 @@ def shard_encode_hip(px_all: torch.Tensor, table_dev: torch.Tensor, num_clips: i
     synchronisation: the caller reads `status` when it wants to."""
     from . import _capi
     dev = px_all.device
-    if encoding not in ENCODINGS:
-        raise ValueError("encoding must be one of %s (got %r)" % (sorted(ENCODINGS), encoding))
-    enc = ENCODINGS[encoding]
+    enc = _encoding_id(encoding, "encoding")
     F = _capi.ENCODE_FLOATS[enc]
-    if px_all.dtype != torch.float32 or not px_all.is_contiguous() or not px_all.is_cuda or px_all.dim() != 3 or px_all.shape[-1] != 2 \
-            or px_all.shape[0] < 1:
+    if not px_all.is_cuda or px_all.dim() != 3 or px_all.shape[0] < 1:
         raise ValueError("px_all: a contiguous float32 (total_frames, J, 2) tensor on a GPU is needed")
+    _need(px_all, "px_all", torch.float32, dev, last=2)
     total, J = int(px_all.shape[0]), int(px_all.shape[1])
-    if table_dev.device != dev or not table_dev.is_contiguous() \
-            or table_dev.numel() * table_dev.element_size() < num_clips * _capi.CLIP_INPUT_DESC_BYTES:
-        raise ValueError("table_dev: %d descriptors of %d bytes on %s are needed" % (num_clips, _capi.CLIP_INPUT_DESC_BYTES, dev))
+    _need_table(table_dev, num_clips, _capi.CLIP_INPUT_DESC_BYTES, dev)
     if (x_mirror_all is not None) and mirror_perm is None:
         raise ValueError("x_mirror_all without mirror_perm")
-    bufs = []
-    for t, name, want in ((x_all, "x_all", True), (x_mirror_all, "x_mirror_all", mirror_perm is not None)):
-        if t is None:
-            t = torch.empty((out_rows, J, F), dtype=torch.float32, device=dev) if want else None
-        elif t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != (out_rows, J, F):
-            raise ValueError("%s: a contiguous float32 (%d, %d, %d) tensor on %s is needed" % (name, out_rows, J, F, dev))
-        bufs.append(t)
-    x_all, x_mirror_all = bufs
-    if status is None:
-        status = torch.empty(num_clips, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or tuple(status.shape) != (num_clips,):
-        raise ValueError("status: a contiguous int32 (%d,) tensor on %s is needed" % (num_clips, dev))
+    x_all = _out_buffer(x_all, "x_all", True, torch.float32, dev, (out_rows, J, F))
+    x_mirror_all = _out_buffer(x_mirror_all, "x_mirror_all", mirror_perm is not None, torch.float32, dev, (out_rows, J, F))
+    status = _status_buffer(status, num_clips, dev)
     with torch.cuda.device(dev):
         _capi.clips_encode(px_all.data_ptr(), total, J, enc, table_dev.data_ptr(), num_clips, max_rows, x_all.data_ptr(), out_rows,
                            x_mirror_all.data_ptr() if x_mirror_all is not None else None,
@@ -610,38 +747,23 @@ def shard_poses_hip(raw_all: torch.Tensor, table_dev: torch.Tensor, raw_first_de
     synchronisation: the caller reads `status` when it wants to."""
     from . import _capi
     dev = raw_all.device
-    if raw_all.dtype != torch.float32 or not raw_all.is_contiguous() or not raw_all.is_cuda or raw_all.dim() not in (3, 4) \
-            or raw_all.shape[-1] != 3 or raw_all.shape[0] < 1 or (raw_all.dim() == 4 and raw_all.shape[1] != 1):
+    if not raw_all.is_cuda or raw_all.dim() not in (3, 4) or raw_all.shape[0] < 1 or (raw_all.dim() == 4 and raw_all.shape[1] != 1):
         raise ValueError("raw_all: a contiguous float32 (raw_rows, J, 3) tensor on a GPU is needed")
+    _need(raw_all, "raw_all", torch.float32, dev, last=3)
     raw_rows, J = int(raw_all.shape[0]), int(raw_all.shape[-2])
     if (raw_mirror_all is None) != (mirror_perm is None):
         raise ValueError("raw_mirror_all and mirror_perm go together")
-    if raw_mirror_all is not None and (raw_mirror_all.dtype != torch.float32 or raw_mirror_all.device != dev
-                                       or not raw_mirror_all.is_contiguous() or raw_mirror_all.shape[0] != raw_rows
-                                       or raw_mirror_all.numel() != raw_all.numel()):
-        raise ValueError("raw_mirror_all: a contiguous float32 (%d, %d, 3) tensor on %s is needed" % (raw_rows, J, dev))
-    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
-        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
-    if raw_first_dev.dtype != torch.int64 or raw_first_dev.device != dev or not raw_first_dev.is_contiguous() \
-            or tuple(raw_first_dev.shape) != (num_clips,):
-        raise ValueError("raw_first_dev: a contiguous int64 (%d,) tensor on %s is needed" % (num_clips, dev))
+    if raw_mirror_all is not None:
+        _need(raw_mirror_all, "raw_mirror_all", torch.float32, dev, rows=raw_rows, numel=raw_all.numel())
+    _need_table(table_dev, num_clips, _capi.CLIP_DESC_BYTES, dev)
+    _need(raw_first_dev, "raw_first_dev", torch.int64, dev, shape=(num_clips,))
     pred = pred or pred_all is not None
     world = world or world_all is not None
     if not pred and not world:
         raise ValueError("neither pred nor world is wanted: nothing to write")
-    bufs = []
-    for t, name, want, dtype in ((pred_all, "pred_all", pred, torch.float32), (world_all, "world_all", world, torch.float64)):
-        if t is None:
-            t = torch.empty((total_frames, J, 3), dtype=dtype, device=dev) if want else None
-        elif t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.dim() < 2 or t.shape[0] != total_frames \
-                or t.numel() != total_frames * J * 3:
-            raise ValueError("%s: a contiguous %s (%d, %d, 3) tensor on %s is needed" % (name, dtype, total_frames, J, dev))
-        bufs.append(t)
-    pred_all, world_all = bufs
-    if status is None:
-        status = torch.empty(num_clips, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.device != dev or not status.is_contiguous() or tuple(status.shape) != (num_clips,):
-        raise ValueError("status: a contiguous int32 (%d,) tensor on %s is needed" % (num_clips, dev))
+    pred_all = _out_buffer(pred_all, "pred_all", pred, torch.float32, dev, (total_frames, J, 3), exact=False)
+    world_all = _out_buffer(world_all, "world_all", world, torch.float64, dev, (total_frames, J, 3), exact=False)
+    status = _status_buffer(status, num_clips, dev)
     with torch.cuda.device(dev):
         _capi.clips_poses(raw_all.data_ptr(), raw_mirror_all.data_ptr() if raw_mirror_all is not None else None, raw_rows, J,
                           [int(v) for v in mirror_perm] if mirror_perm is not None else None, table_dev.data_ptr(),
@@ -651,70 +773,33 @@ def shard_poses_hip(raw_all: torch.Tensor, table_dev: torch.Tensor, raw_first_de
     return pred_all, world_all, status
 
 
-def _lifter_of(lift_clip: Callable, what: str):
-    """The Ray3DLifter whose bound ``forward_clip`` `lift_clip` is, or a ValueError (decided before any shard is cut)."""
-    lifter = getattr(lift_clip, "__self__", None)
-    if lifter is None or getattr(lift_clip, "__name__", "") != "forward_clip" or not hasattr(lifter, "clip_batch_sizes"):
-        raise ValueError("%s: lift_clip must be the bound forward_clip of a Ray3DLifter (its raw_out= and clip_batch_sizes are used)" % what)
-    return lifter
-
-
-def _finished_shard(lift_clip: Callable, lifter, mine: Sequence[Clip], rf: int, dev, flip: bool, kps_left, kps_right, causal: bool,
-                    joints_left, joints_right, mirror: Optional[Callable], encode: Optional[str], table_dev: torch.Tensor,
-                    total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool):
-    """The lifting side of ``evaluate_clips_batched(finish=True)`` and :func:`predict_clips_batched`: every clip of `mine` lifted
-    with ``raw_out=`` into ONE raw buffer (with `flip`, the mirrored pass into a second one; with lanes the clips are dealt to the
-    lanes and joined ONCE), then ONE :func:`shard_poses_hip` call over `table_dev` (:func:`clip_table` of `mine`).  `encode` as in
-    :func:`evaluate_clips_batched`.  Reads the status once; a refused descriptor raises.  -> (pred_all, world_all or None)."""
+def _lift_finished(lift_clip: Callable, lifter, inputs: _ShardInputs, mirror_joints: Optional[tuple], table_dev: torch.Tensor,
+                   total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool):
+    """The raw destination of the forwards - ``evaluate_clips_batched(finish=True)`` and :func:`predict_clips_batched`: every clip of
+    `inputs` lifted with ``raw_out=`` into its rows of ONE raw buffer (with a flip pass - `mirror_joints` (left, right) of the
+    OUTPUT, else None - the mirrored input into a second one), dealt to the lanes and joined once (:func:`_deal`), then ONE
+    :func:`shard_poses_hip` call over `table_dev` (:func:`clip_table` of the shard) whose status is read: a refused descriptor
+    raises.  -> (pred_all, world_all or None)."""
+    mine, dev, flip = inputs.mine, inputs.dev, mirror_joints is not None
     J = lifter.pos.num_joints_in
     sizes_of = lifter.clip_batch_sizes
     raw_first, raw_rows = clip_raw_table([c.rays.shape[0] for c in mine], sizes_of)
     raw_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev)
     raw_m_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev) if flip else None
     raw_first_dev = torch.tensor(raw_first, dtype=torch.int64).to(dev)
-    lanes = getattr(lifter, "num_lanes", lambda: 0)() > 0
-    pad = (rf - 1) // 2
-    jl = kps_left if joints_left is None else joints_left
-    jr = kps_right if joints_right is None else joints_right
-    if encode is not None:
-        itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(sizes_of(n)) - n)
-        px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
-        itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
-        iperm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
-        x_all, xm_all, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode, iperm)
-        bad = torch.nonzero(status).flatten().tolist()
-        if bad:
-            raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
 
-    def lift(k, c):
-        n = c.rays.shape[0]
-        rows = slice(raw_first[k], raw_first[k] + sum(sizes_of(n)))
-        prow = torch.from_numpy(c.camera.param()).to(dev)
-        if encode is not None:
-            xr = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
-            lift_clip(x_all[xr], prow, raw_out=raw_all[rows], n_windows=n)
-            if flip:
-                lift_clip(xm_all[xr], prow, raw_out=raw_m_all[rows], n_windows=n)
-            return
-        padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
-        lift_clip(padded, prow, raw_out=raw_all[rows])
+    def lift(k):
+        rows = slice(raw_first[k], raw_first[k] + sum(sizes_of(mine[k].rays.shape[0])))
+        x, xm, prow, kw = inputs(k)
+        lift_clip(x, prow, raw_out=raw_all[rows], **kw)
         if flip:
-            lift_clip(mirror(padded) if mirror is not None else mirror_input(padded, kps_left, kps_right), prow, raw_out=raw_m_all[rows])
+            lift_clip(xm, prow, raw_out=raw_m_all[rows], **kw)
 
-    for k, c in enumerate(mine):
-        if lanes:
-            with lifter.lane():          # the clip's forwards on the next lane's stream
-                lift(k, c)
-        else:
-            lift(k, c)
-    if lanes:
-        lifter.join_lanes()              # the one join of the pass
-    perm = mirror_permutation(J, jl, jr) if flip else None
+    _deal(lifter, len(mine), lift)
+    perm = mirror_permutation(J, *mirror_joints) if flip else None
     pred_all, world_all, status = shard_poses_hip(raw_all, table_dev, raw_first_dev, len(mine), total, longest, raw_m_all, perm,
                                                   pred=True, world=world, pred_all=pred_all)
-    bad = torch.nonzero(status).flatten().tolist()
-    if bad:
-        raise RuntimeError("r3d_clips_poses refused the descriptors of clips %s of this rank's shard" % bad)
+    _raise_if_refused(status, "r3d_clips_poses")
     return pred_all, world_all
 
 
@@ -733,15 +818,17 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("predict_clips_batched finishes the poses on the GPU (r3d_clips_poses); on CPU tensors use predict_clip")
-    lifter = _lifter_of(lift_clip, "predict_clips_batched")
-    if encode is not None and encode not in ENCODINGS:
-        raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
+    lifter = _lifter_of(lift_clip, need="predict_clips_batched", by_name=True)
+    if encode is not None:
+        _encoding_id(encode)
     if not clips:
         return []
     table, first, total, longest = clip_table(clips, root_relative)
-    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
-    pred_all, world_all = _finished_shard(lift_clip, lifter, clips, rf, dev, flip, kps_left, kps_right, causal, joints_left,
-                                          joints_right, None, encode, table_dev, total, longest, None, world)
+    table_dev = _to_device_bytes(table, dev)
+    inputs = _ShardInputs(clips, rf, dev, causal, encode, lifter, flip, kps_left, kps_right)
+    jl = kps_left if joints_left is None else joints_left
+    jr = kps_right if joints_right is None else joints_right
+    pred_all, world_all = _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, None, world)
     return [(pred_all[first[k]:first[k] + c.rays.shape[0]],
              world_all[first[k]:first[k] + c.rays.shape[0]] if world_all is not None else None) for k, c in enumerate(clips)]
 
@@ -776,100 +863,41 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
-    lifter = getattr(lift_clip, "__self__", None)
+    lifter = _lifter_of(lift_clip)
     if encode is not None:        # (decided before the shards are cut: every rank raises alike, also one with an empty shard)
-        if encode not in ENCODINGS:
-            raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
+        _encoding_id(encode)
         if mirror is not None:
             raise ValueError("encode=: the flip pass mirrors the encoded input on the device; `mirror` must be None")
-        if lifter is None or not hasattr(lifter, "clip_batch_sizes"):
-            raise ValueError("encode=: lift_clip must be the bound forward_clip of a Ray3DLifter")
+        _lifter_of(lift_clip, need="encode=")
     if finish:
-        lifter = _lifter_of(lift_clip, "finish=True")
-    actions = sorted(set(c.action for c in clips))
-    aid = {a: i for i, a in enumerate(actions)}
-    shards = shard_clips([c.rays.shape[0] for c in clips], world_size)
-    mine = [clips[idx] for idx in shards[rank]]
-    local = partial_rows([(idx, aid[clips[idx].action], clips[idx].rays.shape[0]) for idx in shards[rank]], dev)
+        _lifter_of(lift_clip, need="finish=True", by_name=True)
+    actions, aid, shards, mine = _shard_plan(clips, rank, world_size)
+    local = _shard_rows(clips, aid, shards[rank], PARTIAL_COLS, dev)
     dlocal = torch.zeros((len(mine), DETAIL_COLS), dtype=torch.float64, device=dev) if detail else None
-    if mine and finish:
+    if mine:
         table, first, total, longest = clip_table(mine, root_relative)
-        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
-        gt_all = torch.from_numpy(np.concatenate(
-            [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
+        table_dev = _to_device_bytes(table, dev)
+        gt_all = _ground_truth(mine, dev, root_relative)
         pred_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
-        _finished_shard(lift_clip, lifter, mine, rf, dev, flip, kps_left, kps_right, causal, joints_left, joints_right, mirror, encode,
-                        table_dev, total, longest, pred_all, False)
-        shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)
-    elif mine:
-        table, first, total, longest = clip_table(mine, root_relative)
-        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
-        gt_all = torch.from_numpy(np.concatenate(
-            [np.ascontiguousarray(root_relative_gt(c.gt_norm) if root_relative else c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
-        J = gt_all.shape[1]
-        pred_all = torch.empty((total, 1, J, 3), dtype=torch.float32, device=dev)
-        lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
-        pad = (rf - 1) // 2
+        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, mirror)
         jl = kps_left if joints_left is None else joints_left
         jr = kps_right if joints_right is None else joints_right
-
-        if encode is not None:
-            itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(lifter.clip_batch_sizes(n)) - n)
-            px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
-            itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
-            perm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
-            x_all, xm_all, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode, perm)
-            bad = torch.nonzero(status).flatten().tolist()
-            if bad:
-                raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
-
-            def lift_encoded(k, c, dst):
-                n = c.rays.shape[0]
-                rows = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
-                prow = torch.from_numpy(c.camera.param()).to(dev)
-                lift_clip(x_all[rows], prow, out=dst, n_windows=n)
+        if finish:
+            _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, pred_all, False)
+        else:
+            def lift(k):
+                dst = pred_all[first[k]:first[k] + mine[k].rays.shape[0]]
+                x, xm, prow, kw = inputs(k)
+                lift_clip(x, prow, out=dst, **kw)
                 if flip:
-                    pred_m = lift_clip(xm_all[rows], prow, n_windows=n)
-                    torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as lift_into rounds it
+                    pred_m = lift_clip(xm, prow, **kw)
+                    torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as predict_clip rounds it
                     dst.mul_(0.5)
 
-        def lift_into(k, c, dst):
-            padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
-            prow = torch.from_numpy(c.camera.param()).to(dev)
-            lift_clip(padded, prow, out=dst)
-            if flip:
-                pred_m = lift_clip(mirror(padded) if mirror is not None else mirror_input(padded, kps_left, kps_right), prow)
-                torch.add(dst, mirror_output(pred_m, jl, jr), out=dst)     # 0.5 * (pred + mirrored), as predict_clip rounds it
-                dst.mul_(0.5)
-
-        lift = lift_encoded if encode is not None else lift_into
-        for k, c in enumerate(mine):
-            dst = pred_all[first[k]:first[k] + c.rays.shape[0]]
-            if lanes:
-                with lifter.lane():          # the clip's forwards and its flip average on the next lane's stream
-                    lift(k, c, dst)
-            else:
-                lift(k, c, dst)
-        if lanes:
-            lifter.join_lanes()
+            _deal(lifter, len(mine), lift)
         shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)
-    if world_size > 1:
-        counts = [len(s) for s in shards]
-        allrows = gather_partials(local, counts, group)
-        alldetail = gather_partials(dlocal, counts, group, cols=DETAIL_COLS) if detail else None
-    else:
-        allrows, alldetail = local, dlocal
-    if not detail:
-        per = reduce_partials(allrows)
-        return {actions[a]: v for a, v in per.items()}, action_average(per), allrows
-    order = torch.argsort(allrows[:, 0], stable=True)
-    allrows, alldetail = allrows[order], alldetail[order]
-    per = reduce_partials(allrows)
-    named = {actions[a]: v for a, v in per.items()}
-    tables = reduce_detail(allrows, alldetail, clips[0].gt_norm.shape[1] if len(clips) else 0, include_root)
-    out = {(actions[a] if a != "overall" else a): t for a, t in tables.items()}
-    out["rows"] = alldetail
-    return named, action_average(per), allrows, out
+    return _report(_gather(local, shards, group, PARTIAL_COLS), _gather(dlocal, shards, group, DETAIL_COLS) if detail else None,
+                   actions, clips, include_root)
 
 
 def format_detail_report(table: Dict, joint_names: Optional[Sequence[str]] = None) -> List[str]:
@@ -937,6 +965,24 @@ def clip_valid(pos_or_sum: torch.Tensor, trj: Optional[torch.Tensor], clip: Clip
     return row
 
 
+def _valid_plan(clips: Sequence[Clip], group, device):
+    """(shards, this rank's clips, its VALID_COLS rows with the headers in place): whole clips sharded over the ranks of `group`
+    when torch.distributed is initialised, else one shard."""
+    import torch.distributed as dist
+    distributed = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if distributed else (0, 1)
+    _, aid, shards, mine = _shard_plan(clips, rank, world)
+    return shards, mine, _shard_rows(clips, aid, shards[rank], VALID_COLS, device)
+
+
+def _valid_report(local: torch.Tensor, shards, group, clips: Sequence[Clip], parents, bone_pairs):
+    """(:func:`reduce_valid` of all ranks' rows, the rows in clip-id order)."""
+    allrows = _gather(local, shards, group, VALID_COLS)
+    allrows = allrows[torch.argsort(allrows[:, 0], stable=True)]
+    num_joints = int(clips[0].gt_norm.shape[1]) if len(clips) else 1
+    return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
+
+
 def validate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, parents=H36M_17_PARENTS, group=None,
                    pos_is_sum: bool = True, gt_root_relative: bool = False, causal: bool = False,
                    bone_pairs: Optional[Sequence[tuple]] = None):
@@ -946,28 +992,14 @@ def validate_clips(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, 
     trajectory model, the poses alone.  With torch.distributed initialised (`group`: the process group, None the default one)
     whole clips are sharded over the ranks as in :func:`evaluate_clips` and the rows travel in ONE all_gather.
     Every rank returns (:func:`reduce_valid` of all rows, the rows in clip-id order)."""
-    import torch.distributed as dist
-    distributed = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if distributed else (0, 1)
-    actions = sorted(set(c.action for c in clips))
-    aid = {a: i for i, a in enumerate(actions)}
-    shards = shard_clips([c.rays.shape[0] for c in clips], world)
-    local = torch.zeros((len(shards[rank]), VALID_COLS), dtype=torch.float64)
-    if shards[rank]:
-        local[:, :3] = torch.tensor([[float(idx), float(aid[clips[idx].action]), float(clips[idx].rays.shape[0])]
-                                     for idx in shards[rank]], dtype=torch.float64)
-    local = local.to(device)
+    shards, mine, local = _valid_plan(clips, group, device)
     pad = (rf - 1) // 2
-    for k, idx in enumerate(shards[rank]):
-        c = clips[idx]
+    for k, c in enumerate(mine):
         padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(device)
         res = lift_clip(padded, torch.from_numpy(c.camera.param()).to(device))
         poses, trj = res if isinstance(res, tuple) else (res, None)
         clip_valid(poses, trj, c, parents, pos_is_sum and trj is not None, out=local[k], gt_root_relative=gt_root_relative)
-    allrows = gather_partials(local, [len(s) for s in shards], group, cols=VALID_COLS) if world > 1 else local
-    allrows = allrows[torch.argsort(allrows[:, 0], stable=True)]
-    num_joints = int(clips[0].gt_norm.shape[1]) if len(clips) else 1
-    return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
+    return _valid_report(local, shards, group, clips, parents, bone_pairs)
 
 
 def shard_valid_hip(pos_all: torch.Tensor, trj_all: Optional[torch.Tensor], gt_all: torch.Tensor, table_dev: torch.Tensor,
@@ -982,27 +1014,19 @@ def shard_valid_hip(pos_all: torch.Tensor, trj_all: Optional[torch.Tensor], gt_a
     synchronisation."""
     from . import _capi
     dev = pos_all.device
-    for t, name in ((pos_all, "pos_all"), (gt_all, "gt_all")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.shape[0] != total_frames or t.shape[-1] != 3:
-            raise ValueError("%s: a contiguous float32 (total_frames, J, 3) tensor on %s is needed" % (name, dev))
+    _need(pos_all, "pos_all", torch.float32, dev, rows=total_frames, last=3)
+    _need(gt_all, "gt_all", torch.float32, dev, rows=total_frames, last=3)
     J = pos_all.numel() // (3 * total_frames)
     if pos_all.numel() != gt_all.numel():
         raise ValueError("ground truth %s vs prediction %s" % (tuple(gt_all.shape), tuple(pos_all.shape)))
-    if trj_all is not None and (trj_all.dtype != torch.float32 or not trj_all.is_contiguous() or trj_all.device != dev
-                                or trj_all.shape[0] != total_frames or trj_all.numel() != 3 * total_frames):
-        raise ValueError("trj_all: a contiguous float32 (total_frames, 3) tensor on %s is needed" % (dev,))
-    if table_dev.device != dev or not table_dev.is_contiguous() or table_dev.numel() * table_dev.element_size() < num_clips * 112:
-        raise ValueError("table_dev: %d descriptors of 112 bytes on %s are needed" % (num_clips, dev))
-    if rows.dtype != torch.float64 or rows.device != dev or tuple(rows.shape) != (num_clips, VALID_COLS) or not rows.is_contiguous():
-        raise ValueError("rows: a contiguous float64 (%d, %d) matrix of row headers on %s is needed" % (num_clips, VALID_COLS, dev))
-    if frames is not None and (frames.dtype != torch.float64 or frames.device != dev or not frames.is_contiguous()
-                               or tuple(frames.shape) != (total_frames, M.VALID_COUNT)):
-        raise ValueError("frames: a contiguous float64 (%d, %d) tensor on %s is needed" % (total_frames, M.VALID_COUNT, dev))
+    if trj_all is not None:
+        _need(trj_all, "trj_all", torch.float32, dev, rows=total_frames, numel=3 * total_frames)
+    _need_table(table_dev, num_clips, _capi.CLIP_DESC_BYTES, dev)
+    _need(rows, "rows (the matrix of row headers)", torch.float64, dev, shape=(num_clips, VALID_COLS))
+    if frames is not None:
+        _need(frames, "frames", torch.float64, dev, shape=(total_frames, M.VALID_COUNT))
     tree = validate_parents(parents, J) if parents is not None else None
-    nbytes = _capi.clips_valid_scratch_bytes(num_clips, max_frames)
-    scratch = _shard_scratch.get(dev)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _shard_scratch[dev] = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    scratch = _shard_scratch(dev, _capi.clips_valid_scratch_bytes(num_clips, max_frames))
     with torch.cuda.device(dev):
         _capi.clips_valid_losses(pos_all.data_ptr(), trj_all.data_ptr() if trj_all is not None else None, gt_all.data_ptr(), total_frames,
                                  J, tree, flags, table_dev.data_ptr(), num_clips, max_frames, rows.data_ptr() + 3 * 8, VALID_COLS,
@@ -1015,16 +1039,7 @@ def clip_frame_table(lengths: Sequence[int]):
     """(table, first_frame, total_frames, longest) for clips of these frame counts laid out back to back: r3d_clip_desc rows
     with the identity for a transform - what r3d_clips_valid_losses needs of a table (it reads first_frame / n_frames only; a
     caller that also evaluates hands it :func:`clip_table`'s)."""
-    from . import _capi
-    table = np.zeros(len(lengths), dtype=_capi.clip_desc_dtype())
-    first, at, longest = [], 0, 0
-    for k, n in enumerate(lengths):
-        table[k]["first_frame"], table[k]["n_frames"] = at, int(n)
-        table[k]["rn2w"] = np.eye(3).reshape(9)
-        first.append(at)
-        at += int(n)
-        longest = max(longest, int(n))
-    return table, first, at, longest
+    return _desc_table([int(n) for n in lengths], [(_IDENTITY_R, _IDENTITY_T)] * len(lengths))
 
 
 def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, parents=H36M_17_PARENTS, group=None,
@@ -1044,78 +1059,37 @@ def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     shard as well, exactly as in :func:`evaluate_clips_batched` (no mirror): the rank's pixels are uploaded once, ONE
     r3d_clips_encode call pads and encodes every clip, each clip is lifted from its slice with ``n_windows=``; a descriptor
     the encode call refuses raises."""
-    import torch.distributed as dist
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("validate_clips_batched measures on the GPU (r3d_clips_valid_losses); on CPU tensors use validate_clips")
-    lifter = getattr(lift_clip, "__self__", None) or getattr(getattr(lift_clip, "func", None), "__self__", None)
+    lifter = _lifter_of(lift_clip, partial_ok=True)
     if encode is not None:        # (decided before the shards are cut: every rank raises alike, also one with an empty shard)
-        if encode not in ENCODINGS:
-            raise ValueError("encode must be one of %s (got %r)" % (sorted(ENCODINGS), encode))
-        if lifter is None or not hasattr(lifter, "clip_batch_sizes"):
-            raise ValueError("encode=: lift_clip must be (a functools.partial of) the bound forward_clip of a Ray3DLifter")
-    distributed = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if distributed else (0, 1)
-    actions = sorted(set(c.action for c in clips))
-    aid = {a: i for i, a in enumerate(actions)}
-    shards = shard_clips([c.rays.shape[0] for c in clips], world)
-    mine = [clips[idx] for idx in shards[rank]]
-    local = torch.zeros((len(mine), VALID_COLS), dtype=torch.float64)
-    if mine:
-        local[:, :3] = torch.tensor([[float(idx), float(aid[clips[idx].action]), float(clips[idx].rays.shape[0])]
-                                     for idx in shards[rank]], dtype=torch.float64)
-    local = local.to(dev)
+        _encoding_id(encode)
+        _lifter_of(lift_clip, partial_ok=True, need="encode=")
+    shards, mine, local = _valid_plan(clips, group, dev)
     if mine:
         table, first, total, longest = clip_frame_table([c.rays.shape[0] for c in mine])
-        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
-        gt_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.gt_norm, dtype=np.float32) for c in mine], axis=0)).to(dev)
-        J = gt_all.shape[1]
-        pos_all = torch.empty((total, 1, J, 3), dtype=torch.float32, device=dev)
+        table_dev = _to_device_bytes(table, dev)
+        gt_all = _ground_truth(mine, dev)
+        pos_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
         trj_all = torch.empty((total, 1, 1, 3), dtype=torch.float32, device=dev)
-        lanes = lifter is not None and getattr(lifter, "num_lanes", lambda: 0)() > 0
-        pad = (rf - 1) // 2
+        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter)
 
-        if encode is not None:
-            itable, ofirst, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(lifter.clip_batch_sizes(n)) - n)
-            px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
-            itable_dev = torch.from_numpy(itable.view(np.uint8)).to(dev)
-            x_all, _, status = shard_encode_hip(px_all, itable_dev, len(mine), out_rows, max_rows, encode)
-            bad = torch.nonzero(status).flatten().tolist()
-            if bad:
-                raise RuntimeError("r3d_clips_encode refused the descriptors of clips %s of this rank's shard" % bad)
+        def lift(k):
+            rows = slice(first[k], first[k] + mine[k].rays.shape[0])
+            x, _, prow, kw = inputs(k)
+            return isinstance(lift_clip(x, prow, out=pos_all[rows], trj_out=trj_all[rows], **kw), tuple)
 
-        def lift(k, c, dst, tdst):
-            n = c.rays.shape[0]
-            prow = torch.from_numpy(c.camera.param()).to(dev)
-            if encode is not None:
-                rows = slice(ofirst[k], ofirst[k] + int(itable[k]["pad_front"]) + n + int(itable[k]["pad_back"]))
-                return lift_clip(x_all[rows], prow, out=dst, trj_out=tdst, n_windows=n)
-            padded = torch.from_numpy(pad_clip(np.asarray(c.rays, dtype=np.float32), pad, pad if causal else 0)).to(dev)
-            return lift_clip(padded, prow, out=dst, trj_out=tdst)
-
-        with_trj = set()
-        for k, c in enumerate(mine):
-            rows = slice(first[k], first[k] + c.rays.shape[0])
-            if lanes:
-                with lifter.lane():          # the clip's forwards on the next lane's stream
-                    res = lift(k, c, pos_all[rows], trj_all[rows])
-            else:
-                res = lift(k, c, pos_all[rows], trj_all[rows])
-            with_trj.add(isinstance(res, tuple))
+        with_trj = set(_deal(lifter, len(mine), lift))
         if len(with_trj) != 1:
             raise RuntimeError("lift_clip returned a trajectory for some clips of the pass and none for others")
         has_trj = with_trj.pop()
-        if lanes:
-            lifter.join_lanes()
         if gt_root_relative and has_trj:
             raise ValueError("gt_root_relative is for models without a trajectory: with one the ground truth must be absolute")
         from . import _capi
         flags = (_capi.R3D_VALID_POS_IS_SUM if pos_is_sum and has_trj else 0) | (_capi.R3D_VALID_GT_ROOT_RELATIVE if gt_root_relative else 0)
         shard_valid_hip(pos_all, trj_all if has_trj else None, gt_all, table_dev, len(mine), total, longest, local, parents, flags)
-    allrows = gather_partials(local, [len(s) for s in shards], group, cols=VALID_COLS) if world > 1 else local
-    allrows = allrows[torch.argsort(allrows[:, 0], stable=True)]
-    num_joints = int(clips[0].gt_norm.shape[1]) if len(clips) else 1
-    return reduce_valid(allrows, num_joints if parents is not None else 1, bone_pairs), allrows
+    return _valid_report(local, shards, group, clips, parents, bone_pairs)
 
 
 def reduce_valid(rows: torch.Tensor, num_joints: int = 17, bone_pairs: Optional[Sequence[tuple]] = None) -> Dict:

@@ -297,14 +297,26 @@ def test_forward_clip_into_a_slice_equals_forward_clip(n):
         lifter.forward_clip(clip, prow, out=buf[:n + 1])
 
 
-@pytest.mark.parametrize("flip", [False, True], ids=["plain", "flip"])
-def test_evaluate_clips_batched_equals_evaluate_clips(flip):
-    """Three short clips over two actions through the RF-27 model: the rows of the one-call path are those of the per-clip path."""
+def _no_swap_mirror(x):
+    """A `mirror=` callable that is NOT mirror_input's default: x negated, the keypoints left where they are."""
+    from ray3d_amd import evaluate
+    return evaluate.mirror_input(x, (), ())
+
+
+@pytest.mark.parametrize("case", ["plain", "flip", "mirror", "ranks2"])
+def test_evaluate_clips_batched_equals_evaluate_clips(case, monkeypatch):
+    """Three short clips over two actions through the RF-27 model: the rows of the one-call path are those of the per-clip path.
+    `mirror`: the flip pass through a `mirror=` callable, also with finish=True.  `ranks2`: the pass run as rank 0 and as rank 1 of
+    two (both shards hold clips; the all_gather replaced by the rows the two ranks made), finish off and on - row for row the
+    single-rank result."""
     from ray3d_amd import evaluate
     lifter = _lifter()
     dev = torch.device("cuda:0")
     clips = near_clips(lifter.forward_clip, evalcore_clips(), dev)
+    flip = case != "plain"
     kw = dict(flip=flip, kps_left=H36M_LEFT, kps_right=H36M_RIGHT)
+    if case == "mirror":
+        kw["mirror"] = _no_swap_mirror
     with torch.no_grad():
         named, avg, rows = evaluate.evaluate_clips(lifter.forward_clip, clips, 27, dev, **kw)
         named_b, avg_b, rows_b = evaluate.evaluate_clips_batched(lifter.forward_clip, clips, 27, dev, **kw)
@@ -319,3 +331,35 @@ def test_evaluate_clips_batched_equals_evaluate_clips(flip):
         assert detail_e[key] == detail[key], key
     if not flip:     # (the ground truth lies near the plain poses; the synthetic weights are not mirror-symmetric, so the flip average is metres off)
         assert 0.0 < detail_e["overall"]["auc"] < detail_e["overall"]["pck150"] <= 100.0
+    if case == "mirror":
+        with torch.no_grad():
+            _, _, rows_f, detail_f = evaluate.evaluate_clips_batched(lifter.forward_clip, clips, 27, dev, detail=True, finish=True, **kw)
+            _, _, rows_default = evaluate.evaluate_clips_batched(lifter.forward_clip, clips, 27, dev, **dict(kw, mirror=None))
+        assert same_bits(rows_f, rows_d) and same_bits(detail_f["rows"], detail["rows"])
+        assert torch.isfinite(rows_b).all() and not torch.equal(rows_default[:, 3], rows_b[:, 3])      # the callable was used
+    if case == "ranks2":
+        shards = evaluate.shard_clips([c.rays.shape[0] for c in clips], 2)
+        assert all(shards) and sorted(shards[0] + shards[1]) == [0, 1, 2]
+        for finish in (False, True):
+            made = {}                                    # (rank, cols) -> the rows that rank handed to the exchange
+
+            def gather(local_rows, counts, group=None, cols=evaluate.PARTIAL_COLS, rank=None):
+                assert list(counts) == [len(s) for s in shards] and local_rows.shape == (counts[rank], cols)
+                made[rank, cols] = local_rows
+                return torch.cat([made.get((r, cols), local_rows.new_zeros((counts[r], cols))) for r in range(2)], dim=0)
+
+            got = {}
+            for rank in (0, 1, 0):                       # (rank 0 once more, now with rank 1's rows in the exchange)
+                monkeypatch.setattr(evaluate, "gather_partials", functools.partial(gather, rank=rank))
+                with torch.no_grad():
+                    got[rank] = evaluate.evaluate_clips_batched(lifter.forward_clip, clips, 27, dev, rank=rank, world_size=2,
+                                                                finish=finish, **kw), \
+                        evaluate.evaluate_clips_batched(lifter.forward_clip, clips, 27, dev, rank=rank, world_size=2, finish=finish,
+                                                        detail=True, **kw)
+            for rank in (0, 1):
+                (_, _, r_plain), (n_det, a_det, r_det, d_det) = got[rank]
+                ids = [float(i) for i in shards[0] + shards[1]]
+                assert r_plain[:, 0].tolist() == ids                                    # as gathered: rank order, unsorted
+                assert same_bits(r_plain[torch.argsort(r_plain[:, 0])], rows_d), (finish, rank)
+                assert same_bits(r_det, rows_d) and same_bits(d_det["rows"], detail["rows"]), (finish, rank)
+                assert n_det == named_e and a_det == avg_e and all(d_det[k] == detail[k] for k in ("A", "B", "overall"))

@@ -19,40 +19,33 @@ usage:  python tools/clips_poses_ab.py              every step in a fresh proces
                                                     -Rpass-analysis=kernel-resource-usage) of this build and, optionally, of the
                                                     parent's, and store the figures of the kernel r3d_clips_poses runs on and the
                                                     list of kernels whose figures differ in the --out file (kept if it exists)
-        [--out FILE] [--clips N] [--reps R] another result file; a smaller run (rehearsals)."""
-import argparse
+        [--out FILE] [--clips N] [--reps R] another result file; a smaller run (rehearsals) - tools/clips_ab_common.py."""
 import json
 import os
 import re
-import subprocess
 import sys
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clips_ab_common as ab
+from clips_ab_common import H36M_LEFT, H36M_RIGHT, alternate, make_set, ranges_overlap, verdict
+
+TOOL = "clips_poses_ab"
 STEPS = (("finish", 300), ("pass", 560))      # (step, its time limit in seconds)
-PART_DIR = os.path.join(ROOT, "measure_out")
-OUT = os.path.join(ROOT, "profiles", "clips_poses_ab.json")
 KERNEL = "r3d_undistort_rays_f64"             # the elementwise kernel whose third argument set r3d_clips_poses is
-H36M_LEFT, H36M_RIGHT = [4, 5, 6, 11, 12, 13], [1, 2, 3, 14, 15, 16]
 
 
 def compare(a, b, equal, what):
-    from clips_valid_ab import verdict
     res = {"per_clip": a, "one_call": b, "ratio_one_call_over_per_clip": round(b["mean_ms"] / a["mean_ms"], 4),
-           "ranges_overlap": not (b["max_ms"] < a["min_ms"] or b["min_ms"] > a["max_ms"]), "bit_equal": equal,
-           "verdict": verdict(a, b).replace("batched", "one call")}
+           "ranges_overlap": ranges_overlap(a, b), "bit_equal": equal, "verdict": verdict(a, b, "one call")}
     if not equal:
         raise SystemExit("%s: the results of the two paths differ: %s" % (what, json.dumps(res)))
     return res
 
 
 def step_finish(n_clips, reps):
-    import numpy as np
     import torch
     import ray3d_amd
-    from clips_valid_ab import alternate, make_set
     from ray3d_amd import evaluate
     dev = torch.device("cuda", 0)
     clips = make_set(n_clips)
@@ -60,7 +53,7 @@ def step_finish(n_clips, reps):
     lengths = [c.rays.shape[0] for c in clips]
     table, first, total, longest = evaluate.clip_table(clips)
     raw_first, raw_rows = evaluate.clip_raw_table(lengths, sizes_of)
-    table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+    table_dev = evaluate._to_device_bytes(table, dev)
     raw_first_dev = torch.tensor(raw_first, dtype=torch.int64).to(dev)
     g = torch.Generator(device=dev).manual_seed(0)
     raw = torch.randn((raw_rows, 1, 17, 3), generator=g, device=dev)
@@ -95,25 +88,12 @@ def step_finish(n_clips, reps):
 
 
 def step_pass(n_clips, reps):
-    import numpy as np
     import torch
-    import ray3d_amd
-    from clips_valid_ab import alternate, make_set
-    from ray3d_amd import evaluate, synth
-    from ray3d_amd.spec import config_from_dicts
+    from ray3d_amd import evaluate
     dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    mc = ray3d_amd.default_model_config(ARCHITECTURE="3,3,3,3,3")
-    fac = ray3d_amd.Model(mc, {}, is_train=False)
-    pos, trj = fac.get_pos_model(), fac.get_trj_model()
-    for m, kind, seed in ((pos, "pos", 1), (trj, "trj", 2)):
-        cfg = config_from_dicts(mc, kind)
-        ray3d_amd.load_weight(m, {k: torch.from_numpy(np.asarray(v)) for k, v in synth.synth_state(cfg, seed=seed).items()})
-        m.eval()
-    lifter = ray3d_amd.Ray3DLifter(pos, trj).eval()
     clips = make_set(n_clips)
     frames = sum(c.rays.shape[0] for c in clips)
-    lifter.prepare(sorted(set(b for c in clips for b in lifter.clip_batch_sizes(c.rays.shape[0]))), dev)
+    lifter = ab.make_lifter(clips, dev)
     out = {"what": "whole pass (upload, lift, finish, metrics, reduce), RF 243: %d clips, %d frames, no lanes; per_clip = finish=False, "
                    "the parent commit's code" % (len(clips), frames)}
     for flip in (False, True):
@@ -165,39 +145,16 @@ def resources(after, before):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--step", choices=[s for s, _ in STEPS])
-    ap.add_argument("--clips", type=int, default=240)
-    ap.add_argument("--reps", type=int, default=5)
+    ap = ab.parser(__doc__, TOOL, STEPS)
     ap.add_argument("--resources", nargs="+", metavar="LOG")
-    ap.add_argument("--out", default=OUT)
     args = ap.parse_args()
-    os.makedirs(PART_DIR, exist_ok=True)
-    part = lambda s: os.path.join(PART_DIR, "clips_poses_ab.%s.json" % s)
     if args.step:
-        res = (step_finish if args.step == "finish" else step_pass)(args.clips, args.reps)
-        with open(part(args.step), "w") as f:
-            json.dump(res, f, indent=1)
-        print(json.dumps({args.step: res}))
-        return 0
+        return ab.run_step(TOOL, args, (step_finish if args.step == "finish" else step_pass)(args.clips, args.reps))
     if args.resources:
         merged = json.load(open(args.out)) if os.path.exists(args.out) else {}
         merged["kernel_resources"] = resources(args.resources[0], args.resources[1] if len(args.resources) > 1 else None)
-    else:
-        merged = {"set": "%d clips, lengths U(1000, 6000), seed 0" % args.clips, "repetitions": args.reps,
-                  "timing": "device events around each side, sides alternating, one untimed round first"}
-        for step, limit in STEPS:                     # a fresh process per step; the first failure ends the run
-            rc = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step,
-                                 "--clips", str(args.clips), "--reps", str(args.reps)]).returncode
-            if rc != 0:
-                print("step %s ended with status %d: stopping" % (step, rc), file=sys.stderr)
-                return rc
-            merged[step] = json.load(open(part(step)))
-    with open(args.out, "w") as f:
-        json.dump(merged, f, indent=1)
-        f.write("\n")
-    print("wrote", args.out)
-    return 0
+        return ab.write_out(args.out, merged)
+    return ab.run_steps(TOOL, STEPS, args, ab.header(args))
 
 
 if __name__ == "__main__":

@@ -660,6 +660,29 @@ int r3d_debug_plan_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg,
  * the plan of this batch size runs launch by launch (nothing to check), or a negative code. */
 int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int *tiles, int *counters);
 
+/* Census of kernel specialisations: the launches one forward of `batch` windows on `nwg` CUs would make, in order, and for
+ * each the tile kinds its tiles select in the persistent loop's dispatch (r3d_tiles.hpp, gemm_persistent) - host only, no
+ * device.  Plan, tile lists, kernel choice and call form come from the code the driver itself runs; only the in-kernel
+ * dispatch is restated (r3d_hooks.cpp, census_tile_kind).  The call shape: `uv` pixel keypoints (R3D_INPUT_UV) or rays,
+ * `cam_stride` 0 = one camera row (as r3d_input), `window_stride` in frames (1: a clip call), `staged` as R3D_OPT_STAGED,
+ * `captured` as on a stream under capture.  An eager call is reported as the FIRST one on its buffers (with r3d_bind_f32;
+ * a repeat on the same buffers skips it).  Assumes every workgroup resident and no CU mask, as on the device the lists are
+ * built for.  One row per (launch, tile kind), launches in order; a launch without tile lists (r3d_bind_f32, the decoder
+ * tail) has one row with an empty tile kind.  `blocks` is what the launch record reports.  Returns the number of rows
+ * (which may exceed `cap`: nothing is written past it), or a negative code. */
+typedef struct r3d_census_row {
+    int32_t launch;          /* index of the launch in the call, from 0 */
+    int32_t blocks;          /* r3d_launch_record.blocks of that launch */
+    int32_t tiles;           /* tiles of this kind in the launch */
+    char kernel[48];         /* as r3d_profile_read names it */
+    char tile_kind[48];      /* e.g. "gemm_tile<3,1>", "first_level_taps_b3<2,K>64,UV>" */
+} r3d_census_row;
+int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int32_t uv, int64_t cam_stride,
+                             int64_t window_stride, int32_t staged, int32_t captured, r3d_census_row *rows, int32_t cap);
+/* Every (kernel, tile kind) the dispatch instantiates, by the same restatement run over all header values; and with
+ * tile_kind empty, every kernel name a forward's launch record can carry.  Same return convention. */
+int r3d_debug_census_domain(r3d_census_row *rows, int32_t cap);
+
 /* The per-keypoint routine of the R3D_INPUT_UV_DIST pre-pass, run on the host: `row16` one camera row of 16 doubles, `uv`
  * n pixel pairs; out_uv (n, 2) the undistorted pixels, out_rays (n, 3) the float64 rays before the cast (either may be
  * NULL).  Returns 0 or R3D_ERR_ARG. */

@@ -34,6 +34,7 @@ EXPORTS = (
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
+                "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
@@ -92,6 +93,12 @@ def clip_input_desc_dtype():
 class LaunchRecord(C.Structure):
     _fields_ = [("kernel", C.c_char * 48), ("stage", C.c_int32), ("blocks", C.c_int32),
                 ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+class CensusRow(C.Structure):
+    """r3d_census_row: one (launch, tile kind) of r3d_debug_forward_census."""
+    _fields_ = [("launch", C.c_int32), ("blocks", C.c_int32), ("tiles", C.c_int32), ("kernel", C.c_char * 48),
+                ("tile_kind", C.c_char * 48)]
 
 
 class Ray3DHipError(RuntimeError):
@@ -175,6 +182,9 @@ def load():
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_forward_census.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                 C.POINTER(CensusRow), C.c_int32]
+        lib.r3d_debug_census_domain.argtypes = [C.POINTER(CensusRow), C.c_int32]
         lib.r3d_debug_clips_poses_host.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp,
                                                    C.c_int64, vp]
         lib.r3d_debug_clips_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32,
@@ -403,6 +413,45 @@ def debug_clips_poses_host(raw_ptr: int, raw_mirror_ptr: Optional[int], raw_rows
     perm = _mirror_table("r3d_debug_clips_poses_host", mirror_perm, num_joints)
     return int(load().r3d_debug_clips_poses_host(raw_ptr, raw_mirror_ptr or None, raw_rows, num_joints, perm, table_ptr, raw_first_ptr,
                                                  num_clips, max_frames, pred_ptr or None, world_ptr or None, total_frames, status_ptr))
+
+
+def _census_rows(call):
+    cap = 256
+    while True:
+        rows = (CensusRow * cap)()
+        n = call(rows, cap)
+        if n < 0:
+            raise Ray3DHipError("census failed (%d): %s" % (n, load().r3d_last_error().decode()))
+        if n <= cap:
+            return [(r.launch, r.kernel.decode(), r.blocks, r.tile_kind.decode(), r.tiles) for r in rows[:n]]
+        cap = n
+
+
+def debug_forward_census(pos: Optional[Handle], trj: Optional[Handle], batch: int, window_stride: int, nwg: int = 256, uv: bool = False,
+                         cam_stride: int = 0, staged: bool = False, captured: bool = False):
+    """r3d_debug_forward_census (hooks library only: use_hooks(True)): the launches one forward of `batch` windows would make, as a
+    list of ``(kernel, blocks, {tile kind: tiles})`` in launch order - host only.  `window_stride` in frames (RF: independent
+    windows; 1: a clip call), `cam_stride` as r3d_input's (0: one camera row)."""
+    lib = _lib_of(pos, trj)
+    ws = int(window_stride)
+    rows = _census_rows(lambda r, cap: lib.r3d_debug_forward_census(pos.ptr if pos else None, trj.ptr if trj else None, batch, nwg,
+                                                                   1 if uv else 0, cam_stride, ws, 1 if staged else 0,
+                                                                   1 if captured else 0, r, cap))
+    launches = []
+    for launch, kernel, blocks, kind, tiles in rows:
+        if launch == len(launches):
+            launches.append((kernel, blocks, {}))
+        if kind:
+            launches[launch][2][kind] = tiles
+    return launches
+
+
+def debug_census_domain():
+    """r3d_debug_census_domain (hooks library only): ``(kernel names a launch record can carry, {(kernel, tile kind)} the persistent
+    loop's dispatch instantiates)``."""
+    lib = load()
+    rows = _census_rows(lambda r, cap: lib.r3d_debug_census_domain(r, cap))
+    return [k for _, k, _, kind, _ in rows if not kind], {(k, kind) for _, k, _, kind, _ in rows if kind}
 
 
 def _parent_table(parents):

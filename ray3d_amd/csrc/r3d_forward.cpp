@@ -96,6 +96,51 @@ int dist_check(const Model *a, const r3d_input *in, bool need_cam) {
     return R3D_OK;
 }
 
+// The kernels a forward launches, as its launch records name them (r3d_profile_read) - every name a record can carry comes from here
+const char *stage_kernel_name(int kind, bool uv_launch, bool b3_launch) {
+    return kind == STAGE_ENC ? (uv_launch ? "r3d_gemm_enc_uv_f32" : "r3d_gemm_enc_f32")
+         : b3_launch ? (uv_launch ? "r3d_gemm_uv_b3" : "r3d_gemm_b3") : (uv_launch ? "r3d_gemm_uv_f32" : "r3d_gemm_f32");
+}
+const char *decode_kernel_name(int64_t B) { return B >= 128 ? "r3d_decode_w4_f32" : "r3d_decode_f32"; }   // (launch_decode picks by the same test)
+const char *bind_kernel_name() { return "r3d_bind_f32"; }
+const char *undistort_kernel_name() { return "r3d_undistort_rays_f64"; }
+std::vector<const char *> launch_kernel_names() {
+    std::vector<const char *> v;
+    for (int k = 0; k < FWD_KERNEL_COUNT; ++k)
+        for (int uv = 0; uv < 2; ++uv) v.push_back(forward_kernel_name(k, uv != 0));
+    for (int kind : {STAGE_BIG, STAGE_ENC})
+        for (int b3 = 0; b3 < (kind == STAGE_BIG ? 2 : 1); ++b3)
+            for (int uv = 0; uv < 2; ++uv) v.push_back(stage_kernel_name(kind, uv != 0, b3 != 0));
+    v.push_back(bind_kernel_name());
+    v.push_back(decode_kernel_name(1));
+    v.push_back(decode_kernel_name(128));
+    v.push_back(undistort_kernel_name());
+    return v;
+}
+
+// Whether a call's fused first levels read the per-frame buffer (CallShape::shared).
+// Clip calls (window stride one frame, lib/train_val/trainer.py:47-58): consecutive windows share all but one of their
+// frames, and expand_conv is linear - its pre-activations are evaluated once per FRAME by a launch of gathered GEMMs
+// ahead of the forward (Plan::frame_probs) and the first-level tiles read them instead of gathering and multiplying
+// (r3d_kernels.hip, first_level_shared).  Where it pays (four times fewer rows), one camera for the
+// clip, fp32 tiles.  `frame_tiles`: the schedule has the per-frame launch's tile lists.
+bool call_shares_first_layers(const Plan *pl, const Model *a, int64_t B, bool uv, int64_t window_stride, int64_t cam_stride, long long frames,
+                              bool frame_tiles) {
+    bool b3_call = false;
+    for (const Model *mm : pl->m) b3_call = b3_call || (mm && mm->use_b3 && B >= b3_min_batch());
+    // (the per-frame buffer is addressed with 32-bit byte offsets in first_level_shared - row tables, descriptor bound: a
+    //  clip whose buffer would reach 4 GiB, ~349 k windows for a pos + trj pair, keeps the gathered path, which has 64-bit tile bases)
+    return pl->frame_buf >= 0 && frame_tiles && window_stride == 1 && !b3_call && (frames - 2) * 4 <= B * (int64_t)(a->RF / 3) &&
+           !(uv && cam_stride != 0) && !hook_on("R3D_NO_SHARED_L0") &&
+           (unsigned long long)frames * (unsigned long long)pl->frame_ld * 4ull < 0xffffffffull;
+}
+
+// Whether a call runs as ONE persistent launch: `grid` / `kernel` of the schedule's single-launch lists (0: it has none),
+// `has_table`: the relative problem table of the call's variant exists
+bool call_is_single(const Model *a, const Model *b, int grid, bool has_table, int kernel, bool shared) {
+    return forward_single_launch() && !a->opt_staged && !(b && b->opt_staged) && grid > 0 && has_table && !(shared && kernel != FWD_KERNEL_F32);
+}
+
 struct Recorder {
     Model *m;
     hipStream_t stream;
@@ -431,7 +476,7 @@ int px_prepass(Call &c) {
     ua.window_stride = (int)in_px->window_stride;
     ua.last_window = (int)(c.B - 1);
     ua.encoding = px_encoding(in_px->mode);
-    if (const int rc = c.begin("r3d_undistort_rays_f64", (ua.npts + 255) / 256, 0.0, (double)ua.npts * (2 + enc_floats(ua.encoding)) * sizeof(float)); rc != R3D_OK)
+    if (const int rc = c.begin(undistort_kernel_name(), (ua.npts + 255) / 256, 0.0, (double)ua.npts * (2 + enc_floats(ua.encoding)) * sizeof(float)); rc != R3D_OK)
         return rc;
     if (const hipError_t e = launch_undistort(ua, c.stream); e != hipSuccess) return hip_fail(e, "launch r3d_undistort_rays_f64");
     return c.end();
@@ -465,22 +510,11 @@ int pick_schedule(Call &c) {
     c.sched = schedule_get(c.pl, c.B, keys.nwg, false, keys.lane_key0 + c.lane);
     if (!c.sched) return R3D_ERR_HIP;
     const Schedule *sched = c.sched;
-    // Clip calls (window stride one frame, lib/train_val/trainer.py:47-58): consecutive windows share all but one of their
-    // frames, and expand_conv is linear - its pre-activations are evaluated once per FRAME by a launch of gathered GEMMs
-    // ahead of the forward (Plan::frame_probs) and the first-level tiles read them instead of gathering and multiplying
-    // (r3d_kernels.hip, first_level_shared).  Where it pays (four times fewer rows), one camera for the
-    // clip, fp32 tiles.
-    bool b3_call = false;
-    for (const Model *mm : pl->m) b3_call = b3_call || (mm && mm->use_b3 && c.B >= b3_min_batch());
-    // (the per-frame buffer is addressed with 32-bit byte offsets in first_level_shared - row tables, descriptor bound: a
-    //  clip whose buffer would reach 4 GiB, ~349 k windows for a pos + trj pair, keeps the gathered path, which has 64-bit tile bases)
-    c.shared = pl->frame_buf >= 0 && sched->d_frame_tiles != nullptr && in->window_stride == 1 && !b3_call &&
-               (c.frames - 2) * 4 <= c.B * (int64_t)(a->RF / 3) && !(c.uv && in->cam_stride != 0) && !hook_on("R3D_NO_SHARED_L0") &&
-               (unsigned long long)c.frames * (unsigned long long)pl->frame_ld * 4ull < 0xffffffffull;
+    // clip calls: the per-frame first layers where they pay (call_shares_first_layers)
+    c.shared = call_shares_first_layers(pl, a, c.B, c.uv, in->window_stride, in->cam_stride, c.frames, sched->d_frame_tiles != nullptr);
     c.shape.shared = c.shared;
     c.variant = (c.uv ? 1 : 0) + (c.shared ? 2 : 0);
-    c.single = forward_single_launch() && !a->opt_staged && !(b && b->opt_staged) && sched->fwd.grid > 0 && sched->fwd.d_rel[c.variant] != nullptr &&
-               !(c.shared && sched->fwd.kernel != FWD_KERNEL_F32);
+    c.single = call_is_single(a, b, sched->fwd.grid, sched->fwd.d_rel[c.variant] != nullptr, sched->fwd.kernel, c.shared);
     return R3D_OK;
 }
 
@@ -524,7 +558,7 @@ int frame_stage(Call &c) {
         g.enc_bytes = (unsigned)((size_t)c.frames * c.JF * sizeof(float));
         g.res_tap = 1;
     }
-    if (const int rc = c.begin(uv ? "r3d_gemm_uv_f32" : "r3d_gemm_f32", fs.nwg, 0.0, 0.0); rc != R3D_OK) return rc;
+    if (const int rc = c.begin(stage_kernel_name(STAGE_BIG, uv, false), fs.nwg, 0.0, 0.0); rc != R3D_OK) return rc;
     if (const hipError_t e = launch_gemm_stage(la, fs.nwg, STAGE_BIG, uv, c.stream); e != hipSuccess)
         return hip_fail(e, "launch r3d_gemm_f32 (per-frame first layers)");
     return c.end();
@@ -601,7 +635,7 @@ int bind_if_needed(Call &c, const Single &s) {
         ba.arm_vec4 = (long long)(2 * fw.act_bytes / 16);
     }
     hipError_t e;
-    if (const int rc = c.begin("r3d_bind_f32", 1, 0.0, 0.0); rc != R3D_OK) return rc;
+    if (const int rc = c.begin(bind_kernel_name(), 1, 0.0, 0.0); rc != R3D_OK) return rc;
     if ((e = launch_bind(ba, c.stream)) != hipSuccess) return hip_fail(e, "launch r3d_bind_f32");
     if (s.poll) {                 // ... and bank 1's
         BindArgs b1 = ba;
@@ -706,8 +740,7 @@ int staged_level(Call &c, size_t si) {
     for (int i = 0; i < la.nprob; ++i) uv_launch = uv_launch || la.p[i].cam != nullptr;
     bool b3_launch = false;                             // (launch_gemm_stage picks the kernel by the same test)
     for (int i = 0; i < la.nprob; ++i) b3_launch = b3_launch || la.p[i].wb3 != nullptr;
-    const char *kname = ss.kind == STAGE_ENC ? (uv_launch ? "r3d_gemm_enc_uv_f32" : "r3d_gemm_enc_f32")
-                      : b3_launch ? (uv_launch ? "r3d_gemm_uv_b3" : "r3d_gemm_b3") : (uv_launch ? "r3d_gemm_uv_f32" : "r3d_gemm_f32");
+    const char *kname = stage_kernel_name(ss.kind, uv_launch, b3_launch);
     if (const int rc = c.begin(kname, ss.nwg, ss.flops, ss.bytes); rc != R3D_OK) return rc;
 #ifdef R3D_TIMING
     const bool timed = timing_arm_stage(si, la, c.stream);
@@ -762,7 +795,7 @@ int decoder_tail(Call &c) {
         dec_flops += 2.0 * (double)c.B * L.K * L.N;
     }
     if (da.has_pos) output_slots(da.J, firsts, da.slot);
-    if (const int rc = c.begin(c.B >= 128 ? "r3d_decode_w4_f32" : "r3d_decode_f32", 0, dec_flops, (double)c.B * da.nsrc * MLP_HIDDEN * 4.0); rc != R3D_OK) return rc;
+    if (const int rc = c.begin(decode_kernel_name(c.B), 0, dec_flops, (double)c.B * da.nsrc * MLP_HIDDEN * 4.0); rc != R3D_OK) return rc;
     if (const hipError_t e = launch_decode(da, c.stream); e != hipSuccess) return hip_fail(e, "launch r3d_decode_f32");
     if (const int rc = c.end(); rc != R3D_OK) return rc;
     if (c.rec.on()) c.a->nrec = (int)c.rec.n;

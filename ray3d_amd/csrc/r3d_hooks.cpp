@@ -1,6 +1,10 @@
 // The r3d_debug_* exports of libray3d_hip_hooks.so: checkers that run on the host and never touch a device.
 #ifdef R3D_TEST_HOOKS      // (libray3d_hip_hooks.so only: the product library gets an empty translation unit)
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <set>
+#include <utility>
 
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
@@ -8,6 +12,113 @@
 #include "r3d_valid.hpp"
 
 using namespace r3d;
+
+namespace {
+
+// ---- r3d_debug_forward_census: the one restatement of device code in this file.
+// What the persistent loop's dispatch reads of a tile: its problem's operand pointers (set or not) and K, the tile's
+// units (mi) and code (ks); and of its kernel: the template arguments of gemm_persistent (r3d_k_*.hip).
+struct CensusProb { bool w3, lut, wb3, w2; int K; };
+struct CensusKernel { const char *name; bool enc, uv, dep, b3, narrow, clip; };
+
+std::vector<CensusKernel> census_kernels() {
+    std::vector<CensusKernel> v;
+    for (int uv = 0; uv < 2; ++uv) {
+        const bool u = uv != 0;
+        // r3d_k_gemm.hip, r3d_k_gemm_enc.hip, r3d_k_gemm_b3.hip: gemm_persistent<ENC, UV, DEP = false, B3[, NARROW]>, CLIP = !DEP
+        v.push_back({stage_kernel_name(STAGE_BIG, u, false), false, u, false, false, true, true});
+        v.push_back({stage_kernel_name(STAGE_ENC, u, false), true, u, false, false, false, true});
+        v.push_back({stage_kernel_name(STAGE_BIG, u, true), false, u, false, true, true, true});
+        // r3d_k_fwd_*.hip: R3D_FORWARD_KERNEL(name, UV, B3, NARROW, CLIP) = gemm_persistent<false, UV, true, B3, NARROW, CLIP>
+        v.push_back({forward_kernel_name(FWD_KERNEL_F32, u), false, u, true, false, false, false});
+        v.push_back({forward_kernel_name(FWD_KERNEL_B3, u), false, u, true, true, false, false});
+        v.push_back({forward_kernel_name(FWD_KERNEL_LAT, u), false, u, true, false, true, false});
+        v.push_back({forward_kernel_name(FWD_KERNEL_CLIP, u), false, u, true, false, false, true});
+    }
+    return v;
+}
+
+// The tile function and template arguments gemm_persistent's dispatch (r3d_tiles.hpp, the do { } while (false) block of the
+// persistent loop) selects for one tile, as the switches clamp them.  Keep the two in step: a tile kind added there is
+// added here, and tests/test_specialisations_host.py then asks for a case that reaches it.
+std::string census_tile_kind(const CensusKernel &k, const CensusProb &P, int mi, int ks) {
+    char b[48];
+    const char *in = k.uv ? "UV" : "rays";
+    auto enc = [&] { snprintf(b, sizeof b, "enc_tile<%d,%s>", mi == 1 ? 1 : mi == 2 ? 2 : 3, in); return std::string(b); };
+    if (k.enc) return enc();
+    if (P.w3) {                                  // the fused first level
+        const int m = mi >= 2 ? 2 : 1;
+        if (k.clip && !P.lut) snprintf(b, sizeof b, "first_level_shared<%d>", m);
+        else snprintf(b, sizeof b, "first_level_taps%s<%d,%s,%s>", k.b3 && P.wb3 ? "_b3" : "", m, P.K <= 64 ? "K<=64" : "K>64", in);
+        return b;
+    }
+    if (P.lut) return enc();
+    if (k.b3 && P.wb3 && P.w2) { snprintf(b, sizeof b, "gemm_tile_b3t<%d>", mi >= 3 ? 3 : mi == 2 ? 2 : 1); return b; }
+    if (k.b3 && P.wb3) {
+        if (mi == 1) return "gemm_tile_b3p<1>";
+        snprintf(b, sizeof b, "gemm_tile_b3<%d>", mi == 2 ? 2 : mi == 3 ? 3 : 4);
+        return b;
+    }
+    if (k.narrow && ks == 8) return k.dep ? "gemv_run" : "gemv_tile";
+    if (k.narrow && ks == 16) return "lat_tile";
+    if (ks > NB_CODE) { snprintf(b, sizeof b, "gemm_tile_nb<%d>", ks == NB_CODE + 4 ? 4 : ks == NB_CODE + 5 ? 5 : ks == NB_CODE + 6 ? 6 : 7); return b; }
+    if (ks > 1) return ks == 4 ? "gemm_tile<1,4>" : mi == 1 ? "gemm_tile<1,2>" : "gemm_tile<2,2>";
+    if (P.w2) { snprintf(b, sizeof b, "gemm_tile<%d,1,pair>", mi >= 1 && mi <= 3 ? mi : 4); return b; }
+    snprintf(b, sizeof b, "gemm_tile<%d,1>", mi >= 1 && mi <= 5 ? mi : 6);
+    return b;
+}
+
+const CensusKernel *census_find(const std::vector<CensusKernel> &ks, const char *name) {
+    for (const CensusKernel &k : ks)
+        if (!strcmp(k.name, name)) return &k;
+    return nullptr;
+}
+
+CensusProb census_prob(const unsigned char *tg, int K) {       // (fill_prob's base tags: which pointer fields are set)
+    return {tg[13] != BIND_NULL, tg[15] != BIND_NULL, tg[10] != BIND_NULL, tg[8] != BIND_NULL, K};
+}
+
+struct CensusOut {
+    r3d_census_row *rows;
+    int cap, n = 0, launch = 0;
+    void row(const char *kernel, int blocks, const char *kind, int tiles) {
+        if (n < cap) {
+            r3d_census_row &r = rows[n];
+            memset(&r, 0, sizeof r);
+            r.launch = launch;
+            r.blocks = blocks;
+            r.tiles = tiles;
+            strncpy(r.kernel, kernel, sizeof r.kernel - 1);
+            strncpy(r.tile_kind, kind, sizeof r.tile_kind - 1);
+        }
+        ++n;
+    }
+    void launch_of(const char *kernel, int blocks, const std::map<std::string, int> &hist) {
+        if (hist.empty()) row(kernel, blocks, "", 0);
+        for (const auto &kv : hist) row(kernel, blocks, kv.first.c_str(), kv.second);
+        ++launch;
+    }
+};
+
+// the host part of a schedule (what schedule_get builds before it touches the device), kept for the last (pair, plan, B, nwg)
+// asked: a sweep asks every call shape of a size in a row.  (Handles are keyed by their never-reused ids; a development switch
+// that changes the tile lists - R3D_NO_GEMV, R3D_NO_NB, ... - is set before a pair's first census, like before its first forward.)
+struct CensusSched {
+    uint64_t ida = 0, idb = 0;
+    const Plan *pl = nullptr;
+    int64_t B = -1;
+    int nwg = 0;
+    int spill_row0 = -1;
+    std::vector<int4> tiles;
+    std::vector<int> wgoff;
+    std::vector<StageSchedule> stages;
+    const std::vector<std::vector<int>> *levels = nullptr;
+    Schedule::Fwd fw;
+    std::vector<int> ft, fo;
+};
+thread_local CensusSched g_census;
+
+}  // namespace
 
 extern "C" {
 
@@ -240,6 +351,133 @@ int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int n
         for (int u = 0; u < (int)((batch * pl->probs[i].rows_per_window + 31) / 32); ++u)
             if (cnt[fw.cnt_base[i] + u] != (unsigned)gcols[i]) return -24;
     return 0;
+}
+
+// Test hook: census of kernel specialisations (include/ray3d_hip.h).  Plan, tile lists, kernel choice and call form are the
+// driver's own code (plan_kind, schedule_build_host, schedule_build_fwd, forward_kernel_of_lists, forward_variant_table,
+// call_shares_first_layers, call_is_single, fill_prob, the *_kernel_name functions); only census_tile_kind restates device code.
+int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg, int32_t uv, int64_t cam_stride, int64_t window_stride,
+                             int32_t staged, int32_t captured, r3d_census_row *rows, int32_t cap) {
+    const ModelPair mp = model_pair(pos, trj);
+    Model *a = mp.a, *b = mp.b;
+    if (!a || batch <= 0 || nwg <= 0 || window_stride <= 0 || (!rows && cap > 0)) return -1;
+    if (b && !same_input_shape(a, b)) return -1;
+    if (uv && a->cfg.in_features != 3) return -1;              // (check_call: R3D_INPUT_UV needs three input features)
+    Plan *pl = plan_get(a, b, plan_kind(batch));
+    if (!pl) return -2;
+    CensusSched &cs = g_census;
+    if (cs.ida != a->id || cs.idb != (b ? b->id : 0) || cs.pl != pl || cs.B != batch || cs.nwg != nwg) {
+        cs = CensusSched();
+        cs.ida = a->id;
+        cs.idb = b ? b->id : 0;
+        cs.pl = pl;
+        cs.B = batch;
+        cs.nwg = nwg;
+        cs.levels = schedule_build_host(pl, batch, nwg, cs.spill_row0, cs.tiles, cs.wgoff, cs.stages);
+        if (forward_single_launch() && schedule_build_fwd(pl, batch, nwg, *cs.levels, cs.stages, cs.tiles, cs.wgoff, cs.fw, cs.ft, cs.fo)) {
+            bool narrow = false, b3_tiles = false;
+            cs.fw.kernel = forward_kernel_of_lists(pl, batch, cs.ft, narrow, b3_tiles);
+            if (narrow && b3_tiles) cs.fw = Schedule::Fwd();   // (no specialisation carries both: launch by launch, as schedule_get decides)
+        } else {
+            cs.fw = Schedule::Fwd();
+        }
+    }
+    const std::vector<CensusKernel> kernels = census_kernels();
+    const Schedule::Fwd &fw = cs.fw;
+    const long long frames = (batch - 1) * window_stride + a->RF;
+    const bool shared = call_shares_first_layers(pl, a, batch, uv != 0, window_stride, cam_stride, frames, pl->frame_buf >= 0);
+    const int variant = (uv ? 1 : 0) + (shared ? 2 : 0);
+    std::vector<GemmProb> rel;
+    std::vector<unsigned char> tags;
+    const bool has_table = fw.grid > 0 && forward_variant_table(pl, batch, variant, fw.nprob, rel, tags);
+    const bool single = !staged && call_is_single(a, b, fw.grid, has_table, fw.kernel, shared);
+    CensusOut out{rows, cap};
+    // ---- a clip call's launch of per-frame first layers (frame_stage)
+    if (shared) {
+        std::vector<int4> ft;
+        std::vector<int> fo;
+        StageSchedule fs{};
+        schedule_frame_stage(pl, batch, nwg, ft, fo, fs);
+        const char *name = stage_kernel_name(STAGE_BIG, uv != 0, false);
+        const CensusKernel *k = census_find(kernels, name);
+        if (!k) return -4;
+        std::map<std::string, int> hist;
+        for (const int4 &t : ft) {
+            const Plan::FrameProb &f = pl->frame_probs[t.x & 0xff];
+            ++hist[census_tile_kind(*k, CensusProb{false, true, false, false, pl->m[f.model]->layers[f.layer].Kpad}, t.x >> 8, t.w)];
+        }
+        out.launch_of(name, fs.nwg, hist);
+    }
+    if (single) {
+        // ---- r3d_bind_f32 (a captured call binds inside its graph; an eager one unless the table is bound to its buffers
+        // already - reported here as the first call on them), then the persistent launch (launch_tiles)
+        (void)captured;
+        out.launch_of(bind_kernel_name(), 1, {});
+        const int fwd_kernel = shared ? FWD_KERNEL_CLIP : fw.kernel;
+        const char *name = forward_kernel_name(fwd_kernel, uv && fw.uses_gather);
+        const CensusKernel *k = census_find(kernels, name);
+        if (!k) return -4;
+        std::map<std::string, int> hist;
+        const int TI = FWD_TILE_INT4 * 4;
+        for (int t = 0; t < fw.ntiles; ++t) {
+            const int *d = &cs.ft[(size_t)t * TI];
+            const int id = d[0] & 0xff;
+            ++hist[census_tile_kind(*k, census_prob(&tags[(size_t)id * BIND_NPTR], rel[id].K), d[0] >> 8, d[3])];
+        }
+        out.launch_of(name, fw.grid, hist);
+    } else {
+        // ---- one persistent GEMM launch per level (staged_level)
+        CallShape shape;
+        shape.uv = uv != 0;
+        shape.shared = shared;
+        shape.window_stride = window_stride;
+        shape.cam_stride = cam_stride;
+        shape.frames = frames;
+        const Bases none;
+        for (size_t si = 0; si < cs.levels->size(); ++si) {
+            const auto &st = (*cs.levels)[si];
+            const StageSchedule &ss = cs.stages[si];
+            std::vector<CensusProb> P(st.size());
+            bool uv_launch = false, b3_launch = false;
+            for (size_t i = 0; i < st.size(); ++i) {
+                GemmProb g;
+                unsigned char tg[BIND_NPTR];
+                if (fill_prob(pl, pl->probs[st[i] & ~STAGE_SPILL_IN], batch, a, none, shape, g, tg) != R3D_OK) return -3;
+                P[i] = census_prob(tg, g.K);
+                uv_launch = uv_launch || tg[17] != BIND_NULL;
+                b3_launch = b3_launch || P[i].wb3;
+            }
+            const char *name = stage_kernel_name(ss.kind, uv_launch, b3_launch);
+            const CensusKernel *k = census_find(kernels, name);
+            if (!k) return -4;
+            std::map<std::string, int> hist;
+            for (int t = 0; t < ss.ntiles; ++t) {
+                const int4 &tl = cs.tiles[ss.tiles_off + t];
+                const int slot = tl.x & 0xff;
+                if (slot >= (int)st.size()) return -5;
+                ++hist[census_tile_kind(*k, P[slot], tl.x >> 8, tl.w)];
+            }
+            out.launch_of(name, ss.nwg, hist);
+        }
+    }
+    out.launch_of(decode_kernel_name(batch), 0, {});           // (decoder_tail: its record carries no grid)
+    return out.n;
+}
+
+int r3d_debug_census_domain(r3d_census_row *rows, int32_t cap) {
+    if (!rows && cap > 0) return -1;
+    CensusOut out{rows, cap};
+    for (const char *name : launch_kernel_names()) out.row(name, 0, "", 0);
+    const int codes[] = {1, 2, 4, 8, 16, NB_CODE + 4, NB_CODE + 5, NB_CODE + 6, NB_CODE + 7};
+    for (const CensusKernel &k : census_kernels()) {
+        std::set<std::string> kinds;
+        for (int f = 0; f < 16; ++f)
+            for (int K : {64, 96})
+                for (int mi = 1; mi <= GEMM_SCHED_MAX_UNITS + 1; ++mi)
+                    for (int ks : codes) kinds.insert(census_tile_kind(k, CensusProb{(f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (f & 8) != 0, K}, mi, ks));
+        for (const std::string &kind : kinds) out.row(k.name, 0, kind.c_str(), 0);
+    }
+    return out.n;
 }
 
 // Test hook: the pre-pass's per-keypoint routine (r3d_undistort.hpp) on the host.

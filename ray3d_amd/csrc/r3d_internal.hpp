@@ -507,6 +507,16 @@ size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B);
 struct FwdKeys { int cu_limit, nwg, lane_key0, nlanes; };                      // lane keys lane_key0 .. lane_key0 + nlanes - 1 (schedule_key)
 FwdKeys forward_keys(const Model *a, const Model *b);
 int forward_run(Model *a, Model *b, const r3d_input *in, int64_t B, float *out, float *out_trj, void *ws, size_t ws_bytes, void *stream);
+// what a call runs, decided where the driver and the census hook (r3d_debug_forward_census) both ask: the names of its launch records,
+// whether its first levels read the per-frame buffer, whether it is one persistent launch
+const char *stage_kernel_name(int kind, bool uv_launch, bool b3_launch);
+const char *decode_kernel_name(int64_t B);
+const char *bind_kernel_name();
+const char *undistort_kernel_name();
+std::vector<const char *> launch_kernel_names();     // every kernel name a launch record of a forward can carry
+bool call_shares_first_layers(const Plan *pl, const Model *a, int64_t B, bool uv, int64_t window_stride, int64_t cam_stride, long long frames,
+                              bool frame_tiles);
+bool call_is_single(const Model *a, const Model *b, int grid, bool has_table, int kernel, bool shared);
 
 // r3d_order.cpp: the process-wide ordering of single-launch forwards
 extern std::mutex g_fwd_launch_mu;
@@ -587,6 +597,10 @@ bool schedule_build_fwd(const Plan *pl, int64_t B, int nwg, const std::vector<st
                         const std::vector<int4> &tiles, const std::vector<int> &wgoff, Schedule::Fwd &fw, std::vector<int> &out_tiles,
                         std::vector<int> &out_wgoff);
 Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin = false, int lane = 0);   // nullptr + set_error on failure
+// the pieces of schedule_get that need no device (shared with r3d_debug_forward_census)
+void schedule_frame_stage(const Plan *pl, int64_t B, int nwg, std::vector<int4> &ft, std::vector<int> &fo, StageSchedule &ss);
+bool forward_variant_table(const Plan *pl, int64_t B, int v, int nprob, std::vector<GemmProb> &rel, std::vector<unsigned char> &tags);
+int forward_kernel_of_lists(const Plan *pl, int64_t B, const std::vector<int> &ft, bool &narrow, bool &b3_tiles);
 inline int64_t schedule_key(int64_t B, int lane) { return B | ((int64_t)lane << 48); }    // key of Plan::schedules (lane 0: handles without lanes)
 int device_cu_count();
 

@@ -782,6 +782,50 @@ const std::vector<std::vector<int>> *schedule_build_host(const Plan *pl, int64_t
     return levels;
 }
 
+// The launch of per-frame first layers a clip call runs ahead of its forward (Plan::frame_probs): gathered GEMMs over B + RF - 3 rows
+void schedule_frame_stage(const Plan *pl, int64_t B, int nwg, std::vector<int4> &ft, std::vector<int> &fo, StageSchedule &ss) {
+    const int rows = (int)(B + pl->m[0]->RF - 3);
+    std::vector<SchedProb> fp;
+    for (const auto &f : pl->frame_probs) {
+        const Layer &L = pl->m[f.model]->layers[f.layer];
+        SchedProb sp{rows, L.N, L.Kpad / BK, 1, std::max(1, std::min(3, (64 * 1024) / ((L.Kpad + 4) * 4 * 32)))};
+        sp.nk2 = 2;
+        fp.push_back(sp);
+    }
+    schedule_stage(fp, nwg, GEMM_SCHED_MAX_UNITS, ft, fo, ss, false);
+}
+
+// Relative problem table `v` of the single-launch form (v = UV input + 2 * first levels on the per-frame buffer: Schedule::Fwd::d_rel)
+// and its base tags; false when the plan has no such variant (two input features, no per-frame buffer, no UV tables)
+bool forward_variant_table(const Plan *pl, int64_t B, int v, int nprob, std::vector<GemmProb> &rel, std::vector<unsigned char> &tags) {
+    const Model *a = pl->m[0];
+    const int uv = v & 1, shared = v >> 1;
+    if (uv && a->cfg.in_features != 3) return false;
+    if (shared && pl->frame_buf < 0) return false;
+    rel.assign(nprob, GemmProb());
+    tags.assign((size_t)nprob * BIND_NPTR, 0);
+    Bases none;
+    CallShape cs;
+    cs.uv = uv != 0;
+    cs.shared = shared != 0;
+    if (shared) {                              // (a clip call: window stride one frame - r3d_forward.cpp)
+        cs.window_stride = 1;
+        cs.frames = B + a->RF - 1;
+    }
+    for (int i = 0; i < nprob; ++i)
+        if (fill_prob(pl, pl->probs[i], B, a, none, cs, rel[i], tags.data() + (size_t)i * BIND_NPTR) != R3D_OK) return false;
+    return true;
+}
+
+// Which specialisation of the persistent kernel runs the single-launch lists `ft` (r3d_kernels.hip, R3D_FORWARD_KERNEL);
+// `narrow`: GEMV / latency tiles in the lists, `b3_tiles`: the bf16x3 tile kinds - no specialisation carries both
+int forward_kernel_of_lists(const Plan *pl, int64_t B, const std::vector<int> &ft, bool &narrow, bool &b3_tiles) {
+    narrow = false;            // GEMV / latency tiles in the lists: activation banks of the library's own (poll mode)
+    for (size_t t = 0; t * FWD_TILE_INT4 * 4 < ft.size(); ++t) narrow |= tile_is_narrow(ft[t * FWD_TILE_INT4 * 4 + 3]);
+    b3_tiles = B >= b3_min_batch() && ((pl->m[0] && pl->m[0]->use_b3) || (pl->m[1] && pl->m[1]->use_b3));
+    return narrow ? FWD_KERNEL_LAT : b3_tiles ? FWD_KERNEL_B3 : FWD_KERNEL_F32;
+}
+
 Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin, int lane) {
     // (R3D_OPT_LANES: every lane has its own schedule of a batch size - its own tile lists for its share of the CUs and, above all,
     //  its own control region: forwards of different lanes run at the same time)
@@ -835,17 +879,9 @@ Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin, int lane) {
     }
     // ---- the per-frame first layers of a clip call (Plan::frame_probs): one launch of gathered GEMMs over B + RF - 3 rows
     if (pl->frame_buf >= 0) {
-        const int rows = (int)(B + pl->m[0]->RF - 3);
-        std::vector<SchedProb> fp;
-        for (const auto &f : pl->frame_probs) {
-            const Layer &L = pl->m[f.model]->layers[f.layer];
-            SchedProb sp{rows, L.N, L.Kpad / BK, 1, std::max(1, std::min(3, (64 * 1024) / ((L.Kpad + 4) * 4 * 32)))};
-            sp.nk2 = 2;
-            fp.push_back(sp);
-        }
         std::vector<int4> ft;
         std::vector<int> fo;
-        schedule_stage(fp, nwg, GEMM_SCHED_MAX_UNITS, ft, fo, s->frame_stage, false);
+        schedule_frame_stage(pl, B, nwg, ft, fo, s->frame_stage);
         if ((e = hipMalloc((void **)&s->d_frame_tiles, std::max<size_t>(ft.size(), 1) * sizeof(int4))) != hipSuccess ||
             (e = hipMalloc((void **)&s->d_frame_wgoff, std::max<size_t>(fo.size(), 1) * sizeof(int))) != hipSuccess ||
             (e = hipMemcpy(s->d_frame_tiles, ft.data(), ft.size() * sizeof(int4), hipMemcpyHostToDevice)) != hipSuccess ||
@@ -861,29 +897,14 @@ Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin, int lane) {
         std::vector<int> ft, fo;
         Schedule::Fwd &fw = s->fwd;
         if (schedule_build_fwd(pl, B, nwg, *s->levels, s->stages, tiles, wgoff, fw, ft, fo)) {
-            const Model *a = pl->m[0];
             bool ok = (e = hipMalloc((void **)&fw.d_tiles, ft.size() * sizeof(int))) == hipSuccess &&
                       (e = hipMalloc((void **)&fw.d_wgoff, fo.size() * sizeof(int))) == hipSuccess &&
                       (e = hipMemcpy(fw.d_tiles, ft.data(), ft.size() * sizeof(int), hipMemcpyHostToDevice)) == hipSuccess &&
                       (e = hipMemcpy(fw.d_wgoff, fo.data(), fo.size() * sizeof(int), hipMemcpyHostToDevice)) == hipSuccess;
             for (int v = 0; ok && v < 4; ++v) {           // v = UV input + 2 * first levels on the per-frame buffer
-                const int uv = v & 1, shared = v >> 1;
-                if (uv && a->cfg.in_features != 3) continue;
-                if (shared && pl->frame_buf < 0) break;
-                std::vector<GemmProb> rel(fw.nprob);
-                std::vector<unsigned char> tags((size_t)fw.nprob * BIND_NPTR);
-                Bases none;
-                CallShape cs;
-                cs.uv = uv != 0;
-                cs.shared = shared != 0;
-                if (shared) {                              // (a clip call: window stride one frame - r3d_forward.cpp)
-                    cs.window_stride = 1;
-                    cs.frames = B + a->RF - 1;
-                }
-                bool filled = true;
-                for (int i = 0; i < fw.nprob && filled; ++i)
-                    filled = fill_prob(pl, pl->probs[i], B, a, none, cs, rel[i], tags.data() + (size_t)i * BIND_NPTR) == R3D_OK;
-                if (!filled) { if (v) continue; ok = false; break; }
+                std::vector<GemmProb> rel;
+                std::vector<unsigned char> tags;
+                if (!forward_variant_table(pl, B, v, fw.nprob, rel, tags)) { if (v) continue; ok = false; break; }
                 ok = (e = hipMalloc((void **)&fw.d_rel[v], rel.size() * sizeof(GemmProb))) == hipSuccess &&
                      (e = hipMalloc((void **)&fw.d_tags[v], tags.size())) == hipSuccess &&
                      (e = hipMemcpy(fw.d_rel[v], rel.data(), rel.size() * sizeof(GemmProb), hipMemcpyHostToDevice)) == hipSuccess &&
@@ -895,11 +916,8 @@ Schedule *schedule_get(Plan *pl, int64_t B, int nwg, bool pin, int lane) {
                 fw.bank_bytes = ((size_t)(fw.ncnt + 4) * sizeof(unsigned) + 255) / 256 * 256;
                 ok = (e = hipMalloc((void **)&fw.d_ctrl, 2 * fw.bank_bytes + 2 * (size_t)fw.nprob * sizeof(GemmProb))) == hipSuccess;
             }
-            bool narrow = false;       // GEMV / latency tiles in the lists: activation banks of the library's own (poll mode)
-            for (size_t t = 0; t * FWD_TILE_INT4 * 4 < ft.size(); ++t) narrow |= tile_is_narrow(ft[t * FWD_TILE_INT4 * 4 + 3]);
-            // which specialisation of the persistent kernel runs these lists (r3d_kernels.hip, R3D_FORWARD_KERNEL)
-            const bool b3_tiles = B >= b3_min_batch() && ((pl->m[0] && pl->m[0]->use_b3) || (pl->m[1] && pl->m[1]->use_b3));
-            fw.kernel = narrow ? FWD_KERNEL_LAT : b3_tiles ? FWD_KERNEL_B3 : FWD_KERNEL_F32;
+            bool narrow = false, b3_tiles = false;
+            fw.kernel = forward_kernel_of_lists(pl, B, ft, narrow, b3_tiles);
             // The single launch is only correct with ALL its workgroups resident.  Checked here against what the device
             // holds of that kernel; a CU mask (which the occupancy query does not see) or a lists-mix no specialisation
             // carries sends the size to the launch-by-launch form instead.

@@ -3069,6 +3069,7 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
         dbg = dbg_base && t - t0 < 8 ? dbg_base + (t - t0) * 8 : nullptr;
 #endif
         bool signalled = false;
+        // (the dispatch: restated on the host by census_tile_kind, r3d_hooks.cpp - a tile kind added here is added there)
         do {
         if constexpr (ENC) {
             (void)ks;

@@ -35,7 +35,7 @@ def _model_config(name):
             "j14-rf9": dict(ARCHITECTURE="3,3", NUM_KPTS=14), "j15-s2": dict(NUM_KPTS=15, STAGE=2),
             "s1-noemb": dict(STAGE=1, CAMERA_EMBDDING=False), "c64": dict(CHANNELS=64, LATENT_FEATURES_DIM=128),
             "c96": dict(CHANNELS=96, LATENT_FEATURES_DIM=128), "c512": dict(CHANNELS=512, LATENT_FEATURES_DIM=128),
-            "bf16x3": dict(BF16X3=True)}[name]
+            "bf16x3": dict(BF16X3=True), "bf16x3-rf9": dict(ARCHITECTURE="3,3", BF16X3=True)}[name]
     return ray3d_amd.default_model_config(**dict(dict(ARCHITECTURE="3,3,3"), **over))
 
 
@@ -343,6 +343,8 @@ INPUT_CASES = ([pytest.param(lambda B=B: _clip_case(B, False), id="clip-one-row-
                [pytest.param(lambda a=a, pw=pw: _uv_case(a, 37, 9 if a == "rf9" else 27, pw), id="uv-%s-%s" % (a, "cam8" if pw else "cam0"))
                 for a in ("rf9", "default") for pw in (True, False)] +
                [pytest.param(lambda: _uv_case("default", 40, 5, True), id="uv-overlapping-own-cameras")] +
+               # pixel input on a bf16x3 handle from 96 windows on: r3d_forward_uv_b3 (first_level_taps_b3 with the UV gather)
+               [pytest.param(lambda: _uv_case("bf16x3-rf9", 97, 9, True), id="uv-bf16x3")] +
                # the pre-pass modes: one ray per input frame (one camera; stride >= RF), and materialised (B, RF, J, F) windows
                [pytest.param(lambda: _dist_case(40, 1, False), id="uv-dist-per-frame-clip-one-camera"),
                 pytest.param(lambda: _dist_case(37, 27, True), id="uv-dist-per-frame-batch-own-cameras"),

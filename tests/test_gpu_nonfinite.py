@@ -188,6 +188,37 @@ def test_pair_bf16x3():
     assert lifter.precision("cuda:0") == "bf16x3"
 
 
+def test_pair_bf16x3_pixel_input():
+    """... and through r3d_forward_uv_b3 (first_level_taps_b3 with the UV gather): a bad pixel becomes a non-finite ray inside the
+    bf16x3 first level; 97 windows with a 3DHP camera row each, the oracle's camera chain + torch port."""
+    if os.environ.get("R3D_BF16X3") is not None and os.environ["R3D_BF16X3"] != "1":
+        pytest.skip("R3D_BF16X3 in the environment overrides the configuration key")
+    key, B, rf = _key(dict(DEFAULT)), 97, 27
+    lifter, _ = _lifter(key, B, BF16X3=True)
+    cams, ocams, _, _ = _dhp()
+    uv = _px("nonfinite.uvrow.b3.%d" % B, (B, rf, 17, 2), 2048.0)
+    pick = [(5 * i + i // 14) % 14 for i in range(B)]
+    rays = np.stack([ocams[c].rays_from_uv(uv[i].astype(np.float64)) for i, c in enumerate(pick)]).astype(np.float32)
+    rows_d = torch.from_numpy(np.stack([cams[c].cam_row() for c in pick])).cuda()
+    par = np.stack([cams[c].param() for c in pick]).astype(np.float32)
+    par_d = torch.from_numpy(par).cuda()
+
+    def call(u):
+        with torch.no_grad():
+            out = lifter.forward_uv(torch.from_numpy(u).cuda(), rows_d, par_d)
+        lifter.check_status()
+        return out.cpu().numpy()
+    rp, rt = _port(key, rays, par)
+    clean = call(uv)
+    assert lifter.precision("cuda:0") == "bf16x3"
+    spots = [(0, 0, 0), (nf.current_frame(rf, 3), 0, 0), (rf - 1, 16, 1)]
+    for value in BAD_PIXELS:
+        for r in range(3):
+            wins = nf.windows_to_poison(B)
+            bad = nf.poisoned_copy(uv, [(w,) + spots[(k + r) % 3] for k, w in enumerate(wins)], nf.VALUES[value])
+            nf.check_poisoned(call(bad), clean, rp + rt, wins, "uv rows bf16x3 B %d %s rotation %d" % (B, value, r))
+
+
 @pytest.mark.parametrize("B", [3, 200])
 def test_pair_captured_in_a_hip_graph(B):
     """After prepare([B]): one capture, replayed on clean input and on poisoned input behind the same pointers."""

@@ -629,6 +629,90 @@ int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t r
                     float *pred_dev, double *world_dev, int64_t total_frames,   /* either may be NULL, not both */
                     int32_t *status_dev, void *stream);
 
+/* ---- a virtual-camera sweep's model inputs and ground truth from world poses: project, encode and mirror in one call ---- */
+
+/* The input side of a synthetic camera sweep on the device - what the reference does per virtual camera on the host:
+ * data/camera_augmentation.py:626-846 projects the world-frame ground truth through each camera of a grid
+ * (CameraInfoPacket.project, lib/camera/camera.py:485-496, no distortion) and drops the cameras that put a keypoint outside the
+ * frame (check_in_frame); lib/dataset/__init__.py:96-110, 191-203 then turns the pixels into the model's input
+ * (get_cam_ray_given_uv / encode_uv_with_intrinsic / normalize_screen_coordinates) and the world poses into the frame of the
+ * ground truth (world2normalized / world2camera).  ONE launch does all of it for every (clip, camera) pair of a table of
+ * descriptors in DEVICE memory, from world_dev (total_frames, J, 3) float32 - the archive's world poses in metres, uploaded once:
+ * many descriptors (one per camera) may name the same frames.  Descriptor c writes output rows [out_first, out_first + pad_front +
+ * n_frames + pad_back) of x_dev (out_rows, J, F) float32 - what a R3D_INPUT_RAYS forward with window_stride 1 reads, F = 3 for
+ * R3D_ENCODE_RAY and 2 for the other two - and, for its n_frames unpadded frames, rows [gt_first, gt_first + n_frames) of gt_dev
+ * (gt_rows, J, 3) float32 and px_dev (gt_rows, J, 2) float64.  pad_front / pad_back are r3d_clip_input_desc's (pad_back may carry
+ * the surplus rows of a rounded-up batch size).  Descriptors may lie in the buffers in any order, with gaps; overlapping OUTPUT
+ * ranges of two valid descriptors are the caller's error (either value may win, nothing leaves the extents).
+ * ARITHMETIC per output point (row r, joint j).  The source frame is first_frame + clamp(r - pad_front, 0, n_frames - 1); its
+ * point (x, y, z) is promoted to float64.
+ *   pixel:      h_k = ((P[4k] * x + P[4k+1] * y) + P[4k+2] * z) + P[4k+3] for k = 0, 1, 2 with P = proj, every product and every
+ *               sum rounded once (no fused multiply-add: the routine the kernel and the host hook share is compiled with
+ *               floating-point contraction off, as r3d_clips_poses's world transform is); u = h0 / h2, v = h1 / h2, IEEE
+ *               divisions.  This is CameraInfoPacket.project on catesian2homogenous of the float32 pose.
+ *   x_dev:      the FLOAT64 pixel through the routine r3d_clips_encode writes with, and the camera row `cam` (16 doubles, as
+ *               R3D_INPUT_UV_DIST / R3D_INPUT_PX_*): the same float64 encoding, the same single cast to float32.  The reference's
+ *               chain (lib/dataset/__init__.py:191-203, then lib/train_val/trainer.py:298) rounds to float32 there and nowhere
+ *               before; a float32 pixel archive in between rounds once more.  Zero distortion coefficients are the synthetic
+ *               sets' case (undistort=False); non-zero coefficients are simply followed.  A padding row is computed again from
+ *               the frame it repeats and has its bits.
+ *   x_mirror_dev / mirror_perm: both NULL, or both given: r3d_clips_encode's rule - x_mirror_dev[row, j] = x_dev[row,
+ *               mirror_perm[j]] with component 0 negated (exact).  mirror_perm is a HOST array of J entries, a permutation of
+ *               0..J-1; it travels as a kernel argument.
+ *   gt_dev:     optional (NULL: none).  Written by the threads of rows pad_front <= r < pad_front + n_frames only, so every source
+ *               frame once: gt_dev[gt_first + f, j], component k, is the float32 cast of ((R[3k] * x + R[3k+1] * y) + R[3k+2] * z)
+ *               + T[k], R = rw2g, T = tw2g - the world -> normalised transform (Rw2n, Tw2n: world2normalized), or world -> camera
+ *               (Rw2c, Tw2c: world2camera) for a ground truth in the camera frame - in the rounding of r3d_clips_poses's world_dev.
+ *   px_dev:     optional (NULL: none), the same rows: (u, v) as float64.
+ *   outside_dev: optional (NULL: none), num_clips int32: outside_dev[c] has ADDED to it the number of those points (rows pad_front
+ *               <= r < pad_front + n_frames) with !(u >= 0 && u <= res_w && v >= 0 && v <= res_h), res_w / res_h slots 6 / 7 of
+ *               `cam`.  The CALLER zeroes it.  Integer adds (one atomic per wavefront with a non-zero count): their order does
+ *               not matter, the count is deterministic.  A NaN pixel counts as OUTSIDE - the reference's check_in_frame (`u < 0 or
+ *               u > w or ...`) is false for a NaN and would call it inside.
+ *   status_dev: num_clips int32 words, required: 0 for a descriptor that was followed, 1 for an invalid one.
+ * A NaN that the arithmetic produces is stored as the canonical quiet NaN (float32 0x7fc00000, float64 0x7ff8000000000000).
+ * NON-FINITE VALUES.  A NaN or Inf in a world element, a point in the camera's plane (h2 == 0: u, v = +-Inf or NaN) or behind it
+ * makes exactly the outputs that read it non-finite (or, behind the camera, a mirrored pixel); every other output keeps the bits
+ * it would have had without it.  Not an error.
+ * GRID.  max_rows is the caller's bound on any descriptor's pad_front + n_frames + pad_back and sizes the grid:
+ * (ceil(max_rows * num_joints / 256), num_clips) workgroups, one output point per thread; a workgroup past its clip's points
+ * returns at once.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A descriptor is invalid when n_frames < 1, a pad is < 0, pad_front + n_frames +
+ * pad_back > max_rows, [first_frame, first_frame + n_frames) is not inside [0, total_frames), the output rows are not inside
+ * [0, out_rows), or - in a call that writes gt_dev or px_dev - [gt_first, gt_first + n_frames) is not inside [0, gt_rows) (without
+ * the two, gt_first and gt_rows are not read).  The kernel never follows an invalid descriptor: nothing of it is read or written -
+ * outside_dev[c] stays what the caller put there - and status_dev[c] = 1.  Rows no valid descriptor covers are left untouched.
+ * Beyond the descriptors it reads world_dev within total_frames * num_joints * 3 floats and the table within num_clips
+ * descriptors, and writes x_dev / x_mirror_dev within out_rows * num_joints * F floats, gt_dev within gt_rows * num_joints * 3
+ * floats, px_dev within gt_rows * num_joints * 2 doubles and outside_dev / status_dev within num_clips words: no input can make
+ * it touch memory outside these extents.
+ * R3D_ERR_ARG (checked on the host before any HIP call): the rules of r3d_clips_encode - a null required pointer (world_dev,
+ * clips_dev, x_dev, status_dev), num_clips outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, an unknown encoding, max_rows,
+ * total_frames or out_rows < 1, max_rows * num_joints, total_frames or out_rows above R3D_ENCODE_MAX_POINTS (index arithmetic),
+ * exactly one of x_mirror_dev / mirror_perm, a mirror_perm that is not a permutation, a table pointer that is not 8-byte aligned -
+ * and, with gt_dev or px_dev given, gt_rows < 1 or above R3D_ENCODE_MAX_POINTS; a px_dev that is not 8-byte aligned.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
+ * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+typedef struct {
+    int64_t first_frame;  /* row of the clip's first frame in world_dev (many descriptors may name the same frames)        */
+    int64_t n_frames;
+    int64_t out_first;    /* first OUTPUT row in x_dev / x_mirror_dev (pad_front + n_frames + pad_back rows)                */
+    int64_t gt_first;     /* first row in gt_dev / px_dev (n_frames rows, no padding)                                      */
+    int32_t pad_front;    /* as r3d_clip_input_desc                                                                        */
+    int32_t pad_back;
+    double  proj[12];     /* P = K [R|t], row-major 3x4 (lib/camera/camera.py:231)                                         */
+    double  cam[16];      /* the camera row r3d_clips_encode reads; slots 6 / 7 = res_w / res_h                            */
+    double  rw2g[9];      /* row-major: world -> frame of the ground truth (Rw2n, or Rw2c for a camera-frame ground truth) */
+    double  tw2g[3];
+} r3d_clip_project_desc;  /* 360 bytes, 8-byte aligned; lives in DEVICE memory */
+int r3d_clips_project(const float *world_dev, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                      const r3d_clip_project_desc *clips_dev, int32_t num_clips, int64_t max_rows,
+                      float *x_dev, int64_t out_rows,
+                      float *x_mirror_dev, const int32_t *mirror_perm,   /* both NULL or both given */
+                      float *gt_dev, double *px_dev, int64_t gt_rows,    /* each optional (NULL) */
+                      int32_t *outside_dev,                              /* optional (NULL) */
+                      int32_t *status_dev, void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -711,6 +795,12 @@ int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const 
 int r3d_debug_clips_poses_host(const float *raw, const float *raw_mirror, int64_t raw_rows, int32_t num_joints,
                                const int32_t *mirror_perm, const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips,
                                int64_t max_frames, float *pred, double *world, int64_t total_frames, int32_t *status);
+/* r3d_clips_project on the host (HOST pointers throughout, no stream): the same argument checks, the same descriptor rule and the
+ * same per-point routines, descriptors in table order; `outside` is added to, as on the device. */
+int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                                 const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
+                                 float *x_mirror, const int32_t *mirror_perm, float *gt, double *px, int64_t gt_rows,
+                                 int32_t *outside, int32_t *status);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

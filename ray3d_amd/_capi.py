@@ -32,11 +32,13 @@ EXPORTS = (
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
+    "r3d_clips_project",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
-                "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host")
+                "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
+                "r3d_debug_clips_project_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -88,6 +90,18 @@ def clip_input_desc_dtype():
     import numpy as np
     return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("out_first", np.int64),
                      ("pad_front", np.int32), ("pad_back", np.int32), ("cam", np.float64, (16,))])
+
+
+def clip_project_desc_dtype():
+    """The NumPy structured dtype with r3d_clip_project_desc's layout (360 bytes): an array of it, uploaded as bytes, is the
+    table r3d_clips_project reads."""
+    import numpy as np
+    return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("out_first", np.int64), ("gt_first", np.int64),
+                     ("pad_front", np.int32), ("pad_back", np.int32), ("proj", np.float64, (12,)), ("cam", np.float64, (16,)),
+                     ("rw2g", np.float64, (9,)), ("tw2g", np.float64, (3,))])
+
+
+CLIP_PROJECT_DESC_BYTES = 360                                           # sizeof(r3d_clip_project_desc)
 
 
 class LaunchRecord(C.Structure):
@@ -179,9 +193,13 @@ def load():
                                            vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_clips_poses.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_int64,
                                     vp, vp]
+    lib.r3d_clips_project.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
+                                      C.POINTER(C.c_int32), vp, vp, C.c_int64, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_clips_project_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
+                                                     C.POINTER(C.c_int32), vp, vp, C.c_int64, vp, vp]
         lib.r3d_debug_forward_census.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                  C.POINTER(CensusRow), C.c_int32]
         lib.r3d_debug_census_domain.argtypes = [C.POINTER(CensusRow), C.c_int32]
@@ -413,6 +431,31 @@ def debug_clips_poses_host(raw_ptr: int, raw_mirror_ptr: Optional[int], raw_rows
     perm = _mirror_table("r3d_debug_clips_poses_host", mirror_perm, num_joints)
     return int(load().r3d_debug_clips_poses_host(raw_ptr, raw_mirror_ptr or None, raw_rows, num_joints, perm, table_ptr, raw_first_ptr,
                                                  num_clips, max_frames, pred_ptr or None, world_ptr or None, total_frames, status_ptr))
+
+
+def clips_project(world_ptr: int, total_frames: int, num_joints: int, encoding: int, table_ptr: int, num_clips: int, max_rows: int,
+                  x_ptr: int, out_rows: int, x_mirror_ptr: Optional[int], mirror_perm, gt_ptr: Optional[int], px_ptr: Optional[int],
+                  gt_rows: int, outside_ptr: Optional[int], status_ptr: int, stream: int):
+    """r3d_clips_project: every pointer is device memory; `table_ptr` num_clips r3d_clip_project_desc
+    (:func:`clip_project_desc_dtype`) back to back; `x_mirror_ptr` (or None) and `mirror_perm` (a host sequence of num_joints
+    ints, or None) go together; `gt_ptr` / `px_ptr` / `outside_ptr` may be None (`outside_ptr` is ADDED to: zero it first);
+    `status_ptr` num_clips int32."""
+    perm = _mirror_table("r3d_clips_project", mirror_perm, num_joints)
+    check(load().r3d_clips_project(world_ptr, total_frames, num_joints, encoding, table_ptr, num_clips, max_rows, x_ptr, out_rows,
+                                   x_mirror_ptr or None, perm, gt_ptr or None, px_ptr or None, gt_rows, outside_ptr or None,
+                                   status_ptr, stream), "r3d_clips_project")
+
+
+def debug_clips_project_host(world_ptr: int, total_frames: int, num_joints: int, encoding: int, table_ptr: int, num_clips: int,
+                             max_rows: int, x_ptr: int, out_rows: int, x_mirror_ptr: Optional[int], mirror_perm,
+                             gt_ptr: Optional[int], px_ptr: Optional[int], gt_rows: int, outside_ptr: Optional[int],
+                             status_ptr: int) -> int:
+    """r3d_debug_clips_project_host (hooks library only: use_hooks(True)): r3d_clips_project on HOST pointers; returns the
+    status code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    perm = _mirror_table("r3d_debug_clips_project_host", mirror_perm, num_joints)
+    return int(load().r3d_debug_clips_project_host(world_ptr, total_frames, num_joints, encoding, table_ptr, num_clips, max_rows,
+                                                   x_ptr, out_rows, x_mirror_ptr or None, perm, gt_ptr or None, px_ptr or None,
+                                                   gt_rows, outside_ptr or None, status_ptr))
 
 
 def _census_rows(call):

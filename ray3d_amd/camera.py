@@ -79,6 +79,12 @@ class Camera:
             row += [float(v) for v in dist] + [0.0, 0.0, 0.0]
         return np.array(row, dtype=np.float64)
 
+    def proj_row(self) -> np.ndarray:
+        """The 12 float64 numbers of the projection matrix P = K [R|t], row-major 3x4, as CameraInfoPacket builds it
+        (lib/camera/camera.py:231: K @ hstack([R, t])): ``proj`` of an r3d_clip_project_desc - world points to homogeneous
+        pixels on the device (r3d_clips_project), no distortion."""
+        return np.ascontiguousarray(self.K @ np.hstack([self.Rw2c, self.Tw2c]), dtype=np.float64).reshape(12)
+
     # -- host-side equivalents (dataset-load time in the reference, lib/dataset/__init__.py:191-203)
     def undistort_points(self, uv: np.ndarray) -> np.ndarray:
         """Pixel keypoints (..., 2) with the lens distortion removed, float64: the counterpart of

@@ -89,12 +89,11 @@ int r3d::clips_valid_check_args(const char *what, const float *pos, const float 
     return R3D_OK;
 }
 
-// the argument rules of r3d_clips_encode, shared with its host hook (`what`: the name in the message)
-int r3d::clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
-                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
-                                 const float *x_mirror, const int32_t *mirror_perm, const int32_t *status) {
-    static_assert(sizeof(r3d_clip_input_desc) == 160, "r3d_clip_input_desc is documented as 160 bytes");
-    if (!px || !clips || !x || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+// the argument rules r3d_clips_encode and r3d_clips_project share: `src` the source buffer of total_frames rows, `clips` the table
+static int clips_input_check(const char *what, const void *src, int64_t total_frames, int32_t J, int32_t encoding, const void *clips,
+                             int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows, const float *x_mirror,
+                             const int32_t *mirror_perm, const int32_t *status) {
+    if (!src || !clips || !x || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
     if (const int rc = clips_range_check(what, num_clips, J)) return rc;
     if (encoding != R3D_ENCODE_RAY && encoding != R3D_ENCODE_INTRINSIC && encoding != R3D_ENCODE_SCREEN) {
         set_error("%s: unknown encoding %d", what, encoding);
@@ -115,6 +114,32 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
     }
     if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
     if (reinterpret_cast<uintptr_t>(clips) % 8) { set_error("%s: the clip table must be 8-byte aligned", what); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_clips_encode, shared with its host hook (`what`: the name in the message)
+int r3d::clips_encode_check_args(const char *what, const float *px, int64_t total_frames, int32_t J, int32_t encoding,
+                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
+                                 const float *x_mirror, const int32_t *mirror_perm, const int32_t *status) {
+    static_assert(sizeof(r3d_clip_input_desc) == 160, "r3d_clip_input_desc is documented as 160 bytes");
+    return clips_input_check(what, px, total_frames, J, encoding, clips, num_clips, max_rows, x, out_rows, x_mirror, mirror_perm, status);
+}
+
+// the argument rules of r3d_clips_project, shared with its host hook: r3d_clips_encode's on the source, the table and the inputs it
+// writes; then its own - the extent of gt_dev / px_dev when either is given, and the alignment of the float64 pixels
+int r3d::clips_project_check_args(const char *what, const float *world, int64_t total_frames, int32_t J, int32_t encoding,
+                                  const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
+                                  const float *x_mirror, const int32_t *mirror_perm, const float *gt, const double *px, int64_t gt_rows,
+                                  const int32_t *status) {
+    static_assert(sizeof(r3d_clip_project_desc) == 360, "r3d_clip_project_desc is documented as 360 bytes");
+    if (const int rc = clips_input_check(what, world, total_frames, J, encoding, clips, num_clips, max_rows, x, out_rows, x_mirror,
+                                         mirror_perm, status))
+        return rc;
+    if ((gt || px) && (gt_rows < 1 || gt_rows > R3D_ENCODE_MAX_POINTS)) {
+        set_error("%s: gt_rows must be in 1..%d when gt_dev or px_dev is given (got %lld)", what, R3D_ENCODE_MAX_POINTS, (long long)gt_rows);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(px) % 8) { set_error("%s: px_dev must be 8-byte aligned", what); return R3D_ERR_ARG; }
     return R3D_OK;
 }
 
@@ -396,6 +421,38 @@ int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t r
     const hipError_t err = r3d::launch_clips_poses(a, num_clips, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_clips_poses: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_clips_project(const float *world_dev, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                      const r3d_clip_project_desc *clips_dev, int32_t num_clips, int64_t max_rows, float *x_dev, int64_t out_rows,
+                      float *x_mirror_dev, const int32_t *mirror_perm, float *gt_dev, double *px_dev, int64_t gt_rows,
+                      int32_t *outside_dev, int32_t *status_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    const int rc = clips_project_check_args("r3d_clips_project", world_dev, total_frames, num_joints, encoding, clips_dev, num_clips,
+                                            max_rows, x_dev, out_rows, x_mirror_dev, mirror_perm, gt_dev, px_dev, gt_rows, status_dev);
+    if (rc != R3D_OK) return rc;
+    r3d::ClipsProjectArgs a = {};
+    a.table = clips_dev;
+    a.world = world_dev;
+    a.x = x_dev;
+    a.x_mirror = x_mirror_dev;
+    a.gt = gt_dev;
+    a.px = px_dev;
+    a.outside = outside_dev;
+    a.status = status_dev;
+    a.total_frames = total_frames;
+    a.out_rows = out_rows;
+    a.max_rows = max_rows;
+    a.gt_rows = gt_rows;
+    if (mirror_perm) r3d::mirror_pack_inverse(mirror_perm, num_joints, a.mirror_inv);
+    a.J = num_joints;
+    a.encoding = encoding;
+    const hipError_t err = r3d::launch_clips_project(a, num_clips, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_clips_project: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

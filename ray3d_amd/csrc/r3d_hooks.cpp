@@ -8,6 +8,7 @@
 
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
+#include "r3d_project.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
 
@@ -623,6 +624,56 @@ int r3d_debug_clips_poses_host(const float *raw, const float *raw_mirror, int64_
                 const long long dst = 3 * ((first + f) * J + j);
                 if (pred) memcpy(pred + dst, p, sizeof(p));
                 if (world) pose_world(clips[c].rn2w, clips[c].tn2w, p, world + dst);
+            }
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_clips_project on the host - its argument rules (clips_project_check_args), its descriptor rule (clip_project_valid)
+// and the per-point routines of r3d_project.hpp / r3d_undistort.hpp / r3d_poses.hpp, descriptor by descriptor in table order.
+int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32_t num_joints, int32_t encoding,
+                                 const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
+                                 float *x_mirror, const int32_t *mirror_perm, float *gt, double *px, int64_t gt_rows, int32_t *outside,
+                                 int32_t *status) {
+    const int rc = clips_project_check_args("r3d_debug_clips_project_host", world, total_frames, num_joints, encoding, clips, num_clips,
+                                            max_rows, x, out_rows, x_mirror, mirror_perm, gt, px, gt_rows, status);
+    if (rc != R3D_OK) return rc;
+    unsigned long long inv[2] = {0ull, 0ull};
+    if (mirror_perm) mirror_pack_inverse(mirror_perm, num_joints, inv);
+    const int J = num_joints, F = enc_floats(encoding);
+    for (int32_t c = 0; c < num_clips; ++c) {
+        const r3d_clip_project_desc &d = clips[c];
+        const bool ok = clip_project_valid(d.first_frame, d.n_frames, d.out_first, d.pad_front, d.pad_back, d.gt_first, total_frames, out_rows,
+                                           max_rows, gt_rows, gt != nullptr || px != nullptr);
+        status[c] = ok ? 0 : 1;
+        if (!ok) continue;
+        const long long rows = d.pad_front + d.n_frames + d.pad_back;
+        for (long long r = 0; r < rows; ++r)
+            for (int j = 0; j < J; ++j) {
+                const float *p = world + 3 * ((d.first_frame + clip_input_source(r, d.pad_front, d.n_frames)) * J + j);
+                const long long row0 = (d.out_first + r) * J;
+                double u, v;
+                project_pixel(d.proj, p, u, v);
+                const EncodedPoint pt = encode_point_f32(d.cam, encoding, u, v);
+                const float e[3] = {pt.x, pt.y, pt.z};
+                for (int k = 0; k < F; ++k) x[F * (row0 + j) + k] = e[k];
+                if (x_mirror) {
+                    float *m = x_mirror + F * (row0 + mirror_dest(inv[0], inv[1], j));
+                    for (int k = 0; k < F; ++k) m[k] = k == 0 ? -e[k] : e[k];
+                }
+                const long long f = r - d.pad_front;
+                if (f < 0 || f >= d.n_frames) continue;          // a padding row: its frame is written by its own row
+                const long long at = (d.gt_first + f) * J + j;
+                if (gt) {
+                    double w[3];
+                    pose_world(d.rw2g, d.tw2g, p, w);
+                    for (int k = 0; k < 3; ++k) gt[3 * at + k] = encoded_f32(w[k]);
+                }
+                if (px) {
+                    px[2 * at] = pose_f64(u);
+                    px[2 * at + 1] = pose_f64(v);
+                }
+                if (outside && pixel_outside(u, v, d.cam[UNDIST_ROW_RES_W], d.cam[UNDIST_ROW_RES_H])) ++outside[c];
             }
     }
     return R3D_OK;

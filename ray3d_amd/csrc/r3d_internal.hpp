@@ -170,6 +170,23 @@ struct ClipsPosesArgs {
     int J;
 };
 
+// r3d_clips_project: the fourth argument set of r3d_undistort_rays_f64 (table == nullptr: not that mode).  blockIdx.y names a
+// (clip, camera) descriptor of the device-side table; one output point (row, joint) per thread (r3d_project.hpp).
+struct ClipsProjectArgs {
+    const r3d_clip_project_desc *table; // num_clips (= gridDim.y) descriptors in device memory
+    const float *world;                 // (total_frames, J, 3) world poses
+    float *x;                           // (out_rows, J, F) encoded inputs
+    float *x_mirror;                    // the flip pass's inputs, or nullptr
+    float *gt;                          // (gt_rows, J, 3) ground truth in the descriptor's frame, or nullptr
+    double *px;                         // (gt_rows, J, 2) float64 pixels, or nullptr
+    int32_t *outside;                   // num_clips words, added to: points outside the frame; or nullptr
+    int32_t *status;                    // num_clips words: 0 followed, 1 invalid descriptor
+    long long total_frames, out_rows, max_rows, gt_rows;
+    unsigned long long mirror_inv[2];   // mirror_pack_inverse (r3d_undistort.hpp)
+    int J;
+    int encoding;                       // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN
+};
+
 constexpr int MAX_DEC = 6;     // 5 body-part decoders + the trajectory decoder
 // Fused decoder tail: the last Linear (1024 -> 3*n_g) of every Integration block, the joint
 // reassembly (rie.py:415-432) and the trajectory add (trainer.py:353) in one pass.
@@ -545,6 +562,13 @@ int clips_poses_check_args(const char *what, const float *raw, const float *raw_
                            const int32_t *mirror_perm, const r3d_clip_desc *clips, const int64_t *raw_first, int32_t num_clips,
                            int64_t max_frames, const float *pred, const double *world, int64_t total_frames, const int32_t *status);
 
+// the argument rules of r3d_clips_project, shared with its host hook (r3d_api.cpp): those of r3d_clips_encode and those of its own
+// outputs
+int clips_project_check_args(const char *what, const float *world, int64_t total_frames, int32_t J, int32_t encoding,
+                             const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, const float *x, int64_t out_rows,
+                             const float *x_mirror, const int32_t *mirror_perm, const float *gt, const double *px, int64_t gt_rows,
+                             const int32_t *status);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -625,6 +649,7 @@ hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip): every encoding
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // the same kernel, one grid row per clip
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_poses
+hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_project
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

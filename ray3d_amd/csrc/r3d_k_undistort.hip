@@ -23,8 +23,18 @@
 // output point (frame, joint) through pose_finish / pose_world of r3d_poses.hpp - the routines the host hook runs.  It is the
 // elementwise end of a clip pass as r3d_clips_encode is its elementwise start: 12 or 24 bytes read and 12 and / or 24 written per
 // thread, consecutive threads at consecutive addresses (the mirrored read is a permutation inside the row's J * 12 bytes).
+//
+// r3d_clips_project (a camera sweep's model inputs and ground truth from world poses, include/ray3d_hip.h) is the fourth argument set,
+// ClipsProjectArgs: blockIdx.y names a (clip, camera) descriptor of the r3d_clip_project_desc table, the workgroup reads it by scalar
+// loads - projection matrix, camera row, ground-truth transform - and decides on it before anything else, and each thread projects
+// one output point (row, joint) from the clamped source frame through project_pixel of r3d_project.hpp, encodes the float64 pixel
+// through encode_point_f32 - the routine the other two input paths write with - and, in the unpadded rows, writes the ground truth
+// (pose_world), the pixel and its in-frame verdict: one integer atomicAdd per wavefront that saw a point outside.  12 bytes read and up
+// to 12 + 12 + 12 + 16 written per thread, consecutive threads at consecutive addresses (the mirrored write is a permutation inside
+// the row's J * 12 bytes).
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
+#include "r3d_project.hpp"
 #include "r3d_undistort.hpp"
 
 namespace r3d {
@@ -59,7 +69,67 @@ __device__ __forceinline__ void clips_poses_body(const ClipsPosesArgs &q) {
     }
 }
 
-extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q) {
+__device__ __forceinline__ void clips_project_body(const ClipsProjectArgs &g) {
+    const r3d_clip_project_desc *d = g.table + blockIdx.y;
+    const long long first = d->first_frame, n = d->n_frames, out_first = d->out_first, gt_first = d->gt_first;
+    const int pad_front = d->pad_front, pad_back = d->pad_back;
+    const bool ok = clip_project_valid(first, n, out_first, pad_front, pad_back, gt_first, g.total_frames, g.out_rows, g.max_rows, g.gt_rows,
+                                       g.gt != nullptr || g.px != nullptr);
+    if (blockIdx.x == 0 && threadIdx.x == 0) g.status[blockIdx.y] = ok ? 0 : 1;
+    if (!ok) return;                         // an invalid descriptor is not followed: nothing of it is read or written
+    // (max_rows * J fits in 31 bits - checked on the host - and so do the clip's points and this launch's indices)
+    const int npts = (int)(pad_front + n + pad_back) * g.J;
+    if ((int)(blockIdx.x * blockDim.x) >= npts) return;      // uniform: the workgroups past the clip's own count
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    bool outside = false;                    // (no thread leaves before the wavefront's count below)
+    if (pt < npts) {
+        const int r = pt / g.J, j = pt - r * g.J;
+        const float *src = g.world + 3 * ((first + clip_input_source(r, pad_front, n)) * g.J + j);
+        const float p[3] = {src[0], src[1], src[2]};
+        double u, v;
+        project_pixel(d->proj, p, u, v);
+        const long long row0 = (out_first + r) * g.J;
+        const int F = enc_floats(g.encoding);
+        const EncodedPoint e = encode_point_f32(d->cam, g.encoding, u, v);
+        float *o = g.x + F * (row0 + j);
+        o[0] = e.x;
+        o[1] = e.y;
+        if (F == 3) o[2] = e.z;
+        if (g.x_mirror) {                    // r3d_clips_encode's rule: x -> -x (exact), left <-> right
+            float *m = g.x_mirror + F * (row0 + mirror_dest(g.mirror_inv[0], g.mirror_inv[1], j));
+            m[0] = -e.x;
+            m[1] = e.y;
+            if (F == 3) m[2] = e.z;
+        }
+        const long long f = (long long)r - pad_front;
+        if (f >= 0 && f < n) {               // the unpadded rows: every source frame once
+            const long long at = (gt_first + f) * g.J + j;
+            if (g.gt) {
+                double w[3];
+                pose_world(d->rw2g, d->tw2g, p, w);
+                g.gt[3 * at] = encoded_f32(w[0]);
+                g.gt[3 * at + 1] = encoded_f32(w[1]);
+                g.gt[3 * at + 2] = encoded_f32(w[2]);
+            }
+            if (g.px) {
+                g.px[2 * at] = pose_f64(u);
+                g.px[2 * at + 1] = pose_f64(v);
+            }
+            outside = pixel_outside(u, v, d->cam[UNDIST_ROW_RES_W], d->cam[UNDIST_ROW_RES_H]);
+        }
+    }
+    if (g.outside) {                         // uniform.  One integer add per wavefront that saw a point outside the frame
+        const unsigned long long seen = __ballot(outside);
+        if (seen && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(g.outside + blockIdx.y, (int)__popcll(seen));
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
+                                                                         const ClipsProjectArgs g) {
+    if (g.table) {                           // uniform: r3d_clips_project - descriptor blockIdx.y of the table
+        clips_project_body(g);
+        return;
+    }
     if (q.table) {                           // uniform: r3d_clips_poses - clip blockIdx.y of the table
         clips_poses_body(q);
         return;
@@ -113,21 +183,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{});
+    return hipGetLastError();
+}
+
+// r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
+hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
+    const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args);
     return hipGetLastError();
 }
 

@@ -559,6 +559,7 @@ class _ShardInputs:
     def __init__(self, mine: Sequence[Clip], rf: int, dev, causal: bool, encode: Optional[str], lifter, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None):
         self.mine, self.dev, self.flip, self.encode = mine, dev, flip, encode
+        self.lengths = [int(c.rays.shape[0]) for c in mine]
         self.pad, self.shift = (rf - 1) // 2, ((rf - 1) // 2 if causal else 0)
         self.mirror = mirror if mirror is not None else (lambda x: mirror_input(x, kps_left, kps_right))
         if encode is None:
@@ -773,31 +774,34 @@ def shard_poses_hip(raw_all: torch.Tensor, table_dev: torch.Tensor, raw_first_de
     return pred_all, world_all, status
 
 
-def _lift_finished(lift_clip: Callable, lifter, inputs: _ShardInputs, mirror_joints: Optional[tuple], table_dev: torch.Tensor,
-                   total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool):
-    """The raw destination of the forwards - ``evaluate_clips_batched(finish=True)`` and :func:`predict_clips_batched`: every clip of
-    `inputs` lifted with ``raw_out=`` into its rows of ONE raw buffer (with a flip pass - `mirror_joints` (left, right) of the
-    OUTPUT, else None - the mirrored input into a second one), dealt to the lanes and joined once (:func:`_deal`), then ONE
-    :func:`shard_poses_hip` call over `table_dev` (:func:`clip_table` of the shard) whose status is read: a refused descriptor
-    raises.  -> (pred_all, world_all or None)."""
-    mine, dev, flip = inputs.mine, inputs.dev, mirror_joints is not None
+def _lift_finished(lift_clip: Callable, lifter, inputs, mirror_joints: Optional[tuple], table_dev: torch.Tensor,
+                   total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool, raw_first_dev: Optional[torch.Tensor] = None):
+    """The raw destination of the forwards - ``evaluate_clips_batched(finish=True)``, :func:`predict_clips_batched` and
+    :func:`evaluate_camera_sweep`: every clip of `inputs` (:class:`_ShardInputs` / :class:`_SliceInputs`) lifted with ``raw_out=``
+    into its rows of ONE raw buffer (with a flip pass - `mirror_joints` (left, right) of the OUTPUT, else None - the mirrored
+    input into a second one), dealt to the lanes and joined once (:func:`_deal`), then ONE :func:`shard_poses_hip` call over
+    `table_dev` (:func:`clip_table` of the shard) whose status is read: a refused descriptor raises.  `raw_first_dev`: the
+    :func:`clip_raw_table` of ``inputs.lengths`` already on the device (a caller that uploads the tables of many passes at once).
+    -> (pred_all, world_all or None)."""
+    lengths, dev, flip = inputs.lengths, inputs.dev, mirror_joints is not None
     J = lifter.pos.num_joints_in
     sizes_of = lifter.clip_batch_sizes
-    raw_first, raw_rows = clip_raw_table([c.rays.shape[0] for c in mine], sizes_of)
+    raw_first, raw_rows = clip_raw_table(lengths, sizes_of)
     raw_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev)
     raw_m_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev) if flip else None
-    raw_first_dev = torch.tensor(raw_first, dtype=torch.int64).to(dev)
+    if raw_first_dev is None:
+        raw_first_dev = torch.tensor(raw_first, dtype=torch.int64).to(dev)
 
     def lift(k):
-        rows = slice(raw_first[k], raw_first[k] + sum(sizes_of(mine[k].rays.shape[0])))
+        rows = slice(raw_first[k], raw_first[k] + sum(sizes_of(lengths[k])))
         x, xm, prow, kw = inputs(k)
         lift_clip(x, prow, raw_out=raw_all[rows], **kw)
         if flip:
             lift_clip(xm, prow, raw_out=raw_m_all[rows], **kw)
 
-    _deal(lifter, len(mine), lift)
+    _deal(lifter, len(lengths), lift)
     perm = mirror_permutation(J, *mirror_joints) if flip else None
-    pred_all, world_all, status = shard_poses_hip(raw_all, table_dev, raw_first_dev, len(mine), total, longest, raw_m_all, perm,
+    pred_all, world_all, status = shard_poses_hip(raw_all, table_dev, raw_first_dev, len(lengths), total, longest, raw_m_all, perm,
                                                   pred=True, world=world, pred_all=pred_all)
     _raise_if_refused(status, "r3d_clips_poses")
     return pred_all, world_all
@@ -898,6 +902,242 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         shard_metrics_hip(pred_all, gt_all, table_dev, len(mine), total, longest, local, dlocal)
     return _report(_gather(local, shards, group, PARTIAL_COLS), _gather(dlocal, shards, group, DETAIL_COLS) if detail else None,
                    actions, clips, include_root)
+
+
+# ------------------------------------------------------------------------------------ a virtual-camera sweep from world poses
+
+SWEEP_COLS = PARTIAL_COLS + 2   # a partial row, then the camera's index in the sweep and the clip's keypoints outside its frame
+
+
+@dataclass
+class WorldClip:
+    world: np.ndarray         # (N, J, 3) float32 poses in WORLD coordinates, metres (the 3D archive's)
+    action: str = ""
+    clip_id: int = 0
+
+
+def _ground_truth_transform(camera: Camera, frame: str):
+    """((R, T) world -> the frame of the ground truth, (R, T) back to the world) of `camera`: the normalised frame, or the
+    camera frame of the 2-feature baselines (trainer.py:361-362)."""
+    if frame == "normalized":
+        return (camera.Rw2n, camera.Tw2n), (camera.Rn2w, camera.Tn2w)
+    if frame == "camera":
+        return (camera.Rw2c, camera.Tw2c), (camera.Rc2w, camera.Tc2w)
+    raise ValueError("frame must be 'normalized' or 'camera' (got %r)" % (frame,))
+
+
+def clip_project_table(world_clips: Sequence[WorldClip], pairs: Sequence[tuple], cameras: Sequence[Camera], rf: int,
+                       causal: bool = False, surplus: Optional[Callable[[int], int]] = None, frame: str = "normalized"):
+    """(table, out_first, out_rows, max_rows, gt_first, gt_rows) for the (clip index, camera index) `pairs` of a camera sweep:
+    `table` a NumPy structured array of r3d_clip_project_desc rows (``_capi.clip_project_desc_dtype()``), one per pair.  The
+    SOURCE buffer holds `world_clips` back to back in the given order, each once: every camera's descriptors name the same
+    frames.  Pair k's padded, encoded input is rows [out_first[k], out_first[k] + pad_front + N + pad_back) of an output buffer
+    of `out_rows` rows and its ground truth rows [gt_first[k], gt_first[k] + N) of a buffer of `gt_rows` rows, both back to back
+    in the order of `pairs`; padding and `surplus` as in :func:`clip_input_table`.  Per pair the camera's ``proj_row()``,
+    ``cam_row(distortion=True)`` (the frame size in slots 6 / 7: the cameras need res_w / res_h) and the world -> `frame`
+    transform ("normalized": Rw2n / Tw2n, "camera": Rw2c / Tw2c).  Uploaded once and handed to :func:`shard_project_hip`."""
+    from . import _capi
+    pad = (rf - 1) // 2
+    shift = pad if causal else 0
+    src_first = np.concatenate([[0], np.cumsum([int(np.asarray(c.world).shape[0]) for c in world_clips])]).astype(np.int64)
+    table = np.zeros(len(pairs), dtype=_capi.clip_project_desc_dtype())
+    out_first, gt_first, at, gat, longest = [], [], 0, 0, 0
+    for k, (ci, cam_i) in enumerate(pairs):
+        cam = cameras[cam_i]
+        if cam.res_w is None or cam.res_h is None:
+            raise ValueError("camera %r has no res_w / res_h: the in-frame count and the screen encoding need the frame size" % (cam.name,))
+        n = int(np.asarray(world_clips[ci].world).shape[0])
+        extra = int(surplus(n)) if surplus is not None else 0
+        if extra < 0:
+            raise ValueError("surplus(%d) is negative" % n)
+        (R, T), _ = _ground_truth_transform(cam, frame)
+        d = table[k]
+        d["first_frame"], d["n_frames"], d["out_first"], d["gt_first"] = src_first[ci], n, at, gat
+        d["pad_front"], d["pad_back"] = pad + shift, pad - shift + extra
+        d["proj"], d["cam"] = cam.proj_row(), cam.cam_row(distortion=True)
+        d["rw2g"], d["tw2g"] = np.asarray(R, dtype=np.float64).reshape(9), np.asarray(T, dtype=np.float64).reshape(3)
+        out_first.append(at)
+        gt_first.append(gat)
+        rows = 2 * pad + n + extra
+        at += rows
+        gat += n
+        longest = max(longest, rows)
+    return table, out_first, at, longest, gt_first, gat
+
+
+def shard_project_hip(world_all: torch.Tensor, table_dev: torch.Tensor, num_clips: int, out_rows: int, max_rows: int, gt_rows: int,
+                      encoding: str = "ray", mirror_perm: Optional[Sequence[int]] = None, x_all: Optional[torch.Tensor] = None,
+                      x_mirror_all: Optional[torch.Tensor] = None, gt_all: Optional[torch.Tensor] = None,
+                      px_all: Optional[torch.Tensor] = None, outside: Optional[torch.Tensor] = None,
+                      status: Optional[torch.Tensor] = None, gt: bool = True, px: bool = False, count: bool = True):
+    """ONE r3d_clips_project call on the current stream for every (clip, camera) pair of a pass: `world_all` (total_frames, J, 3)
+    float32 world poses, `table_dev` the uploaded bytes of :func:`clip_project_table` (or a slice of them: a pass's descriptors),
+    `encoding` "ray" | "intrinsic" | "screen"; with `mirror_perm` (:func:`mirror_permutation`) the same launch writes the flip
+    pass's inputs as well.  Returns (x_all (out_rows, J, F) float32, x_mirror_all or None, gt_all (gt_rows, J, 3) float32 or None,
+    px_all (gt_rows, J, 2) float64 or None, outside (num_clips,) int32 or None: the pair's keypoints outside its camera's frame,
+    status (num_clips,) int32: 0 = followed, 1 = invalid descriptor) - `gt` / `px` / `count` say which optional outputs are wanted.
+    `x_all` / ... / `status`: tensors to write into (contiguous, of exactly these shapes) instead of new ones - needed under
+    hipGraph capture; new buffers are NOT zeroed: rows no pair covers keep what they held.  `outside` IS zeroed here, on the
+    current stream (the call adds to it).  No copy and no synchronisation: the caller reads `status` when it wants to."""
+    from . import _capi
+    dev = world_all.device
+    enc = _encoding_id(encoding, "encoding")
+    F = _capi.ENCODE_FLOATS[enc]
+    if not world_all.is_cuda or world_all.dim() != 3 or world_all.shape[0] < 1:
+        raise ValueError("world_all: a contiguous float32 (total_frames, J, 3) tensor on a GPU is needed")
+    _need(world_all, "world_all", torch.float32, dev, last=3)
+    total, J = int(world_all.shape[0]), int(world_all.shape[1])
+    _need_table(table_dev, num_clips, _capi.CLIP_PROJECT_DESC_BYTES, dev)
+    if (x_mirror_all is not None) and mirror_perm is None:
+        raise ValueError("x_mirror_all without mirror_perm")
+    x_all = _out_buffer(x_all, "x_all", True, torch.float32, dev, (out_rows, J, F))
+    x_mirror_all = _out_buffer(x_mirror_all, "x_mirror_all", mirror_perm is not None, torch.float32, dev, (out_rows, J, F))
+    gt_all = _out_buffer(gt_all, "gt_all", gt, torch.float32, dev, (gt_rows, J, 3))
+    px_all = _out_buffer(px_all, "px_all", px, torch.float64, dev, (gt_rows, J, 2))
+    outside = _out_buffer(outside, "outside", count, torch.int32, dev, (num_clips,))
+    status = _status_buffer(status, num_clips, dev)
+    with torch.cuda.device(dev):
+        if outside is not None:
+            outside.zero_()
+        _capi.clips_project(world_all.data_ptr(), total, J, enc, table_dev.data_ptr(), num_clips, max_rows, x_all.data_ptr(), out_rows,
+                            x_mirror_all.data_ptr() if x_mirror_all is not None else None,
+                            [int(v) for v in mirror_perm] if mirror_perm is not None else None,
+                            gt_all.data_ptr() if gt_all is not None else None, px_all.data_ptr() if px_all is not None else None,
+                            gt_rows, outside.data_ptr() if outside is not None else None, status.data_ptr(),
+                            torch.cuda.current_stream(dev).cuda_stream)
+    return x_all, x_mirror_all, gt_all, px_all, outside, status
+
+
+class _SliceInputs:
+    """``inputs(k)`` (as :class:`_ShardInputs`) of clips whose padded inputs already lie in buffers on the device: clip k is rows
+    [first[k], first[k] + rows[k]) of `x_all` (and of `xm_all`, the mirrored inputs, or None), lifted with ``n_windows=lengths[k]``
+    and the parameter row ``params[k]`` (a device tensor)."""
+
+    def __init__(self, dev, lengths: Sequence[int], first: Sequence[int], rows: Sequence[int], x_all: torch.Tensor,
+                 xm_all: Optional[torch.Tensor], params: Sequence[torch.Tensor]):
+        self.dev, self.lengths, self.first, self.rows, self.x_all, self.xm_all, self.params = dev, lengths, first, rows, x_all, xm_all, params
+
+    def __call__(self, k: int):
+        rows = slice(self.first[k], self.first[k] + self.rows[k])
+        return self.x_all[rows], (self.xm_all[rows] if self.xm_all is not None else None), self.params[k], {"n_windows": self.lengths[k]}
+
+
+def reduce_camera_sweep(rows: torch.Tensor, actions: Sequence[str], camera_names: Sequence[str]) -> List[tuple]:
+    """[(camera name, per_action {name: (e1, e2, e3, ev, er) mm}, action-wise average, keypoints outside the frame)] in the order
+    of `camera_names` from the gathered SWEEP_COLS-wide rows of :func:`evaluate_camera_sweep` - per camera what one
+    ``main.py --evaluate`` run of scripts/synthetic/test_aug.py logs; a camera without rows (an empty sweep) is left out."""
+    rows = rows.detach().to("cpu", torch.float64)
+    out = []
+    for ci, name in enumerate(camera_names):
+        sel = rows[rows[:, PARTIAL_COLS] == ci]
+        if sel.shape[0] == 0:
+            continue
+        sel = sel[torch.argsort(sel[:, 0], stable=True)]            # clip-id order: the sums do not depend on the sharding
+        per = reduce_partials(sel[:, :PARTIAL_COLS])
+        out.append((str(name), {actions[a]: v for a, v in per.items()}, action_average(per), int(sel[:, PARTIAL_COLS + 1].sum().item())))
+    return out
+
+
+def evaluate_camera_sweep(lift_clip: Callable, world_clips: Sequence[WorldClip], cameras: Sequence[Camera], rf: int, device,
+                          flip: bool = False, kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
+                          joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
+                          causal: bool = False, encode: str = "ray", frame: str = "normalized", finish: bool = True,
+                          cameras_per_pass: Optional[int] = None, rank: int = 0, world_size: int = 1, group=None):
+    """The reference's synthetic camera sweep (data/camera_augmentation.py:626-846 + scripts/synthetic/test_aug.py: the world-frame
+    ground truth projected through every virtual camera, one whole evaluation per camera) from WORLD poses, on the device: every
+    clip of `world_clips` is seen through every camera of `cameras` (:func:`ray3d_amd.camera.camera_grid`; each needs res_w /
+    res_h) and evaluated as :func:`evaluate_clips_batched` evaluates a clip of that camera.  The world poses, the descriptor
+    tables of ALL (clip, camera) pairs and the cameras' parameter rows are uploaded ONCE; then, per pass of `cameras_per_pass`
+    cameras (None: all in one pass; the buffers of a pass are reused by the next), ONE :func:`shard_project_hip` call makes the
+    padded, encoded - with `flip` also the mirrored - inputs, the ground truth in `frame` and the in-frame counts, the clips are
+    lifted from their slices with ``raw_out=`` (dealt to the lanes, one join), ONE :func:`shard_poses_hip` call finishes the
+    poses and ONE :func:`shard_metrics_hip` call measures them through the camera's Rn2w / Tn2w (`frame` "camera": Rc2w / Tc2w).
+    No per-camera upload, no per-clip host arithmetic.  `lift_clip` must be the bound ``forward_clip`` of a lifter; `finish`
+    must be True (the poses are finished on the device); `encode` "ray" | "intrinsic" | "screen".  `rank` / `world_size`: the
+    (clip, camera) pairs are dealt to the ranks as :func:`evaluate_clips` deals clips, the rows travel in ONE all_gather.
+    Every rank returns (:func:`reduce_camera_sweep` of all rows - per camera, in order, (camera name, per_action, action-wise
+    average, keypoints outside the frame) -, the gathered (pairs, SWEEP_COLS) float64 rows: a partial row with the clip's index
+    in column 0, then the camera's index and the pair's outside count).  A camera that loses keypoints is still evaluated: the
+    reference drops it when it builds its sets (check_in_frame), here the count says so and the caller decides."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("evaluate_camera_sweep runs on the GPU (r3d_clips_project)")
+    if not finish:
+        raise ValueError("evaluate_camera_sweep finishes the poses on the device: finish must be True")
+    lifter = _lifter_of(lift_clip, need="evaluate_camera_sweep", by_name=True)
+    enc_name = encode
+    _encoding_id(encode)
+    if frame not in ("normalized", "camera"):
+        raise ValueError("frame must be 'normalized' or 'camera' (got %r)" % (frame,))
+    if cameras_per_pass is not None and cameras_per_pass < 1:
+        raise ValueError("cameras_per_pass must be >= 1 (got %r)" % (cameras_per_pass,))
+    actions = sorted(set(c.action for c in world_clips))
+    aid = {a: i for i, a in enumerate(actions)}
+    lengths = [int(np.asarray(c.world).shape[0]) for c in world_clips]
+    pairs = [(k, ci) for ci in range(len(cameras)) for k in range(len(world_clips))]
+    shards = shard_clips([lengths[k] for k, _ in pairs], world_size)
+    per_pass = len(cameras) if cameras_per_pass is None else int(cameras_per_pass)
+    mine = sorted(shards[rank], key=lambda i: pairs[i][1] // per_pass)     # stable: pass by pass, the shard's order within
+    local = _header_rows([(pairs[i][0], aid[world_clips[pairs[i][0]].action], lengths[pairs[i][0]]) for i in mine], PARTIAL_COLS, dev)
+    extra = torch.zeros((len(mine), 2), dtype=torch.float64)
+    if mine:
+        extra[:, 0] = torch.tensor([float(pairs[i][1]) for i in mine], dtype=torch.float64)
+    extra = extra.to(dev)
+    if mine:
+        sizes_of = lifter.clip_batch_sizes
+        J = int(np.asarray(world_clips[0].world).shape[1])
+        jl = kps_left if joints_left is None else joints_left
+        jr = kps_right if joints_right is None else joints_right
+        in_perm = mirror_permutation(J, kps_left, kps_right) if flip else None
+        # the passes' tables, host side: descriptors, metric descriptors and raw rows, each pass laid out from row 0 of its buffers
+        passes, at = [], 0
+        while at < len(mine):
+            end = at
+            while end < len(mine) and pairs[mine[end]][1] // per_pass == pairs[mine[at]][1] // per_pass:
+                end += 1
+            pp = [pairs[i] for i in mine[at:end]]
+            ptable, out_first, out_rows, max_rows, gt_first, gt_rows = clip_project_table(
+                world_clips, pp, cameras, rf, causal, lambda n: sum(sizes_of(n)) - n, frame)
+            ns = [lengths[k] for k, _ in pp]
+            mtable, _, total, longest = _desc_table(ns, [_ground_truth_transform(cameras[ci], frame)[1] for _, ci in pp])
+            assert total == gt_rows and list(mtable["first_frame"]) == gt_first
+            raw_first, _ = clip_raw_table(ns, sizes_of)
+            rows_of = [int(d["pad_front"]) + int(d["n_frames"]) + int(d["pad_back"]) for d in ptable]
+            passes.append(dict(at=at, end=end, pairs=pp, ptable=ptable, mtable=mtable, raw_first=raw_first, out_first=out_first,
+                               rows=rows_of, out_rows=out_rows, max_rows=max_rows, gt_rows=gt_rows, longest=longest, lengths=ns))
+            at = end
+        # the uploads of the whole sweep: the world poses, the three tables of every pass, the cameras' parameter rows
+        world_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.world, dtype=np.float32) for c in world_clips], axis=0)).to(dev)
+        ptable_dev = _to_device_bytes(np.concatenate([p["ptable"] for p in passes]), dev)
+        mtable_dev = _to_device_bytes(np.concatenate([p["mtable"] for p in passes]), dev)
+        raw_first_dev = torch.tensor([v for p in passes for v in p["raw_first"]], dtype=torch.int64).to(dev)
+        params_dev = torch.from_numpy(np.stack([c.param() for c in cameras])).to(dev)
+        from . import _capi
+        F = _capi.ENCODE_FLOATS[ENCODINGS[enc_name]]
+        most_out, most_gt = max(p["out_rows"] for p in passes), max(p["gt_rows"] for p in passes)
+        x_buf = torch.empty((most_out, J, F), dtype=torch.float32, device=dev)
+        xm_buf = torch.empty((most_out, J, F), dtype=torch.float32, device=dev) if flip else None
+        gt_buf = torch.empty((most_gt, J, 3), dtype=torch.float32, device=dev)
+        pred_buf = torch.empty((most_gt, 1, J, 3), dtype=torch.float32, device=dev)
+        outside = torch.empty(len(mine), dtype=torch.int32, device=dev)
+        status = torch.empty(len(mine), dtype=torch.int32, device=dev)
+        for p in passes:
+            a, b, k = p["at"], p["end"], p["end"] - p["at"]
+            x_all, xm_all, gt_all, _, _, _ = shard_project_hip(
+                world_all, ptable_dev[a * _capi.CLIP_PROJECT_DESC_BYTES:b * _capi.CLIP_PROJECT_DESC_BYTES], k, p["out_rows"],
+                p["max_rows"], p["gt_rows"], enc_name, in_perm, x_all=x_buf[:p["out_rows"]],
+                x_mirror_all=xm_buf[:p["out_rows"]] if flip else None, gt_all=gt_buf[:p["gt_rows"]], outside=outside[a:b],
+                status=status[a:b])
+            _raise_if_refused(status[a:b], "r3d_clips_project")
+            inputs = _SliceInputs(dev, p["lengths"], p["out_first"], p["rows"], x_all, xm_all, [params_dev[ci] for _, ci in p["pairs"]])
+            mtab = mtable_dev[a * _capi.CLIP_DESC_BYTES:b * _capi.CLIP_DESC_BYTES]
+            pred_all = pred_buf[:p["gt_rows"]]
+            _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, mtab, p["gt_rows"], p["longest"], pred_all, False,
+                           raw_first_dev=raw_first_dev[a:b])
+            shard_metrics_hip(pred_all, gt_all, mtab, k, p["gt_rows"], p["longest"], local[a:b])
+        extra[:, 1] = outside.to(torch.float64)
+    allrows = _gather(torch.cat([local, extra], dim=1), shards, group, SWEEP_COLS)
+    return reduce_camera_sweep(allrows, actions, [c.name for c in cameras]), allrows
 
 
 def format_detail_report(table: Dict, joint_names: Optional[Sequence[str]] = None) -> List[str]:

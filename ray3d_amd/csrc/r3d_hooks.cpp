@@ -133,6 +133,7 @@ int r3d_debug_schedule_check(int nprob, const int *M, const int *N, const int *n
         probs.push_back({M[i], N[i], nk[i], max_ks[i], max_units[i]});
         // (as sched_prob_of marks the plan's wide plain layers: their single-unit tiles may be 4 .. 7 column blocks wide)
         probs.back().nb_ok = !enc && N[i] % 32 == 0 && N[i] >= 512 && nk[i] >= 8 && max_units[i] == 0 && !hook_on("R3D_NO_NB");
+        probs.back().run_ok = probs.back().nb_ok;
     }
     std::vector<int4> tiles;
     std::vector<int> wgoff;
@@ -148,7 +149,20 @@ int r3d_debug_schedule_check(int nprob, const int *M, const int *N, const int *n
     std::vector<std::vector<int>> cover(nprob);
     for (int i = 0; i < nprob; ++i) cover[i].assign((size_t)((M[i] + 31) / 32) * ((N[i] + COL_GRANULE - 1) / COL_GRANULE), 0);
     for (const int4 &t : tiles) {
-        const int pi = t.x & 0xff, mi = t.x >> 8, ks = t.w;
+        const int pi = t.x & 0xff, mi = tile_units(t.x), ks = t.w;
+        if (tile_src2(t.x) >= 0) {                 // a two-source tile: one unit, the rest of its row and the start of the next source's
+            const int p2 = tile_src2(t.x);
+            if (!tile_is_nb(ks) || mi != 1 || pi >= nprob || p2 >= nprob || t.z < 0 || t.z % 32 || t.z >= N[pi] || t.z + tile_width(ks) <= N[pi]) return -7;
+            if (t.y % 32 || t.y < 0 || t.y >= M[pi] || nk[p2] != nk[pi]) return -7;
+            TileSrc src[2];
+            tile_sources(t.x, t.y, t.z, ks, N[pi], src);
+            if (src[1].row0 >= M[p2] || src[1].cols > N[p2] || (p2 == pi ? false : t.y + 32 < M[pi])) return -7;
+            for (const TileSrc &sc : src) {
+                const int gc = (N[sc.prob] + COL_GRANULE - 1) / COL_GRANULE;
+                for (int g = sc.col0 / COL_GRANULE; g < (sc.col0 + sc.cols) / COL_GRANULE; ++g) ++cover[sc.prob][(size_t)(sc.row0 / 32) * gc + g];
+            }
+            continue;
+        }
         if (pi >= nprob || mi < 1 || (ks != 1 && ks != 2 && ks != 4 && ks != 8 && ks != 16 && !(ks >= NB_CODE + 4 && ks <= NB_CODE + 7))) return -4;
         if (ks < 8 && ks > max_ks[pi]) return -5;
         if ((ks == 1 && mi > (max_units[pi] > 0 ? std::min(max_units[pi], GEMM_SCHED_MAX_UNITS) : GEMM_SCHED_MAX_UNITS)) || (ks == 2 && mi > 2) || (ks >= 4 && mi != 1)) return -6;
@@ -204,8 +218,8 @@ int r3d_debug_plan_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg,
         }
         for (int t = 0; t < ss.ntiles; ++t) {
             const int4 &tl = tiles[ss.tiles_off + t];
-            const int slot = tl.x & 0xff, mi = tl.x >> 8, ks = tl.w;
-            if (slot >= (int)st.size() || mi < 1) return -4;
+            const int slot = tl.x & 0xff, mi = tile_units(tl.x), ks = tl.w;
+            if (slot >= (int)st.size() || mi < 1 || tile_src2(tl.x) >= (int)st.size()) return -4;
             const int id = st[slot] & ~STAGE_SPILL_IN;
             const ProbSpec &q = pl->probs[id];
             const int M = (int)(batch * q.rows_per_window), N = pl->m[q.model]->layers[q.layer].N;
@@ -222,6 +236,18 @@ int r3d_debug_plan_check(r3d_model *pos, r3d_model *trj, int64_t batch, int nwg,
             }
             last_launch[id] = std::max(last_launch[id], (int)si);
             first_launch[id] = std::min(first_launch[id], (int)si);
+            if (tile_src2(tl.x) >= 0) {            // the second source of a two-source tile: the first blocks of one more unit
+                TileSrc src[2];
+                tile_sources(tl.x, tl.y, tl.z, ks, N, src);
+                const int id2 = st[src[1].prob] & ~STAGE_SPILL_IN;
+                const ProbSpec &q2 = pl->probs[id2];
+                const int M2 = (int)(batch * q2.rows_per_window), N2 = pl->m[q2.model]->layers[q2.layer].N;
+                if (!tile_is_nb(ks) || mi != 1 || (st[src[1].prob] & STAGE_SPILL_IN) || src[1].row0 >= M2 || src[1].cols > N2 || src[1].cols <= 0) return -5;
+                const int gc2 = (N2 + COL_GRANULE - 1) / COL_GRANULE;
+                for (int g = 0; g < src[1].cols / COL_GRANULE; ++g) ++cover[id2][(size_t)(src[1].row0 / 32) * gc2 + g];
+                last_launch[id2] = std::max(last_launch[id2], (int)si);
+                first_launch[id2] = std::min(first_launch[id2], (int)si);
+            }
         }
     }
     for (int i = 0; i < np; ++i) {
@@ -322,24 +348,32 @@ int r3d_debug_forward_check(r3d_model *pos, r3d_model *trj, int64_t batch, int n
                     for (int u = 0; u < n && ready; ++u) ready = cnt[base + u] >= need;
                 }
                 if (!ready) break;
-                const int id = d[0] & 0xff, mi = d[0] >> 8;
-                const ProbSpec &q = pl->probs[id];
-                const int M = (int)(batch * q.rows_per_window);
-                const int r1 = std::min(d[1] + mi * 32, M);
-                const int w0 = d[1] / q.rows_per_window, w1 = (r1 - 1) / q.rows_per_window + 1;
-                const Acc wr = writes(q);
-                for (int o = 0; o < id; ++o) {                 // (problems are created in the reference's execution order)
-                    const ProbSpec &oq = pl->probs[o];
-                    bool hazard = false;
-                    for (const Acc &rd : reads(q)) hazard = hazard || overlap(rd, writes(oq));        // read after write
-                    for (const Acc &rd : reads(oq)) hazard = hazard || overlap(rd, wr);               // write after read
-                    hazard = hazard || overlap(writes(oq), wr);                                      // write after write
-                    if (hazard && !complete(o, w0, w1)) return -20;
-                }
-                if (d[5] != fw.cnt_base[id] + d[1] / 32 || d[5] + mi > fw.ncnt) return -21;
-                for (int u = 0; u < mi; ++u) {
-                    cnt[d[5] + u] += (unsigned)d[6];
-                    if (cnt[d[5] + u] > (unsigned)gcols[id]) return -22;
+                const int mi = tile_units(d[0]);
+                TileSrc src[2];           // (a two-source tile: both sources' hazards, both sources' counters)
+                const int nsrc = tile_sources(d[0], d[1], d[2], d[3], pl->m[pl->probs[d[0] & 0xff].model]->layers[pl->probs[d[0] & 0xff].layer].N, src);
+                for (int sc = 0; sc < nsrc; ++sc) {
+                    const int id = src[sc].prob;
+                    const ProbSpec &q = pl->probs[id];
+                    const int M = (int)(batch * q.rows_per_window);
+                    if (src[sc].row0 >= M) return -21;
+                    const int r1 = std::min(src[sc].row0 + mi * 32, M);
+                    const int w0 = src[sc].row0 / q.rows_per_window, w1 = (r1 - 1) / q.rows_per_window + 1;
+                    const Acc wr = writes(q);
+                    for (int o = 0; o < id; ++o) {                 // (problems are created in the reference's execution order)
+                        const ProbSpec &oq = pl->probs[o];
+                        bool hazard = false;
+                        for (const Acc &rd : reads(q)) hazard = hazard || overlap(rd, writes(oq));        // read after write
+                        for (const Acc &rd : reads(oq)) hazard = hazard || overlap(rd, wr);               // write after read
+                        hazard = hazard || overlap(writes(oq), wr);                                      // write after write
+                        if (hazard && !complete(o, w0, w1)) return -20;
+                    }
+                    const int c0 = sc == 0 ? d[5] : d[7] >> 8, add = sc == 0 ? d[6] : src[1].cols / COL_GRANULE;
+                    if (nsrc == 2 && (mi != 1 || !tile_is_nb(d[3]) || src[sc].cols <= 0 || src[sc].cols % COL_GRANULE || (sc == 0 && d[6] != src[0].cols / COL_GRANULE))) return -21;
+                    if (c0 != fw.cnt_base[id] + src[sc].row0 / 32 || c0 + mi > fw.ncnt) return -21;
+                    for (int u = 0; u < mi; ++u) {
+                        cnt[c0 + u] += (unsigned)add;
+                        if (cnt[c0 + u] > (unsigned)gcols[id]) return -22;
+                    }
                 }
                 ++next[w];
                 ++done;
@@ -405,7 +439,7 @@ int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int 
         std::map<std::string, int> hist;
         for (const int4 &t : ft) {
             const Plan::FrameProb &f = pl->frame_probs[t.x & 0xff];
-            ++hist[census_tile_kind(*k, CensusProb{false, true, false, false, pl->m[f.model]->layers[f.layer].Kpad}, t.x >> 8, t.w)];
+            ++hist[census_tile_kind(*k, CensusProb{false, true, false, false, pl->m[f.model]->layers[f.layer].Kpad}, tile_units(t.x), t.w)];
         }
         out.launch_of(name, fs.nwg, hist);
     }
@@ -423,7 +457,7 @@ int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int 
         for (int t = 0; t < fw.ntiles; ++t) {
             const int *d = &cs.ft[(size_t)t * TI];
             const int id = d[0] & 0xff;
-            ++hist[census_tile_kind(*k, census_prob(&tags[(size_t)id * BIND_NPTR], rel[id].K), d[0] >> 8, d[3])];
+            ++hist[census_tile_kind(*k, census_prob(&tags[(size_t)id * BIND_NPTR], rel[id].K), tile_units(d[0]), d[3])];
         }
         out.launch_of(name, fw.grid, hist);
     } else {
@@ -456,7 +490,7 @@ int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int 
                 const int4 &tl = cs.tiles[ss.tiles_off + t];
                 const int slot = tl.x & 0xff;
                 if (slot >= (int)st.size()) return -5;
-                ++hist[census_tile_kind(*k, P[slot], tl.x >> 8, tl.w)];
+                ++hist[census_tile_kind(*k, P[slot], tile_units(tl.x), tl.w)];
             }
             out.launch_of(name, ss.nwg, hist);
         }

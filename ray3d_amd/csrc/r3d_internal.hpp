@@ -75,7 +75,7 @@ struct GemmProb {
 // Kernel argument of one persistent GEMM launch.  `tiles`/`wg_off` live in HBM (built once per
 // (plan, batch size) by r3d_schedule.cpp); the problem table travels in the kernarg segment.
 struct LaunchArgs {
-    const int4 *tiles;    // {problem | MI << 8, first row, first column, 0}
+    const int4 *tiles;    // {problem | MI << 8 | (second source's problem + 1) << 16, first row, first column, split-K factor / tile code}
     const int *wg_off;    // [grid + 1]: chunk c executes tiles [wg_off[c], wg_off[c+1])
     int nprob;
     int ks;               // (unused: the split-K factor travels with each tile)
@@ -89,10 +89,15 @@ struct LaunchArgs {
 // windows: one ready counter per (problem, 32-row unit) in the caller's workspace counts finished 32-column granules.
 constexpr int FWD_TILE_INT4 = 6;        // a tile descriptor: 24 ints (below)
 constexpr int FWD_MAX_DEP = 8;
-// ints of a descriptor: [0] problem | units << 8   [1] first row   [2] first column   [3] split-K factor
+// ints of a descriptor: [0] problem | units << 8 | (second source's problem + 1) << 16   [1] first row   [2] first column   [3] split-K factor
 //                       [4] number of dependency ranges   [5] index of the first unit's ready counter
-//                       [6] granules (32 columns) this tile adds to each of its units' counters   [7] unused
+//                       [6] granules (32 columns) this tile adds to each of its units' counters
+//                       [7] bit 0: FWD_TILE_NOSIGNAL; from bit 8: the ready counter of a two-source tile's second source
 //                       [8 + 2d] first counter of range d   [9 + 2d] counters in the range | granules required << 16
+// A two-source tile (gemm_tile_nb only: a run of column blocks that crosses the end of a row, r3d_schedule.cpp pack_runs) computes the
+// last n0 = (N - first column) / 32 blocks of its first source's unit and the first nb - n0 blocks of its second source's: the next
+// unit of the same problem, or unit 0 of another problem.  Its dependency ranges are both sources'; it adds n0 granules to the
+// first source's counter and nb - n0 to the second's.
 struct FwdArgs {
     const int4 *tiles;        // FWD_TILE_INT4 int4 per tile
     const int *wg_off;        // [grid + 1]: workgroup b executes tiles [wg_off[b], wg_off[b+1])
@@ -601,6 +606,9 @@ struct SchedProb {
     bool gemv = false;   // M <= GEMV_ROWS rows of a plain layer: 32-column GEMV tiles (tile code ks == 8), r3d_kernels.hip gemv_tile
     bool lat = false;    // ... of up to 32 rows: 32-column latency tiles on the matrix cores (tile code 16), lat_tile
     bool nb_ok = false;  // a plain fp32 layer of whole 32-column blocks whose single-unit tiles may be 4 - 7 blocks wide (gemm_tile_nb)
+    bool one_seg = false;  // ... whose A operand is a single segment: a run of blocks may cross into another such problem of the same K
+    bool run_ok = false;   // ... and whose rows may be cut into runs of blocks that cross the end of a row (pack_runs): not beside bf16x3 tiles
+    int ndeps = 0;       // producer problems (a two-source tile lists both sources' in one descriptor: FWD_MAX_DEP)
 };
 constexpr int GEMV_ROWS = 4;          // == GEMV_MAX_M of the kernels (at eight rows the MFMA split-K tiles are the faster ones: 0.207 against 0.222 ms)
 constexpr int COL_GRANULE = 32;       // ready counters and cover checks count columns in granules of this many
@@ -608,6 +616,17 @@ constexpr int NB_CODE = 64;           // tile code NB_CODE + nb: one 32-row unit
 constexpr bool tile_is_nb(int ks) { return ks > NB_CODE; }
 constexpr bool tile_is_narrow(int ks) { return ks >= 8 && ks < NB_CODE; }    // GEMV (8) / latency (16) tiles
 constexpr int tile_width(int ks) { return ks > NB_CODE ? (ks - NB_CODE) * 32 : ks >= 8 ? 32 : 256 / ks; }   // columns of a tile by its code
+constexpr int tile_units(int x) { return (x >> 8) & 0xff; }     // 32-row units of a tile by the first int of its descriptor
+constexpr int tile_src2(int x) { return (x >> 16) - 1; }        // a two-source tile's second problem (the same index space as the first), or -1
+// the two sources of a tile as (problem, first row, first column, columns); `N`: the first problem's columns
+struct TileSrc { int prob, row0, col0, cols; };
+inline int tile_sources(int x, int row0, int col0, int ks, int N, TileSrc (&s)[2]) {
+    const int w = tile_width(ks), p2 = tile_src2(x);
+    s[0] = {x & 0xff, row0, col0, p2 >= 0 ? N - col0 : w};
+    if (p2 < 0) return 1;
+    s[1] = {p2, p2 == (x & 0xff) ? row0 + 32 : 0, 0, w - (N - col0)};
+    return 2;
+}
 void schedule_stage(const std::vector<SchedProb> &probs, int nwg, int max_units, std::vector<int4> &tiles,
                     std::vector<int> &wgoff, StageSchedule &out, bool enc = false);
 // index of weight element (output channel o, GEMM column k) in the fragment-ordered packing

@@ -53,16 +53,16 @@ static void dump_fwd(const Plan *pl, int64_t B, int grid, const std::vector<int>
             for (int i = 0; i < np; ++i) {
                 const ProbSpec &q = pl->probs[i];
                 const Model *mm = pl->m[q.model];
-                fprintf(f, "P %d %s rpw %d M %d N %d K %d K2 %d K3 %d deps", i, mm->layers[q.layer].weight_key.c_str(), q.rows_per_window, M[i],
+                fprintf(f, "P %d %s rpw %d M %d N %d K %d K2 %d K3 %d nseg %d deps", i, mm->layers[q.layer].weight_key.c_str(), q.rows_per_window, M[i],
                         mm->layers[q.layer].N, mm->layers[q.layer].Kpad, q.layer2 >= 0 ? mm->layers[q.layer2].Kpad : 0,
-                        q.layer3 >= 0 ? mm->layers[q.layer3].Kpad : 0);
+                        q.layer3 >= 0 ? mm->layers[q.layer3].Kpad : 0, q.nseg);
                 for (int dpi : q.deps) fprintf(f, " %d", dpi);
                 fprintf(f, "\n");
             }
             for (int b = 0; b < grid; ++b)
                 for (int t = out_wgoff[b]; t < out_wgoff[b + 1]; ++t) {
                     const int *d = &out_tiles[(size_t)t * FWD_TILE_INT4 * 4];
-                    fprintf(f, "T %d %d %d %d %d %d %d\n", b, t, d[0] & 0xff, d[0] >> 8, d[1], d[2], d[3]);
+                    fprintf(f, "T %d %d %d %d %d %d %d %d\n", b, t, d[0] & 0xff, tile_units(d[0]), d[1], d[2], d[3], tile_src2(d[0]));   // (last: a two-source tile's second problem, or -1)
                 }
             fclose(f);
         }
@@ -133,11 +133,11 @@ bool schedule_build_fwd(const Plan *pl, int64_t B, int nwg, const std::vector<st
             if (c >= n) continue;                  // (n < 8: workgroups b >= n do not exist in the staged launch either)
             for (int t = wgoff[ss.wgoff_off + c]; t < wgoff[ss.wgoff_off + c + 1]; ++t) {
                 const int4 &tl = tiles[ss.tiles_off + t];
-                const int slot = tl.x & 0xff, mi = tl.x >> 8, ks = tl.w;
+                const int slot = tl.x & 0xff, mi = tile_units(tl.x), ks = tl.w;
                 const int id = st[slot] & ~STAGE_SPILL_IN;
-                const ProbSpec &q = pl->probs[id];
+                const int id2 = tile_src2(tl.x) >= 0 ? st[tile_src2(tl.x)] & ~STAGE_SPILL_IN : -1;     // (a two-source tile: r3d_internal.hpp)
                 int d[FWD_TILE_INT4 * 4] = {0};
-                d[0] = id | (mi << 8);
+                d[0] = id | (mi << 8) | ((id2 + 1) << 16);
                 d[1] = tl.y;
                 d[2] = tl.z;
                 d[3] = ks;
@@ -147,24 +147,47 @@ bool schedule_build_fwd(const Plan *pl, int64_t B, int nwg, const std::vector<st
                     d[6] = std::max(g1 - g0, 0);
                     if (d[6] <= 0) return false;
                 }
-                const int r1 = std::min(tl.y + mi * 32, M[id]);
-                const int w0 = tl.y / q.rows_per_window, w1 = (r1 - 1) / q.rows_per_window + 1;
-                std::vector<int> deps(q.deps);
-                std::sort(deps.begin(), deps.end());
-                deps.erase(std::unique(deps.begin(), deps.end()), deps.end());
+                // the producer units of the tile's windows, per source; ranges of one producer that touch are one range
                 int nd = 0;
-                for (int dp : deps) {
-                    const ProbSpec &pq = pl->probs[dp];
-                    const int a0 = w0 * pq.rows_per_window, a1 = std::min(w1 * pq.rows_per_window, M[dp]);
-                    if (a1 <= a0) continue;
-                    const int u0 = a0 / 32, u1 = (a1 + 31) / 32;
-                    if (nd == FWD_MAX_DEP || u1 - u0 > 0xffff || gcols[dp] > 0x7fff) return false;
-                    d[8 + 2 * nd] = fw.cnt_base[dp] + u0;
-                    d[9 + 2 * nd] = (u1 - u0) | (gcols[dp] << 16);
-                    ++nd;
+                TileSrc src[2];
+                const int nsrc = tile_sources(d[0], tl.y, tl.z, ks, pl->m[pl->probs[id].model]->layers[pl->probs[id].layer].N, src);
+                for (int s = 0; s < nsrc; ++s) {
+                    const ProbSpec &q = pl->probs[src[s].prob];
+                    const int r1 = std::min(src[s].row0 + mi * 32, M[src[s].prob]);
+                    const int w0 = src[s].row0 / q.rows_per_window, w1 = (r1 - 1) / q.rows_per_window + 1;
+                    std::vector<int> deps(q.deps);
+                    std::sort(deps.begin(), deps.end());
+                    deps.erase(std::unique(deps.begin(), deps.end()), deps.end());
+                    for (int dp : deps) {
+                        const ProbSpec &pq = pl->probs[dp];
+                        const int a0 = w0 * pq.rows_per_window, a1 = std::min(w1 * pq.rows_per_window, M[dp]);
+                        if (a1 <= a0) continue;
+                        const int u0 = a0 / 32, u1 = (a1 + 31) / 32;
+                        if (u1 - u0 > 0xffff || gcols[dp] > 0x7fff) return false;
+                        const int c0 = fw.cnt_base[dp] + u0, c1 = fw.cnt_base[dp] + u1;
+                        bool merged = false;
+                        for (int k = 0; k < nd && !merged; ++k) {
+                            const int k0 = d[8 + 2 * k], k1 = k0 + (d[9 + 2 * k] & 0xffff);
+                            if ((d[9 + 2 * k] >> 16) != gcols[dp] || c0 > k1 || k0 > c1 || k0 < fw.cnt_base[dp] || k1 > fw.cnt_base[dp] + (int)units_of(B, pq)) continue;
+                            const int n0 = std::min(k0, c0), n1 = std::max(k1, c1);
+                            d[8 + 2 * k] = n0;
+                            d[9 + 2 * k] = (n1 - n0) | (gcols[dp] << 16);
+                            merged = true;
+                        }
+                        if (merged) continue;
+                        if (nd == FWD_MAX_DEP) return false;
+                        d[8 + 2 * nd] = c0;
+                        d[9 + 2 * nd] = (u1 - u0) | (gcols[dp] << 16);
+                        ++nd;
+                    }
                 }
                 d[4] = nd;
-                d[7] = quiet[id] ? 1 : 0;              // (any kind of tile: a first-layer tile whose consumers all poll needs no drain either)
+                d[7] = quiet[id] && (id2 < 0 || quiet[id2]) ? 1 : 0;   // (any kind of tile: a first-layer tile whose consumers all poll needs no drain either)
+                if (id2 >= 0) {
+                    const int c2 = fw.cnt_base[id2] + src[1].row0 / 32;
+                    if (c2 >= (1 << 22)) return false;
+                    d[7] |= c2 << 8;
+                }
                 lists[b].insert(lists[b].end(), d, d + FWD_TILE_INT4 * 4);
             }
         }
@@ -247,6 +270,7 @@ double lat_cycles(int nk) { return 9000.0 + nk / 8.0 * 2600.0; }
 
 struct Run {           // `n` consecutive row units of one column block, all in one workgroup's chunk
     int prob, col0, ks, u0, n, cap;
+    int prob2 = -1;    // a two-source tile (pack_runs): the problem its blocks past the end of the row belong to
 };
 
 struct Seg {           // one column block of a problem
@@ -443,29 +467,52 @@ void pack(const std::vector<SchedProb> &probs, int nbins_max, int max_units, Pac
 
 }  // namespace
 
+// What pack_nb and pack_runs share: the launch's problems that gemm_tile_nb may cut (`elig`) and the others (`rest`, with their indices),
+// and whether the classic packing gives the eligible ones one whole tile per workgroup (its budget is then a single unit's time)
+struct NbSplit {
+    std::vector<int> elig, rest_idx;
+    std::vector<SchedProb> rest;
+    bool one_tile_deep = false;
+};
+static NbSplit nb_split(const std::vector<SchedProb> &probs, int nwg, const Packed &classic, bool force) {
+    NbSplit sp;
+    for (int i = 0; i < (int)probs.size(); ++i) {
+        const SchedProb &p = probs[i];
+        if (p.nb_ok && p.row0 == 0 && p.M > 0 && p.N % 32 == 0) sp.elig.push_back(i);
+        else { sp.rest_idx.push_back(i); sp.rest.push_back(p); }
+    }
+    double unit_max = 0;
+    long long whole_tiles = 0;
+    for (int i : sp.elig) {
+        unit_max = std::max(unit_max, unit_cycles(probs[i].nk, 1));
+        whole_tiles += (long long)((probs[i].M + 31) / 32) * ((probs[i].N + 255) / 256);
+    }
+    sp.one_tile_deep = !sp.elig.empty() && whole_tiles <= nwg && (classic.T <= 1.05 * unit_max || force);
+    return sp;
+}
+// ... and the rest of the launch, packed classically into the workgroups left, behind the narrow tiles
+static void nb_append_rest(const NbSplit &sp, const Packed &rest, double T, Packed &out) {
+    for (const auto &bin : rest.a.bins) {
+        if (bin.empty()) continue;
+        std::vector<Run> b2 = bin;
+        for (Run &r : b2) r.prob = sp.rest_idx[r.prob];
+        out.a.bins.push_back(b2);
+    }
+    out.total += rest.total;
+    out.a.worst = T;
+}
+
 // One-tile-deep launches (the M = B levels of a 256-window call: 160 - 224 whole 32 x 256 tiles for 256 CUs): the launch is
 // as long as one tile whatever the packing, and a quarter of the chip idles.  gemm_tile_nb's tiles of 4 - 7 column blocks are
 // proportionally shorter, so the eligible problems' rows of N / 32 blocks are cut into more, narrower tiles - one per
 // workgroup - and the rest of the launch (pyramid riders, short layers) is packed classically into the workgroups left.
 // Returns false when that is not shorter than the classic packing by the cost model.
 static bool pack_nb(const std::vector<SchedProb> &probs, int nwg, int max_units, const Packed &classic, Packed &out) {
-    std::vector<int> elig, rest_idx;
-    std::vector<SchedProb> rest;
-    for (int i = 0; i < (int)probs.size(); ++i) {
-        const SchedProb &p = probs[i];
-        if (p.nb_ok && p.row0 == 0 && p.M > 0 && p.N % 32 == 0) elig.push_back(i);
-        else { rest_idx.push_back(i); rest.push_back(p); }
-    }
-    if (elig.empty()) return false;
-    // only where the classic packing is one whole tile per workgroup for these problems: its budget is a single unit's time
-    double unit_max = 0;
-    long long whole_tiles = 0;
-    for (int i : elig) {
-        unit_max = std::max(unit_max, unit_cycles(probs[i].nk, 1));
-        whole_tiles += (long long)((probs[i].M + 31) / 32) * ((probs[i].N + 255) / 256);
-    }
     const bool force = hook_on("R3D_NB_FORCE");        // (hooks build: A/B of the cost model's verdict)
-    if (whole_tiles > nwg || (classic.T > 1.05 * unit_max && !force)) return false;
+    const NbSplit sp = nb_split(probs, nwg, classic, force);
+    if (!sp.one_tile_deep) return false;               // only where the classic packing is one whole tile per workgroup for these problems
+    const std::vector<int> &elig = sp.elig;
+    const std::vector<SchedProb> &rest = sp.rest;
     double best_T = force ? 1e30 : classic.T * 0.97;   // (modelled gains of a few percent do not materialise)
     int best_nb = 0;
     Packed best_rest;
@@ -506,24 +553,99 @@ static bool pack_nb(const std::vector<SchedProb> &probs, int nwg, int max_units,
             b0 += w;
         }
     }
-    for (const auto &bin : best_rest.a.bins) {
-        if (bin.empty()) continue;
-        std::vector<Run> b2 = bin;
-        for (Run &r : b2) r.prob = rest_idx[r.prob];
-        out.a.bins.push_back(b2);
+    nb_append_rest(sp, best_rest, best_T, out);
+    return true;
+}
+
+// The same launches, cut finer: pack_nb cuts inside one row of N / 32 blocks, and 32 blocks divide by neither 7 nor 6 - a FuseBlocks
+// level of seven problems at 256 windows is 1792 cells (problem, 32-row unit, 32-column block), exactly 7 per workgroup, and takes 280
+// tiles cut row by row.  Here the eligible problems' cells are put in one linear order (problem, unit, block) and cut into evenly
+// sized runs of 4 - 7 cells; a run that crosses the end of a row is a two-source tile (r3d_internal.hpp: the rest of one unit's row and
+// the start of the next).  A run may cross into the next unit of its problem, and into the next problem when both have a
+// single-segment operand of the same K (and one descriptor holds both dependency lists); elsewhere the run ends.  Returns false
+// unless the cost model makes the launch at least 3 % shorter than `today` (the better of pack and pack_nb).
+static bool pack_runs(const std::vector<SchedProb> &probs, int nwg, int max_units, const Packed &classic, double today_T, Packed &out) {
+    if (hook_on("R3D_NO_RUNS")) return false;          // (hooks build: A/B against the row-by-row cut)
+    const NbSplit sp = nb_split(probs, nwg, classic, false);
+    if (!sp.one_tile_deep) return false;
+    const std::vector<int> &elig = sp.elig;
+    const std::vector<SchedProb> &rest = sp.rest;
+    for (int i : elig)
+        if (!probs[i].run_ok || probs[i].M > 256) return false;                // (bf16x3 handles keep their packing; calls of <= 256 windows)
+    // chains of cells no run may leave
+    struct Chain { int first, last; long long cells; };      // positions in `elig`
+    std::vector<Chain> chains;
+    for (int e = 0; e < (int)elig.size(); ++e) {
+        const SchedProb &p = probs[elig[e]];
+        const long long cells = (long long)((p.M + 31) / 32) * (p.N / 32);
+        bool joins = false;
+        if (e > 0) {
+            const SchedProb &o = probs[elig[e - 1]];
+            joins = p.one_seg && o.one_seg && p.nk == o.nk && p.ndeps + o.ndeps <= FWD_MAX_DEP;
+        }
+        if (joins) { chains.back().last = e; chains.back().cells += cells; }
+        else chains.push_back({e, e, cells});
     }
-    out.total += best_rest.total;
-    out.a.worst = best_T;
+    double best_T = today_T * 0.97;
+    int best_w = 0;
+    Packed best_rest;
+    for (int w = 5; w <= 7; ++w) {                     // (as pack_nb: 4-block tiles only as the narrow end of an uneven cut)
+        long long nruns = 0;
+        int widest = 0;
+        bool ok = true;
+        for (const Chain &c : chains) {
+            const long long n = (c.cells + w - 1) / w;
+            if (c.cells / n < 4) { ok = false; break; }
+            widest = std::max(widest, (int)((c.cells + n - 1) / n));
+            nruns += n;
+        }
+        for (int i : elig) ok = ok && probs[i].N / 32 >= 8;               // (a run of <= 7 cells then has at most two sources)
+        if (!ok || nruns > nwg) continue;
+        double T = 0;
+        for (int i : elig) T = std::max(T, nb_cycles(probs[i].nk, widest));
+        Packed pr;
+        if (!rest.empty()) {
+            if (nwg - nruns < 1) continue;
+            pack(rest, (int)(nwg - nruns), max_units, pr);
+            T = std::max(T, pr.T);
+        }
+        if (T < best_T) { best_T = T; best_w = w; best_rest = pr; }
+    }
+    if (!best_w) return false;
+    out = Packed();
+    out.T = best_T;
+    out.ks = best_rest.ks ? best_rest.ks : 1;
+    out.total = 0;
+    for (const Chain &c : chains) {
+        const long long n = (c.cells + best_w - 1) / best_w;
+        int e = c.first, u = 0, b = 0;                 // the next cell: problem elig[e], unit u, block b
+        for (long long r = 0; r < n; ++r) {
+            const int width = (int)((c.cells * (r + 1)) / n - (c.cells * r) / n);       // evenly sized: floor / ceil of cells / n
+            const SchedProb &p = probs[elig[e]];
+            const int nblk = p.N / 32, units = (p.M + 31) / 32;
+            Run run{elig[e], b * 32, NB_CODE + width, u, 1, 1};
+            out.total += nb_cycles(p.nk, width);
+            b += width;
+            if (b >= nblk) {                           // the row ends in (or with) this run
+                b -= nblk;
+                if (++u == units) { u = 0; ++e; }
+                if (b > 0) run.prob2 = elig[e];        // (e <= c.last: the chain's cells are not used up)
+            }
+            out.a.bins.push_back({run});
+        }
+    }
+    nb_append_rest(sp, best_rest, best_T, out);
     return true;
 }
 
 void schedule_stage(const std::vector<SchedProb> &probs, int nwg, int max_units, std::vector<int4> &tiles,
                     std::vector<int> &wgoff, StageSchedule &out, bool enc) {
-    Packed big, narrow;
+    Packed big, narrow, runs;
     const Packed *best = &big;
     out.kind = enc ? STAGE_ENC : STAGE_BIG;
     pack(probs, nwg, max_units, big);
     if (!enc && pack_nb(probs, nwg, max_units, big, narrow)) best = &narrow;
+    if (!enc && pack_runs(probs, nwg, max_units, big, best->T, runs)) best = &runs;
     out.ks = 1;
     out.tiles_off = tiles.size();
     out.wgoff_off = wgoff.size();
@@ -538,7 +660,7 @@ void schedule_stage(const std::vector<SchedProb> &probs, int nwg, int max_units,
             int done = 0;
             for (int k = 0; k < nt; ++k) {
                 const int sz = (r.n - done + (nt - k) - 1) / (nt - k);
-                tiles.push_back(make_int4(r.prob | (sz << 8), probs[r.prob].row0 + (r.u0 + done) * 32, r.col0, r.ks));
+                tiles.push_back(make_int4(r.prob | (sz << 8) | ((r.prob2 + 1) << 16), probs[r.prob].row0 + (r.u0 + done) * 32, r.col0, r.ks));
                 done += sz;
             }
             out.ks = std::max(out.ks, r.ks);
@@ -558,7 +680,8 @@ void schedule_stage(const std::vector<SchedProb> &probs, int nwg, int max_units,
             fprintf(stderr, "[sched] chunk %3d:", b);
             for (int t = wgoff[out.wgoff_off + b]; t < wgoff[out.wgoff_off + b + 1]; ++t) {
                 const int4 &tl = tiles[t0 + t];
-                fprintf(stderr, " p%d/mi%d/r%d/c%d/ks%d", tl.x & 0xff, tl.x >> 8, tl.y, tl.z, tl.w);
+                fprintf(stderr, " p%d/mi%d/r%d/c%d/ks%d", tl.x & 0xff, tile_units(tl.x), tl.y, tl.z, tl.w);
+                if (tile_src2(tl.x) >= 0) fprintf(stderr, "+p%d", tile_src2(tl.x));
             }
             fprintf(stderr, "\n");
         }
@@ -593,6 +716,13 @@ static SchedProb sched_prob_of(const Plan *pl, const ProbSpec &q, int64_t B) {
         // single-unit tiles of 5 - 7 column blocks (gemm_tile_nb) for the wide plain fp32 layers: the FCBlocks' 1024-wide Linears
         sp.nb_ok = q.enc_lut < 0 && q.layer2 < 0 && !sp.gemv && !sp.lat && !(b3 && L.bf3) && L.N % 32 == 0 && L.N >= 512 &&
                    L.Kpad / BK >= 8 && !hook_on("R3D_NO_NB");
+        sp.one_seg = q.nseg == 1;
+        sp.run_ok = sp.nb_ok && !pl->m[q.model]->use_b3;
+        {
+            std::vector<int> deps(q.deps);
+            std::sort(deps.begin(), deps.end());
+            sp.ndeps = (int)(std::unique(deps.begin(), deps.end()) - deps.begin());
+        }
         if (b3 && L.bf3 && q.layer2 < 0 && q.enc_lut < 0) {   // bf16-matrix-core tiles: whole tiles of <= 128 rows, ~1.5x the iteration rate
             sp.max_ks = 1;
             sp.max_units = 4;
@@ -671,7 +801,7 @@ static void build_stage(const Plan *pl, const std::vector<int> &st, int64_t B, i
     // launch's packing is a function of its problems' shapes, so it is computed once per distinct launch of a build.
     std::vector<int> key{enc ? 1 : 0, nwg};
     for (const SchedProb &sp : probs)
-        key.insert(key.end(), {sp.M, sp.N, sp.nk, sp.max_ks, sp.max_units, sp.nk2, sp.row0, (sp.gemv ? 1 : sp.lat ? 2 : 0) + (sp.nb_ok ? 4 : 0)});
+        key.insert(key.end(), {sp.M, sp.N, sp.nk, sp.max_ks, sp.max_units, sp.nk2, sp.row0, (sp.gemv ? 1 : sp.lat ? 2 : 0) + (sp.nb_ok ? 4 : 0) + (sp.one_seg ? 8 : 0) + (sp.run_ok ? 16 : 0) + sp.ndeps * 32});
     auto hit = g_stage_memo.find(key);
     if (hit == g_stage_memo.end()) {
         StageMemo m;

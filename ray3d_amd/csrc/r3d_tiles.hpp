@@ -98,6 +98,12 @@ __device__ __forceinline__ void tile_signal(const gu32 cnt, const int sig_base, 
     asm volatile("" : "+v"(t));      // (opaque: `cnt + 4 t` would be hoisted out of the persistent loop and stay live - and spill - across every tile)
     if (t < units) __hip_atomic_fetch_add(cnt + sig_base + t, (unsigned)sig_add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// ... of a two-source tile: one unit of each source, its own number of granules
+__device__ __forceinline__ void tile_signal2(const gu32 cnt, const int base0, const int add0, const int base1, const int add1) {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    if (t < 2) __hip_atomic_fetch_add(cnt + (t == 0 ? base0 : base1), (unsigned)(t == 0 ? add0 : add1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 // LeakyReLU for slopes in (0, 1] (0.2, 0.01; 1 = linear layer): max(v, slope v) - a multiply and a max instead of
 // multiply, compare, select
 __device__ __forceinline__ float lrelu(const float v, const float slope) { return __builtin_fmaxf(v, v * slope); }
@@ -577,8 +583,14 @@ __device__ __forceinline__ void gemm_tile(ProbRef P, const int row0, const int c
 // SIMD issues 16 + 4 (NB - 4) MFMAs per K tile instead of 32.  The partial sums of a split block are added through LDS
 // before the epilogue (as the split-K tiles do).  Operand paths as in gemm_tile<1, 1>: A through the three-stage ring,
 // weights fragment-ordered straight into VGPRs two K tiles ahead (a split block's wavefront requests its own q only).
+// Two sources (n0 < NB; r3d_schedule.cpp, pack_runs): blocks 0 .. n0 - 1 are the LAST n0 blocks of unit `row0` of P (col0 = N - 32 n0),
+// blocks n0 .. NB - 1 the FIRST blocks of unit `row0b` of P2 - the next unit of P or the first unit of another problem of the same K.
+// The second source's A rows are staged in rows 32 .. 63 of a ring stage, which a one-source tile fills with a second copy of its
+// own rows; which rows and which weights a slot reads is an offset and a descriptor fixed before the K loop, the loop is the
+// same code.  Bias, slope, residual, output and row clamp are chosen per block in the epilogue.
 template <int NB>
-__device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const int col0, float *smem, long long *dbg, const LateWait late = LateWait{0, 0, nullptr, nullptr, 0}) {
+__device__ __forceinline__ void gemm_tile_nb(ProbRef P, ProbRef P2, const int row0, const int row0b, const int col0, const int n0, float *smem, long long *dbg,
+                                             const LateWait late = LateWait{0, 0, nullptr, nullptr, 0}) {
     static_assert(NB >= 4 && NB <= 7, "NB = 8 is gemm_tile<1, 1>");   // (NB = 4: the narrow end of an uneven row - wavefronts 4-7 only stage)
     constexpr int SF = STAGE_FLOATS;
     constexpr int NX = NB - 4;               // quarter-blocks per extra wavefront
@@ -590,7 +602,11 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
     const int li = lane & 31, lh = lane >> 5;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const bool main_w = wave_u < 4;
-    const int M = P.M, K = P.K;
+    const bool two = n0 < NB;                                            // (uniform)
+    // wavefronts 4 - 7 stage rows 32 .. 63: the second source's rows
+    ProbRef PA = two && !main_w ? P2 : P;
+    const int rowA = two && !main_w ? row0b : row0;
+    const int M = PA.M, K = P.K;
     const int nk = K / BK;
     const int srow = tid >> 3, a_kq = (tid & 7) * 4;
     // ---- this wavefront's share, as slots (column block of the tile, q): wavefront w < 4 the four q of block w; wavefront
@@ -606,16 +622,16 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
         s_q[s] = main_w ? s : (NX > 0 ? (xg0 + sc) & 3 : 0);
     }
     // ---- A staging (one segment list, as gemm_tile)
-    const bool multi = P.kend[0] < K;
-    int seg_ld = P.lda[0], seg_k0 = 0, seg_end = P.kend[0], seg_i = 0;
+    const bool multi = PA.kend[0] < K;
+    int seg_ld = PA.lda[0], seg_k0 = 0, seg_end = PA.kend[0], seg_i = 0;
     int a_voff;
     __amdgpu_buffer_rsrc_t arsrc;
     auto open_seg = [&]() {
-        const float *base = P.a[seg_i] + (size_t)row0 * seg_ld;
-        const long long b = ((long long)(M - 1 - row0) * seg_ld + (seg_end < K ? seg_end : K) - seg_k0) * 4;
+        const float *base = PA.a[seg_i] + (size_t)rowA * seg_ld;
+        const long long b = ((long long)(M - 1 - rowA) * seg_ld + (seg_end < K ? seg_end : K) - seg_k0) * 4;
         arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, b < 0x7fffffffLL ? (int)b : 0x7fffffff, 0x00020000);
-        const int gr = row0 + (srow & 31);                               // (staged rows 32 .. 63 re-read the tile's rows)
-        a_voff = (((gr < M ? gr : M - 1) - row0) * seg_ld + a_kq) * 4;
+        const int gr = rowA + (srow & 31);                               // (one source: staged rows 32 .. 63 re-read the tile's rows)
+        a_voff = (((gr < M ? gr : M - 1) - rowA) * seg_ld + a_kq) * 4;
     };
     open_seg();
     auto prep_seg = [&](int kt) {
@@ -623,8 +639,8 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
         while (kt * BK >= seg_end) {
             ++seg_i;
             seg_k0 = seg_end;
-            seg_ld = P.lda[seg_i];
-            seg_end = P.kend[seg_i];
+            seg_ld = PA.lda[seg_i];
+            seg_end = PA.kend[seg_i];
             open_seg();
         }
     };
@@ -639,18 +655,24 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
     };
     // ---- W fragments: one descriptor over the tile's NB column blocks; slot s of K tile kt at scalar offset
     // (s_blk * nk + kt) * 4096 + s_q * 1024 bytes
-    __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+    // (a second-source slot: the second problem's blocks from 0, its own descriptor - the two may lie in different arenas)
+    const __amdgpu_buffer_rsrc_t wrsrc0 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(P.w + (size_t)(col0 >> 5) * nk * 1024), 0, NB * nk * 4096, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P2.w), 0, NB * nk * 4096, 0x00020000);
     const int w_voff = lane * 16;
+    __amdgpu_buffer_rsrc_t wrsrc[4];
     int w_soff[4], a_off[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        w_soff[s] = __builtin_amdgcn_readfirstlane((s_blk[s] * nk) * 4096 + s_q[s] * 1024);
-        a_off[s] = li * LDS_LD + lh * 16 + s_q[s] * 4;                   // lane (i, h) reads A[row i][k = 16 h + 4 q ..] of a stage
+        const bool second = s_blk[s] >= n0;                              // (uniform)
+        wrsrc[s] = second ? wrsrc1 : wrsrc0;
+        w_soff[s] = __builtin_amdgcn_readfirstlane(((second ? s_blk[s] - n0 : s_blk[s]) * nk) * 4096 + s_q[s] * 1024);
+        // lane (i, h) reads A[row i][k = 16 h + 4 q ..] of a stage; the second source's rows are staged rows 32 .. 63
+        a_off[s] = (second ? 32 * LDS_LD : 0) + li * LDS_LD + lh * 16 + s_q[s] * 4;
     }
     const int last = nk - 1;
     // One role's whole K loop: NS slots per K tile, slot s into acc[s % NACC] (main: one accumulator, extra: one per slot)
-    auto k_loop = [&](auto ns_tag, auto nacc_tag, f32x16 *acc) {
+    auto k_loop = [&](auto ns_tag, auto nacc_tag, f32x16 *acc, const __amdgpu_buffer_rsrc_t (&wrs)[4]) {
         constexpr int NS = decltype(ns_tag)::value, NACC = decltype(nacc_tag)::value;
         constexpr int NSL = NS > 0 ? NS : 1;                             // (a wavefront without a share still stages A)
         f32x4 rb[NSL], rbn[NSL], rbn2[NSL];
@@ -658,7 +680,7 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
             if (NS == 0) return;
 #pragma unroll
             for (int s = 0; s < NSL; ++s)
-                dst[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, w_voff, w_soff[s] + kt * 4096, 0));
+                dst[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs[s], w_voff, w_soff[s] + kt * 4096, 0));
         };
         load_w(0, rb);
         load_w(1 < last ? 1 : last, rbn);
@@ -718,7 +740,9 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
         f32x16 acc[1];
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[0][r] = 0.0f;
-        k_loop(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{}, acc);
+        // (a main wavefront's four slots are one block: one descriptor)
+        const __amdgpu_buffer_rsrc_t wm[4] = {wrsrc[0], wrsrc[0], wrsrc[0], wrsrc[0]};
+        k_loop(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{}, acc, wm);
         fin = acc[0];
         R3D_TSTAMP(2);
         if (NX > 0) __syncthreads();                                     // (the extra wavefronts publish their partial sums)
@@ -729,7 +753,7 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
         for (int a = 0; a < NA_; ++a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][r] = 0.0f;
-        k_loop(std::integral_constant<int, NX>{}, std::integral_constant<int, NA_>{}, acc);
+        k_loop(std::integral_constant<int, NX>{}, std::integral_constant<int, NA_>{}, acc, wrsrc);
         // the split blocks' partial sums -> LDS (the ring is idle: the K loop ended on a barrier), quarter-block g at g * PART;
         // then wavefront 4 + e adds up block 4 + e: quarter-blocks 4 e .. 4 e + 3
         if (NX > 0) {
@@ -751,6 +775,38 @@ __device__ __forceinline__ void gemm_tile_nb(ProbRef P, const int row0, const in
         }
     }
     R3D_TSTAMP(3);
+    // ---- epilogue of a two-source tile: the same transposition; every block has its own bias, slope, residual, output rows and row
+    // clamp.  A block's 32 x 32 floats are 256 16-byte pieces - four wavefronts - so the source is uniform per wavefront.
+    if (two) {
+        const bool writer = wave_u < NB, wsecond = wave_u >= n0;
+        const float slope = wsecond ? P2.slope : P.slope;
+        const float bias = writer ? gload1((wsecond ? P2.bias + (wave_u - n0) * 32 : P.bias + col0 + wave_u * 32) + li) : 0.0f;
+        __syncthreads();                                                 // the partial sums have been read
+        if (writer) {
+            float *wr = smem + (4 * lh) * EPI_LD + wave * 32 + li;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) wr[((r & 3) + 8 * (r >> 2)) * EPI_LD] = lrelu(fin[r] + bias, slope);
+        }
+        __syncthreads();
+        const int lr = (tid >> 3) & 31, c4 = (tid & 7) * 4;
+#pragma unroll
+        for (int it = 0; it < (NB + 1) / 2; ++it) {
+            const int blk = (wave_u >> 2) + 2 * it;                      // (uniform)
+            if (blk >= NB) break;
+            const bool second = blk >= n0;
+            ProbRef Q = second ? P2 : P;
+            const int qrow = second ? row0b : row0, qcol = second ? (blk - n0) * 32 : col0 + blk * 32;
+            if (qrow + lr >= Q.M) continue;
+            const float *res = Q.res;
+            const int ldc = Q.ldc, ldr = Q.ldr;
+            const __amdgpu_buffer_rsrc_t crs = act_rsrc(Q.c + (size_t)qrow * ldc + qcol);
+            const __amdgpu_buffer_rsrc_t rrs = act_rsrc(res ? res + (size_t)qrow * ldr + qcol : Q.c);
+            f32x4 v = *reinterpret_cast<const f32x4 *>(smem + lr * EPI_LD + blk * 32 + c4);
+            if (res) v += act_load4(rrs, (lr * ldr + c4) * 4);
+            act_store4(crs, (lr * ldc + c4) * 4, v);
+        }
+        __syncthreads();
+    } else
     // ---- epilogue: the NB slabs of 32 columns transposed through LDS, 16-byte accesses along the rows (store_tile)
     {
         constexpr int COLS = NB * 32, TPR = COLS / 4;                    // threads per output row
@@ -3027,11 +3083,11 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
         const int pi = __builtin_amdgcn_readfirstlane(td.x & 0xff);
         const bool new_prob = pi != prev_pi;
         prev_pi = pi;
-        const int mi = __builtin_amdgcn_readfirstlane(td.x >> 8);
+        const int mi = __builtin_amdgcn_readfirstlane((td.x >> 8) & 0xff);
         const int row0 = __builtin_amdgcn_readfirstlane(td.y);
         const int col0 = __builtin_amdgcn_readfirstlane(td.z);
         const int ks = __builtin_amdgcn_readfirstlane(td.w);      // split-K factor of this tile (1, 2 or 4)
-        int sig_base = 0, sig_add = 0, tflags = 0;
+        int sig_base = 0, sig_add = 0, tflags = 0, sig_base2 = -1;
         LateWait late{0, 0, nullptr, nullptr, 0};
         TileDeps tdep{nullptr, 0, nullptr, nullptr, false, nullptr, 0};
         if constexpr (DEP) {
@@ -3168,11 +3224,17 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
                 break;
             }
             }
-            if (ks > NB_CODE) {          // a single-unit tile of 4 .. 7 column blocks
-                if (ks == NB_CODE + 4) gemm_tile_nb<4>(P, row0, col0, smem, dbg, late);
-                else if (ks == NB_CODE + 5) gemm_tile_nb<5>(P, row0, col0, smem, dbg, late);
-                else if (ks == NB_CODE + 6) gemm_tile_nb<6>(P, row0, col0, smem, dbg, late);
-                else gemm_tile_nb<7>(P, row0, col0, smem, dbg, late);
+            if (ks > NB_CODE) {          // a single-unit tile of 4 .. 7 column blocks, of one source or two (descriptor int 0, from bit 16)
+                const int pi2 = __builtin_amdgcn_readfirstlane(td.x >> 16) - 1;
+                const int pj = pi2 >= 0 ? pi2 : pi;
+                ProbRef P2 = DEP ? *((const GemmProb __attribute__((address_space(4))) *)fargs->probs + pj) : args->p[pj];
+                const int n0 = pi2 >= 0 ? (P.N - col0) >> 5 : ks - NB_CODE;
+                const int row0b = pi2 < 0 ? row0 : pi2 == pi ? row0 + 32 : 0;
+                sig_base2 = pi2 >= 0 ? tflags >> 8 : -1;
+                if (ks == NB_CODE + 4) gemm_tile_nb<4>(P, P2, row0, row0b, col0, n0, smem, dbg, late);
+                else if (ks == NB_CODE + 5) gemm_tile_nb<5>(P, P2, row0, row0b, col0, n0, smem, dbg, late);
+                else if (ks == NB_CODE + 6) gemm_tile_nb<6>(P, P2, row0, row0b, col0, n0, smem, dbg, late);
+                else gemm_tile_nb<7>(P, P2, row0, row0b, col0, n0, smem, dbg, late);
                 break;
             }
             if (ks > 1) {
@@ -3214,7 +3276,10 @@ __device__ __forceinline__ void gemm_persistent(float *smem) {
                 tile_drain();
                 __syncthreads();
                 // (test hook: workgroup 0's n-th tile of this kind never reports - what the bounded spins are for)
-                if (!(blockIdx.x == 0 && plain_seen++ == fargs->fault_tile1 - 1)) tile_signal(cnt, sig_base, sig_add, mi);
+                if (!(blockIdx.x == 0 && plain_seen++ == fargs->fault_tile1 - 1)) {
+                    if (sig_base2 >= 0) tile_signal2(cnt, sig_base, sig_add, sig_base2, ks - NB_CODE - sig_add);
+                    else tile_signal(cnt, sig_base, sig_add, mi);
+                }
 #ifdef R3D_TIMING
                 if (dbg_arg && threadIdx.x == 0) {
                     dbg_arg[16384 + (long long)t * 4 + 2] = wall_clock64();                               // tile finished

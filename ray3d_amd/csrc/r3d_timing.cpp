@@ -51,9 +51,10 @@ void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArg
                 for (int w = 0; w < fw.grid; ++w)
                     for (int t = fw.h_wgoff[w]; t < fw.h_wgoff[w + 1]; ++t) {
                         const int *d = &fw.h_tiles[(size_t)t * FWD_TILE_INT4 * 4];
-                        fprintf(f, "T %d %d %d %d %d %d %d %d %.2f %.2f %.2f %lld\n", w, t, d[0] & 0xff, d[0] >> 8, d[1], d[2], d[3], d[4],
+                        fprintf(f, "T %d %d %d %d %d %d %d %d %.2f %.2f %.2f %lld %d\n", w, t, d[0] & 0xff, tile_units(d[0]), d[1], d[2], d[3], d[4],
                                 tt[(size_t)t * 4] ? (tt[(size_t)t * 4] - w0) / 100.0 : -1.0, tt[(size_t)t * 4 + 1] ? (tt[(size_t)t * 4 + 1] - w0) / 100.0 : -1.0,
-                                tt[(size_t)t * 4 + 2] ? (tt[(size_t)t * 4 + 2] - w0) / 100.0 : -1.0, tt[(size_t)t * 4 + 3]);
+                                tt[(size_t)t * 4 + 2] ? (tt[(size_t)t * 4 + 2] - w0) / 100.0 : -1.0, tt[(size_t)t * 4 + 3],
+                                tile_src2(d[0]));      // (last: a two-source tile's second problem, or -1)
                     }
                 fclose(f);
             }

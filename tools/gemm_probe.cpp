@@ -163,7 +163,7 @@ int main(int argc, char **argv) {
             if (bad) { if (nbad < 40) printf(" %d:%d", u, bad); ++nbad; }
         }
         printf("  (%d of %d units bad)\n", nbad, units);
-        for (int t = 0; t < 12 && t < (int)tiles.size(); ++t) printf("tile %d: prob %d mi %d row0 %d col0 %d\n", t, tiles[t].x & 255, tiles[t].x >> 8, tiles[t].y, tiles[t].z);
+        for (int t = 0; t < 12 && t < (int)tiles.size(); ++t) printf("tile %d: prob %d mi %d row0 %d col0 %d\n", t, tiles[t].x & 255, tile_units(tiles[t].x), tiles[t].y, tiles[t].z);
         if (getenv("PROBE_DUMPROW")) {
             const int r = atoi(getenv("PROBE_DUMPROW"));
             for (int rr = r; rr < r + 3; ++rr) { printf("row %d got:", rr);
@@ -200,7 +200,7 @@ int main(int argc, char **argv) {
                 for (int t = 0; t < 8 && t < wgoff[w + 1] - wgoff[w]; ++t) {
                     const long long *q = &ht[w * 64 + t * 8];
                     const int4 td = tiles[wgoff[w] + t];
-                    printf("  wg %2d tile %d (p%d mi%d ks%d): %7.2f %7.2f %7.2f %7.2f %7.2f | %6.2f %6.2f %6.2f %6.2f\n", w, t, td.x & 255, td.x >> 8, td.w,
+                    printf("  wg %2d tile %d (p%d mi%d ks%d): %7.2f %7.2f %7.2f %7.2f %7.2f | %6.2f %6.2f %6.2f %6.2f\n", w, t, td.x & 255, tile_units(td.x), td.w,
                            (q[0] - w0) / 100.0, (q[1] - w0) / 100.0, (q[2] - w0) / 100.0, (q[3] - w0) / 100.0, (q[4] - w0) / 100.0,
                            (q[1] - q[0]) / 100.0, (q[2] - q[1]) / 100.0, (q[3] - q[2]) / 100.0, (q[4] - q[3]) / 100.0);
                 }
@@ -208,7 +208,7 @@ int main(int argc, char **argv) {
         printf("chunk: tiles units | start_us end_us | cycles | eff GHz\n");
         for (int w = 0; w < ss.nwg; w += (w < 8 || w > ss.nwg - 9) ? 1 : 13) {
             int units = 0;
-            for (int t = wgoff[w]; t < wgoff[w + 1]; ++t) units += tiles[t].x >> 8;
+            for (int t = wgoff[w]; t < wgoff[w + 1]; ++t) units += tile_units(tiles[t].x);
             const double us0 = (hw[w * 4 + 2] - w0) / 100.0, us1 = (hw[w * 4 + 3] - w0) / 100.0;
             printf("  %3d: %d %2d | %7.1f %7.1f | %7lld | %.2f\n", w, wgoff[w + 1] - wgoff[w], units, us0, us1,
                    hw[w * 4 + 1] - hw[w * 4 + 0], (hw[w * 4 + 1] - hw[w * 4 + 0]) / (us1 - us0) / 1e3);

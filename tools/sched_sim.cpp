@@ -29,7 +29,7 @@ int main(int argc, char **argv) {
         std::vector<int4> tiles; std::vector<int> wgoff; StageSchedule ss{};
         schedule_stage(s.p, nwg, 6, tiles, wgoff, ss);
         std::map<int, int> shapes;
-        for (auto &t : tiles) shapes[(t.w << 8) | (t.x >> 8)]++;
+        for (auto &t : tiles) shapes[(t.w << 8) | tile_units(t.x)]++;
         printf("%-12s ks_cap %d grid %3d tiles %4d imbalance %.3f  shapes:", s.name, ss.ks, ss.nwg, ss.ntiles, ss.imbalance);
         for (auto &kv : shapes) printf(" ks%d/mi%d x%d", kv.first >> 8, kv.first & 255, kv.second);
         printf("\n");
@@ -37,7 +37,7 @@ int main(int argc, char **argv) {
             std::map<std::string, int> hist;
             for (int c = 0; c < ss.nwg; ++c) {
                 char buf[128]; int n = 0; int cnt[5] = {0, 0, 0, 0, 0}; int kt = 0;
-                for (int t = wgoff[c]; t < wgoff[c + 1]; ++t) { cnt[tiles[t].w] += tiles[t].x >> 8; kt += (tiles[t].x >> 8) * ((s.p[tiles[t].x & 255].nk + tiles[t].w - 1) / tiles[t].w); }
+                for (int t = wgoff[c]; t < wgoff[c + 1]; ++t) { cnt[tiles[t].w] += tile_units(tiles[t].x); kt += tile_units(tiles[t].x) * ((s.p[tiles[t].x & 255].nk + tiles[t].w - 1) / tiles[t].w); }
                 n = snprintf(buf, sizeof buf, "k1:%d k2:%d k4:%d iters:%d", cnt[1], cnt[2], cnt[4], kt);
                 hist[buf]++;
             }

@@ -225,6 +225,24 @@ int r3d_forward_pair(r3d_model *pos, r3d_model *trj, const r3d_input *in, int64_
                      float *out_dev, float *out_trj_dev, void *workspace_dev,
                      size_t workspace_bytes, void *hip_stream);
 
+/* r3d_forward_pair with the two networks' outputs kept apart, for callers that follow the reference's evaluation to the
+ * letter (lib/train_val/trainer.py:337-353): it calls pos(x), pos(x_flip), trj(x), trj(x_flip), averages the flip pass
+ * per network and only then adds the trajectory to the pose - so it needs both outputs of one pass separately.
+ *   out_pos_dev (B,1,J,3): the pos network alone;  out_trj_dev (B,1,1,3): the trj network - required.
+ * Everything else is r3d_forward_pair: the same plan, tile schedule, launches and r3d_workspace_bytes, every input mode and
+ * window_stride, the single-launch / staged / bf16x3 / <= 32-window forms, the hipGraph capture and lanes rules, the
+ * non-finite-input contract, and R3D_ERR_ABORTED through r3d_status with BOTH outputs NaN.  Only the decode kernel's last
+ * add differs (a mode of the same two kernels).  Either model NULL or either output NULL: R3D_ERR_ARG, before any HIP call.
+ * Contract:
+ *   - out_trj_dev has the bits of r3d_forward_pair's out_trj_dev;
+ *   - out_pos_dev + out_trj_dev (a float32 add, the trajectory broadcast over the joints) has the bits of r3d_forward_pair's
+ *     out_dev: (v + bj) + 0 followed by + trj rounds like (v + bj) + trj;
+ *   - against r3d_forward(pos, ...) alone the plan and the order of summation differ: out_pos_dev agrees with it within the
+ *     library's usual bound against the reference, not bit for bit. */
+int r3d_forward_pair_split(r3d_model *pos, r3d_model *trj, const r3d_input *in, int64_t B,
+                           float *out_pos_dev, float *out_trj_dev, void *workspace_dev,
+                           size_t workspace_bytes, void *hip_stream);
+
 /* ---- errors of a forward that surface on the device; per-handle options ---- */
 
 /* The reference's seam reports errors as Python exceptions.  A forward is asynchronous, so what can only

@@ -32,7 +32,7 @@ EXPORTS = (
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
-    "r3d_clips_project",
+    "r3d_clips_project", "r3d_forward_pair_split",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
@@ -169,6 +169,7 @@ def load():
     lib.r3d_input_workspace_bytes.restype = C.c_size_t
     lib.r3d_forward.argtypes = [vp, C.POINTER(Input), C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_forward_pair.argtypes = [vp, vp, C.POINTER(Input), C.c_int64, vp, vp, vp, C.c_size_t, vp]
+    lib.r3d_forward_pair_split.argtypes = [vp, vp, C.POINTER(Input), C.c_int64, vp, vp, vp, C.c_size_t, vp]
     lib.r3d_prepare.argtypes = [vp, vp, C.c_int64]
     lib.r3d_release.argtypes = [vp, vp, C.c_int64]
     lib.r3d_precision.argtypes = [vp]
@@ -234,6 +235,7 @@ class Handle:
 
     def __init__(self, cfg):
         lib = self._lib = load()          # (a handle stays with the library that created it: see use_hooks)
+        self.options = {}                 # R3D_OPT_* -> the value last set through set_option
         c = Config(C.sizeof(Config), R3D_KIND_POS if cfg.kind == "pos" else R3D_KIND_TRJ, cfg.num_joints,
                    cfg.in_features, len(cfg.filter_widths), cfg.channels, cfg.latent, cfg.stage,
                    cfg.extrinsic_dim if cfg.camera_embedding else 0,
@@ -269,6 +271,7 @@ class Handle:
 
     def set_option(self, option: int, value: int):
         check(self._lib.r3d_set_option(self.ptr, option, value), "r3d_set_option")
+        self.options[int(option)] = int(value)
 
     def lane_stream(self, lane: int) -> int:
         """r3d_lane_stream: the hipStream_t of lane `lane` of a handle with R3D_OPT_LANES (the library owns it)."""
@@ -531,3 +534,10 @@ def forward_pair(pos: Handle, trj: Handle, inp: Input, batch: int, out_ptr: int,
                  out_trj_ptr: Optional[int], ws_ptr: int, ws_bytes: int, stream: int):
     check(pos._lib.r3d_forward_pair(pos.ptr, trj.ptr, C.byref(inp), batch, out_ptr, out_trj_ptr,
                                   ws_ptr, ws_bytes, stream), "r3d_forward_pair")
+
+
+def forward_pair_split(pos: Handle, trj: Handle, inp: Input, batch: int, out_pos_ptr: int,
+                       out_trj_ptr: int, ws_ptr: int, ws_bytes: int, stream: int):
+    """r3d_forward_pair_split: r3d_forward_pair with the pos network's output and the trajectory kept apart (both required)."""
+    check(pos._lib.r3d_forward_pair_split(pos.ptr, trj.ptr, C.byref(inp), batch, out_pos_ptr, out_trj_ptr,
+                                        ws_ptr, ws_bytes, stream), "r3d_forward_pair_split")

@@ -286,6 +286,15 @@ int r3d_forward_pair(r3d_model *pos, r3d_model *trj, const r3d_input *in, int64_
     return forward_run(p, t, in, B, out_dev, out_trj_dev, ws, ws_bytes, stream);
 }
 
+int r3d_forward_pair_split(r3d_model *pos, r3d_model *trj, const r3d_input *in, int64_t B, float *out_pos_dev, float *out_trj_dev,
+                           void *ws, size_t ws_bytes, void *stream) {
+    Model *p = reinterpret_cast<Model *>(pos), *t = reinterpret_cast<Model *>(trj);
+    if (!p || !t) { set_error("r3d_forward_pair_split: both models are required"); return R3D_ERR_ARG; }
+    if (!out_pos_dev || !out_trj_dev) { set_error("r3d_forward_pair_split: both outputs are required"); return R3D_ERR_ARG; }
+    if (p->cfg.kind != R3D_KIND_POS || t->cfg.kind != R3D_KIND_TRJ) { set_error("r3d_forward_pair_split: (pos, trj) expected in that order"); return R3D_ERR_ARG; }
+    return forward_run(p, t, in, B, out_pos_dev, out_trj_dev, ws, ws_bytes, stream, /*split=*/true);
+}
+
 int r3d_profile_enable(r3d_model *m, int on) {
     Model *mm = reinterpret_cast<Model *>(m);
     if (!mm) { set_error("r3d_profile_enable: null model"); return R3D_ERR_ARG; }

@@ -328,6 +328,7 @@ struct Call {
     const unsigned *abort_flag = nullptr;
     Recorder rec{nullptr, nullptr};
     int stage_no = 0;
+    bool split = false;                    // r3d_forward_pair_split: the decode keeps pos and trj apart
 
     // the profile record around a launch: begin .. launch .. end
     int begin(const char *kernel, int blocks, double flops, double bytes) {
@@ -772,6 +773,7 @@ int decoder_tail(Call &c) {
     da.has_trj = pl->trj_model >= 0;
     da.out = c.out;
     da.out_trj = da.has_pos ? c.out_trj : nullptr;
+    da.split = c.split && da.has_pos && da.has_trj && da.out_trj != nullptr;
     da.abort_flag = c.abort_flag;
     da.status = a->status_host;
     double dec_flops = 0;
@@ -813,10 +815,11 @@ int relay_done(Call &c) {
 
 }  // namespace
 
-// One forward of (a, b) - r3d_forward / r3d_forward_pair - as the steps above, in this order
+// One forward of (a, b) - r3d_forward / r3d_forward_pair / r3d_forward_pair_split - as the steps above, in this order
 int forward_run(Model *a, Model *b, const r3d_input *in, int64_t B, float *out, float *out_trj, void *ws, size_t ws_bytes,
-                void *stream) {
+                void *stream, bool split) {
     Call c{a, b, in, B, out, out_trj, ws, ws_bytes, stream, (hipStream_t)stream};
+    c.split = split;
     int rc = check_call(c);
     if (rc == R3D_OK) rc = redirect_px(c);
     if (rc == R3D_OK) rc = pick_plan(c);

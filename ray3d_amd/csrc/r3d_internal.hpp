@@ -206,7 +206,8 @@ struct DecodeArgs {
     int J;
     long long B;
     float *out;                // pos: (B, J, 3);  trj-only: (B, 3)
-    float *out_trj;            // optional (B, 3)
+    float *out_trj;            // optional (B, 3); required with `split`
+    int split;                 // pair only (r3d_forward_pair_split): `out` is the pos network alone, the trajectory goes to out_trj only
     const unsigned *abort_flag;   // single-launch forward: nonzero when a dependency spin gave up - the outputs become NaN
     unsigned *status;             // ... and this word (pinned host memory of the handle: Model::status_host) becomes 1 - r3d_status
     int slot[5 * 16];          // flat pos output index -> element of (J,3) it lands in
@@ -528,7 +529,8 @@ int dist_check(const Model *a, const r3d_input *in, bool need_cam);           //
 size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B);
 struct FwdKeys { int cu_limit, nwg, lane_key0, nlanes; };                      // lane keys lane_key0 .. lane_key0 + nlanes - 1 (schedule_key)
 FwdKeys forward_keys(const Model *a, const Model *b);
-int forward_run(Model *a, Model *b, const r3d_input *in, int64_t B, float *out, float *out_trj, void *ws, size_t ws_bytes, void *stream);
+int forward_run(Model *a, Model *b, const r3d_input *in, int64_t B, float *out, float *out_trj, void *ws, size_t ws_bytes, void *stream,
+                bool split = false);
 // what a call runs, decided where the driver and the census hook (r3d_debug_forward_census) both ask: the names of its launch records,
 // whether its first levels read the per-frame buffer, whether it is one persistent launch
 const char *stage_kernel_name(int kind, bool uv_launch, bool b3_launch);

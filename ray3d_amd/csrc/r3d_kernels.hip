@@ -268,7 +268,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs &a) {
         rj.dot(hv[i & 1], v);
         if (live && lane == 0) {
 #pragma unroll
-            for (int n = 0; n < 3; ++n) a.out[b * (a.J * 3) + e + n] = v[n] + bj[n] + trj[n] + poison;
+            for (int n = 0; n < 3; ++n)     // (a.split: a kernel argument, the same for every wavefront; its trajectory went to out_trj above)
+                a.out[b * (a.J * 3) + e + n] = a.split ? v[n] + bj[n] + poison : v[n] + bj[n] + trj[n] + poison;
         }
     }
 }

@@ -94,6 +94,7 @@ class LiftModule(nn.Module):
         self._staged = False
         self._spin_timeout_ms: Optional[int] = None
         self._cu_limit = 0
+        self._generation = 0          # bumped whenever the weights may have changed (_invalidate): what the pair seam compares
         self._ws = _Workspace()
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
@@ -114,6 +115,7 @@ class LiftModule(nn.Module):
     # ---- weight sync ---------------------------------------------------------------------
     def _invalidate(self):
         self._synced = False
+        self._generation = getattr(self, "_generation", 0) + 1
 
     def _apply(self, fn, *args, **kwargs):   # .cuda() / .to() / .float() move the tensors
         self._invalidate()
@@ -232,11 +234,23 @@ class _SingleDeviceParallel(nn.Module):
     like from the outside - a ``.module`` attribute and 'module.'-prefixed state_dict keys - without
     the per-call replicate/scatter/gather: multi-GPU here is one process per GPU (ray3d_amd.dist)."""
 
-    def __init__(self, module: LiftModule):
+    def __init__(self, module: LiftModule, seam: Optional["_PairSeam"] = None):
         super().__init__()
         self.module = module
+        self._seam = seam          # shared with the other network's wrapper (Model); not a Module: no state_dict entry
 
     def forward(self, *args, **kwargs):
+        seam = self._seam
+        if seam is not None and not kwargs and len(args) == 2 and all(torch.is_tensor(a) for a in args):
+            out = seam.call(self.module.KIND, args[0], args[1])
+            if out is not None:
+                return out
+        # DataParallel's scatter: CPU tensor arguments go to the module's device (lib/train_val/trainer.py:304-313 passes
+        # CPU inputs_2d / inputs_param); the outputs stay there - the caller's .cpu() brings them back
+        dev = _module_device(self.module)
+        if dev is not None and dev.type == "cuda":
+            args = tuple(_to_device(a, dev) for a in args)
+            kwargs = {k: _to_device(v, dev) for k, v in kwargs.items()}
         return self.module(*args, **kwargs)
 
     def receptive_field(self):
@@ -248,10 +262,111 @@ class _SingleDeviceParallel(nn.Module):
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
 
-class Model(object):
-    """Factory with the reference's surface (lib/model/__init__.py:5-62)."""
+def _module_device(m: nn.Module):
+    for t in m.parameters():
+        return t.device
+    return None
 
-    def __init__(self, model_config: dict, data_config: Optional[dict] = None, is_train: bool = True):
+
+def _to_device(a, dev):
+    return a.to(dev) if torch.is_tensor(a) and a.device.type == "cpu" else a
+
+
+_fuse_pair_default = False
+
+
+def fuse_pair_default(on: Optional[bool] = None) -> bool:
+    """What ``Model(...)`` takes for ``fuse_pair`` when the caller does not say (False unless set here): the switch for code
+    that builds its models through the reference's unchanged ``Model(model_config, data_config, is_train)`` call.  Sets it
+    when `on` is given; returns the value in force.  Models built before a change keep what they were built with."""
+    global _fuse_pair_default
+    if on is not None:
+        _fuse_pair_default = bool(on)
+    return _fuse_pair_default
+
+
+class _PairSeam:
+    """One pair launch behind the reference's two module calls.  Shared by the two wrappers Model returns.
+    When on, ``pos(x, p)`` runs Ray3DLifter.forward_split once, returns the pose and parks the trajectory; a following
+    ``trj(x, p)`` on the same inputs takes the parked tensor (and drops the entry) instead of running the trj network.  The
+    park holds the two most recent pos calls: the reference's order is pos, pos_flip, trj, trj_flip
+    (lib/train_val/trainer.py:337-353).
+
+    A hit needs: the same caller tensor OBJECTS for x and param (the entry keeps strong references, so a freed-and-reused
+    address cannot match), each at the ``_version`` it had (any in-place edit in between is a miss), the same device and
+    current stream, both modules' weight generations unchanged and both in eval mode.  Anything else is a miss: ``call``
+    returns None and the wrapper runs its network alone, as without the seam.  Not fused at all (silently): while either
+    handle has lanes or a CU limit, or the two modules sit on different devices."""
+
+    DEPTH = 2
+
+    def __init__(self, pos: LiftModule, trj: LiftModule, on: bool = False):
+        self.pos, self.trj = pos, trj
+        self.on = bool(on)
+        self._lifter: Optional["Ray3DLifter"] = None
+        self._park: list = []
+
+    # -- the three things a host-only test replaces: where a stream is asked for, an upload, the device forward
+    def _stream_of(self, dev) -> int:
+        return torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+
+    def _upload(self, t: torch.Tensor, dev) -> torch.Tensor:
+        return t.to(dev)
+
+    def _split(self, x: torch.Tensor, p: torch.Tensor):
+        if self._lifter is None:
+            self._lifter = Ray3DLifter(self.pos, self.trj)
+        return self._lifter.forward_split(x, p)
+
+    def release(self):
+        self._park = []
+
+    def _fusible(self):
+        """The device the pair runs on when a pos call may be fused right now, else None."""
+        if not self.on or self.pos.training or self.trj.training:
+            return None
+        for m in (self.pos, self.trj):
+            h = m._handle
+            if m._cu_limit or (h is not None and h.options.get(_capi.R3D_OPT_LANES, 0) > 1):
+                return None
+        dev = _module_device(self.pos)
+        if dev is None or dev != _module_device(self.trj):
+            return None
+        return dev
+
+    def _key(self, x, p, dev):
+        return (x._version, p._version, dev, self._stream_of(dev), self.pos._generation, self.trj._generation)
+
+    def call(self, kind: str, x: torch.Tensor, p: torch.Tensor):
+        """The wrapper's forward asks here first; None: not served, run the network alone."""
+        dev = self._fusible()
+        if dev is None:
+            self._park = []
+            return None
+        if x.device.type != "cpu":
+            dev = x.device
+        if kind == "pos":
+            xd = self._upload(x, dev) if x.device.type == "cpu" else x
+            pd = self._upload(p, dev) if p.device.type == "cpu" else p
+            pos, trj = self._split(xd, pd)
+            # (for CPU callers the key is the CPU tensor; the entry holds the device copies the forward reads)
+            self._park.append((x, p, self._key(x, p, dev), trj, xd, pd))
+            del self._park[:-self.DEPTH]
+            return pos
+        for i, e in enumerate(self._park):
+            if e[0] is x and e[1] is p and e[2] == self._key(x, p, dev):
+                del self._park[i]
+                return e[3]
+        return None
+
+
+class Model(object):
+    """Factory with the reference's surface (lib/model/__init__.py:5-62).  `fuse_pair` (None: :func:`fuse_pair_default`, which
+    is False unless set): with a trajectory model, ``pos(x, p)`` followed by ``trj(x, p)`` on the same inputs costs ONE pair
+    launch instead of two whole-chip launches (:class:`_PairSeam`); off, every call runs its own network, as ever."""
+
+    def __init__(self, model_config: dict, data_config: Optional[dict] = None, is_train: bool = True,
+                 fuse_pair: Optional[bool] = None):
         pos_model = RIEModel(config_from_dicts(model_config, "pos"))
         trj_model = RIETrajectoryModel(config_from_dicts(model_config, "trj")) \
             if model_config["TRAJECTORY_MODEL"] else None
@@ -259,11 +374,18 @@ class Model(object):
             if m is not None:
                 m.is_train = is_train
                 m.train(is_train)
+        self._seam = _PairSeam(pos_model, trj_model, fuse_pair_default() if fuse_pair is None else fuse_pair) \
+            if trj_model is not None else None
         if torch.cuda.is_available():
-            pos_model = _SingleDeviceParallel(pos_model).cuda()
-            trj_model = _SingleDeviceParallel(trj_model).cuda() if trj_model is not None else None
+            pos_model = _SingleDeviceParallel(pos_model, self._seam).cuda()
+            trj_model = _SingleDeviceParallel(trj_model, self._seam).cuda() if trj_model is not None else None
         self.pos_model = pos_model
         self.trj_model = trj_model
+
+    def release_parked(self):
+        """Drop the trajectories the pair seam has parked (and the input tensors they keep alive)."""
+        if self._seam is not None:
+            self._seam.release()
 
     def get_pos_model(self):
         return self.pos_model
@@ -422,7 +544,7 @@ class Ray3DLifter(nn.Module):
         return out
 
     def _run(self, mode, x, window_stride, B, param, param_stride, cam=None, cam_stride=0,
-             return_trj=False, out=None, workspace=None, out_trj=None):
+             return_trj=False, out=None, workspace=None, out_trj=None, split=False):
         dev = x.device
         if self.pos.training or self.trj.training:
             raise RuntimeError("ray3d_amd modules are inference-only: call .eval() first")
@@ -442,7 +564,7 @@ class Ray3DLifter(nn.Module):
             if kk is None:
                 caller = torch.cuda.current_stream(dev)
                 with self.lane() as k2:
-                    res = self._run(mode, x, window_stride, B, param, param_stride, cam, cam_stride, return_trj, out, self._lane_ws[k2], out_trj)
+                    res = self._run(mode, x, window_stride, B, param, param_stride, cam, cam_stride, return_trj, out, self._lane_ws[k2], out_trj, split)
                     # the caller's tensors are read / written on the lane's stream: keep them alive until the lane is past this forward
                     # (a caller on a side stream that drops its input right after the call would otherwise get the block back from
                     # the caching allocator and overwrite it on its own stream while the lane still reads it).  Not record_stream on
@@ -465,9 +587,13 @@ class Ray3DLifter(nn.Module):
         nbytes = _capi.input_workspace_bytes(hp, ht, inp, B) if mode in _capi.PX_MODES else _capi.workspace_bytes(hp, ht, B)
         ws = (workspace or self._ws).get(nbytes, dev)
         with torch.cuda.device(dev):
-            _capi.forward_pair(hp, ht, inp, B, out.data_ptr(),
-                               out_trj.data_ptr() if out_trj is not None else None,
-                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+            if split:                  # (the pos network alone in `out`: r3d_forward_pair_split; needs return_trj)
+                _capi.forward_pair_split(hp, ht, inp, B, out.data_ptr(), out_trj.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+            else:
+                _capi.forward_pair(hp, ht, inp, B, out.data_ptr(),
+                                   out_trj.data_ptr() if out_trj is not None else None,
+                                   ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
         return (out, out_trj) if return_trj else out
 
     def forward(self, x: torch.Tensor, param: Optional[torch.Tensor] = None, return_trj: bool = False):
@@ -477,6 +603,18 @@ class Ray3DLifter(nn.Module):
         p = param.detach().to(x.device, torch.float32).contiguous() if self.pos.camera_embedding else None
         return self._run(_capi.R3D_INPUT_RAYS, x, self.receptive_field(), x.shape[0], p,
                          self.pos.extrinsic_dim, return_trj=return_trj)
+
+    def forward_split(self, x: torch.Tensor, param: Optional[torch.Tensor] = None):
+        """forward() with the two networks' outputs kept apart: x (B,RF,J,F), param (B,E) -> ((B,1,J,3) the pos network alone,
+        (B,1,1,3) the trajectory) from the same pass (r3d_forward_pair_split) - what the reference's evaluation adds only after
+        it has averaged the flip pass per network (lib/train_val/trainer.py:337-353).  ``pos + trj`` has the bits of
+        ``forward(x, param)``, and trj those of its ``return_trj`` output.  With lanes it behaves as ``forward(return_trj=True)``
+        does: the outputs are ordered behind :meth:`join_lanes`."""
+        self.pos._check_inputs(x, param)
+        x = x.detach().to(torch.float32).contiguous()
+        p = param.detach().to(x.device, torch.float32).contiguous() if self.pos.camera_embedding else None
+        return self._run(_capi.R3D_INPUT_RAYS, x, self.receptive_field(), x.shape[0], p,
+                         self.pos.extrinsic_dim, return_trj=True, split=True)
 
     def forward_overlapped(self, x: torch.Tensor, param: Optional[torch.Tensor] = None, parts: int = 2):
         """forward() with the batch cut into `parts` row ranges that run concurrently on separate HIP

@@ -99,49 +99,55 @@ def gen_models(only=None):
     for name, (over, batch, out_scale) in CASES.items():
         if only and name not in only:
             continue
-        mc = default_model_config(**over)
-        ref = RefModel(mc, {}, is_train=False)
-        pos, trj = ref.get_pos_model(), ref.get_trj_model()
-        cpos, ctrj = config_from_dicts(mc, "pos"), config_from_dicts(mc, "trj")
-        load_synth(pos, cpos, 1, out_scale)
-        load_synth(trj, ctrj, 2, out_scale)
-        x = synth.synth_rays(batch, cpos, seed=3)
-        p = synth.synth_param(batch, seed=4)
-        nlev = len(cpos.filter_widths)
-        pos_taps = (["LocalLayer_%s" % b for b in cpos.branch_names()] + ["GlobalInfo"]
-                    + ["Integration_%s" % b for b in cpos.branch_names()])
-        if cpos.stage != 1:
-            pos_taps += ["FuseBlocks.%d" % i for i in range(5)]
-        if cpos.camera_embedding:
-            pos_taps += ["embedder"]
-        # per-level pre-activation BN outputs, Torso only (clone happens before inplace LeakyReLU)
-        # (the dilated form keeps every frame of every level: its per-level tensors are not the strided ones)
-        per_level = not mc["DISABLE_OPTIMIZATIONS"]
-        if per_level:
-            pos_taps += ["LocalLayer_Torso.expand_bn"] + ["LocalLayer_Torso.layers_bn.%d" % i
-                                                         for i in range(2 * (nlev - 1))]
-        trj_taps = ["LocalLayer", "GlobalInfo", "Integration"]
-        if per_level:
-            trj_taps += ["LocalLayer.expand_bn"] + ["LocalLayer.layers_bn.%d" % i for i in range(2 * (nlev - 1))]
-        if ctrj.camera_embedding:
-            trj_taps += ["embedder"]
-        out_pos, tp = run_with_taps(pos, x, p, pos_taps)
-        out_trj, tt = run_with_taps(trj, x, p, trj_taps)
-        blob = dict(x=x, param=p, out_pos=out_pos, out_trj=out_trj,
-                    n_state_pos=np.int64(len(pos.state_dict())),
-                    n_state_trj=np.int64(len(trj.state_dict())),
-                    receptive_field=np.int64(pos.receptive_field()))
-        for k, v in tp.items():
-            # per-level taps: keep window 0 only to stay small; channels-first (C, T) as in torch
-            blob["pos/" + k] = v[0] if ("_bn" in k) else v
-        for k, v in tt.items():
-            blob["trj/" + k] = v[0] if ("_bn" in k) else v
-        blob["model_config_keys"] = np.array(sorted(mc.keys()))
-        blob["model_config_vals"] = np.array([str(mc[k]) for k in sorted(mc.keys())])
-        np.savez_compressed(os.path.join(HERE, "model_%s.npz" % name), **blob)
-        print("model_%s: out_pos %s |max| %.3f  out_trj |max| %.3f  states %d/%d" % (
-            name, out_pos.shape, np.abs(out_pos).max(), np.abs(out_trj).max(),
-            len(pos.state_dict()), len(trj.state_dict())))
+        write_model_fixture(name, default_model_config(**over), batch,
+                            lambda module, cfg, seed: load_synth(module, cfg, seed, out_scale))
+
+
+def write_model_fixture(name, mc, batch, load):
+    """model_<name>.npz: the reference's pos and trj modules on synth_rays(batch, seed 3) / synth_param(batch, seed 4), their
+    weights put in by load(module, cfg, seed) (seed 1 for pos, 2 for trj), outputs and taps."""
+    ref = RefModel(mc, {}, is_train=False)
+    pos, trj = ref.get_pos_model(), ref.get_trj_model()
+    cpos, ctrj = config_from_dicts(mc, "pos"), config_from_dicts(mc, "trj")
+    load(pos, cpos, 1)
+    load(trj, ctrj, 2)
+    x = synth.synth_rays(batch, cpos, seed=3)
+    p = synth.synth_param(batch, seed=4)
+    nlev = len(cpos.filter_widths)
+    pos_taps = (["LocalLayer_%s" % b for b in cpos.branch_names()] + ["GlobalInfo"]
+                + ["Integration_%s" % b for b in cpos.branch_names()])
+    if cpos.stage != 1:
+        pos_taps += ["FuseBlocks.%d" % i for i in range(5)]
+    if cpos.camera_embedding:
+        pos_taps += ["embedder"]
+    # per-level pre-activation BN outputs, Torso only (clone happens before inplace LeakyReLU)
+    # (the dilated form keeps every frame of every level: its per-level tensors are not the strided ones)
+    per_level = not mc["DISABLE_OPTIMIZATIONS"]
+    if per_level:
+        pos_taps += ["LocalLayer_Torso.expand_bn"] + ["LocalLayer_Torso.layers_bn.%d" % i
+                                                     for i in range(2 * (nlev - 1))]
+    trj_taps = ["LocalLayer", "GlobalInfo", "Integration"]
+    if per_level:
+        trj_taps += ["LocalLayer.expand_bn"] + ["LocalLayer.layers_bn.%d" % i for i in range(2 * (nlev - 1))]
+    if ctrj.camera_embedding:
+        trj_taps += ["embedder"]
+    out_pos, tp = run_with_taps(pos, x, p, pos_taps)
+    out_trj, tt = run_with_taps(trj, x, p, trj_taps)
+    blob = dict(x=x, param=p, out_pos=out_pos, out_trj=out_trj,
+                n_state_pos=np.int64(len(pos.state_dict())),
+                n_state_trj=np.int64(len(trj.state_dict())),
+                receptive_field=np.int64(pos.receptive_field()))
+    for k, v in tp.items():
+        # per-level taps: keep window 0 only to stay small; channels-first (C, T) as in torch
+        blob["pos/" + k] = v[0] if ("_bn" in k) else v
+    for k, v in tt.items():
+        blob["trj/" + k] = v[0] if ("_bn" in k) else v
+    blob["model_config_keys"] = np.array(sorted(mc.keys()))
+    blob["model_config_vals"] = np.array([str(mc[k]) for k in sorted(mc.keys())])
+    np.savez_compressed(os.path.join(HERE, "model_%s.npz" % name), **blob)
+    print("model_%s: out_pos %s |max| %.3f  out_trj |max| %.3f  states %d/%d" % (
+        name, out_pos.shape, np.abs(out_pos).max(), np.abs(out_trj).max(),
+        len(pos.state_dict()), len(trj.state_dict())))
 
 
 def ref_cameras():

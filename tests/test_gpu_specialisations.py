@@ -9,6 +9,12 @@
   clip calls               against their materialised windows at 2e-5 * max(1, |out|) (another summation order at most);
   captured                 the graph's replay has the bits of the eager call.
 
+A case at 128 workgroups runs on a lifter with set_lanes(2), one at 64 with set_lanes(4) (R3D_OPT_LANES: device CUs / lanes
+workgroups per forward): every call of the case is issued on lane 0's own stream (lifter.lane(0)), then join_lanes() and
+check_status() - a forward that gave up (R3D_ERR_ABORTED) fails the case, nothing is repeated - and set_lanes(0) in a finally.
+Lane forwards do give launch records (the records' events are recorded on the stream the forward runs on, the lane's), so the
+census is held to them exactly as on the whole chip: kernel names and grids, asked of r3d_debug_forward_census at CUs / lanes.
+
 Rays are synth_rays; pixels are uniform over a 1000-pixel image through the reference cameras of tests/golden/cameras.npz;
 per-window cameras cycle over its four H36M S9 rows.
 
@@ -47,6 +53,15 @@ r3d_gemm_uv_f32: enc_tile<2,UV>, enc_tile<3,UV>, first_level_shared<1>, first_le
     first_level_taps<1,K>64,UV>, first_level_taps<2,K<=64,UV>, first_level_taps<2,K>64,UV>, gemm_tile<1,1,pair>,
     gemm_tile<1,1>, gemm_tile<1,2>, gemm_tile<1,4>, gemm_tile<2,1,pair>, gemm_tile<2,1>, gemm_tile<3,1,pair>,
     gemm_tile<3,1>, gemm_tile<4,1,pair>, gemm_tile<4,1>, gemm_tile<5,1>, gemm_tile<6,1>
+
+First executed under test with the workgroup axis (128 / 64: lanes) and the wider configuration domain (six levels, latent 512, 640
+and 768 channels) - 28 more pairs, 274 in all; before, no test of any kind selected them (the case that reaches each):
+r3d_forward_lat / r3d_forward_uv_lat: enc_tile<3,*>, gemm_tile<2,1> (rf729, 26 windows), gemm_tile<3,1>, gemm_tile<4,1> (rf729,
+    31 windows, 128 workgroups), gemm_tile<5,1>, gemm_tile<6,1> (rf729, 23 windows, 64 workgroups), gemm_tile_nb<4>, <5>, <6>
+    (c512, 22 windows, 64 workgroups), gemm_tile_nb<7> (c640 bf16x3, 22 windows, 64 workgroups)
+r3d_forward_b3 / r3d_forward_uv_b3: gemm_tile_nb<5>, gemm_tile_nb<6> (n512 bf16x3, 292 windows)
+r3d_gemm_b3: gemm_tile_nb<4> (c768_rf9 bf16x3, 196 windows), gemm_tile_nb<7> (c640 bf16x3, 292 windows)
+r3d_gemm_uv_b3: gemm_tile<1,2> (j17_rf243_s3 bf16x3 staged, 96 windows, 128 workgroups), gemm_tile<1,4> (the same at 64)
 """
 import functools
 import os
@@ -172,14 +187,38 @@ def _call(lifter, mode, x, stride, B, p=None, cam=None, **kw):
                            0 if (cam is None or cam.dim() == 1) else cam.shape[1], return_trj=True, **kw)
 
 
+def _on_lane(lifter, fn):
+    """fn() - forwards through `lifter` - on lane 0's own stream when the lifter has lanes (on the current stream otherwise), joined
+    and checked: an aborted forward raises here."""
+    with lifter.lane(0):
+        res = fn()
+    lifter.join_lanes()
+    lifter.check_status(DEV)
+    return res
+
+
 @pytest.mark.parametrize("case", sc.CASES, ids=[sc.case_id(c) for c in sc.CASES])
 def test_case_runs_what_the_census_says_and_matches_the_oracle(case):
+    config, b3, form, shape, B, case_nwg = case
+    lifter = _lifter(config, b3, form == "staged")
+    lanes = sc.NWG // case_nwg
+    assert lanes in (1, 2, 4) and (lanes == 1 or form != "captured")
+    try:
+        if lanes > 1:
+            lifter.set_lanes(lanes, DEV)
+            assert lifter.num_lanes() == lanes
+        _run_case(case, lifter, lanes)
+    finally:
+        if lanes > 1:
+            lifter.set_lanes(0, DEV)
+
+
+def _run_case(case, lifter, lanes):
     from ray3d_amd import _capi
-    config, b3, form, shape, B = case
+    config, b3, form, shape, B, _ = case
     if os.environ.get("R3D_BF16X3") is not None and b3 != (os.environ["R3D_BF16X3"] == "1"):
         pytest.skip("R3D_BF16X3 in the environment overrides the configuration key")
     uv, per_window, _ = sc.SHAPES[shape]
-    lifter = _lifter(config, b3, form == "staged")
     assert lifter.precision(DEV) == ("bf16x3" if b3 else "f32")
     inp = _inputs(config, shape, B)
     rf, stride = lifter.receptive_field(), inp["stride"]
@@ -191,17 +230,16 @@ def test_case_runs_what_the_census_says_and_matches_the_oracle(case):
 
     # ---- census against reality: the FIRST call on these buffers (it binds), with launch records
     got = {}
-    recs = lifter.profile_call(lambda: got.update(out=_call(lifter, mode, x, stride, B, p, cam)), DEV)
-    lifter.check_status(DEV)
+    recs = lifter.profile_call(lambda: got.update(out=_on_lane(lifter, lambda: _call(lifter, mode, x, stride, B, p, cam))), DEV)
     out, out_trj = got["out"]
-    nwg = torch.cuda.get_device_properties(dev).multi_processor_count
+    nwg = torch.cuda.get_device_properties(dev).multi_processor_count // lanes
     census = _capi.debug_forward_census(hp, ht, B, stride, nwg=nwg, uv=uv, cam_stride=8 if per_window else 0,
                                         staged=form == "staged", captured=form == "captured")
     launched = [(r["kernel"], r["blocks"]) for r in recs if r["stage"] >= 0]
     print("launches of %s: %s" % (sc.case_id(case), launched))
     assert launched == [(k, blocks) for k, blocks, _ in census], (launched, census)
     kernels = [k for k, _ in launched]
-    if case == ("j17_rf81_s2_big", True, "single", "uv-clip", 200) and os.environ.get("R3D_STAGED") != "1":
+    if case == ("j17_rf81_s2_big", True, "single", "uv-clip", 200, sc.NWG) and os.environ.get("R3D_STAGED") != "1":
         # a clip call on a bf16x3 handle keeps the gathered first level: no per-frame launch, no clip kernel
         assert kernels == ["r3d_bind_f32", "r3d_forward_uv_b3", "r3d_decode_w4_f32"], kernels
 
@@ -213,16 +251,17 @@ def test_case_runs_what_the_census_says_and_matches_the_oracle(case):
     # ---- pixel input: the bits of the same handle fed the rays of those pixels
     if uv:
         if inp["seq_rays"] is not None:
-            r_out, r_trj = _call(lifter, _capi.R3D_INPUT_RAYS, _dev(inp["seq_rays"]), stride, B, p_rows)
+            seq = _dev(inp["seq_rays"])
+            r_out, r_trj = _on_lane(lifter, lambda: _call(lifter, _capi.R3D_INPUT_RAYS, seq, stride, B, p_rows))
         else:
-            r_out, r_trj = _call(lifter, _capi.R3D_INPUT_RAYS, _dev(inp["windows"]), rf, B, p_rows)
-        lifter.check_status(DEV)
+            wins = _dev(inp["windows"])
+            r_out, r_trj = _on_lane(lifter, lambda: _call(lifter, _capi.R3D_INPUT_RAYS, wins, rf, B, p_rows))
         assert torch.equal(out, r_out) and torch.equal(out_trj, r_trj), float((out - r_out).abs().max())
 
     # ---- clip calls: their materialised windows
     if stride == 1:
-        w_out, w_trj = _call(lifter, _capi.R3D_INPUT_RAYS, _dev(inp["windows"]), rf, B, p_rows)
-        lifter.check_status(DEV)
+        wins = _dev(inp["windows"])
+        w_out, w_trj = _on_lane(lifter, lambda: _call(lifter, _capi.R3D_INPUT_RAYS, wins, rf, B, p_rows))
         check_parity(out, w_out.cpu().numpy(), "clip call vs its materialised windows", tol=2e-5 * max(1.0, float(w_out.abs().max())))
         check_parity(out_trj, w_trj.cpu().numpy(), "clip call vs its materialised windows, trj", tol=2e-5 * max(1.0, float(w_trj.abs().max())))
 

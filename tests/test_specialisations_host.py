@@ -1,9 +1,17 @@
 """Census of kernel specialisations, on the host (hooks library, no GPU): which (kernel, tile kind) pairs the library's calls
 run, by r3d_debug_forward_census - the driver's own plan / schedule / kernel / call-form selection plus ONE restatement of the
-persistent loop's dispatch (r3d_hooks.cpp, census_tile_kind) - swept over the domain of tests/specialisation_cases.py at 256
-workgroups.  B runs over every value 1 ... 300 plus 511, 512, 513, 700, 1023, 1024, 1025, 1100 and 4096 for the default model at
-RF 9, 27 and 243; for the other configurations (fixtures, channel counts, one level) the range is thinned to every value up to 140,
-every fourth from there to 300, and the same large sizes (specialisation_cases.sweep_batches) - the whole module stays under a minute.
+persistent loop's dispatch (r3d_hooks.cpp, census_tile_kind) - swept over the domain of tests/specialisation_cases.py at 256,
+128 and 64 workgroups (the whole chip; a lane of R3D_OPT_LANES = 2 or an R3D_OPT_CU_LIMIT of 128; a lane of four).  At 256
+workgroups B runs over every value 1 ... 300 plus 511, 512, 513, 700, 1023, 1024, 1025, 1100 and 4096 for the default model at
+RF 9, 27 and 243; for the other configurations (fixtures, channel counts, one level, and the four of the wider accepted domain:
+six levels, latent 512, 640 and 768 channels) the range is thinned to every value up to 140, every fourth from there to 300, and
+the same large sizes.  At 128 and 64 workgroups every configuration runs every value up to 140 (the small and latency plans, all
+plan switches), every eighth from there to 300 (192, 224 and 256 among them), 1024 and 1025.  The six-level model stops at 300
+windows everywhere (specialisation_cases.sweep_batches).
+
+Wall time of the module, one core: 36 s before the workgroup axis (18 configurations, 256 workgroups only); 119 s with it (22
+configurations, three workgroup counts) - within three times the old time plus the added configurations' share (3 x 36 s x 22 / 18
+= 133 s).  With every fourth value kept to 300 on the two new axes the sweep alone took 128 s: hence every eighth there.
 
 tests/test_gpu_specialisations.py holds every case of the table to the oracle on the GPU, and the census to the launch records."""
 import fnmatch
@@ -21,7 +29,7 @@ UNREACHABLE_KERNELS = {
 
 # Instantiations of the dispatch that no call of the domain selects: (kernel pattern, tile-kind pattern, why).  "code": the
 # selection code excludes it; "domain": a call outside the domain reaches it; "packer": nothing excludes it, but the tile packer
-# (r3d_schedule.cpp, pack / assign) produces it for no swept size at 256 workgroups.
+# (r3d_schedule.cpp, pack / assign) produces it for no swept size at 256, 128 or 64 workgroups.
 UNREACHABLE = [
     # --- code
     ("r3d_forward_clip_*", "first_level_taps<*",
@@ -43,21 +51,16 @@ UNREACHABLE = [
      "domain: in a bf16x3 call the fused first levels of a bf16x3 model carry bf16x3 weights (Layer::bf3_conv); fp32 ones beside "
      "them need a pair with ONE bf16x3 handle - model_config['BF16X3'] sets both"),
     ("r3d_*b3", "gemm_tile<?,1,pair>", "domain: as the first level: the fused pairs of a bf16x3 model run gemm_tile_b3t"),
-    ("r3d_forward_*b3", "gemm_tile_nb<?>",
-     "domain: a bf16x3 model's 1024-wide Linears run gemm_tile_b3; the other layers wide enough for gemm_tile_nb (N >= 512) exist "
-     "with more than 256 channels only, and those plans run launch by launch"),
     # --- packer
     ("r3d_*", "gemm_tile<2,2>", "packer: assign() may give a workgroup two split-K-2 units of a column block; no swept size does"),
-    ("r3d_forward_*lat", "gemm_tile<[2-6],1>",
-     "packer: calls of <= 32 windows spread a launch over min(256, 4 x units) workgroups - one-unit tiles only"),
-    ("r3d_forward_*lat", "enc_tile<3,*", "packer: as above (GlobalInfo's gathered rows: at most two units per tile)"),
-    ("r3d_forward_*lat", "gemm_tile_nb<?>", "packer: pack_nb needs a one-tile-deep launch of whole tiles; not at <= 32 windows"),
+    ("r3d_forward_*b3", "gemm_tile_nb<[47]>",
+     "packer: a bf16x3 model's 1024-wide Linears run gemm_tile_b3; its other layers wide enough for gemm_tile_nb (N >= 512: a latent "
+     "size of 512 or more at <= 256 channels - wider models run launch by launch) are cut into 5- and 6-block tiles at every swept size"),
     ("r3d_gemm_uv_*", "gemm_tile_nb<?>",
      "packer: the launch that gathers is the plan's first; the wide plain layers (N >= 512, K >= 256) read the pyramids' outputs "
      "and sit in later launches"),
-    ("r3d_gemm_b3", "gemm_tile_nb<[47]>", "packer: pack_nb cuts the staged bf16x3 launches' fp32 rows into 5- and 6-block tiles only"),
-    ("r3d_gemm_uv_b3", "gemm_tile<1,[24]>", "packer: no split-K riders in the bf16x3 launch that gathers"),
-    ("r3d_gemm_uv_b3", "gemm_tile_b3<4>", "packer: the bf16x3 Linears beside a gathering first level get tiles of <= 3 units"),
+    ("r3d_gemm_uv_b3", "gemm_tile_b3<4>",
+     "packer: the bf16x3 Linears beside a gathering first level get tiles of <= 3 units at every swept size and workgroup count"),
 ]
 
 
@@ -86,7 +89,7 @@ def test_the_table_reaches_every_pair_the_sweep_reaches(census, reached):
     table = {case: reached[case] if case in reached else frozenset(census.pairs(case)) for case in sc.CASES}
     swept, covered = _union(reached.values()), _union(table.values())
     first = {}
-    for case in sorted(table, key=lambda c: (c[4], sc.CASES.index(c))):
+    for case in sorted(table, key=lambda c: (c[4], sc.CASES.index(c))):        # (ties in B: the whole chip first - the table's order)
         for p in table[case]:
             first.setdefault(p, case)
     print("\ncensus: %d cases swept, %d (kernel, tile kind) pairs, %d cases in the table" % (len(reached), len(swept), len(sc.CASES)))
@@ -139,16 +142,16 @@ def test_the_census_names_the_launches_of_known_calls(census):
     the census: the hook agrees with them without a device."""
     kernels = lambda case: [k for k, _, _ in census.launches(case)]
     # a clip call: the per-frame launch, the bind, r3d_forward_clip_f32, the decoder tail (test_clip_calls_run_the_per_frame_first_layers)
-    assert kernels(("j17_rf81_causal_s3", False, "single", "rays-clip", 200)) == ["r3d_gemm_f32", "r3d_bind_f32", "r3d_forward_clip_f32", "r3d_decode_w4_f32"]
-    assert kernels(("j17_rf81_causal_s3", False, "single", "uv-clip", 200))[:3] == ["r3d_gemm_uv_f32", "r3d_bind_f32", "r3d_forward_clip_uv_f32"]
+    assert kernels(("j17_rf81_causal_s3", False, "single", "rays-clip", 200, sc.NWG)) == ["r3d_gemm_f32", "r3d_bind_f32", "r3d_forward_clip_f32", "r3d_decode_w4_f32"]
+    assert kernels(("j17_rf81_causal_s3", False, "single", "uv-clip", 200, sc.NWG))[:3] == ["r3d_gemm_uv_f32", "r3d_bind_f32", "r3d_forward_clip_uv_f32"]
     # ... which a bf16x3 handle does not take: the gathered first level on the bf16 matrix cores (DESIGN 4.4)
-    assert kernels(("j17_rf81_s2_big", True, "single", "uv-clip", 200)) == ["r3d_bind_f32", "r3d_forward_uv_b3", "r3d_decode_w4_f32"]
+    assert kernels(("j17_rf81_s2_big", True, "single", "uv-clip", 200, sc.NWG)) == ["r3d_bind_f32", "r3d_forward_uv_b3", "r3d_decode_w4_f32"]
     # more than 256 channels: launch by launch, r3d_gemm_enc_* in front (test_forward_uv_on_the_unfused_first_layer_kernel)
-    ks = kernels(("c512", True, "single", "uv-cam8", 97))
+    ks = kernels(("c512", True, "single", "uv-cam8", 97, sc.NWG))
     assert ks[0] == "r3d_gemm_enc_uv_f32" and "r3d_gemm_b3" in ks and not any(k.startswith("r3d_forward") for k in ks)
     # calls of a few windows: the _lat kernel with GEMV tiles, one block of the decoder per wavefront
-    launches = census.launches(("j17_rf27_s3", False, "single", "rays", 3))
+    launches = census.launches(("j17_rf27_s3", False, "single", "rays", 3, sc.NWG))
     assert [k for k, _, _ in launches] == ["r3d_bind_f32", "r3d_forward_lat", "r3d_decode_f32"] and "gemv_run" in launches[1][2]
     # both K kinds of the bf16x3 first level in one pair call, with pixel input
-    hist = census.launches(("j17_rf27_s3", True, "single", "uv-cam8", 97))[1][2]
+    hist = census.launches(("j17_rf27_s3", True, "single", "uv-cam8", 97, sc.NWG))[1][2]
     assert {"first_level_taps_b3<1,K<=64,UV>", "first_level_taps_b3<1,K>64,UV>"} <= set(hist)

@@ -1,6 +1,6 @@
 """The table of tests/specialisation_cases.py: sweeps the census of kernel specialisations (r3d_debug_forward_census, hooks library,
 host only - no GPU) over the domain defined there and prints the COVER list to paste into that module - a greedy cover of every
-(kernel, tile kind) pair the sweep reaches that prefers the smallest B - and, with --table, the census table: per pair the smallest
+(kernel, tile kind) pair the sweep reaches that prefers the smallest B, tier by tier (256 workgroups, then 128, then 64) - and, with --table, the census table: per pair the smallest
 case that reaches it.
 
     python tools/specialisation_cover.py [--table]

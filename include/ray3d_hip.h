@@ -107,6 +107,28 @@ int r3d_set_weight(r3d_model *m, const char *key, const float *host, const int64
  * tensor was not set. */
 int r3d_finalize(r3d_model *m);
 
+/* r3d_finalize from DEVICE-resident tensors: the same fold and repack, run on the device on `hip_stream` - for a model whose
+ * parameters live in device memory and change (a validation pass after every epoch).  `weights_dev` and `numel` are HOST arrays
+ * of `count` entries: entry i is the device pointer and the element count of tensor r3d_weight_key(m, i), contiguous float32 in
+ * torch layout, on the current HIP device.  No weight is copied to the host, nothing waits for the device, and the number of
+ * launches (two, of r3d_undistort_rays_f64's pack argument set, behind one small copy of the pointer table) does not depend on
+ * the number of layers.  The packed image is BIT FOR BIT what r3d_finalize produces from the same values (the same float64
+ * arithmetic, per element, without contraction); non-finite inputs are outside that promise (NaN payloads may differ).
+ * Checked on the host before any device call: count != r3d_num_weights, a null argument or a null entry -> R3D_ERR_ARG; a numel[i]
+ * that is not the tensor's element count -> R3D_ERR_SHAPE; r3d_last_error names the key.  A stream that is being captured is
+ * refused with R3D_ERR_STATE (the call may allocate, and it copies the pointer table from a staging buffer it reuses).
+ * Works on a fresh handle - it allocates the packed arena, zero-fills it on the stream and uploads the gather tables - and on a
+ * finalized one, where it packs IN PLACE: the arena does not move, so plans, prepared (pinned) schedules and captured graphs stay
+ * valid.  r3d_set_weight + r3d_finalize keep working afterwards; the last finalize of either kind wins.  The tensors are only read,
+ * and must stay alive and unchanged until the stream has passed the call.
+ * Ordering: the pack is ordered on `hip_stream`.  Forwards of this handle issued on the same stream before the call see the old
+ * weights, those issued after it the new ones.  With R3D_OPT_LANES > 1 the call first makes `hip_stream` wait for the lanes (the
+ * events r3d_lanes_join waits for; the stream counts as joined afterwards), and a forward relayed to a lane later waits for its
+ * caller's stream as always - so forwards issued from `hip_stream` are ordered around the pack with lanes too.  Forwards in
+ * flight on OTHER caller streams (or issued directly on a lane's stream) are the caller's to order against the call, as for any
+ * buffer two streams share.  There is no device-wide synchronisation on this path. */
+int r3d_finalize_dev(r3d_model *m, const float *const *weights_dev, const int64_t *numel, int32_t count, void *hip_stream);
+
 /* ---- forward: replaces pos_model(inputs_2d, inputs_param) [+ trj_model(...)] ---- */
 
 #define R3D_INPUT_RAYS 0 /* x is what the reference feeds the model: ray-encoded keypoints  */
@@ -819,6 +841,14 @@ int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32
                                  const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
                                  float *x_mirror, const int32_t *mirror_perm, float *gt, double *px, int64_t gt_rows,
                                  int32_t *outside, int32_t *status);
+/* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
+ * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
+ * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index
+ * the first one's index (-1: none).  No device call.  Returns 0, R3D_ERR_KEY (a weight is missing) or R3D_ERR_ARG. */
+int r3d_debug_pack_replay_host(r3d_model *m, int64_t *mismatches, int64_t *first_index);
+/* The packed image as it is on the device, copied back after a device synchronise: *need_floats its size (always written);
+ * `out` receives it when cap_floats suffices (else R3D_ERR_WORKSPACE).  R3D_ERR_STATE before a finalize. */
+int r3d_debug_weights_image(r3d_model *m, float *out, size_t cap_floats, size_t *need_floats);
 #endif /* R3D_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -21,6 +21,7 @@ R3D_INPUT_RAYS, R3D_INPUT_UV, R3D_INPUT_UV_DIST = 0, 1, 2
 R3D_INPUT_PX_INTRINSIC, R3D_INPUT_PX_SCREEN = 3, 4     # the 2-feature models' inputs from raw pixels (same pre-pass kernel)
 PX_MODES = (R3D_INPUT_UV_DIST, R3D_INPUT_PX_INTRINSIC, R3D_INPUT_PX_SCREEN)   # modes whose workspace carries the pre-pass's output
 R3D_ERR_ARG, R3D_ERR_WORKSPACE = -1, -6
+R3D_ERR_SHAPE, R3D_ERR_STATE = -3, -4
 R3D_ERR_ABORTED = -7
 R3D_OPT_STAGED, R3D_OPT_SPIN_TIMEOUT_MS, R3D_OPT_CU_LIMIT, R3D_OPT_LANES = 1, 2, 3, 4
 
@@ -32,13 +33,13 @@ EXPORTS = (
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
-    "r3d_clips_project", "r3d_forward_pair_split",
+    "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
-                "r3d_debug_clips_project_host")
+                "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -163,6 +164,7 @@ def load():
     lib.r3d_weight_shape.argtypes = [vp, C.c_int, i64p, C.POINTER(C.c_int)]
     lib.r3d_set_weight.argtypes = [vp, C.c_char_p, vp, i64p, C.c_int]
     lib.r3d_finalize.argtypes = [vp]
+    lib.r3d_finalize_dev.argtypes = [vp, C.POINTER(vp), i64p, C.c_int32, vp]
     lib.r3d_workspace_bytes.argtypes = [vp, vp, C.c_int64]
     lib.r3d_workspace_bytes.restype = C.c_size_t
     lib.r3d_input_workspace_bytes.argtypes = [vp, vp, C.POINTER(Input), C.c_int64]
@@ -199,6 +201,8 @@ def load():
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_pack_replay_host.argtypes = [vp, i64p, i64p]
+        lib.r3d_debug_weights_image.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.r3d_debug_clips_project_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
                                                      C.POINTER(C.c_int32), vp, vp, C.c_int64, vp, vp]
         lib.r3d_debug_forward_census.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
@@ -264,6 +268,36 @@ class Handle:
 
     def finalize(self):
         check(self._lib.r3d_finalize(self.ptr), "r3d_finalize")
+
+    def finalize_dev_raw(self, ptrs, numel, count: int, stream: int) -> int:
+        """r3d_finalize_dev as the C ABI takes it (`ptrs` / `numel`: ctypes arrays or None); returns the status code."""
+        return int(self._lib.r3d_finalize_dev(self.ptr, ptrs, numel, count, stream))
+
+    def finalize_dev(self, tensors, stream: int):
+        """r3d_finalize_dev: `tensors` one contiguous float32 device tensor per key of :meth:`keys`, in that order (anything with
+        data_ptr() and numel()); the pack is ordered on `stream`.  The tensors must stay alive until the stream has passed it."""
+        n = len(tensors)
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
+        numel = (C.c_int64 * n)(*[int(t.numel()) for t in tensors])
+        check(self.finalize_dev_raw(ptrs, numel, n, stream), "r3d_finalize_dev")
+
+    def debug_pack_replay_host(self):
+        """r3d_debug_pack_replay_host (hooks library only): ``(mismatches, first_index)`` of the device path's tables and routines
+        replayed on the CPU against the host pack of the weights set so far."""
+        mism, first = C.c_int64(-1), C.c_int64(-1)
+        check(self._lib.r3d_debug_pack_replay_host(self.ptr, C.byref(mism), C.byref(first)), "r3d_debug_pack_replay_host")
+        return int(mism.value), int(first.value)
+
+    def debug_weights_image(self):
+        """r3d_debug_weights_image (hooks library only): the packed image on the device as a float32 numpy array."""
+        import numpy as np
+        need = C.c_size_t(0)
+        rc = self._lib.r3d_debug_weights_image(self.ptr, None, 0, C.byref(need))
+        if rc != R3D_ERR_WORKSPACE:
+            check(rc, "r3d_debug_weights_image")
+        out = np.empty(int(need.value), np.float32)
+        check(self._lib.r3d_debug_weights_image(self.ptr, out.ctypes.data_as(C.c_void_p), out.size, C.byref(need)), "r3d_debug_weights_image")
+        return out
 
     def precision(self) -> str:
         """'f32' or 'bf16x3': what the handle's large GEMMs run in (r3d_config.bf16x3 or the R3D_BF16X3 override)."""

@@ -226,6 +226,10 @@ int r3d_set_weight(r3d_model *m, const char *key, const float *host, const int64
 
 int r3d_finalize(r3d_model *m) { return model_finalize(reinterpret_cast<Model *>(m)); }
 
+int r3d_finalize_dev(r3d_model *m, const float *const *weights_dev, const int64_t *numel, int32_t count, void *hip_stream) {
+    return model_finalize_dev(reinterpret_cast<Model *>(m), weights_dev, numel, count, hip_stream);
+}
+
 size_t r3d_workspace_bytes(const r3d_model *pos, const r3d_model *trj, int64_t B) {
     const auto [a, b] = model_pair(pos, trj);
     if (!a || B <= 0) return 0;

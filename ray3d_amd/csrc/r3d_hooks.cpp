@@ -1,4 +1,5 @@
-// The r3d_debug_* exports of libray3d_hip_hooks.so: checkers that run on the host and never touch a device.
+// The r3d_debug_* exports of libray3d_hip_hooks.so: checkers that run on the host and never touch a device (one exception, at the
+// end: r3d_debug_weights_image copies the packed image back).
 #ifdef R3D_TEST_HOOKS      // (libray3d_hip_hooks.so only: the product library gets an empty translation unit)
 #include <algorithm>
 #include <cstdio>
@@ -710,6 +711,24 @@ int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32
                 if (outside && pixel_outside(u, v, d.cam[UNDIST_ROW_RES_W], d.cam[UNDIST_ROW_RES_H])) ++outside[c];
             }
     }
+    return R3D_OK;
+}
+
+// Test hook: the tables and per-element routines of r3d_finalize_dev against model_pack_host, on the CPU (r3d_model.cpp)
+int r3d_debug_pack_replay_host(r3d_model *m, int64_t *mismatches, int64_t *first_index) {
+    return model_pack_replay_host(reinterpret_cast<Model *>(m), mismatches, first_index);
+}
+
+// Test hook: the packed image as the device holds it (the one device call of this file: tests compare the two finalize paths' bytes)
+int r3d_debug_weights_image(r3d_model *m, float *out, size_t cap_floats, size_t *need_floats) {
+    Model *mm = reinterpret_cast<Model *>(m);
+    if (!mm || !need_floats) { set_error("r3d_debug_weights_image: null argument"); return R3D_ERR_ARG; }
+    if (!mm->finalized || !mm->d_arena) { set_error("r3d_debug_weights_image: the handle is not finalized"); return R3D_ERR_STATE; }
+    *need_floats = mm->arena_floats;
+    if (!out || cap_floats < mm->arena_floats) { set_error("r3d_debug_weights_image: %zu floats are needed", mm->arena_floats); return R3D_ERR_WORKSPACE; }
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "hipDeviceSynchronize");
+    if ((e = hipMemcpy(out, mm->d_arena, mm->arena_floats * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "hipMemcpy(image)");
     return R3D_OK;
 }
 

@@ -308,7 +308,9 @@ struct Model {
     size_t global_lut_uv_off = 0;
     bool use_b3 = false;              // opt-in (R3D_BF16X3=1 at r3d_create): M = B layers on the bf16 matrix cores
     bool fold_shrink = false;         // the TemporalBlocks' shrink folded into its consumers (Layer::pre)
-    std::vector<float> arena;         // packed floats (host mirror)
+    std::vector<float> arena;         // packed floats (host mirror; filled by r3d_finalize only, not by r3d_finalize_dev)
+    size_t arena_floats = 0;          // size of the packed image (model_layout): what d_arena holds
+    struct PackState *pack = nullptr; // r3d_finalize_dev: descriptor / inverse / segment tables and the pointer table's staging (r3d_model.cpp)
     std::vector<int> iarena;          // LUTs
     float *d_arena = nullptr;
     int *d_iarena = nullptr;
@@ -589,7 +591,13 @@ int hip_fail(hipError_t e, const char *what);
 
 Model *model_create(const r3d_config &cfg);
 int model_set_weight(Model *m, const char *key, const float *host, const int64_t *shape, int rank);
-int model_finalize(Model *m);
+int model_finalize(Model *m);       // = model_layout + model_pack_host + the upload
+size_t model_layout(Model *m);      // the arena layout (Layer::w_off / b_off / wb3_off); returns its floats
+int model_pack_host(Model *m);      // fills Model::arena from host_weights; no device call
+int model_finalize_dev(Model *m, const float *const *weights_dev, const int64_t *numel, int32_t count, void *stream);   // r3d_finalize_dev
+#ifdef R3D_TEST_HOOKS
+int model_pack_replay_host(Model *m, int64_t *mismatches, int64_t *first_index);        // r3d_debug_pack_replay_host
+#endif
 enum { PLAN_FUSED = 0, PLAN_SMALL = 1, PLAN_MEDIUM = 2, PLAN_LARGE = 3 };   // everything but the top level fused / nothing / first level only / the top level too (r3d_plan.cpp)
 int plan_kind(int64_t B);                       // the plan a call of B windows runs
 std::vector<int64_t> plan_kind_edges();         // the largest window count of every plan kind that has one (r3d_workspace_bytes)
@@ -671,6 +679,8 @@ hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // the same kernel, one grid row per clip
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_poses
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_project
+struct PackArgs;                                                                                     // r3d_pack.hpp
+hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // the same kernel: r3d_finalize_dev
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -32,7 +32,14 @@
 // (pose_world), the pixel and its in-frame verdict: one integer atomicAdd per wavefront that saw a point outside.  12 bytes read and up
 // to 12 + 12 + 12 + 16 written per thread, consecutive threads at consecutive addresses (the mirrored write is a permutation inside
 // the row's J * 12 bytes).
+//
+// r3d_finalize_dev (a handle's packed weights from device-resident state_dict tensors, include/ray3d_hip.h) is the fifth argument set,
+// PackArgs, for the same reason: a flat grid cut into runs of workgroups by a segment list in device memory (blockIdx.x finds its
+// segment by bisection, uniformly), each thread one work item of r3d_pack.hpp - four consecutive columns of one output channel of
+// one layer's image, or one bias - through pack_item, the routine the host replay (r3d_debug_pack_replay_host) runs.  One 16-byte
+// store per thread, consecutive threads at consecutive addresses of the destination; the strided source rows go through the caches.
 #include "r3d_internal.hpp"
+#include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_undistort.hpp"
@@ -124,8 +131,25 @@ __device__ __forceinline__ void clips_project_body(const ClipsProjectArgs &g) {
     }
 }
 
+__device__ __forceinline__ void pack_body(const PackArgs &k) {
+    int lo = 0, hi = k.nseg - 1;             // the last segment that starts at or before this workgroup (the list is sorted, blk0[0] == 0)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (k.segs[mid].blk0 <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const PackSeg sg = k.segs[lo];
+    const int blk = (int)blockIdx.x - sg.blk0;
+    if (blk >= sg.nblk) return;              // (the grid is exactly the segments' workgroups: never taken)
+    pack_item(k, sg, blk * PACK_THREADS + (int)threadIdx.x);
+}
+
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
-                                                                         const ClipsProjectArgs g) {
+                                                                         const ClipsProjectArgs g, const PackArgs k) {
+    if (k.segs) {                            // uniform: r3d_finalize_dev - the segment of blockIdx.x
+        pack_body(k);
+        return;
+    }
     if (g.table) {                           // uniform: r3d_clips_project - descriptor blockIdx.y of the table
         clips_project_body(g);
         return;
@@ -183,28 +207,36 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{});
+    return hipGetLastError();
+}
+
+// r3d_finalize_dev: one launch per phase (the layers' own images and biases; then the copies derived from them), `nblk` workgroups
+hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
+    static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
+    if (nblk <= 0) return hipSuccess;
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 // Reference constructors this mirrors: lib/model/rie.py:13-63 (TemporalBlock), :108-120 (Linear),
 // :138-157 (FCBlock), :178-253 (RIEModel), :443-494 (RIETrajectoryModel),
 // lib/model/embedding.py:4-13 (Embedding).  Eval-mode BatchNorm1d: y = (x-mean)/sqrt(var+1e-5)*g+b.
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -13,6 +14,7 @@
 #include <cstring>
 
 #include "r3d_internal.hpp"
+#include "r3d_pack.hpp"
 
 namespace r3d {
 
@@ -130,7 +132,28 @@ struct Grammar {
 
 }  // namespace
 
+// r3d_finalize_dev's state of a handle: the tables that drive the pack (host copies, built once from Model::layers), their device
+// copies and the caller's pointer table on its way to the device (a pinned staging copy, reused call after call behind `staged`)
+struct PackState {
+    std::vector<PackLayer> layers;
+    std::vector<int> inv;
+    std::vector<PackSeg> segs[2];          // phase 0: the layers' own images and biases; phase 1: the copies derived from them
+    int nblk[2] = {0, 0};
+    int device = -1;                       // where the device copies live (-1: nowhere yet)
+    char *d_tables = nullptr;              // layers | inv | segs[0] | segs[1] | pointer table, each 16-byte aligned
+    size_t off_inv = 0, off_seg[2] = {0, 0}, off_ptr = 0;
+    const float **h_ptrs = nullptr;        // pinned
+    hipEvent_t staged = nullptr;           // behind the last upload of h_ptrs
+    void drop_device() {
+        if (d_tables) (void)hipFree(d_tables);
+        if (h_ptrs) (void)hipHostFree(h_ptrs);
+        if (staged) (void)hipEventDestroy(staged);
+        d_tables = nullptr; h_ptrs = nullptr; staged = nullptr; device = -1;
+    }
+};
+
 Model::~Model() {
+    if (pack) { pack->drop_device(); delete pack; }
     plans_drop(this);
     if (d_arena) (void)hipFree(d_arena);
     if (d_iarena) (void)hipFree(d_iarena);
@@ -378,16 +401,19 @@ struct Folder {
 
 }  // namespace
 
-int model_finalize(Model *m) {
-    if (!m) { set_error("r3d_finalize: null model"); return R3D_ERR_ARG; }
+static int model_check_complete(const Model *m, const char *what) {
     for (size_t i = 0; i < m->specs.size(); ++i)
         if (!m->have[i]) {
             int missing = 0;
             for (size_t j = 0; j < m->specs.size(); ++j) missing += !m->have[j];
-            set_error("Missing key(s) in state_dict: '%s' (and %d more)", m->specs[i].key.c_str(), missing - 1);
+            set_error("%sMissing key(s) in state_dict: '%s' (and %d more)", what, m->specs[i].key.c_str(), missing - 1);
             return R3D_ERR_KEY;
         }
-    // ---- lay out the arenas
+    return R3D_OK;
+}
+
+// ---- lay out the arena: the same offsets every time (they depend on the configuration alone), shared by both finalize paths
+size_t model_layout(Model *m) {
     size_t off = 0;
     for (auto &L : m->layers) {
         L.w_off = off;
@@ -400,6 +426,14 @@ int model_finalize(Model *m) {
             off += (size_t)L.Npad * L.Kpad;
         }
     }
+    m->arena_floats = off;
+    return off;
+}
+
+// ---- fold and pack host_weights into Model::arena (the host mirror); every weight must have been set
+int model_pack_host(Model *m) {
+    if (const int rc = model_check_complete(m, "")) return rc;
+    const size_t off = model_layout(m);
     m->arena.assign(off, 0.0f);
     Folder f{m};
     std::vector<double> s, t;
@@ -496,6 +530,12 @@ int model_finalize(Model *m) {
                 }
         }
     }
+    return R3D_OK;
+}
+
+int model_finalize(Model *m) {
+    if (!m) { set_error("r3d_finalize: null model"); return R3D_ERR_ARG; }
+    if (const int rc = model_pack_host(m)) return rc;
     // ---- upload
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -524,5 +564,223 @@ int model_finalize(Model *m) {
     m->dirty = false;
     return R3D_OK;
 }
+
+// ---- r3d_finalize_dev: the same image from device-resident tensors, packed on the caller's stream (r3d_pack.hpp)
+
+// The tables that drive the pack, from Model::layers (after model_layout).  Per layer a descriptor; per first layer the inverse of
+// colmap / colmap_neg: for every operand column the sources that add into it, in model_pack_host's visiting order (c outer, tap
+// inner, a source's + before its -); per phase the segment list that cuts the flat grid.
+static PackState *model_pack_tables(Model *m) {
+    if (m->pack) return m->pack;
+    PackState *ps = new PackState();
+    auto idx = [&](const std::string &key) { return key.empty() ? -1 : m->spec_index.at(key); };
+    for (const Layer &L : m->layers) {
+        PackLayer d{};
+        d.w = idx(L.weight_key);
+        d.bias = idx(L.bias_key);
+        d.g = d.beta = d.mu = d.var = -1;
+        if (!L.bn_prefix.empty()) {
+            d.g = idx(L.bn_prefix + ".weight");
+            d.beta = idx(L.bn_prefix + ".bias");
+            d.mu = idx(L.bn_prefix + ".running_mean");
+            d.var = idx(L.bn_prefix + ".running_var");
+        }
+        d.N = L.N; d.Npad = L.Npad; d.Kpad = L.Kpad;
+        d.taps = L.taps; d.cin = L.cin; d.cin_ref = L.cin_ref;
+        d.frag = L.frag ? 1 : 0;
+        d.npre = (int)L.pre.size();
+        if (d.npre > PACK_MAX_PRE) { delete ps; set_error("r3d_finalize_dev: a layer folds %d input ranges (at most %d)", d.npre, PACK_MAX_PRE); return nullptr; }
+        int c = 0, k = 0;
+        for (int r = 0; r < d.npre; ++r) {
+            const Layer::Pre &p = L.pre[r];
+            const Layer &S = m->layers[p.shrink_layer];
+            k += p.ref_col0 - c;
+            d.pre[r] = {p.ref_col0, p.ref_width, p.new_width, k, idx(S.weight_key), idx(S.bias_key)};
+            c = p.ref_col0 + p.ref_width;
+            k += p.new_width;
+        }
+        d.inv0 = -1;
+        if (!L.colmap.empty()) {
+            std::vector<std::vector<int>> cols(L.Kpad);
+            for (int ch = 0; ch < L.cin; ++ch)
+                for (int j = 0; j < L.taps; ++j) {
+                    const int t = j * L.cin + ch, src = ch * L.taps + j;
+                    cols[L.colmap[t]].push_back(src << 1);
+                    if (L.colmap_neg[t] >= 0) cols[L.colmap_neg[t]].push_back(src << 1 | 1);
+                }
+            d.inv0 = (int)ps->inv.size();
+            ps->inv.resize(ps->inv.size() + L.Kpad + 1);
+            for (int kk = 0; kk < L.Kpad; ++kk) {
+                ps->inv[d.inv0 + kk] = (int)ps->inv.size();
+                ps->inv.insert(ps->inv.end(), cols[kk].begin(), cols[kk].end());
+            }
+            ps->inv[d.inv0 + L.Kpad] = (int)ps->inv.size();
+        }
+        d.shared_of = L.shared_of;
+        d.shared_split = L.shared_split;
+        d.w_off = (long long)L.w_off; d.b_off = (long long)L.b_off;
+        d.wb3_off = (L.bf3 || L.bf3_conv) ? (long long)L.wb3_off : -1;
+        if (L.shared_of >= 0) {
+            const Layer &S = m->layers[L.shared_of];
+            d.src_N = S.N;
+            d.src_w_off = (long long)S.w_off; d.src_b_off = (long long)S.b_off;
+        }
+        ps->layers.push_back(d);
+    }
+    // segments: the biases first (a `pre` layer's bias is the longest chain of the launch), then the images
+    auto add = [&](int phase, int layer, int kind, long long items) {
+        const int nb = (int)(items / PACK_THREADS);      // (Npad is a multiple of 256: whole workgroups)
+        ps->segs[phase].push_back({layer, kind, ps->nblk[phase], nb});
+        ps->nblk[phase] += nb;
+    };
+    const int nl = (int)ps->layers.size();
+    for (int l = 0; l < nl; ++l)
+        if (ps->layers[l].shared_of < 0) add(0, l, PACK_BIAS, ps->layers[l].Npad);
+    for (int l = 0; l < nl; ++l)
+        if (ps->layers[l].shared_of < 0) add(0, l, PACK_WEIGHT, (long long)ps->layers[l].Npad * ps->layers[l].Kpad / 4);
+    for (int l = 0; l < nl; ++l) {
+        const PackLayer &d = ps->layers[l];
+        if (d.shared_of >= 0) {
+            add(1, l, PACK_SHARED_B, d.Npad);
+            add(1, l, PACK_SHARED_W, (long long)d.Npad * d.Kpad / 4);
+        }
+        if (d.wb3_off >= 0) add(1, l, PACK_BF3, (long long)d.Npad * d.Kpad / 4);
+    }
+    m->pack = ps;
+    return ps;
+}
+
+static PackArgs pack_args(const PackState *ps, int phase, const char *base, const float *const *T, float *arena) {
+    PackArgs a{};
+    a.segs = reinterpret_cast<const PackSeg *>(base + ps->off_seg[phase]);
+    a.nseg = (int)ps->segs[phase].size();
+    a.layers = reinterpret_cast<const PackLayer *>(base);
+    a.inv = reinterpret_cast<const int *>(base + ps->off_inv);
+    a.T = T;
+    a.arena = arena;
+    return a;
+}
+
+int model_finalize_dev(Model *m, const float *const *weights_dev, const int64_t *numel, int32_t count, void *stream_) {
+    // ---- argument rules: before any device call
+    if (!m || !weights_dev || !numel) { set_error("r3d_finalize_dev: null argument"); return R3D_ERR_ARG; }
+    if (count != (int32_t)m->specs.size()) {
+        set_error("r3d_finalize_dev: count is %d, this configuration has %d tensors (r3d_num_weights)", count, (int)m->specs.size());
+        return R3D_ERR_ARG;
+    }
+    for (int32_t i = 0; i < count; ++i) {
+        if (!weights_dev[i]) { set_error("r3d_finalize_dev: null pointer for '%s'", m->specs[i].key.c_str()); return R3D_ERR_ARG; }
+        if (numel[i] != m->specs[i].numel()) {
+            set_error("r3d_finalize_dev: size mismatch for '%s': got %lld elements, expected %lld", m->specs[i].key.c_str(), (long long)numel[i],
+                      (long long)m->specs[i].numel());
+            return R3D_ERR_SHAPE;
+        }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(stream, &cap);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
+    if (cap != hipStreamCaptureStatusNone) {
+        set_error("r3d_finalize_dev: the stream is being captured (the call may allocate, and it copies the pointer table)");
+        return R3D_ERR_STATE;
+    }
+    const size_t floats = model_layout(m);
+    PackState *ps = model_pack_tables(m);
+    if (!ps) return R3D_ERR_ARG;
+    int dev = 0;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return hip_fail(e, "hipGetDevice");
+    if (m->d_arena && m->device != dev) {
+        (void)hipFree(m->d_arena); (void)hipFree(m->d_iarena);
+        m->d_arena = nullptr; m->d_iarena = nullptr;
+        plans_drop(m);
+    }
+    m->device = dev;
+    if (!m->status_host) {
+        if ((e = hipHostMalloc((void **)&m->status_host, 64, hipHostMallocPortable | hipHostMallocMapped)) != hipSuccess) return hip_fail(e, "hipHostMalloc(status)");
+        *m->status_host = 0u;
+    }
+    if (!m->d_arena) {
+        // a fresh handle: the arena zero-filled (padding rows and columns stay zero for good) and the LUTs, both on the stream
+        if ((e = hipMalloc((void **)&m->d_arena, floats * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc(weights)");
+        if ((e = hipMalloc((void **)&m->d_iarena, m->iarena.size() * sizeof(int))) != hipSuccess) return hip_fail(e, "hipMalloc(luts)");
+        if ((e = hipMemsetAsync(m->d_arena, 0, floats * sizeof(float), stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(weights)");
+        if ((e = hipMemcpyAsync(m->d_iarena, m->iarena.data(), m->iarena.size() * sizeof(int), hipMemcpyHostToDevice, stream)) != hipSuccess) return hip_fail(e, "hipMemcpyAsync(luts)");
+    }
+    // ---- the tables, once per handle and device
+    if (ps->device != dev) {
+        ps->drop_device();
+        auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+        ps->off_inv = up16(ps->layers.size() * sizeof(PackLayer));
+        ps->off_seg[0] = up16(ps->off_inv + ps->inv.size() * sizeof(int));
+        ps->off_seg[1] = up16(ps->off_seg[0] + ps->segs[0].size() * sizeof(PackSeg));
+        ps->off_ptr = up16(ps->off_seg[1] + ps->segs[1].size() * sizeof(PackSeg));
+        const size_t total = ps->off_ptr + (size_t)count * sizeof(float *);
+        if ((e = hipMalloc((void **)&ps->d_tables, total)) != hipSuccess) return hip_fail(e, "hipMalloc(pack tables)");
+        if ((e = hipHostMalloc((void **)&ps->h_ptrs, (size_t)count * sizeof(float *), hipHostMallocDefault)) != hipSuccess) return hip_fail(e, "hipHostMalloc(pointer table)");
+        if ((e = hipEventCreateWithFlags(&ps->staged, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+        // (the host vectors live as long as the handle: the copies may complete after this call returns)
+        struct { size_t off; const void *src; size_t bytes; } parts[4] = {
+            {0, ps->layers.data(), ps->layers.size() * sizeof(PackLayer)}, {ps->off_inv, ps->inv.data(), ps->inv.size() * sizeof(int)},
+            {ps->off_seg[0], ps->segs[0].data(), ps->segs[0].size() * sizeof(PackSeg)},
+            {ps->off_seg[1], ps->segs[1].data(), ps->segs[1].size() * sizeof(PackSeg)}};
+        for (const auto &pt : parts)
+            if (pt.bytes && (e = hipMemcpyAsync(ps->d_tables + pt.off, pt.src, pt.bytes, hipMemcpyHostToDevice, stream)) != hipSuccess)
+                return hip_fail(e, "hipMemcpyAsync(pack tables)");
+        ps->device = dev;
+    } else if ((e = hipEventSynchronize(ps->staged)) != hipSuccess) {      // the previous call's copy of the staging table (a few KiB)
+        return hip_fail(e, "hipEventSynchronize(pointer table)");
+    }
+    // ---- the lanes' forwards in flight read the image this call overwrites: `stream` joins them (r3d_lanes_join's events)
+    for (int k = 0; k < m->lanes; ++k) {
+        Model::Lane &ln = m->lane[k];
+        if ((e = hipStreamWaitEvent(stream, ln.done, 0)) != hipSuccess) return hip_fail(e, "hipStreamWaitEvent(lane)");
+        ln.waiters.erase(std::remove(ln.waiters.begin(), ln.waiters.end(), stream_), ln.waiters.end());
+    }
+    for (int32_t i = 0; i < count; ++i) ps->h_ptrs[i] = weights_dev[i];
+    const float **d_ptrs = reinterpret_cast<const float **>(ps->d_tables + ps->off_ptr);
+    if ((e = hipMemcpyAsync(d_ptrs, ps->h_ptrs, (size_t)count * sizeof(float *), hipMemcpyHostToDevice, stream)) != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pointer table)");
+    if ((e = hipEventRecord(ps->staged, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(pointer table)");
+    for (int phase = 0; phase < 2; ++phase)
+        if ((e = launch_pack(pack_args(ps, phase, ps->d_tables, d_ptrs, m->d_arena), ps->nblk[phase], stream)) != hipSuccess)
+            return hip_fail(e, "launch r3d_undistort_rays_f64 (pack)");
+    m->finalized = true;
+    m->dirty = false;
+    return R3D_OK;
+}
+
+#ifdef R3D_TEST_HOOKS
+// r3d_debug_pack_replay_host: model_pack_host's image against the tables and the per-element routines run on the CPU over the same
+// host_weights, work item by work item in the launches' order; compared as 32-bit patterns.  No device call.
+int model_pack_replay_host(Model *m, int64_t *mismatches, int64_t *first_index) {
+    if (!m || !mismatches || !first_index) { set_error("r3d_debug_pack_replay_host: null argument"); return R3D_ERR_ARG; }
+    if (const int rc = model_pack_host(m)) return rc;
+    PackState *ps = model_pack_tables(m);
+    if (!ps) return R3D_ERR_ARG;
+    std::vector<const float *> T(m->specs.size());
+    for (size_t i = 0; i < T.size(); ++i) T[i] = m->host_weights[i].data();
+    std::vector<float> image(m->arena_floats + 4, 0.0f);
+    float *base = image.data();
+    while (reinterpret_cast<uintptr_t>(base) % 16) ++base;      // the quads are stored 16 bytes at a time
+    for (int phase = 0; phase < 2; ++phase) {
+        PackArgs a{};
+        a.segs = ps->segs[phase].data();
+        a.nseg = (int)ps->segs[phase].size();
+        a.layers = ps->layers.data();
+        a.inv = ps->inv.data();
+        a.T = T.data();
+        a.arena = base;
+        for (const PackSeg &sg : ps->segs[phase])
+            for (int item = 0; item < sg.nblk * PACK_THREADS; ++item) pack_item(a, sg, item);
+    }
+    *mismatches = 0;
+    *first_index = -1;
+    for (size_t i = 0; i < m->arena_floats; ++i)
+        if (memcmp(&base[i], &m->arena[i], 4) != 0) {
+            if (*mismatches == 0) *first_index = (int64_t)i;
+            ++*mismatches;
+        }
+    return R3D_OK;
+}
+#endif
 
 }  // namespace r3d

@@ -94,6 +94,7 @@ class LiftModule(nn.Module):
         self._staged = False
         self._spin_timeout_ms: Optional[int] = None
         self._cu_limit = 0
+        self._device_weights = False  # set_device_weights: handle() packs from the parameters where they live (r3d_finalize_dev)
         self._generation = 0          # bumped whenever the weights may have changed (_invalidate): what the pair seam compares
         self._ws = _Workspace()
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
@@ -152,6 +153,28 @@ class LiftModule(nn.Module):
         if self._handle is not None:
             self._handle.set_option(_capi.R3D_OPT_CU_LIMIT, self._cu_limit)
 
+    def set_device_weights(self, on: bool = True):
+        """With it on, the handle is (re)packed from the parameters and buffers where they live - r3d_finalize_dev: a fold-and-pack
+        kernel on torch's current stream, no copy of a weight to the host, no wait for the device - instead of r3d_finalize's trip
+        through the host.  For a model whose parameters sit on the GPU and change (``refresh_weights()`` after every epoch, then a
+        validation pass).  The packed weights have the bits of the host path.  Every tensor must then be on the forward's device:
+        one that is not raises (there is no fallback to the host path).  Off by default."""
+        self._device_weights = bool(on)
+        self._invalidate()
+
+    def _finalize_from_device(self, device: torch.device):
+        sd = self.state_dict()
+        tensors = []
+        for key in self._handle.keys():
+            t = sd[key].detach()
+            if t.device != device:
+                raise RuntimeError("device_weights: '%s' is on %s, the forward runs on %s - move the module there or call "
+                                   "set_device_weights(False); there is no fallback to the host path" % (key, t.device, device))
+            tensors.append(t.to(torch.float32).contiguous())      # (a view of the parameter, or a device copy where it is not float32-contiguous)
+        with torch.cuda.device(device):
+            self._handle.finalize_dev(tensors, torch.cuda.current_stream(device).cuda_stream)
+        self._packed_from = tensors           # (alive until the next pack: the kernel reads them on the stream)
+
     def check_status(self, device=None) -> None:
         """Synchronises the current stream of `device` and raises when a forward of this module since the last check
         gave up waiting for its own tiles (r3d_status: its outputs are NaN).  The reference's seam reports errors as
@@ -173,6 +196,9 @@ class LiftModule(nn.Module):
                 self._handle.set_option(_capi.R3D_OPT_SPIN_TIMEOUT_MS, self._spin_timeout_ms)
             if self._cu_limit:
                 self._handle.set_option(_capi.R3D_OPT_CU_LIMIT, self._cu_limit)
+        if self._device_weights and (not self._synced or getattr(self, "_device", None) != device):
+            self._finalize_from_device(device)
+            self._synced, self._device = True, device
         if not self._synced or getattr(self, "_device", None) != device:
             sd = self.state_dict()
             for key in self._handle.keys():
@@ -363,10 +389,12 @@ class _PairSeam:
 class Model(object):
     """Factory with the reference's surface (lib/model/__init__.py:5-62).  `fuse_pair` (None: :func:`fuse_pair_default`, which
     is False unless set): with a trajectory model, ``pos(x, p)`` followed by ``trj(x, p)`` on the same inputs costs ONE pair
-    launch instead of two whole-chip launches (:class:`_PairSeam`); off, every call runs its own network, as ever."""
+    launch instead of two whole-chip launches (:class:`_PairSeam`); off, every call runs its own network, as ever.
+    `device_weights` (False): both networks pack their weights from the parameters on the device
+    (:meth:`LiftModule.set_device_weights`) - for ``refresh_weights()`` + a validation pass after every epoch."""
 
     def __init__(self, model_config: dict, data_config: Optional[dict] = None, is_train: bool = True,
-                 fuse_pair: Optional[bool] = None):
+                 fuse_pair: Optional[bool] = None, device_weights: bool = False):
         pos_model = RIEModel(config_from_dicts(model_config, "pos"))
         trj_model = RIETrajectoryModel(config_from_dicts(model_config, "trj")) \
             if model_config["TRAJECTORY_MODEL"] else None
@@ -374,6 +402,8 @@ class Model(object):
             if m is not None:
                 m.is_train = is_train
                 m.train(is_train)
+                if device_weights:
+                    m.set_device_weights(True)
         self._seam = _PairSeam(pos_model, trj_model, fuse_pair_default() if fuse_pair is None else fuse_pair) \
             if trj_model is not None else None
         if torch.cuda.is_available():
@@ -425,6 +455,11 @@ class Ray3DLifter(nn.Module):
     def set_spin_timeout_ms(self, ms: int):
         self.pos.set_spin_timeout_ms(ms)
         self.trj.set_spin_timeout_ms(ms)
+
+    def set_device_weights(self, on: bool = True):
+        """Both networks pack their weights from the parameters on the device: see LiftModule.set_device_weights."""
+        self.pos.set_device_weights(on)
+        self.trj.set_device_weights(on)
 
     def set_cu_limit(self, n: int):
         """The pair's forwards run on a CU-masked stream that can use `n` CUs (R3D_OPT_CU_LIMIT; 0: the whole device): the

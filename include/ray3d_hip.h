@@ -753,6 +753,69 @@ int r3d_clips_project(const float *world_dev, int64_t total_frames, int32_t num_
                       int32_t *outside_dev,                              /* optional (NULL) */
                       int32_t *status_dev, void *stream);
 
+/* ---- a batch of materialised windows gathered from a pool of windows drawn from many clips ---- */
+
+/* The step that lets a shard of SHORT clips be lifted in full, uniform batches of the plain (B, RF, J, F) forward: the reference's
+ * np.pad(..., 'edge') (lib/dataloader/generators.py:213-216) plus eval_data_prepare (lib/train_val/trainer.py:47-58), for windows of
+ * many clips at once, each with its camera-parameter row beside it - and, with one-window runs, ChunkedGenerator's (sequence, start,
+ * flip) chunks.  src_dev holds model-input rows (total_frames, J, F) float32, F = 2 or 3: the rays of a data set, or what
+ * r3d_clips_encode writes with pads 0.  The shard's windows form one POOLED list, cut into runs: run r is windows [win_first,
+ * win_first + n_windows) of the list, all from one clip (source rows [first_frame, first_frame + n_frames)).  One call writes the
+ * pooled windows [window0, window0 + batch) into x_dev (batch, RF, J, F) - what a R3D_INPUT_RAYS forward with window_stride = RF
+ * reads - and their parameter rows into param_dev (batch, E).
+ * ARITHMETIC (integers only; nothing rounds).  Pooled window g is looked up in the LAST run of the table with win_first <= g (run 0
+ * when there is none): a table sorted by win_first, as evaluate.clip_window_table builds it, finds the run that holds g.  When that
+ * run is valid and win_first <= g < win_first + n_windows, then with k = g - win_first row i (0 <= i < RF) of the window is source
+ * frame first_frame + clamp(start + k * step + i, 0, n_frames - 1), in int64: the clamp IS the edge padding, no padded copy exists
+ * anywhere.  Values are copied as 32-bit patterns, NaN payloads included.  A run with flip = 1 writes x[.., j, :] = src[..,
+ * mirror_perm[j], :] with the sign bit of component 0 turned (the exact negation): r3d_clips_encode's rule, trainer.py:299-302.
+ * param_dev[g - window0] = run_param_dev[r] (E 32-bit patterns).  Rows of x_dev / param_dev whose window no valid run holds are
+ * left untouched.
+ *   status_dev: num_runs int32 words, required.  Each window of the launch reports on the run it was looked up in: 1 when that
+ *               descriptor is invalid, 0 when it is valid and holds the window; a valid run that does not hold the window is not
+ *               reported on.  So every run with a window in [window0, window0 + batch) of a sorted table has its word written; the
+ *               words of the other runs keep what they held.
+ *   mirror_perm: HOST array of J entries, a permutation of 0..J-1, or NULL; it travels as a kernel argument.  Without it a flip
+ *               run is invalid.
+ * GRID.  (ceil(RF * J / 256), batch) workgroups, one output point (row, joint) per thread; the workgroup bisects the table and
+ * validates the descriptor, uniformly, before any thread follows it.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A run is invalid when n_frames < 1, n_windows < 1, step < 1, flip is not 0 or 1,
+ * flip is 1 and mirror_perm is NULL, [first_frame, first_frame + n_frames) is not inside [0, total_frames), win_first < 0,
+ * n_windows > R3D_ENCODE_MAX_POINTS, start is outside [-R3D_ENCODE_MAX_POINTS, R3D_ENCODE_MAX_POINTS], or the last window's first
+ * frame start + (n_windows - 1) * step exceeds R3D_ENCODE_MAX_POINTS (with these limits no product or sum of the index arithmetic
+ * can overflow 64 bits).  The kernel never follows an invalid run: nothing of its clip is read, nothing is written for a window
+ * that was looked up in it, its status word is 1.  Whatever the table holds - unsorted, overlapping, garbage - the bisection ends on
+ * an index inside [0, num_runs), and that descriptor is validated like any other.  Beyond the descriptors the kernel reads src_dev
+ * within total_frames * J * F floats, the table within num_runs descriptors and run_param_dev within num_runs * E words, and writes
+ * x_dev within batch * RF * J * F floats, param_dev within batch * E words and status_dev within num_runs words: no input can make
+ * it touch memory outside these extents.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (src_dev, runs_dev, x_dev, status_dev), num_runs
+ * outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, in_features other than 2 or 3, receptive_field < 1, total_frames < 1, batch
+ * outside 1..65535 (the grid's second dimension), window0 outside [0, 2^62], receptive_field * num_joints, total_frames or batch *
+ * receptive_field * num_joints above R3D_ENCODE_MAX_POINTS (index arithmetic), exactly one of run_param_dev / param_dev,
+ * extrinsic_dim < 1 with run_param_dev given, a mirror_perm that is not a permutation, a table pointer that is not 8-byte aligned.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
+ * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+typedef struct {
+    int64_t first_frame;  /* row of the run's source clip in src_dev                                  */
+    int64_t n_frames;     /* frames of that clip (>= 1)                                               */
+    int64_t win_first;    /* index of the run's first window in the shard's pooled window list        */
+    int64_t n_windows;    /* windows of the run (>= 1)                                                */
+    int64_t start;        /* frame, relative to the clip's frame 0, of window 0's first frame; may be
+                             negative: -(pad + causal_shift) for an evaluation clip                   */
+    int32_t step;         /* frames between the starts of consecutive windows (>= 1; 1 for a clip)    */
+    int32_t flip;         /* 0 | 1: the mirrored input (component 0 negated, joints permuted)         */
+} r3d_window_run_desc;    /* 48 bytes, 8-byte aligned; lives in DEVICE memory */
+int r3d_clips_windows(const float *src_dev, int64_t total_frames, int32_t num_joints, int32_t in_features,
+                      int32_t receptive_field,
+                      const r3d_window_run_desc *runs_dev, int32_t num_runs,
+                      const float *run_param_dev, int32_t extrinsic_dim,   /* (num_runs, E) float32, or NULL / 0 */
+                      int64_t window0, int64_t batch,                      /* pooled windows [window0, window0 + batch) */
+                      float *x_dev,                                        /* (batch, RF, J, F) */
+                      float *param_dev,                                    /* (batch, E), or NULL with run_param_dev */
+                      const int32_t *mirror_perm,                          /* HOST, J entries; required if any run may flip */
+                      int32_t *status_dev, void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -841,6 +904,12 @@ int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32
                                  const r3d_clip_project_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
                                  float *x_mirror, const int32_t *mirror_perm, float *gt, double *px, int64_t gt_rows,
                                  int32_t *outside, int32_t *status);
+/* r3d_clips_windows on the host (HOST pointers throughout, no stream): the same argument checks, the same bisection, descriptor rule
+ * and per-point routine, windows of the batch in order. */
+int r3d_debug_clips_windows_host(const float *src, int64_t total_frames, int32_t num_joints, int32_t in_features,
+                                 int32_t receptive_field, const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param,
+                                 int32_t extrinsic_dim, int64_t window0, int64_t batch, float *x, float *param,
+                                 const int32_t *mirror_perm, int32_t *status);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

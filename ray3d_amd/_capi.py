@@ -33,13 +33,14 @@ EXPORTS = (
     "r3d_prepare", "r3d_release", "r3d_abi_version", "r3d_precision", "r3d_status", "r3d_set_option", "r3d_last_clock",
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
-    "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev",
+    "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
-                "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image")
+                "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
+                "r3d_debug_clips_windows_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -103,6 +104,18 @@ def clip_project_desc_dtype():
 
 
 CLIP_PROJECT_DESC_BYTES = 360                                           # sizeof(r3d_clip_project_desc)
+
+
+def window_run_dtype():
+    """The NumPy structured dtype with r3d_window_run_desc's layout (48 bytes): an array of it, uploaded as bytes, is the table
+    r3d_clips_windows reads."""
+    import numpy as np
+    return np.dtype([("first_frame", np.int64), ("n_frames", np.int64), ("win_first", np.int64), ("n_windows", np.int64),
+                     ("start", np.int64), ("step", np.int32), ("flip", np.int32)])
+
+
+WINDOW_RUN_DESC_BYTES = 48                                              # sizeof(r3d_window_run_desc)
+WINDOWS_BATCH_MAX = 65535                                               # `batch` of r3d_clips_windows (the grid's second dimension)
 
 
 class LaunchRecord(C.Structure):
@@ -198,9 +211,13 @@ def load():
                                     vp, vp]
     lib.r3d_clips_project.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
                                       C.POINTER(C.c_int32), vp, vp, C.c_int64, vp, vp, vp]
+    lib.r3d_clips_windows.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int64,
+                                      vp, vp, C.POINTER(C.c_int32), vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_clips_windows_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64,
+                                                     C.c_int64, vp, vp, C.POINTER(C.c_int32), vp]
         lib.r3d_debug_pack_replay_host.argtypes = [vp, i64p, i64p]
         lib.r3d_debug_weights_image.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.r3d_debug_clips_project_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
@@ -493,6 +510,29 @@ def debug_clips_project_host(world_ptr: int, total_frames: int, num_joints: int,
     return int(load().r3d_debug_clips_project_host(world_ptr, total_frames, num_joints, encoding, table_ptr, num_clips, max_rows,
                                                    x_ptr, out_rows, x_mirror_ptr or None, perm, gt_ptr or None, px_ptr or None,
                                                    gt_rows, outside_ptr or None, status_ptr))
+
+
+def clips_windows(src_ptr: int, total_frames: int, num_joints: int, in_features: int, receptive_field: int, runs_ptr: int,
+                  num_runs: int, run_param_ptr: Optional[int], extrinsic_dim: int, window0: int, batch: int, x_ptr: int,
+                  param_ptr: Optional[int], mirror_perm, status_ptr: int, stream: int):
+    """r3d_clips_windows: every pointer is device memory; `runs_ptr` num_runs r3d_window_run_desc (:func:`window_run_dtype`) back
+    to back; `run_param_ptr` (num_runs, extrinsic_dim) float32 and `param_ptr` (batch, extrinsic_dim) go together (both or None);
+    `mirror_perm` a host sequence of num_joints ints, or None (then no run may flip); `status_ptr` num_runs int32."""
+    perm = _mirror_table("r3d_clips_windows", mirror_perm, num_joints)
+    check(load().r3d_clips_windows(src_ptr, total_frames, num_joints, in_features, receptive_field, runs_ptr, num_runs,
+                                   run_param_ptr or None, extrinsic_dim, window0, batch, x_ptr, param_ptr or None, perm, status_ptr,
+                                   stream), "r3d_clips_windows")
+
+
+def debug_clips_windows_host(src_ptr: int, total_frames: int, num_joints: int, in_features: int, receptive_field: int, runs_ptr: int,
+                             num_runs: int, run_param_ptr: Optional[int], extrinsic_dim: int, window0: int, batch: int, x_ptr: int,
+                             param_ptr: Optional[int], mirror_perm, status_ptr: int) -> int:
+    """r3d_debug_clips_windows_host (hooks library only: use_hooks(True)): r3d_clips_windows on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    perm = _mirror_table("r3d_debug_clips_windows_host", mirror_perm, num_joints)
+    return int(load().r3d_debug_clips_windows_host(src_ptr or None, total_frames, num_joints, in_features, receptive_field,
+                                                   runs_ptr or None, num_runs, run_param_ptr or None, extrinsic_dim, window0, batch,
+                                                   x_ptr or None, param_ptr or None, perm, status_ptr or None))
 
 
 def _census_rows(call):

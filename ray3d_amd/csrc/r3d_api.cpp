@@ -4,6 +4,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_undistort.hpp"
+#include "r3d_windows.hpp"
 
 using namespace r3d;
 
@@ -179,6 +180,52 @@ int r3d::clips_poses_check_args(const char *what, const float *raw, const float 
                 set_error("%s: %s overlaps %s: the call does not work in place", what, o ? "world_dev" : "pred_dev", i ? "raw_mirror_dev" : "raw_dev");
                 return R3D_ERR_ARG;
             }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_clips_windows, shared with its host hook; fills the kernel's argument set
+int r3d::clips_windows_check_args(const char *what, const float *src, int64_t total_frames, int32_t J, int32_t F, int32_t RF,
+                                  const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t E, int64_t window0,
+                                  int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status, WindowsArgs *args) {
+    static_assert(sizeof(r3d_window_run_desc) == 48, "r3d_window_run_desc is documented as 48 bytes");
+    if (!src || !runs || !x || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (const int rc = clips_range_check(what, num_runs, J)) return rc;
+    if (F != 2 && F != 3) { set_error("%s: in_features must be 2 or 3 (got %d)", what, F); return R3D_ERR_ARG; }
+    if (RF < 1 || total_frames < 1) {
+        set_error("%s: receptive_field and total_frames must be >= 1 (got %d, %lld)", what, RF, (long long)total_frames);
+        return R3D_ERR_ARG;
+    }
+    if (batch < 1 || batch > 65535) { set_error("%s: batch must be in 1..65535 (got %lld)", what, (long long)batch); return R3D_ERR_ARG; }
+    if (window0 < 0 || window0 > (1ll << 62)) { set_error("%s: window0 must be in 0..2^62 (got %lld)", what, (long long)window0); return R3D_ERR_ARG; }
+    if (RF > R3D_ENCODE_MAX_POINTS / J || total_frames > R3D_ENCODE_MAX_POINTS || batch > R3D_ENCODE_MAX_POINTS / ((int64_t)RF * J)) {
+        set_error("%s: receptive_field * num_joints, total_frames and batch * receptive_field * num_joints must not exceed %d", what,
+                  R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if ((run_param != nullptr) != (param != nullptr)) {
+        set_error("%s: run_param_dev and param_dev go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (run_param && E < 1) { set_error("%s: extrinsic_dim must be >= 1 with run_param_dev (got %d)", what, E); return R3D_ERR_ARG; }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
+    if (reinterpret_cast<uintptr_t>(runs) % 8) { set_error("%s: the run table must be 8-byte aligned", what); return R3D_ERR_ARG; }
+    WindowsArgs a = {};
+    a.runs = runs;
+    a.src = reinterpret_cast<const uint32_t *>(src);
+    a.run_param = reinterpret_cast<const uint32_t *>(run_param);
+    a.x = reinterpret_cast<uint32_t *>(x);
+    a.param = reinterpret_cast<uint32_t *>(param);
+    a.status = status;
+    a.total_frames = total_frames;
+    a.window0 = window0;
+    if (mirror_perm) window_pack_perm(mirror_perm, J, a.mirror_perm);
+    a.num_runs = num_runs;
+    a.RF = RF;
+    a.J = J;
+    a.F = F;
+    a.E = run_param ? E : 0;
+    a.has_perm = mirror_perm != nullptr;
+    *args = a;
     return R3D_OK;
 }
 
@@ -466,6 +513,23 @@ int r3d_clips_project(const float *world_dev, int64_t total_frames, int32_t num_
     const hipError_t err = r3d::launch_clips_project(a, num_clips, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_clips_project: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_clips_windows(const float *src_dev, int64_t total_frames, int32_t num_joints, int32_t in_features, int32_t receptive_field,
+                      const r3d_window_run_desc *runs_dev, int32_t num_runs, const float *run_param_dev, int32_t extrinsic_dim,
+                      int64_t window0, int64_t batch, float *x_dev, float *param_dev, const int32_t *mirror_perm, int32_t *status_dev,
+                      void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::WindowsArgs a;
+    const int rc = clips_windows_check_args("r3d_clips_windows", src_dev, total_frames, num_joints, in_features, receptive_field, runs_dev,
+                                            num_runs, run_param_dev, extrinsic_dim, window0, batch, x_dev, param_dev, mirror_perm, status_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_clips_windows(a, (int)batch, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_clips_windows: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -12,6 +12,7 @@
 #include "r3d_project.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
+#include "r3d_windows.hpp"
 
 using namespace r3d;
 
@@ -710,6 +711,29 @@ int r3d_debug_clips_project_host(const float *world, int64_t total_frames, int32
                 }
                 if (outside && pixel_outside(u, v, d.cam[UNDIST_ROW_RES_W], d.cam[UNDIST_ROW_RES_H])) ++outside[c];
             }
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_clips_windows on the host - its argument rules (clips_windows_check_args) and the routines of r3d_windows.hpp the
+// kernel's workgroups run: the lookup (bisection, descriptor rule, membership) once per window, then window_point per output point.
+int r3d_debug_clips_windows_host(const float *src, int64_t total_frames, int32_t num_joints, int32_t in_features, int32_t receptive_field,
+                                 const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t extrinsic_dim,
+                                 int64_t window0, int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status) {
+    WindowsArgs a;
+    const int rc = clips_windows_check_args("r3d_debug_clips_windows_host", src, total_frames, num_joints, in_features, receptive_field, runs,
+                                            num_runs, run_param, extrinsic_dim, window0, batch, x, param, mirror_perm, status, &a);
+    if (rc != R3D_OK) return rc;
+    const long long npts = (long long)a.RF * a.J;
+    for (long long w = 0; w < batch; ++w) {
+        const WindowRun q = window_lookup(a, w);
+        if (!q.ok || q.member) status[q.r] = q.ok ? 0 : 1;
+        if (!q.member) continue;
+        for (int e = 0; a.param && e < a.E; ++e) a.param[w * a.E + e] = a.run_param[(long long)q.r * a.E + e];
+        for (long long pt = 0; pt < npts; ++pt) {
+            const int i = (int)(pt / a.J), j = (int)(pt - (long long)i * a.J);
+            window_point(a, q.first + window_source_frame(q.start, q.k, q.step, i, q.n), q.flip, j, a.x + a.F * (w * npts + pt));
+        }
     }
     return R3D_OK;
 }

@@ -578,6 +578,12 @@ int clips_project_check_args(const char *what, const float *world, int64_t total
                              const float *x_mirror, const int32_t *mirror_perm, const float *gt, const double *px, int64_t gt_rows,
                              const int32_t *status);
 
+struct WindowsArgs;     // r3d_windows.hpp
+// the argument rules of r3d_clips_windows, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int clips_windows_check_args(const char *what, const float *src, int64_t total_frames, int32_t J, int32_t F, int32_t RF,
+                             const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t E, int64_t window0,
+                             int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status, WindowsArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -681,6 +687,7 @@ hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStre
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_project
 struct PackArgs;                                                                                     // r3d_pack.hpp
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // the same kernel: r3d_finalize_dev
+hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream);             // the same kernel: r3d_clips_windows
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -38,11 +38,19 @@
 // segment by bisection, uniformly), each thread one work item of r3d_pack.hpp - four consecutive columns of one output channel of
 // one layer's image, or one bias - through pack_item, the routine the host replay (r3d_debug_pack_replay_host) runs.  One 16-byte
 // store per thread, consecutive threads at consecutive addresses of the destination; the strided source rows go through the caches.
+//
+// r3d_clips_windows (a batch of materialised (RF, J, F) windows gathered from a pool of windows drawn from many clips, include/ray3d_hip.h)
+// is the sixth argument set, WindowsArgs: blockIdx.y names a window of the batch, the workgroup finds the run of the device-side table
+// that holds it by bisection over win_first - uniformly, by scalar loads, as pack_body finds its segment - decides on that descriptor
+// before anything else, and each thread copies one output point (row, joint) from the clamped source frame through window_point of
+// r3d_windows.hpp, the routine the host hook runs.  8 or 12 bytes read and written per thread, consecutive threads at consecutive
+// addresses on both sides except where the clamp repeats a frame (the mirrored read is a permutation inside the row's J * F * 4 bytes).
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_undistort.hpp"
+#include "r3d_windows.hpp"
 
 namespace r3d {
 
@@ -144,8 +152,30 @@ __device__ __forceinline__ void pack_body(const PackArgs &k) {
     pack_item(k, sg, blk * PACK_THREADS + (int)threadIdx.x);
 }
 
+__device__ __forceinline__ void clips_windows_body(const WindowsArgs &v) {
+    const WindowRun q = window_lookup(v, blockIdx.y);          // uniform: blockIdx.y < batch, the run index inside [0, num_runs)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (!q.ok || q.member)) v.status[q.r] = q.ok ? 0 : 1;
+    if (!q.member) return;                   // an invalid descriptor is not followed; a window no run holds is left untouched
+    if (v.param && blockIdx.x == 0)          // uniform.  The run's parameter row beside the window
+        for (int e = threadIdx.x; e < v.E; e += blockDim.x) v.param[(long long)blockIdx.y * v.E + e] = v.run_param[(long long)q.r * v.E + e];
+    // (RF * J and batch * RF * J fit in 31 bits - checked on the host)
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= v.RF * v.J) return;
+    const int i = pt / v.J, j = pt - i * v.J;
+    uint32_t o[3];
+    window_point(v, q.first + window_source_frame(q.start, q.k, q.step, i, q.n), q.flip, j, o);
+    uint32_t *dst = v.x + v.F * ((long long)blockIdx.y * (v.RF * v.J) + pt);
+    dst[0] = o[0];
+    dst[1] = o[1];
+    if (v.F == 3) dst[2] = o[2];
+}
+
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
-                                                                         const ClipsProjectArgs g, const PackArgs k) {
+                                                                         const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn) {
+    if (wn.runs) {                            // uniform: r3d_clips_windows - window blockIdx.y of the batch
+        clips_windows_body(wn);
+        return;
+    }
     if (k.segs) {                            // uniform: r3d_finalize_dev - the segment of blockIdx.x
         pack_body(k);
         return;
@@ -207,28 +237,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{});
     return hipGetLastError();
 }
 
@@ -236,7 +266,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{});
+    return hipGetLastError();
+}
+
+// r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
+hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
+    const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args);
     return hipGetLastError();
 }
 

@@ -554,10 +554,11 @@ class _ShardInputs:
     * `encode` given: ``Clip.rays`` holds raw pixels - here, once, the shard's pixels and its :func:`clip_input_table` are
       uploaded, ONE :func:`shard_encode_hip` call on the current stream pads, encodes and - with `flip` - mirrors every clip and
       its status is read (a refused descriptor raises); a clip's inputs are its slices of the two buffers, lifted with
-      ``n_windows=``.  `lifter`'s ``clip_batch_sizes`` size the slices."""
+      ``n_windows=``.  `lifter`'s ``clip_batch_sizes`` size the slices.  Clips of fewer than `pool_below` frames (0: none) are
+      encoded without padding: they are not lifted from slices but gathered from the buffer (:class:`_Pool`)."""
 
     def __init__(self, mine: Sequence[Clip], rf: int, dev, causal: bool, encode: Optional[str], lifter, flip: bool = False,
-                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None):
+                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None, pool_below: int = 0):
         self.mine, self.dev, self.flip, self.encode = mine, dev, flip, encode
         self.lengths = [int(c.rays.shape[0]) for c in mine]
         self.pad, self.shift = (rf - 1) // 2, ((rf - 1) // 2 if causal else 0)
@@ -566,6 +567,16 @@ class _ShardInputs:
             return
         sizes_of = lifter.clip_batch_sizes
         itable, self.first, out_rows, max_rows = clip_input_table(mine, rf, causal, lambda n: sum(sizes_of(n)) - n)
+        if pool_below and any(n < pool_below for n in self.lengths):
+            # a pooled clip (``pool_below=``) is gathered by r3d_clips_windows, whose clamp is the padding: pads 0 for it
+            self.first, out_rows, max_rows = [], 0, 0
+            for d in itable:
+                if int(d["n_frames"]) < pool_below:
+                    d["pad_front"] = d["pad_back"] = 0
+                d["out_first"] = out_rows
+                self.first.append(out_rows)
+                rows = int(d["pad_front"]) + int(d["n_frames"]) + int(d["pad_back"])
+                out_rows, max_rows = out_rows + rows, max(max_rows, rows)
         self.rows = [int(d["pad_front"]) + int(d["n_frames"]) + int(d["pad_back"]) for d in itable]
         px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
         perm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
@@ -774,19 +785,136 @@ def shard_poses_hip(raw_all: torch.Tensor, table_dev: torch.Tensor, raw_first_de
     return pred_all, world_all, status
 
 
+# ------------------------------------------------------------------------------------ a shard of short clips lifted in full batches
+
+def clip_window_table(clips: Sequence, rf: int, causal: bool = False, flip: bool = False, surplus: int = 0,
+                      first_frames: Optional[Sequence[int]] = None):
+    """(table, win_first, total_windows) for the POOLED windows of `clips` (:class:`Clip` objects, or plain frame counts): `table`
+    a NumPy structured array of r3d_window_run_desc rows (``_capi.window_run_dtype()``), one run per clip in the given order -
+    clip k's N_k windows are [win_first[k], win_first[k] + N_k) of the pooled list of `total_windows` = sum N_k windows, window i
+    of it the frames [i - pad - shift, i - pad - shift + RF) of the clip clamped to the clip (``start = -(pad + shift)``,
+    ``step = 1``): :func:`pad_clip` plus the sliding windows of eval_data_prepare, with pad = (RF-1)//2 and shift = pad for
+    `causal` models.  The clips' frames are rows [first_frames[k], first_frames[k] + N_k) of the source buffer (None: back to
+    back).  `flip`: every run carries ``flip = 1`` - the table of the flip pass, a second table over the same windows.
+    `surplus` extra windows go to the LAST run (not counted in `total_windows`): they slide over the clamped last frame, as the
+    surplus windows of ``forward_clip`` do, so that ``sum(lifter.clip_batch_sizes(total_windows)) - total_windows`` of them make
+    every batch of ``Ray3DLifter.forward_windows`` full.  Uploaded once (``torch.from_numpy(table.view(np.uint8))``)."""
+    from . import _capi
+    pad = (rf - 1) // 2
+    shift = pad if causal else 0
+    if surplus < 0:
+        raise ValueError("surplus is negative")
+    table = np.zeros(len(clips), dtype=_capi.window_run_dtype())
+    win_first, src, at = [], 0, 0
+    for k, c in enumerate(clips):
+        n = int(c) if isinstance(c, (int, np.integer)) else int(np.asarray(c.rays).shape[0])
+        if n < 1:
+            raise ValueError("clip %d has no frame" % k)
+        table[k]["first_frame"] = src if first_frames is None else int(first_frames[k])
+        table[k]["n_frames"], table[k]["win_first"], table[k]["n_windows"] = n, at, n
+        table[k]["start"], table[k]["step"], table[k]["flip"] = -(pad + shift), 1, 1 if flip else 0
+        win_first.append(at)
+        src += n
+        at += n
+    if len(clips):
+        table[-1]["n_windows"] += int(surplus)
+    return table, win_first, at
+
+
+def shard_windows_hip(src_all: torch.Tensor, table_dev: torch.Tensor, num_runs: int, run_param: Optional[torch.Tensor],
+                      window0: int, batch: int, rf: int, x: Optional[torch.Tensor] = None, param: Optional[torch.Tensor] = None,
+                      perm: Optional[Sequence[int]] = None, status: Optional[torch.Tensor] = None):
+    """ONE r3d_clips_windows call on the current stream: the pooled windows [window0, window0 + batch) of the run table
+    `table_dev` (the uploaded bytes of :func:`clip_window_table`, or any r3d_window_run_desc rows) gathered from `src_all`
+    (total_frames, J, F) float32 model-input rows into `x` (batch, RF, J, F), with `run_param` (num_runs, E) float32 - or None -
+    each window's parameter row into `param` (batch, E).  `perm` (:func:`mirror_permutation` of the input keypoints): needed when
+    a run may flip.  Returns (x, param or None, status (num_runs,) int32: written for the runs with a window in the range, 0 =
+    followed, 1 = invalid descriptor).  `x` / `param` / `status`: tensors to write into (contiguous, of exactly these shapes)
+    instead of new ones - needed under hipGraph capture; new buffers are NOT zeroed, a new status is.  No copy and no
+    synchronisation: the caller reads `status` when it wants to."""
+    from . import _capi
+    dev = src_all.device
+    if not src_all.is_cuda or src_all.dim() != 3 or src_all.shape[0] < 1 or src_all.shape[2] not in (2, 3):
+        raise ValueError("src_all: a contiguous float32 (total_frames, J, 2 | 3) tensor on a GPU is needed")
+    _need(src_all, "src_all", torch.float32, dev)
+    total, J, F = (int(v) for v in src_all.shape)
+    _need_table(table_dev, num_runs, _capi.WINDOW_RUN_DESC_BYTES, dev)
+    if (param is not None) and run_param is None:
+        raise ValueError("param without run_param")
+    E = 0
+    if run_param is not None:
+        if run_param.dim() != 2:
+            raise ValueError("run_param: a (num_runs, E) tensor is needed")
+        E = int(run_param.shape[1])
+        _need(run_param, "run_param", torch.float32, dev, shape=(num_runs, E))
+    x = _out_buffer(x, "x", True, torch.float32, dev, (batch, rf, J, F))
+    param = _out_buffer(param, "param", run_param is not None, torch.float32, dev, (batch, E))
+    if status is None:
+        status = torch.zeros((num_runs,), dtype=torch.int32, device=dev)
+    else:
+        _need(status, "status", torch.int32, dev, shape=(num_runs,))
+    with torch.cuda.device(dev):
+        _capi.clips_windows(src_all.data_ptr(), total, J, F, rf, table_dev.data_ptr(), num_runs,
+                            run_param.data_ptr() if run_param is not None else None, E, int(window0), int(batch), x.data_ptr(),
+                            param.data_ptr() if param is not None else None, [int(v) for v in perm] if perm is not None else None,
+                            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return x, param, status
+
+
+class _Pool:
+    """The clips of a shard that are lifted as pooled windows (``pool_below=``): `index` their positions in the shard,
+    `win_first` {position: first pooled window = the clip's compact row in the raw buffers}, the run tables of the straight and
+    the flip pass on the device, the source buffer the runs name, the runs' parameter rows."""
+
+    def __init__(self, mine: Sequence[Clip], inputs: "_ShardInputs", rf: int, causal: bool, flip: bool, lifter, below: int,
+                 kps_left: Sequence[int], kps_right: Sequence[int]):
+        dev = inputs.dev
+        self.index = [k for k, n in enumerate(inputs.lengths) if n < below]
+        sub = [mine[k] for k in self.index]
+        self.windows = sum(inputs.lengths[k] for k in self.index)
+        if not self.index:
+            return
+        surplus = sum(lifter.clip_batch_sizes(self.windows)) - self.windows
+        if inputs.encode is not None:     # the encode call's output: the pooled clips lie in it without padding
+            self.src, firsts = inputs.x_all, [inputs.first[k] for k in self.index]
+        else:                             # the pooled clips' rays, uploaded once
+            self.src, firsts = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in sub], axis=0)).to(dev), None
+        table, win_first, _ = clip_window_table(sub, rf, causal, False, surplus, firsts)
+        self.win_first = dict(zip(self.index, win_first))
+        self.table_dev = _to_device_bytes(table, dev)
+        self.table_m_dev = _to_device_bytes(clip_window_table(sub, rf, causal, True, surplus, firsts)[0], dev) if flip else None
+        self.perm = mirror_permutation(int(self.src.shape[1]), kps_left, kps_right) if flip else None
+        self.run_param = torch.from_numpy(np.stack([np.asarray(c.camera.param(), dtype=np.float32) for c in sub])).to(dev) \
+            if lifter.pos.camera_embedding else None
+
+
 def _lift_finished(lift_clip: Callable, lifter, inputs, mirror_joints: Optional[tuple], table_dev: torch.Tensor,
-                   total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool, raw_first_dev: Optional[torch.Tensor] = None):
+                   total: int, longest: int, pred_all: Optional[torch.Tensor], world: bool, raw_first_dev: Optional[torch.Tensor] = None,
+                   pool: Optional[_Pool] = None):
     """The raw destination of the forwards - ``evaluate_clips_batched(finish=True)``, :func:`predict_clips_batched` and
     :func:`evaluate_camera_sweep`: every clip of `inputs` (:class:`_ShardInputs` / :class:`_SliceInputs`) lifted with ``raw_out=``
     into its rows of ONE raw buffer (with a flip pass - `mirror_joints` (left, right) of the OUTPUT, else None - the mirrored
     input into a second one), dealt to the lanes and joined once (:func:`_deal`), then ONE :func:`shard_poses_hip` call over
     `table_dev` (:func:`clip_table` of the shard) whose status is read: a refused descriptor raises.  `raw_first_dev`: the
     :func:`clip_raw_table` of ``inputs.lengths`` already on the device (a caller that uploads the tables of many passes at once).
+    `pool` (``pool_below=``): its clips are not lifted one by one - the first ``sum(clip_batch_sizes(pool.windows))`` rows of the raw
+    buffers are the pooled windows, written by ``lifter.forward_windows`` in full batches, and a pooled clip's raw_first is its
+    compact position among them; the other clips follow behind, lifted as without a pool.
     -> (pred_all, world_all or None)."""
     lengths, dev, flip = inputs.lengths, inputs.dev, mirror_joints is not None
     J = lifter.pos.num_joints_in
     sizes_of = lifter.clip_batch_sizes
-    raw_first, raw_rows = clip_raw_table(lengths, sizes_of)
+    if pool is not None and pool.index:
+        if raw_first_dev is not None:
+            raise ValueError("a pool lays the raw buffers out itself: raw_first_dev must be None")
+        pool_rows = sum(sizes_of(pool.windows))
+        raw_first, raw_rows = [], pool_rows
+        for k, n in enumerate(lengths):
+            raw_first.append(pool.win_first[k] if k in pool.win_first else raw_rows)
+            raw_rows += 0 if k in pool.win_first else sum(sizes_of(n))
+    else:
+        pool = None
+        raw_first, raw_rows = clip_raw_table(lengths, sizes_of)
     raw_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev)
     raw_m_all = torch.empty((raw_rows, 1, J, 3), dtype=torch.float32, device=dev) if flip else None
     if raw_first_dev is None:
@@ -799,7 +927,15 @@ def _lift_finished(lift_clip: Callable, lifter, inputs, mirror_joints: Optional[
         if flip:
             lift_clip(xm, prow, raw_out=raw_m_all[rows], **kw)
 
-    _deal(lifter, len(lengths), lift)
+    if pool is None:
+        _deal(lifter, len(lengths), lift)
+    else:
+        lifter.forward_windows(pool.src, pool.table_dev, len(pool.index), pool.run_param, pool.windows, raw_all[:pool_rows])
+        if flip:
+            lifter.forward_windows(pool.src, pool.table_m_dev, len(pool.index), pool.run_param, pool.windows, raw_m_all[:pool_rows],
+                                   perm=pool.perm)
+        rest = [k for k in range(len(lengths)) if k not in pool.win_first]
+        _deal(lifter, len(rest), lambda i: lift(rest[i]))
     perm = mirror_permutation(J, *mirror_joints) if flip else None
     pred_all, world_all, status = shard_poses_hip(raw_all, table_dev, raw_first_dev, len(lengths), total, longest, raw_m_all, perm,
                                                   pred=True, world=world, pred_all=pred_all)
@@ -810,7 +946,8 @@ def _lift_finished(lift_clip: Callable, lifter, inputs, mirror_joints: Optional[
 def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, flip: bool = False,
                           kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                           joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
-                          causal: bool = False, encode: Optional[str] = None, world: bool = True, root_relative: bool = False):
+                          causal: bool = False, encode: Optional[str] = None, world: bool = True, root_relative: bool = False,
+                          pool_below: Optional[int] = None):
     """:func:`predict_clip` for many clips, with the poses in world coordinates on top - the numerical core of the reference's
     Trainer.render (lib/train_val/trainer.py:505-526: cam.normalized2world / cam.camera2world on the flip-averaged poses) without
     its height rebase and its animation.  Every clip is lifted with ``raw_out=`` into one raw buffer and ONE r3d_clips_poses call
@@ -818,7 +955,8 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     (poses (N, J, 3) float32 - the bits of :func:`predict_clip` - , world (N, J, 3) float64 or None without `world`): views of the
     two shard buffers.  The transform is :func:`clip_world_transform`'s: a ``frame="camera"`` clip goes through Rc2w / Tc2w,
     `root_relative` is the identity.  `lift_clip` must be the bound ``forward_clip`` of a lifter; `encode` as in
-    :func:`evaluate_clips_batched`.  Single rank, GPU only.  No ground truth is needed: ``Clip.gt_norm`` may be an empty array."""
+    :func:`evaluate_clips_batched`, and so is `pool_below`.  Single rank, GPU only.  No ground truth is needed: ``Clip.gt_norm``
+    may be an empty array."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("predict_clips_batched finishes the poses on the GPU (r3d_clips_poses); on CPU tensors use predict_clip")
@@ -829,10 +967,13 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
         return []
     table, first, total, longest = clip_table(clips, root_relative)
     table_dev = _to_device_bytes(table, dev)
-    inputs = _ShardInputs(clips, rf, dev, causal, encode, lifter, flip, kps_left, kps_right)
+    below = int(pool_below or 0)
+    inputs = _ShardInputs(clips, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, pool_below=below)
     jl = kps_left if joints_left is None else joints_left
     jr = kps_right if joints_right is None else joints_right
-    pred_all, world_all = _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, None, world)
+    pool = _Pool(clips, inputs, rf, causal, flip, lifter, below, kps_left, kps_right) if below else None
+    pred_all, world_all = _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, None, world,
+                                         pool=pool)
     return [(pred_all[first[k]:first[k] + c.rays.shape[0]],
              world_all[first[k]:first[k] + c.rays.shape[0]] if world_all is not None else None) for k, c in enumerate(clips)]
 
@@ -842,7 +983,8 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
                            rank: int = 0, world_size: int = 1, group=None, causal: bool = False,
                            joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
                            root_relative: bool = False, mirror: Optional[Callable] = None, detail: bool = False,
-                           include_root: bool = False, encode: Optional[str] = None, finish: bool = False):
+                           include_root: bool = False, encode: Optional[str] = None, finish: bool = False,
+                           pool_below: Optional[int] = None):
     """:func:`evaluate_clips` (with `detail`: :func:`evaluate_clips_detail`, `include_root` as there) with the measuring side in
     ONE call per shard: the rank's clip table and ground truth are uploaded once, every clip is lifted into its slice of one
     prediction buffer (``lift_clip(padded, param_row, out=slice)``: ``Ray3DLifter.forward_clip``; the flip average is written
@@ -863,7 +1005,22 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     ``raw_out=`` into one raw buffer (with `flip` the mirrored pass into a second one; with lanes ONE join in all, also for clips
     with tails), ONE r3d_clips_poses call (:func:`shard_poses_hip`) writes the prediction buffer - flip average included - and the
     one metrics call runs as before.  `lift_clip` must be the bound ``forward_clip`` of a lifter.  Same return values, the same
-    bits in every row."""
+    bits in every row.
+
+    `pool_below` (None or 0: off, exactly the path and the bits above): the clips of a shard with FEWER than this many frames are
+    not lifted clip by clip.  Their windows form one pool that ``Ray3DLifter.forward_windows`` lifts in full batches of the plain
+    (B, RF, J, F) forward - per batch one r3d_clips_windows gather (:func:`shard_windows_hip`; the clamp of its index is the edge
+    padding, a flip run mirrors on the way) and one forward written straight into the raw buffers, where a pooled clip's rows are
+    its compact position in the pool; the longer clips go through ``forward_clip(raw_out=)`` as before, and the same single
+    r3d_clips_poses and r3d_clips_metrics calls finish and measure all of them.  Implies `finish`.  With `encode` the pooled
+    clips are encoded without padding and gathered from the encode call's output; without it their rays are uploaded once.  Not
+    with lanes (the pooled batches fill the chip by themselves) and not with a `mirror` callable.  A pooled clip's poses come
+    from the materialised-window kernels instead of the clip kernels: they agree with the per-clip path within the bound the
+    clip forwards are held to against materialised windows, not bit for bit; the rows of the other clips keep their bits.
+    Recommended: ``pool_below=1024``.  Measured at RF 243, flip on (profiles/clips_windows_ab.json): pooling 2 000
+    clips of 40 - 400 frames takes 0.62 of the per-clip path's time (run-to-run spread 3.6 % / 0.3 %); thresholds of 512, 1 024
+    and 2 048 on a mixed shard cannot be told apart; pooling clips of 1 000 - 6 000 frames is 5 % SLOWER than lifting them per
+    clip (the clip kernels' per-frame first level), so the crossover lies between 400 and about 2 000 frames."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
@@ -873,8 +1030,13 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         if mirror is not None:
             raise ValueError("encode=: the flip pass mirrors the encoded input on the device; `mirror` must be None")
         _lifter_of(lift_clip, need="encode=")
+    below = int(pool_below or 0)
+    if below:
+        if mirror is not None:
+            raise ValueError("pool_below=: the flip pass is mirrored by the gather on the device; `mirror` must be None")
+        finish = True
     if finish:
-        _lifter_of(lift_clip, need="finish=True", by_name=True)
+        _lifter_of(lift_clip, need="pool_below=" if below else "finish=True", by_name=True)
     actions, aid, shards, mine = _shard_plan(clips, rank, world_size)
     local = _shard_rows(clips, aid, shards[rank], PARTIAL_COLS, dev)
     dlocal = torch.zeros((len(mine), DETAIL_COLS), dtype=torch.float64, device=dev) if detail else None
@@ -883,11 +1045,12 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         table_dev = _to_device_bytes(table, dev)
         gt_all = _ground_truth(mine, dev, root_relative)
         pred_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
-        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, mirror)
+        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, mirror, pool_below=below)
         jl = kps_left if joints_left is None else joints_left
         jr = kps_right if joints_right is None else joints_right
         if finish:
-            _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, pred_all, False)
+            pool = _Pool(mine, inputs, rf, causal, flip, lifter, below, kps_left, kps_right) if below else None
+            _lift_finished(lift_clip, lifter, inputs, (jl, jr) if flip else None, table_dev, total, longest, pred_all, False, pool=pool)
         else:
             def lift(k):
                 dst = pred_all[first[k]:first[k] + mine[k].rays.shape[0]]

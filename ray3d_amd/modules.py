@@ -867,6 +867,70 @@ class Ray3DLifter(nn.Module):
             start += b
         return (raw_out, raw_trj_out) if return_trj else raw_out
 
+    def forward_windows(self, src_all: torch.Tensor, table_dev: torch.Tensor, num_runs: int, run_param: Optional[torch.Tensor],
+                        total_windows: int, out: torch.Tensor, out_trj: Optional[torch.Tensor] = None, perm=None):
+        """A pool of windows drawn from many clips, lifted in full batches of the plain (B, RF, J, F) forward - for shards of
+        clips too short to fill a call of their own.  `src_all` (total_frames, J, F) float32 model-input rows on the GPU,
+        `table_dev` the uploaded bytes of `num_runs` r3d_window_run_desc rows (``evaluate.clip_window_table``: one run per clip,
+        the LAST one carrying ``sum(clip_batch_sizes(total_windows)) - total_windows`` surplus windows), `run_param` (num_runs, E)
+        float32 - one camera parameter row per run - or None for models without the camera embedding, `perm` the input
+        keypoints' mirror permutation when runs flip.  The `total_windows` pooled windows are cut into
+        ``clip_batch_sizes(total_windows)``; per batch ONE r3d_clips_windows gather into one reused (CLIP_CHUNK, RF, J, F) buffer
+        and one forward, both on the current stream, the forward writing straight into ``out[w0:w0 + b]``: `out` is a
+        contiguous float32 (sum(sizes), 1, J, 3) tensor (a slice of a shard's raw buffer), `out_trj` (sum(sizes), 1, 1, 3) or
+        None.  Each batch's poses have the bits of ``forward`` on the same windows at the same batch size.  The gather's status
+        is read once, after the last batch (the call's one synchronisation): a refused run raises RuntimeError.  With lanes
+        (``set_lanes``) a ValueError: the pooled batches fill the chip by themselves.  Returns `out`, or (out, out_trj)."""
+        if self.num_lanes():
+            raise ValueError("forward_windows: not with lanes (set_lanes): the pooled batches fill the chip by themselves")
+        rf, J, F = self.receptive_field(), self.pos.num_joints_in, self.pos.in_features
+        dev = src_all.device
+        if not src_all.is_cuda or src_all.dim() != 3 or tuple(src_all.shape[1:]) != (J, F) or src_all.dtype != torch.float32 \
+                or not src_all.is_contiguous() or src_all.shape[0] < 1:
+            raise ValueError("forward_windows(src_all): a contiguous float32 (total_frames, %d, %d) tensor on a GPU is needed" % (J, F))
+        num_runs, total_windows = int(num_runs), int(total_windows)
+        if num_runs < 1 or total_windows < 1:
+            raise ValueError("forward_windows: num_runs and total_windows must be >= 1")
+        if table_dev.device != dev or not table_dev.is_contiguous() \
+                or table_dev.numel() * table_dev.element_size() < num_runs * _capi.WINDOW_RUN_DESC_BYTES:
+            raise ValueError("forward_windows(table_dev): %d descriptors of %d bytes on %s are needed" % (num_runs, _capi.WINDOW_RUN_DESC_BYTES, dev))
+        E = self.pos.extrinsic_dim if self.pos.camera_embedding else 0
+        if E:
+            if run_param is None or tuple(run_param.shape) != (num_runs, E) or run_param.dtype != torch.float32 or run_param.device != dev \
+                    or not run_param.is_contiguous():
+                raise ValueError("forward_windows(run_param): a contiguous float32 (%d, %d) tensor on %s is needed" % (num_runs, E, dev))
+        else:
+            run_param = None
+        sizes = self.clip_batch_sizes(total_windows)
+        total = sum(sizes)
+        for t, name, cols in ((out, "out", J), (out_trj, "out_trj", 1)):
+            if t is not None and (tuple(t.shape) != (total, 1, cols, 3) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+                raise ValueError("forward_windows(%s): a contiguous float32 (%d, 1, %d, 3) tensor on %s is needed - sum(clip_batch_sizes(%d)) "
+                                 "rows (got %s %s on %s)" % (name, total, cols, dev, total_windows, tuple(t.shape), t.dtype, t.device))
+        if out is None:
+            raise ValueError("forward_windows: `out` is required")
+        cap = max(sizes)
+        buf = getattr(self, "_win_buf", None)
+        if buf is None or buf[0].device != dev or buf[0].shape[0] < cap or tuple(buf[0].shape[1:]) != (rf, J, F) or buf[1].shape[1] != max(E, 1):
+            buf = self._win_buf = (torch.empty((max(cap, self.CLIP_CHUNK), rf, J, F), dtype=torch.float32, device=dev),
+                                   torch.empty((max(cap, self.CLIP_CHUNK), max(E, 1)), dtype=torch.float32, device=dev))
+        status = torch.zeros((num_runs,), dtype=torch.int32, device=dev)
+        perm = [int(v) for v in perm] if perm is not None else None
+        w0 = 0
+        for b in sizes:
+            x, p = buf[0][:b], (buf[1][:b] if E else None)
+            with torch.cuda.device(dev):
+                _capi.clips_windows(src_all.data_ptr(), int(src_all.shape[0]), J, F, rf, table_dev.data_ptr(), num_runs,
+                                    run_param.data_ptr() if E else None, E, w0, b, x.data_ptr(), p.data_ptr() if E else None, perm,
+                                    status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            extra = {"out_trj": out_trj[w0:w0 + b]} if out_trj is not None else {}
+            self._run(_capi.R3D_INPUT_RAYS, x, rf, b, p, self.pos.extrinsic_dim, return_trj=out_trj is not None, out=out[w0:w0 + b], **extra)
+            w0 += b
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            raise RuntimeError("r3d_clips_windows refused the descriptors of runs %s of the pool" % bad)
+        return (out, out_trj) if out_trj is not None else out
+
     def prepare(self, batch_sizes, device=None):
         """Build and upload the tile schedules of these batch sizes now (r3d_prepare) instead of inside the first
         forward that meets them: needed before capturing a forward into a hipGraph, useful before a timed run."""

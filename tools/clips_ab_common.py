@@ -1,4 +1,4 @@
-"""What the four A/B tools of the calls over a whole shard of clips share (tools/clips_{metrics,encode,valid,poses}_ab.py): the
+"""What the A/B tools of the calls over a whole shard of clips share (tools/clips_{metrics,encode,valid,poses,windows}_ab.py): the
 240-clip stand-in sets, the RF-243 lifter on synthetic weights, the alternating timed loop, the statistics and the verdict, and
 the runner - every step in a fresh process of its own under its own time limit, the first failure ending the run.
 Common options: --step S (one step: writes measure_out/<tool>.S.json), --clips N and --reps R (a smaller run, rehearsals),
@@ -47,14 +47,14 @@ def baseline_entry(mine, runs):
             "per_clip_ranges_overlap": not (mine["max_ms"] < lo or mine["min_ms"] > hi)}
 
 
-def make_set(n_clips, seed=0, pixels=False):
-    """bench.py's evaluation stand-in: clip lengths ~ U(1000, 6000), four cameras, 15 actions.  `pixels`: the same poses seen
-    through distorted cameras (undistort=True), Clip.rays holding the RAW float32 pixels."""
+def make_set(n_clips, seed=0, pixels=False, shortest=1000, longest=6000):
+    """bench.py's evaluation stand-in: clip lengths ~ U(1000, 6000) (or U(shortest, longest)), four cameras, 15 actions.  `pixels`:
+    the same poses seen through distorted cameras (undistort=True), Clip.rays holding the RAW float32 pixels."""
     import numpy as np
     import ray3d_amd
     from ray3d_amd import evaluate
     rng = np.random.default_rng(seed)
-    lengths = [int(rng.integers(1000, 6001)) for _ in range(n_clips)]
+    lengths = [int(rng.integers(shortest, longest + 1)) for _ in range(n_clips)]
     cams = []
     for i, yaw in enumerate((20, 110, 200, 290)):
         c = ray3d_amd.synthetic_camera(yaw, 4.5, -12.0, name="cam%d" % i)

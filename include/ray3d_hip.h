@@ -816,6 +816,80 @@ int r3d_clips_windows(const float *src_dev, int64_t total_frames, int32_t num_jo
                       const int32_t *mirror_perm,                          /* HOST, J entries; required if any run may flip */
                       int32_t *status_dev, void *stream);
 
+/* ---- live streams lifted a frame at a time: a head and a ring of RF frames per stream, one call per tick ---- */
+
+/* The input side of a LIVE caller: S streams (cameras) each deliver at most one new frame of J keypoints per tick and want the pose
+ * of the newest frame their window is complete for.  The state - caller-owned DEVICE memory of r3d_streams_state_bytes bytes, 8-byte
+ * aligned - holds S heads (r3d_stream_head) followed by S rings of (RF, J, F) float32; an all-zero state is S freshly reset streams.
+ * One call advances every stream by its action word and writes, for every stream that emits a frame this tick, that frame's window
+ * into row s of x_dev (S, RF, J, F) - what a R3D_INPUT_RAYS forward with window_stride = RF and batch = S reads: the reference's
+ * np.pad(..., 'edge') (lib/dataloader/generators.py:213-216) plus eval_data_prepare (lib/train_val/trainer.py:47-58), one window
+ * at a time, without a history buffer that grows and without re-encoding the RF - 1 frames the window shares with the last tick.
+ *   frame_dev:  encoding R3D_ENCODE_RAY / R3D_ENCODE_INTRINSIC / R3D_ENCODE_SCREEN: (S, J, 2) float32 raw pixels; stream s's go
+ *               through row s of cam_dev (S, 16) float64 - the camera rows of R3D_INPUT_UV_DIST / R3D_INPUT_PX_* - by the routine
+ *               r3d_clips_encode writes with: the same bits; in_features is 3, 2, 2.  R3D_ENCODE_NONE: (S, J, F) float32
+ *               model-input rows, F = in_features = 2 or 3, copied as 32-bit patterns, NaN payloads included; cam_dev may be NULL.
+ *               Rows of streams that do not PUSH or RESTART this tick are not read.
+ *   lag:        in [0, RF - 1]: the future frames a window needs - the reference's pad - causal_shift: 0 for a CAUSAL model (the
+ *               pose of the newest frame), pad = (RF - 1) / 2 for a centred one (the pose of frame newest - pad).
+ *   action_dev: S int32 words, R3D_STREAM_IDLE | R3D_STREAM_PUSH | R3D_STREAM_RESTART | R3D_STREAM_DRAIN.
+ *   x_mirror_dev / mirror_perm: both NULL, or both given: x_mirror_dev[s, i, j] = x_dev[s, i, mirror_perm[j]] with the sign bit of
+ *               component 0 turned (r3d_clips_windows's flip rule, trainer.py:299-302).  mirror_perm is a HOST array of J entries,
+ *               a permutation of 0..J-1; it travels as a kernel argument.
+ *   emit_dev:   S int64 words: the index (from 0, in PUSH order since the last RESTART) of the frame whose window was written into
+ *               row s this tick, or -1.
+ *   status_dev: S int32 words: 0 followed, 1 refused.
+ * ARITHMETIC PER STREAM AND TICK (integers only; nothing rounds).  c is the head's count, k the drain step.
+ *   IDLE     nothing happens (the head is not looked at): emit -1, status 0.
+ *   PUSH     the new frame goes to ring slot c % RF; c += 1; k = 0.
+ *   RESTART  the head is zeroed - whatever it held -, then the action is a PUSH: how a stream starts on a state that was not zeroed.
+ *   DRAIN    c == 0 or drained == lag: a valid no-op, emit -1.  Otherwise drained += 1, k = drained: the stream has ended and
+ *            the frames whose windows lack future frames are emitted one per tick, `lag` of them.
+ * After a PUSH, RESTART or DRAIN that took effect n = c - 1 - lag + k.  n < 0: nothing is emitted, emit -1.  Otherwise emit = n and
+ * row i of x_dev[s] is the ring's copy of frame clamp(n - (RF - 1 - lag) + i, 0, c - 1), found at slot frame % RF.  The clamp at 0
+ * is the reference's front edge padding, the clamp at c - 1 (during a drain) its back edge padding; the oldest frame a window can
+ * name is c - RF, which the ring still holds.  A stream fed N frames and then drained emits the frames 0 .. N - 1 once each, in order.
+ * Rows of x_dev / x_mirror_dev of streams that emit nothing this tick are left untouched.
+ * REFUSED STREAMS.  status 1, emit -1, and NOTHING else of the stream is written - not its head, not its ring, not its rows - when
+ * the action word is unknown; when a PUSH comes after a drain began (drained > 0: RESTART starts the next clip); when the head a
+ * PUSH or DRAIN meets is invalid: count < 0, count > 2^62, drained < 0 or drained > lag; when a PUSH meets count == 2^62 (the
+ * counter is full).
+ * TWO LAUNCHES on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own.  Advance: S workgroups; each
+ * reads and judges its stream's head and action uniformly, puts the J points of the new frame into the ring slot, and one thread
+ * writes the head, emit and status.  Gather: (ceil(RF * J / 256), S) workgroups, one output point (row, joint) per thread, from the
+ * head, emit and status words the advance launch wrote: no head is written by the launch other workgroups read it in.
+ * THE WHOLE BOUNDS STORY.  Whatever the state and the action words hold, the kernel reads frame_dev, cam_dev and action_dev within
+ * their S rows, and writes the state within r3d_streams_state_bytes, x_dev and x_mirror_dev within S * RF * J * F floats, emit_dev
+ * and status_dev within S words: a ring slot is a remainder modulo RF of a non-negative number, a frame index is clamped into
+ * [0, c - 1] of a head that passed the rule above, and the gather follows no head that fails it.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (state_dev, frame_dev, action_dev, x_dev, emit_dev,
+ * status_dev), num_streams outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, receptive_field < 1, lag outside [0,
+ * receptive_field - 1], an unknown encoding, in_features that does not go with it, cam_dev NULL with a pixel encoding, exactly one
+ * of x_mirror_dev / mirror_perm, a mirror_perm that is not a permutation, receptive_field * num_joints or num_streams *
+ * receptive_field * num_joints above R3D_ENCODE_MAX_POINTS (index arithmetic), a state, emit_dev or cam_dev pointer that is not
+ * 8-byte aligned.  r3d_streams_state_bytes returns 0 for shapes the call refuses.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+typedef struct {
+    int64_t count;        /* frames pushed since the stream's last RESTART                            */
+    int64_t drained;      /* DRAIN ticks that took effect since the last PUSH (0 .. lag)              */
+} r3d_stream_head;        /* 16 bytes, 8-byte aligned; lives in DEVICE memory */
+#define R3D_ENCODE_NONE 3       /* r3d_streams_step only: frame_dev holds model-input rows, copied bit for bit */
+#define R3D_STREAM_IDLE 0
+#define R3D_STREAM_PUSH 1
+#define R3D_STREAM_RESTART 2
+#define R3D_STREAM_DRAIN 3
+size_t r3d_streams_state_bytes(int32_t num_streams, int32_t receptive_field, int32_t num_joints, int32_t in_features);
+int r3d_streams_step(void *state_dev, int32_t num_streams, int32_t receptive_field, int32_t lag,
+                     int32_t num_joints, int32_t in_features, int32_t encoding,
+                     const float *frame_dev,          /* (S, J, 2) pixels, or (S, J, F) model-input rows        */
+                     const double *cam_dev,           /* (S, 16) camera rows; NULL with R3D_ENCODE_NONE          */
+                     const int32_t *action_dev,       /* (S) R3D_STREAM_IDLE | PUSH | RESTART | DRAIN            */
+                     float *x_dev,                    /* (S, RF, J, F): stream s owns row s                      */
+                     float *x_mirror_dev, const int32_t *mirror_perm,   /* both NULL, or both given (HOST perm)  */
+                     int64_t *emit_dev,               /* (S) frame index of the window written this tick, or -1  */
+                     int32_t *status_dev,             /* (S) 0 followed, 1 refused                               */
+                     void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -910,6 +984,11 @@ int r3d_debug_clips_windows_host(const float *src, int64_t total_frames, int32_t
                                  int32_t receptive_field, const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param,
                                  int32_t extrinsic_dim, int64_t window0, int64_t batch, float *x, float *param,
                                  const int32_t *mirror_perm, int32_t *status);
+/* r3d_streams_step on the host (HOST pointers throughout, no stream): the same argument checks, the same head rule, action step,
+ * slot index and point routines, every stream advanced and then every stream gathered, as the two launches do. */
+int r3d_debug_streams_step_host(void *state, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                                int32_t in_features, int32_t encoding, const float *frame, const double *cam, const int32_t *action,
+                                float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *status);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

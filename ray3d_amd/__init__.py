@@ -8,6 +8,7 @@ Public surface (drop-in for the reference's lifting path):
     from ray3d_amd import evaluate              # lib/train_val/trainer.py:283 evaluation loop
     from ray3d_amd import dataset               # lib/dataset/__init__.py:49  pose archives -> clips
     from ray3d_amd import skeleton              # joint trees for the bone terms of evaluate.validate_clips
+    from ray3d_amd import OnlineLifter          # live streams lifted a frame at a time (no counterpart in the reference)
 
 All arithmetic of the networks runs in libray3d_hip.so (hand-written gfx950 kernels behind the C
 ABI of include/ray3d_hip.h).  No CPU fallback exists.
@@ -17,5 +18,6 @@ from .modules import (Model, RIEModel, RIETrajectoryModel, Ray3DLifter, fuse_pai
                       masked_stream)   # noqa: F401
 from .camera import Camera, augment_camera, camera_grid, synthetic_camera   # noqa: F401
 from . import dataset, evaluate, metrics, skeleton, synth   # noqa: F401
+from .online import OnlineLifter   # noqa: F401
 
 __version__ = "0.1.0"

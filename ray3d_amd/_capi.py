@@ -34,13 +34,14 @@ EXPORTS = (
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
+    "r3d_streams_state_bytes", "r3d_streams_step",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
-                "r3d_debug_clips_windows_host")
+                "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -115,6 +116,18 @@ def window_run_dtype():
 
 
 WINDOW_RUN_DESC_BYTES = 48                                              # sizeof(r3d_window_run_desc)
+R3D_ENCODE_NONE = 3                                                     # r3d_streams_step only: model-input rows, copied bit for bit
+R3D_STREAM_IDLE, R3D_STREAM_PUSH, R3D_STREAM_RESTART, R3D_STREAM_DRAIN = 0, 1, 2, 3   # action words of r3d_streams_step
+STREAM_HEAD_BYTES = 16                                                  # sizeof(r3d_stream_head)
+
+
+def stream_head_dtype():
+    """The NumPy structured dtype with r3d_stream_head's layout (16 bytes): the front of a r3d_streams_step state viewed as an array
+    of it is the streams' heads."""
+    import numpy as np
+    return np.dtype([("count", np.int64), ("drained", np.int64)])
+
+
 WINDOWS_BATCH_MAX = 65535                                               # `batch` of r3d_clips_windows (the grid's second dimension)
 
 
@@ -213,9 +226,15 @@ def load():
                                       C.POINTER(C.c_int32), vp, vp, C.c_int64, vp, vp, vp]
     lib.r3d_clips_windows.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int64,
                                       vp, vp, C.POINTER(C.c_int32), vp, vp]
+    lib.r3d_streams_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.r3d_streams_state_bytes.restype = C.c_size_t
+    lib.r3d_streams_step.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
+                                     C.POINTER(C.c_int32), vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_step_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
+                                                    C.POINTER(C.c_int32), vp, vp]
         lib.r3d_debug_clips_windows_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64,
                                                      C.c_int64, vp, vp, C.POINTER(C.c_int32), vp]
         lib.r3d_debug_pack_replay_host.argtypes = [vp, i64p, i64p]
@@ -533,6 +552,35 @@ def debug_clips_windows_host(src_ptr: int, total_frames: int, num_joints: int, i
     return int(load().r3d_debug_clips_windows_host(src_ptr or None, total_frames, num_joints, in_features, receptive_field,
                                                    runs_ptr or None, num_runs, run_param_ptr or None, extrinsic_dim, window0, batch,
                                                    x_ptr or None, param_ptr or None, perm, status_ptr or None))
+
+
+def streams_state_bytes(num_streams: int, receptive_field: int, num_joints: int, in_features: int) -> int:
+    """r3d_streams_state_bytes: the bytes of the state r3d_streams_step keeps for `num_streams` streams - the heads, then the rings
+    (0 for a shape the call refuses)."""
+    return int(load().r3d_streams_state_bytes(num_streams, receptive_field, num_joints, in_features))
+
+
+def streams_step(state_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int, in_features: int, encoding: int,
+                 frame_ptr: int, cam_ptr: Optional[int], action_ptr: int, x_ptr: int, x_mirror_ptr: Optional[int], mirror_perm,
+                 emit_ptr: int, status_ptr: int, stream: int):
+    """r3d_streams_step: every pointer is device memory; `state_ptr` :func:`streams_state_bytes` bytes, 8-byte aligned; `cam_ptr`
+    (num_streams, 16) float64 or None (R3D_ENCODE_NONE); `x_mirror_ptr` (or None) and `mirror_perm` (a host sequence of num_joints
+    ints, or None) go together; `emit_ptr` num_streams int64, `status_ptr` num_streams int32."""
+    perm = _mirror_table("r3d_streams_step", mirror_perm, num_joints)
+    check(load().r3d_streams_step(state_ptr, num_streams, receptive_field, lag, num_joints, in_features, encoding, frame_ptr,
+                                  cam_ptr or None, action_ptr, x_ptr, x_mirror_ptr or None, perm, emit_ptr, status_ptr, stream),
+          "r3d_streams_step")
+
+
+def debug_streams_step_host(state_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int, in_features: int,
+                            encoding: int, frame_ptr: int, cam_ptr: Optional[int], action_ptr: int, x_ptr: int,
+                            x_mirror_ptr: Optional[int], mirror_perm, emit_ptr: int, status_ptr: int) -> int:
+    """r3d_debug_streams_step_host (hooks library only: use_hooks(True)): r3d_streams_step on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    perm = _mirror_table("r3d_debug_streams_step_host", mirror_perm, num_joints)
+    return int(load().r3d_debug_streams_step_host(state_ptr or None, num_streams, receptive_field, lag, num_joints, in_features, encoding,
+                                                  frame_ptr or None, cam_ptr or None, action_ptr or None, x_ptr or None,
+                                                  x_mirror_ptr or None, perm, emit_ptr or None, status_ptr or None))
 
 
 def _census_rows(call):

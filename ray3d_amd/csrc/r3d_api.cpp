@@ -3,6 +3,7 @@
 
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
+#include "r3d_streams.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -225,6 +226,65 @@ int r3d::clips_windows_check_args(const char *what, const float *src, int64_t to
     a.F = F;
     a.E = run_param ? E : 0;
     a.has_perm = mirror_perm != nullptr;
+    *args = a;
+    return R3D_OK;
+}
+
+// the shape rules of r3d_streams_step that r3d_streams_state_bytes answers with 0 (no message) and the call with R3D_ERR_ARG
+static bool streams_shape_ok(int32_t S, int32_t RF, int32_t J, int32_t F) {
+    return S >= 1 && S <= R3D_CLIPS_MAX && J >= 1 && J <= 17 && RF >= 1 && (F == 2 || F == 3) && RF <= R3D_ENCODE_MAX_POINTS / J &&
+           S <= R3D_ENCODE_MAX_POINTS / ((int64_t)RF * J);
+}
+
+// the argument rules of r3d_streams_step, shared with its host hook; fills the kernel's argument set
+int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
+                            const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror,
+                            const int32_t *mirror_perm, int64_t *emit, int32_t *status, StreamsArgs *args) {
+    static_assert(sizeof(r3d_stream_head) == 16, "r3d_stream_head is documented as 16 bytes");
+    static_assert(R3D_ENCODE_RAY == ENC_RAY && R3D_ENCODE_INTRINSIC == ENC_INTRINSIC && R3D_ENCODE_SCREEN == ENC_SCREEN, "encode_point_f32 takes them");
+    if (!state || !frame || !action || !x || !emit || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (S < 1 || S > R3D_CLIPS_MAX) { set_error("%s: num_streams must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, S); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (RF < 1) { set_error("%s: receptive_field must be >= 1 (got %d)", what, RF); return R3D_ERR_ARG; }
+    if (lag < 0 || lag > RF - 1) { set_error("%s: lag must be in 0..receptive_field - 1 (got %d)", what, lag); return R3D_ERR_ARG; }
+    const bool pixels = encoding == R3D_ENCODE_RAY || encoding == R3D_ENCODE_INTRINSIC || encoding == R3D_ENCODE_SCREEN;
+    if (!pixels && encoding != R3D_ENCODE_NONE) { set_error("%s: unknown encoding %d", what, encoding); return R3D_ERR_ARG; }
+    if (pixels ? F != enc_floats(encoding) : (F != 2 && F != 3)) {
+        set_error("%s: in_features %d does not go with encoding %d", what, F, encoding);
+        return R3D_ERR_ARG;
+    }
+    if (pixels && !cam) { set_error("%s: a pixel encoding needs cam_dev", what); return R3D_ERR_ARG; }
+    if ((x_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
+    if (!streams_shape_ok(S, RF, J, F)) {
+        set_error("%s: receptive_field * num_joints and num_streams * receptive_field * num_joints must not exceed %d", what,
+                  R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(emit) % 8 || reinterpret_cast<uintptr_t>(cam) % 8) {
+        set_error("%s: the state, emit_dev and cam_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    StreamsArgs a = {};
+    a.heads = static_cast<r3d_stream_head *>(state);
+    a.ring = reinterpret_cast<uint32_t *>(a.heads + S);
+    a.frame = reinterpret_cast<const uint32_t *>(frame);
+    a.cam = pixels ? cam : nullptr;
+    a.action = action;
+    a.x = reinterpret_cast<uint32_t *>(x);
+    a.x_mirror = reinterpret_cast<uint32_t *>(x_mirror);
+    a.emit = reinterpret_cast<long long *>(emit);
+    a.status = status;
+    if (mirror_perm) window_pack_perm(mirror_perm, J, a.mirror_perm);
+    a.S = S;
+    a.RF = RF;
+    a.lag = lag;
+    a.J = J;
+    a.F = F;
+    a.encoding = encoding;
     *args = a;
     return R3D_OK;
 }
@@ -530,6 +590,27 @@ int r3d_clips_windows(const float *src_dev, int64_t total_frames, int32_t num_jo
     const hipError_t err = r3d::launch_clips_windows(a, (int)batch, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_clips_windows: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+size_t r3d_streams_state_bytes(int32_t num_streams, int32_t receptive_field, int32_t num_joints, int32_t in_features) {
+    if (!streams_shape_ok(num_streams, receptive_field, num_joints, in_features)) return 0;
+    return r3d::streams_state_bytes(num_streams, receptive_field, num_joints, in_features);
+}
+
+int r3d_streams_step(void *state_dev, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints, int32_t in_features,
+                     int32_t encoding, const float *frame_dev, const double *cam_dev, const int32_t *action_dev, float *x_dev,
+                     float *x_mirror_dev, const int32_t *mirror_perm, int64_t *emit_dev, int32_t *status_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsArgs a;
+    const int rc = streams_check_args("r3d_streams_step", state_dev, num_streams, receptive_field, lag, num_joints, in_features, encoding,
+                                      frame_dev, cam_dev, action_dev, x_dev, x_mirror_dev, mirror_perm, emit_dev, status_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_step(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_step: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -10,6 +10,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
+#include "r3d_streams.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
 #include "r3d_windows.hpp"
@@ -734,6 +735,35 @@ int r3d_debug_clips_windows_host(const float *src, int64_t total_frames, int32_t
             const int i = (int)(pt / a.J), j = (int)(pt - (long long)i * a.J);
             window_point(a, q.first + window_source_frame(q.start, q.k, q.step, i, q.n), q.flip, j, a.x + a.F * (w * npts + pt));
         }
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_step on the host - its argument rules (streams_check_args) and the routines of r3d_streams.hpp the kernel's
+// two launches run: every stream advanced (stream_step, stream_store_point, the head, emit and status), then every stream's window
+// gathered from what that pass left (stream_emits, stream_gather_point).
+int r3d_debug_streams_step_host(void *state, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                                int32_t in_features, int32_t encoding, const float *frame, const double *cam, const int32_t *action,
+                                float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *status) {
+    StreamsArgs a;
+    const int rc = streams_check_args("r3d_debug_streams_step_host", state, num_streams, receptive_field, lag, num_joints, in_features,
+                                      encoding, frame, cam, action, x, x_mirror, mirror_perm, emit, status, &a);
+    if (rc != R3D_OK) return rc;
+    for (int s = 0; s < a.S; ++s) {
+        const StreamStep st = stream_step(a.heads[s].count, a.heads[s].drained, a.action[s], a.lag, a.RF);
+        for (int j = 0; st.push && j < a.J; ++j) stream_store_point(a, s, st.slot, j);
+        if (st.write_head) {
+            a.heads[s].count = st.count;
+            a.heads[s].drained = st.drained;
+        }
+        a.emit[s] = st.emit;
+        a.status[s] = st.refused ? 1 : 0;
+    }
+    for (int s = 0; s < a.S; ++s) {
+        const long long c = a.heads[s].count, n = a.emit[s];
+        if (!stream_emits(c, a.heads[s].drained, n, a.status[s], a.lag)) continue;
+        for (int i = 0; i < a.RF; ++i)
+            for (int j = 0; j < a.J; ++j) stream_gather_point(a, s, n, c, i, j);
     }
     return R3D_OK;
 }

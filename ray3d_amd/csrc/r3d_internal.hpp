@@ -584,6 +584,12 @@ int clips_windows_check_args(const char *what, const float *src, int64_t total_f
                              const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t E, int64_t window0,
                              int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status, WindowsArgs *args);
 
+struct StreamsArgs;     // r3d_streams.hpp
+// the argument rules of r3d_streams_step, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
+                       const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror, const int32_t *mirror_perm,
+                       int64_t *emit, int32_t *status, StreamsArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -688,6 +694,7 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 struct PackArgs;                                                                                     // r3d_pack.hpp
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // the same kernel: r3d_finalize_dev
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream);             // the same kernel: r3d_clips_windows
+hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);                         // the same kernel, two launches: r3d_streams_step
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -45,10 +45,21 @@
 // before anything else, and each thread copies one output point (row, joint) from the clamped source frame through window_point of
 // r3d_windows.hpp, the routine the host hook runs.  8 or 12 bytes read and written per thread, consecutive threads at consecutive
 // addresses on both sides except where the clamp repeats a frame (the mirrored read is a permutation inside the row's J * F * 4 bytes).
+//
+// r3d_streams_step (live streams lifted a frame at a time: a head and a ring of RF frames per stream in device memory,
+// include/ray3d_hip.h) is the seventh argument set, StreamsArgs, launched TWICE per call.  The advance launch: one workgroup of one
+// wavefront per stream; it reads the stream's head and action word - one address for the workgroup: scalar loads -, decides on them
+// through stream_step of r3d_streams.hpp before anything else, has thread j put point j of the new frame into the ring slot
+// (encode_point_f32, or a 32-bit copy), and thread 0 write the new head, emit and status.  The gather launch: blockIdx.y names a
+// stream, the workgroup reads the head, emit and status the advance launch wrote - no launch writes a head that another of its
+// workgroups reads -, and each thread copies one output point (row, joint) of the window from its ring slot through
+// stream_gather_point, the routine the host hook runs: 8 or 12 bytes read and written per thread, consecutive threads at
+// consecutive addresses of x; the ring is read in rows of J * F * 4 bytes that wrap once.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
+#include "r3d_streams.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -170,8 +181,44 @@ __device__ __forceinline__ void clips_windows_body(const WindowsArgs &v) {
     if (v.F == 3) dst[2] = o[2];
 }
 
+// The advance launch: stream blockIdx.x < S.  The head and the action word are the same for every thread of the workgroup, so the
+// verdict is uniform; the workgroup is ONE wavefront (launch_streams_step), and the barrier in front of the head's store keeps the
+// order also for a wider one: every load of the head is done before thread 0 replaces it.
+__device__ __forceinline__ void streams_advance_body(const StreamsArgs &t) {
+    const int s = blockIdx.x;
+    const long long count = t.heads[s].count, drained = t.heads[s].drained;
+    const StreamStep st = stream_step(count, drained, t.action[s], t.lag, t.RF);
+    if (st.push && (int)threadIdx.x < t.J) stream_store_point(t, s, st.slot, threadIdx.x);     // (slot < RF, j < J: inside ring s)
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (st.write_head) {
+        t.heads[s].count = st.count;
+        t.heads[s].drained = st.drained;
+    }
+    t.emit[s] = st.emit;
+    t.status[s] = st.refused ? 1 : 0;
+}
+
+// The gather launch: stream blockIdx.y < S, output point blockIdx.x * 256 + threadIdx.x of its window
+__device__ __forceinline__ void streams_gather_body(const StreamsArgs &t) {
+    const int s = blockIdx.y;
+    const long long c = t.heads[s].count, n = t.emit[s];
+    if (!stream_emits(c, t.heads[s].drained, n, t.status[s], t.lag)) return;      // uniform: the stream's row is left untouched
+    // (RF * J and S * RF * J fit in 31 bits - checked on the host)
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= t.RF * t.J) return;
+    const int i = pt / t.J;
+    stream_gather_point(t, s, n, c, i, pt - i * t.J);
+}
+
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
-                                                                         const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn) {
+                                                                         const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
+                                                                         const StreamsArgs sm) {
+    if (sm.heads) {                           // uniform: r3d_streams_step - the advance launch, then the gather launch
+        if (sm.phase == 0) streams_advance_body(sm);
+        else streams_gather_body(sm);
+        return;
+    }
     if (wn.runs) {                            // uniform: r3d_clips_windows - window blockIdx.y of the batch
         clips_windows_body(wn);
         return;
@@ -237,28 +284,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{});
     return hipGetLastError();
 }
 
@@ -266,14 +313,27 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_step: S workgroups of one wavefront advance the heads; then (ceil(RF * J / 256), S) workgroups gather the windows
+hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
+    StreamsArgs t = args;
+    t.phase = 0;
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    t.phase = 1;
+    const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t);
     return hipGetLastError();
 }
 

@@ -1,0 +1,212 @@
+"""Live streams lifted a frame at a time (r3d_streams_step, include/ray3d_hip.h): several cameras each deliver one new frame of 2D
+keypoints per tick and each wants its newest pose back.  :class:`OnlineLifter` keeps a head and a ring of the last RF frames per
+stream in device memory; a tick is one r3d_streams_step call - the new frames go into the rings, the windows of the frames that
+are now complete are written into a fixed (S, RF, J, F) batch - followed by the plain forward of that batch.  Nothing is rebuilt
+from a history with torch ops, nothing is encoded twice, and the whole tick can be captured into one hipGraph.
+"""
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _capi, evaluate
+
+IDLE, PUSH, RESTART, DRAIN = _capi.R3D_STREAM_IDLE, _capi.R3D_STREAM_PUSH, _capi.R3D_STREAM_RESTART, _capi.R3D_STREAM_DRAIN
+
+
+class OnlineLifter:
+    """`num_streams` live streams through `lifter` (a :class:`Ray3DLifter`), one frame per stream and tick.
+
+    `encoding`: None - :meth:`step` takes model-input rows (S, J, F), copied bit for bit - or "ray" / "intrinsic" / "screen": it
+    takes raw pixels (S, J, 2), encoded on the device through the streams' camera rows (:meth:`set_cameras`) by the routine
+    r3d_clips_encode writes with.  The window of a CAUSAL model ends at the newest frame (lag 0: a pose per pushed frame); a
+    centred model's pose of frame n needs the `pad` frames behind it (lag = pad): it is emitted `pad` ticks later, and the last
+    `pad` frames of a stream that ends come out of :meth:`drain`.  `flip`: the reference's test-time flip (trainer.py:299-353) -
+    the mirrored windows are gathered by the same call (`kps_left` / `kps_right`), lifted by a second forward, and the two passes
+    averaged through :func:`evaluate.mirror_output` (`joints_left` / `joints_right`, default the keypoint lists).
+    The lifter is prepared for batches of `num_streams` windows here, once."""
+
+    def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
+                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), joints_left: Optional[Sequence[int]] = None,
+                 joints_right: Optional[Sequence[int]] = None, device=None):
+        pos = lifter.pos
+        if lifter.num_lanes():
+            raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
+        self.lifter = lifter
+        self.S, self.rf, self.J, self.F = int(num_streams), lifter.receptive_field(), pos.num_joints_in, pos.in_features
+        self.lag = 0 if pos.cfg.causal else pos.pad
+        if encoding is None:
+            self.encoding, self.width = _capi.R3D_ENCODE_NONE, self.F
+        else:
+            self.encoding, self.width = evaluate._encoding_id(encoding, "encoding"), 2
+            if _capi.ENCODE_FLOATS[self.encoding] != self.F:
+                raise ValueError("encoding=%r writes %d floats per keypoint; this pair takes %d" % (encoding, _capi.ENCODE_FLOATS[self.encoding], self.F))
+        nbytes = _capi.streams_state_bytes(self.S, self.rf, self.J, self.F)
+        if nbytes == 0:
+            raise ValueError("OnlineLifter: num_streams must be in 1..%d (got %d)" % (_capi.CLIPS_MAX, self.S))
+        self.flip = bool(flip)
+        self.perm = evaluate.mirror_permutation(self.J, kps_left, kps_right) if self.flip else None
+        self.joints = (list(kps_left if joints_left is None else joints_left), list(kps_right if joints_right is None else joints_right))
+        dev = self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        S, rf, J, F = self.S, self.rf, self.J, self.F
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)                 # all zero: S freshly reset streams
+        self.x = torch.zeros((S, rf, J, F), dtype=torch.float32, device=dev)
+        self.x_mirror = torch.zeros((S, rf, J, F), dtype=torch.float32, device=dev) if self.flip else None
+        self.emit = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        self.status = torch.zeros((S,), dtype=torch.int32, device=dev)
+        self.frame = torch.zeros((S, J, self.width), dtype=torch.float32, device=dev)
+        self.action = torch.zeros((S,), dtype=torch.int32, device=dev)
+        self.cam = torch.zeros((S, 16), dtype=torch.float64, device=dev) if encoding is not None else None
+        self.param = torch.zeros((S, pos.extrinsic_dim), dtype=torch.float32, device=dev) if pos.camera_embedding else None
+        self._cameras_set = encoding is None and self.param is None
+        self._graph = None
+        self._captured = None       # the captured tick's (poses, out, out_mirror) buffers
+        if self.flip:               # the flip finish without host-built index tensors: what a captured tick runs
+            out_perm = evaluate.mirror_permutation(J, *self.joints)
+            self._out_perm = torch.tensor(out_perm, dtype=torch.int64, device=dev)
+            self._out_sign = torch.tensor([-1.0, 1.0, 1.0], dtype=torch.float32, device=dev)
+        lifter.prepare([S], dev)
+
+    # ---- setup -----------------------------------------------------------------------------------------------------------
+    def set_cameras(self, cam_rows=None, params=None):
+        """The streams' cameras: `cam_rows` (S, 16) float64 - :meth:`Camera.cam_row` with distortion=True, what the pixel encodings
+        read - and `params` (S, E) float32, the forward's camera-parameter rows (models with a camera embedding).  Copied into
+        the buffers the ticks read (also the captured one's): it may be called between ticks."""
+        for given, buf, name, dtype in ((cam_rows, self.cam, "cam_rows", torch.float64), (params, self.param, "params", torch.float32)):
+            if buf is None:
+                continue
+            if given is None:
+                raise ValueError("set_cameras: %s %s are needed" % (name, tuple(buf.shape)))
+            t = torch.as_tensor(given).to(dtype)
+            if tuple(t.shape) != tuple(buf.shape):
+                raise ValueError("set_cameras: %s must be %s (got %s)" % (name, tuple(buf.shape), tuple(t.shape)))
+            buf.copy_(t)
+        self._cameras_set = True
+
+    # ---- one tick --------------------------------------------------------------------------------------------------------
+    def _mirror_finish(self, pred, pred_m):
+        """0.5 * (pred + mirror_output(pred_m)) with device-resident indices (the values of evaluate.mirror_output exactly: a
+        negation and a permutation)."""
+        return 0.5 * (pred + pred_m.index_select(2, self._out_perm) * self._out_sign)
+
+    def _tick(self, out=None, out_m=None):
+        """r3d_streams_step, the forward(s), the flip finish - on the current stream -> poses (S, 1, J, 3)."""
+        dev, lifter = self.device, self.lifter
+        with torch.cuda.device(dev):
+            _capi.streams_step(self.state.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding, self.frame.data_ptr(),
+                               self.cam.data_ptr() if self.cam is not None else None, self.action.data_ptr(), self.x.data_ptr(),
+                               self.x_mirror.data_ptr() if self.flip else None, self.perm, self.emit.data_ptr(), self.status.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+        if out is None:             # eager: the public forward, the reference's flip finish
+            pred = lifter.forward(self.x, self.param)
+            if self.flip:
+                pred = 0.5 * (pred + evaluate.mirror_output(lifter.forward(self.x_mirror, self.param), *self.joints))
+            return pred
+        E = lifter.pos.extrinsic_dim
+        pred = lifter._run(_capi.R3D_INPUT_RAYS, self.x, self.rf, self.S, self.param, E, out=out)
+        if self.flip:
+            pred = self._mirror_finish(pred, lifter._run(_capi.R3D_INPUT_RAYS, self.x_mirror, self.rf, self.S, self.param, E, out=out_m))
+        return pred
+
+    def step(self, frame=None, actions=None, check: bool = True):
+        """One tick.  `frame` (S, J, 2) pixels or (S, J, F) model-input rows, a tensor or an array (None: no stream delivers one -
+        a tick of DRAIN / IDLE actions); `actions` (S,) R3D_STREAM_* words (None: every stream PUSHes).
+        -> (poses (S, J, 3), frames (S,) int64): frames[s] is the index of the frame poses[s] belongs to - the newest one for a causal
+        model, `pad` frames back for a centred one - or -1: stream s has no pose this tick and poses[s] is not meaningful.
+        Raises on a refused stream (an unknown action, a PUSH after a drain began: RESTART starts the next clip) unless `check`
+        is off - the check reads the status words back, the tick's one synchronisation."""
+        if not self._cameras_set:
+            raise RuntimeError("OnlineLifter: call set_cameras first (this configuration reads camera rows / parameter rows)")
+        if frame is not None:
+            t = torch.as_tensor(frame)
+            if tuple(t.shape) != tuple(self.frame.shape):
+                raise ValueError("step: frame must be %s (got %s)" % (tuple(self.frame.shape), tuple(t.shape)))
+            self.frame.copy_(t.to(torch.float32))
+        elif actions is None:
+            raise ValueError("step: without a frame the actions must be given")
+        if actions is None:
+            self.action.fill_(PUSH)
+        else:
+            a = torch.as_tensor(actions)
+            if tuple(a.shape) != (self.S,):
+                raise ValueError("step: actions must be (%d,) (got %s)" % (self.S, tuple(a.shape)))
+            self.action.copy_(a.to(torch.int32))
+        with torch.no_grad():
+            if self._graph is not None:
+                self._graph.replay()
+                poses = self._captured[0].clone()
+            else:
+                poses = self._tick()
+        frames = self.emit.clone()
+        if check:
+            bad = torch.nonzero(self.status).flatten().tolist()
+            if bad:
+                raise RuntimeError("r3d_streams_step refused streams %s (an unknown action, a PUSH after a drain began, or a "
+                                   "corrupted head): RESTART them" % bad)
+        return poses[:, 0], frames
+
+    def drain(self, check: bool = True) -> List[tuple]:
+        """The streams have ended: `lag` ticks of DRAIN for every stream -> the list of their (poses, frames).  Nothing for a
+        causal model.  Afterwards a stream takes RESTART (its next clip), not PUSH."""
+        act = torch.full((self.S,), DRAIN, dtype=torch.int32)
+        return [self.step(None, act, check) for _ in range(self.lag)]
+
+    def lift_clips(self, clips: Sequence, cam_rows=None, params=None) -> List[torch.Tensor]:
+        """Clips of unequal length - at most S arrays (N_k, J, 2 or F) - fed side by side, one stream each: RESTART, PUSH ..., the
+        drain when a clip ends, then IDLE.  -> per clip its poses (N_k, J, 3) in frame order: what the reference's evaluation
+        computes for the clip (edge padding, eval_data_prepare, the forward, the flip average)."""
+        if len(clips) > self.S:
+            raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
+        if cam_rows is not None or params is not None:
+            self.set_cameras(cam_rows, params)
+        clips = [np.ascontiguousarray(torch.as_tensor(c).cpu().numpy(), dtype=np.float32) for c in clips]
+        lengths = [c.shape[0] for c in clips]
+        if min(lengths) < 1:
+            raise ValueError("lift_clips: a clip needs at least one frame")
+        outs = [torch.empty((n, self.J, 3), dtype=torch.float32, device=self.device) for n in lengths]
+        seen = [0] * len(clips)
+        frame = np.zeros(tuple(self.frame.shape), np.float32)
+        for t in range(max(lengths) + self.lag):
+            act = np.full(self.S, IDLE, np.int32)
+            for s, (c, n) in enumerate(zip(clips, lengths)):
+                if t < n:
+                    act[s], frame[s] = (RESTART if t == 0 else PUSH), c[t]
+                elif t < n + self.lag:
+                    act[s] = DRAIN
+            poses, frames = self.step(frame, act)
+            for s, n in enumerate(frames.tolist()[:len(clips)]):
+                if n >= 0:
+                    outs[s][n] = poses[s]
+                    seen[s] += 1
+        assert seen == lengths, (seen, lengths)
+        return outs
+
+    # ---- capture ---------------------------------------------------------------------------------------------------------
+    def capture(self):
+        """Record one tick - r3d_streams_step, the forward or forwards, the flip finish - into a hipGraph on a side stream; from
+        then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
+        capture may come between two ticks."""
+        if self._graph is not None:
+            return
+        if not self._cameras_set:
+            raise RuntimeError("OnlineLifter: call set_cameras before capture")
+        dev, S, J = self.device, self.S, self.J
+        out = torch.empty((S, 1, J, 3), dtype=torch.float32, device=dev)
+        out_m = torch.empty((S, 1, J, 3), dtype=torch.float32, device=dev) if self.flip else None
+        E = self.lifter.pos.extrinsic_dim
+        with torch.no_grad():       # the workspace and the schedules exist before the capture: nothing allocates inside it
+            self.lifter._run(_capi.R3D_INPUT_RAYS, self.x, self.rf, S, self.param, E, out=out)
+        torch.cuda.synchronize(dev)
+        self.lifter.check_status(dev)
+        g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream(dev)
+        with torch.no_grad(), torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                poses = self._tick(out, out_m)
+        torch.cuda.synchronize(dev)
+        self._graph, self._captured = g, (poses, out, out_m)
+
+    def release(self):
+        """Drop the captured graph (before the lifter's prepared schedules are released or its options change)."""
+        if self._graph is not None:
+            torch.cuda.synchronize(self.device)
+            self._graph = self._captured = None

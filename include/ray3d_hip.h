@@ -890,6 +890,77 @@ int r3d_streams_step(void *state_dev, int32_t num_streams, int32_t receptive_fie
                      int32_t *status_dev,             /* (S) 0 followed, 1 refused                               */
                      void *stream);
 
+/* ---- a live tick's finished poses: flip average, world coordinates and a quality signal without ground truth, one call ---- */
+
+/* The output side of a LIVE caller, between a tick's forward(s) and its consumer: for every stream that FINISHED a frame this tick -
+ * status_dev[s] == 0 && emit_dev[s] >= 0, the words r3d_streams_step wrote - the flip average of lib/train_val/trainer.py:340-346,
+ * the world transform every prediction gets (cam.normalized2world, lib/camera/camera.py:401-410; trainer.py:358-359, :514-523), and
+ * the one check a stream without ground truth has: the predicted absolute pose taken back to the camera (normalized2camera,
+ * camera.py:379-388), projected, and compared with the keypoints that were fed in (get_uv_given_cam_ray, camera.py:473-483 - the
+ * overlay of trainer.py:535-537).  For every other stream nothing of rows s is read - apart from those two words - and nothing of
+ * rows s is written in any output.
+ *   raw_dev / raw_mirror_dev: (S, J, 3) float32, what the forward of x_dev and of x_mirror_dev wrote (pos + trj, normalised frame).
+ *   mirror_perm: HOST array of J entries, a permutation of 0..J-1 (the output joints' left <-> right); given exactly when
+ *               raw_mirror_dev is; it travels as a kernel argument.
+ *   desc_dev:   S r3d_stream_pose_desc in device memory, 8-byte aligned: rn2w / tn2w as r3d_clip_desc, `height` the camera height
+ *               in metres (Tc2n = (0, -height, 0), camera.py:340-343).  NULL only if world_dev and reproj_dev are NULL.
+ *   cam_dev:    (S, 16) float64 camera rows (those of r3d_streams_step); slots 0, 1 (fx, fy) and 4, 5 (cos, sin of the pitch) are read.
+ *   x_dev, receptive_field, lag: the (S, RF, J, 3) windows r3d_streams_step wrote this tick and its lag: row RF - 1 - lag of a
+ *               window is the frame the pose belongs to (the step's clamp never touches it: 0 <= emit <= count - 1).  reproj_dev is
+ *               defined for 3-feature (ray) inputs only.
+ * ARITHMETIC PER FINISHED STREAM s, JOINT j.
+ *   p           without a mirrored pass the bits of raw[s, j]; with one fl32(fl32(raw + m) * 0.5f), m = raw_mirror[s, mirror_perm[j]]
+ *               with component 0 negated: r3d_clips_poses's rule, the bits of torch.add(...).mul_(0.5) in float32.
+ *   pred_dev[s, j]  = p.
+ *   world_dev[s, j] = rn2w p + tn2w in float64, p promoted; component r = ((R[3r] x + R[3r+1] y) + R[3r+2] z) + T[r], every product
+ *               and every sum rounded once (r3d_clips_poses's rule).
+ *   reproj_dev[s, j], float64, no contraction, c = cam[4], sn = cam[5], fx = cam[0], fy = cam[1], h = height:
+ *               predicted  yy = (double)p[1] + h;  Xc = (double)p[0];  Yc = c * yy - sn * z;  Zc = sn * yy + c * z  (z = (double)p[2]);
+ *                          a = Xc / Zc;  b = Yc / Zc  (IEEE divisions)
+ *               observed   r = x_dev[s, RF - 1 - lag, j, 0..2];  xo = (double)r[0];  yo = c * r[1] - sn * r[2]  (the reference does
+ *                          not divide by the third component either)
+ *               residual   du = fx * (a - xo);  dv = fy * (b - yo);  reproj = sqrt(du * du + dv * dv), the correctly rounded sqrt:
+ *               a distance in UNDISTORTED pixels; the principal point cancels and is not read.
+ *   quality_dev[s]  word 0 the mean of row s of reproj (summed in joint order j = 0 .. J - 1 from zero, then one division by J),
+ *               word 1 its maximum; both the canonical quiet NaN if any residual of the row is NaN.
+ * NON-FINITE VALUES.  A NaN the arithmetic produces leaves as the canonical quiet NaN; raw bits that are only copied (pred_dev
+ * without a mirrored pass) keep their payload.  A point behind the camera or in its plane (Zc <= 0) is simply followed, as
+ * r3d_clips_project does: a mirrored, infinite or NaN residual, not an error.  A non-finite raw element touches its own point's
+ * outputs and its stream's quality words, nothing else.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: S workgroups of one wavefront;
+ * each reads its stream's emit and status words uniformly before anything else; thread j < J finishes joint j; one thread sums the
+ * residuals it finds parked in LDS.  Launch-latency-bound by construction.
+ * THE WHOLE BOUNDS STORY.  Whatever emit_dev, status_dev, the descriptors and the inputs hold, the kernel reads emit_dev and
+ * status_dev within S words, raw_dev / raw_mirror_dev within S * J * 3 floats (a mirrored joint is an entry of a checked
+ * permutation), desc_dev within S descriptors, cam_dev within S rows, x_dev within S * RF * J * 3 floats (row RF - 1 - lag of
+ * window s, lag checked on the host), and writes pred_dev and world_dev within S * J * 3, reproj_dev within S * J and quality_dev
+ * within S * 2 elements: no index depends on a value read from device memory.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (raw_dev, emit_dev, status_dev; desc_dev with
+ * world_dev or reproj_dev; cam_dev and x_dev with reproj_dev), pred_dev, world_dev and reproj_dev all NULL, exactly one of
+ * raw_mirror_dev / mirror_perm, a mirror_perm that is not a permutation, num_streams outside 1..R3D_CLIPS_MAX, num_joints outside
+ * 1..17, quality_dev without reproj_dev, and with reproj_dev: receptive_field < 1, lag outside [0, receptive_field - 1], num_streams *
+ * receptive_field * num_joints above R3D_ENCODE_MAX_POINTS; emit_dev, desc_dev, cam_dev, world_dev, reproj_dev or quality_dev not
+ * 8-byte aligned; an output extent that overlaps raw_dev, raw_mirror_dev or (with reproj_dev) x_dev, compared as address ranges.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+typedef struct {
+    double rn2w[9];       /* row-major, normalised -> world rotation (as r3d_clip_desc)               */
+    double tn2w[3];
+    double height;        /* camera height in metres: Tc2n = (0, -height, 0), camera.py:340-343       */
+    double reserved;      /* 0                                                                        */
+} r3d_stream_pose_desc;   /* 112 bytes, 8-byte aligned; lives in DEVICE memory */
+int r3d_streams_poses(const float *raw_dev, const float *raw_mirror_dev,   /* (S, J, 3): the forwards' outputs */
+                      int32_t num_streams, int32_t num_joints,
+                      const int32_t *mirror_perm,              /* HOST, J entries; given exactly when raw_mirror_dev is */
+                      const int64_t *emit_dev, const int32_t *status_dev,   /* (S): what r3d_streams_step wrote this tick */
+                      const r3d_stream_pose_desc *desc_dev,    /* (S); NULL only if world_dev and reproj_dev are NULL */
+                      const double *cam_dev,                   /* (S, 16) camera rows; required with reproj_dev */
+                      const float *x_dev, int32_t receptive_field, int32_t lag,   /* (S, RF, J, 3); required with reproj_dev */
+                      float *pred_dev,       /* (S, J, 3) float32, may be NULL */
+                      double *world_dev,     /* (S, J, 3) float64, may be NULL */
+                      double *reproj_dev,    /* (S, J) float64 pixels, may be NULL */
+                      double *quality_dev,   /* (S, 2) float64: mean, max of the stream's row of reproj; NULL unless reproj_dev */
+                      void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -989,6 +1060,12 @@ int r3d_debug_clips_windows_host(const float *src, int64_t total_frames, int32_t
 int r3d_debug_streams_step_host(void *state, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
                                 int32_t in_features, int32_t encoding, const float *frame, const double *cam, const int32_t *action,
                                 float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *status);
+/* r3d_streams_poses on the host (HOST pointers throughout, no stream): the same argument checks, the same finished-stream rule and
+ * the same per-point and quality routines, streams in order. */
+int r3d_debug_streams_poses_host(const float *raw, const float *raw_mirror, int32_t num_streams, int32_t num_joints,
+                                 const int32_t *mirror_perm, const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc,
+                                 const double *cam, const float *x, int32_t receptive_field, int32_t lag, float *pred, double *world,
+                                 double *reproj, double *quality);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

@@ -34,14 +34,14 @@ EXPORTS = (
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
-    "r3d_streams_state_bytes", "r3d_streams_step",
+    "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
-                "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host")
+                "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -127,6 +127,15 @@ def stream_head_dtype():
     import numpy as np
     return np.dtype([("count", np.int64), ("drained", np.int64)])
 
+
+def stream_pose_desc_dtype():
+    """The NumPy structured dtype with r3d_stream_pose_desc's layout (112 bytes): an array of it, uploaded as bytes, is the table
+    r3d_streams_poses reads - a (S, 14) float64 array of :meth:`Camera.stream_pose_row` rows has the same bytes."""
+    import numpy as np
+    return np.dtype([("rn2w", np.float64, (9,)), ("tn2w", np.float64, (3,)), ("height", np.float64), ("reserved", np.float64)])
+
+
+STREAM_POSE_DESC_BYTES = 112                                            # sizeof(r3d_stream_pose_desc)
 
 WINDOWS_BATCH_MAX = 65535                                               # `batch` of r3d_clips_windows (the grid's second dimension)
 
@@ -230,9 +239,13 @@ def load():
     lib.r3d_streams_state_bytes.restype = C.c_size_t
     lib.r3d_streams_step.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
                                      C.POINTER(C.c_int32), vp, vp, vp]
+    lib.r3d_streams_poses.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, C.c_int32, C.c_int32,
+                                      vp, vp, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_poses_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, C.c_int32,
+                                                     C.c_int32, vp, vp, vp, vp]
         lib.r3d_debug_streams_step_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
                                                     C.POINTER(C.c_int32), vp, vp]
         lib.r3d_debug_clips_windows_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64,
@@ -581,6 +594,43 @@ def debug_streams_step_host(state_ptr: int, num_streams: int, receptive_field: i
     return int(load().r3d_debug_streams_step_host(state_ptr or None, num_streams, receptive_field, lag, num_joints, in_features, encoding,
                                                   frame_ptr or None, cam_ptr or None, action_ptr or None, x_ptr or None,
                                                   x_mirror_ptr or None, perm, emit_ptr or None, status_ptr or None))
+
+
+def _streams_poses_features(what: str, in_features: int, reproj_ptr):
+    """The residual is defined for ray inputs only; the C call has no in_features to check (x_dev is (S, RF, J, 3) by contract), so
+    the binding refuses the other shape with the call's own code."""
+    if reproj_ptr and in_features != 3:
+        raise Ray3DHipError("%s failed (%d): reproj_dev is defined for 3-feature (ray) inputs only (in_features is %d)"
+                            % (what, R3D_ERR_ARG, in_features))
+
+
+def streams_poses(raw_ptr: int, raw_mirror_ptr: Optional[int], num_streams: int, num_joints: int, mirror_perm, emit_ptr: int,
+                  status_ptr: int, desc_ptr: Optional[int], cam_ptr: Optional[int], x_ptr: Optional[int], receptive_field: int, lag: int,
+                  pred_ptr: Optional[int], world_ptr: Optional[int], reproj_ptr: Optional[int], quality_ptr: Optional[int], stream: int,
+                  in_features: int = 3):
+    """r3d_streams_poses: every pointer is device memory; `raw_ptr` / `raw_mirror_ptr` (num_streams, num_joints, 3) float32;
+    `raw_mirror_ptr` (or None) and `mirror_perm` (a host sequence of num_joints ints, or None) go together; `emit_ptr` /
+    `status_ptr` the words r3d_streams_step wrote; `desc_ptr` num_streams r3d_stream_pose_desc (:func:`stream_pose_desc_dtype`);
+    `cam_ptr` (num_streams, 16) float64 and `x_ptr` (num_streams, receptive_field, num_joints, 3) go with `reproj_ptr`; any of
+    `pred_ptr`, `world_ptr`, `reproj_ptr` may be None, not all; `quality_ptr` only with `reproj_ptr`.  `in_features`: the width of
+    the rows behind `x_ptr` - anything but 3 with `reproj_ptr` is refused here (R3D_ERR_ARG)."""
+    _streams_poses_features("r3d_streams_poses", in_features, reproj_ptr)
+    perm = _mirror_table("r3d_streams_poses", mirror_perm, num_joints)
+    check(load().r3d_streams_poses(raw_ptr, raw_mirror_ptr or None, num_streams, num_joints, perm, emit_ptr, status_ptr, desc_ptr or None,
+                                   cam_ptr or None, x_ptr or None, receptive_field, lag, pred_ptr or None, world_ptr or None,
+                                   reproj_ptr or None, quality_ptr or None, stream), "r3d_streams_poses")
+
+
+def debug_streams_poses_host(raw_ptr: int, raw_mirror_ptr: Optional[int], num_streams: int, num_joints: int, mirror_perm, emit_ptr: int,
+                             status_ptr: int, desc_ptr: Optional[int], cam_ptr: Optional[int], x_ptr: Optional[int], receptive_field: int,
+                             lag: int, pred_ptr: Optional[int], world_ptr: Optional[int], reproj_ptr: Optional[int],
+                             quality_ptr: Optional[int]) -> int:
+    """r3d_debug_streams_poses_host (hooks library only: use_hooks(True)): r3d_streams_poses on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    perm = _mirror_table("r3d_debug_streams_poses_host", mirror_perm, num_joints)
+    return int(load().r3d_debug_streams_poses_host(raw_ptr or None, raw_mirror_ptr or None, num_streams, num_joints, perm, emit_ptr or None,
+                                                   status_ptr or None, desc_ptr or None, cam_ptr or None, x_ptr or None, receptive_field,
+                                                   lag, pred_ptr or None, world_ptr or None, reproj_ptr or None, quality_ptr or None))
 
 
 def _census_rows(call):

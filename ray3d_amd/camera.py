@@ -85,6 +85,13 @@ class Camera:
         pixels on the device (r3d_clips_project), no distortion."""
         return np.ascontiguousarray(self.K @ np.hstack([self.Rw2c, self.Tw2c]), dtype=np.float64).reshape(12)
 
+    def stream_pose_row(self) -> np.ndarray:
+        """The 14 float64 numbers of an r3d_stream_pose_desc: Rn2w row-major, Tn2w, the camera height, 0 - what r3d_streams_poses
+        (``OnlineLifter(world=True / quality=True).set_cameras(transforms=)``) turns a live stream's finished pose into world
+        coordinates with (camera.py:401-410) and takes it back to the camera with (Tc2n = (0, -height, 0), camera.py:340-343)."""
+        return np.concatenate([np.ascontiguousarray(self.Rn2w, dtype=np.float64).reshape(9), self.Tn2w.reshape(3),
+                               [self.height, 0.0]]).astype(np.float64)
+
     # -- host-side equivalents (dataset-load time in the reference, lib/dataset/__init__.py:191-203)
     def undistort_points(self, uv: np.ndarray) -> np.ndarray:
         """Pixel keypoints (..., 2) with the lens distortion removed, float64: the counterpart of

@@ -4,6 +4,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_poses.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -285,6 +286,73 @@ int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF
     a.J = J;
     a.F = F;
     a.encoding = encoding;
+    *args = a;
+    return R3D_OK;
+}
+
+// the argument rules of r3d_streams_poses, shared with its host hook; fills the kernel's argument set
+int r3d::streams_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int32_t S, int32_t J,
+                                  const int32_t *mirror_perm, const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc,
+                                  const double *cam, const float *x, int32_t RF, int32_t lag, float *pred, double *world, double *reproj,
+                                  double *quality, StreamsPosesArgs *args) {
+    static_assert(sizeof(r3d_stream_pose_desc) == 112, "r3d_stream_pose_desc is documented as 112 bytes");
+    if (!raw || !emit || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (!pred && !world && !reproj) { set_error("%s: pred_dev, world_dev and reproj_dev are all null: nothing to write", what); return R3D_ERR_ARG; }
+    if (quality && !reproj) { set_error("%s: quality_dev needs reproj_dev", what); return R3D_ERR_ARG; }
+    if ((world || reproj) && !desc) { set_error("%s: world_dev and reproj_dev need desc_dev", what); return R3D_ERR_ARG; }
+    if (reproj && (!cam || !x)) { set_error("%s: reproj_dev needs cam_dev and x_dev", what); return R3D_ERR_ARG; }
+    if (S < 1 || S > R3D_CLIPS_MAX) { set_error("%s: num_streams must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, S); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if ((raw_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: raw_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
+    if (reproj) {
+        if (RF < 1) { set_error("%s: receptive_field must be >= 1 (got %d)", what, RF); return R3D_ERR_ARG; }
+        if (lag < 0 || lag > RF - 1) { set_error("%s: lag must be in 0..receptive_field - 1 (got %d)", what, lag); return R3D_ERR_ARG; }
+        if (S > R3D_ENCODE_MAX_POINTS / ((int64_t)RF * J)) {
+            set_error("%s: num_streams * receptive_field * num_joints must not exceed %d", what, R3D_ENCODE_MAX_POINTS);
+            return R3D_ERR_ARG;
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(emit) % 8 || reinterpret_cast<uintptr_t>(desc) % 8 || reinterpret_cast<uintptr_t>(cam) % 8 ||
+        reinterpret_cast<uintptr_t>(world) % 8 || reinterpret_cast<uintptr_t>(reproj) % 8 || reinterpret_cast<uintptr_t>(quality) % 8) {
+        set_error("%s: emit_dev, desc_dev, cam_dev, world_dev, reproj_dev and quality_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    // in-place use is refused: an output extent may not overlap an input extent (address ranges; the sizes fit in 64 bits).  x_dev is
+    // an input only with reproj_dev (its extent is known only then).
+    const uintptr_t pts = (uintptr_t)S * J;
+    const char *out_name[4] = {"pred_dev", "world_dev", "reproj_dev", "quality_dev"}, *in_name[3] = {"raw_dev", "raw_mirror_dev", "x_dev"};
+    const uintptr_t outs[4] = {reinterpret_cast<uintptr_t>(pred), reinterpret_cast<uintptr_t>(world), reinterpret_cast<uintptr_t>(reproj),
+                               reinterpret_cast<uintptr_t>(quality)};
+    const uintptr_t out_bytes[4] = {pts * 3 * sizeof(float), pts * 3 * sizeof(double), pts * sizeof(double), (uintptr_t)S * 2 * sizeof(double)};
+    const uintptr_t ins[3] = {reinterpret_cast<uintptr_t>(raw), reinterpret_cast<uintptr_t>(raw_mirror), reproj ? reinterpret_cast<uintptr_t>(x) : 0};
+    const uintptr_t in_bytes[3] = {pts * 3 * sizeof(float), pts * 3 * sizeof(float), reproj ? pts * (uintptr_t)RF * 3 * sizeof(float) : 0};
+    for (int o = 0; o < 4; ++o)
+        for (int i = 0; i < 3; ++i)
+            if (outs[o] && ins[i] && outs[o] < ins[i] + in_bytes[i] && ins[i] < outs[o] + out_bytes[o]) {
+                set_error("%s: %s overlaps %s: the call does not work in place", what, out_name[o], in_name[i]);
+                return R3D_ERR_ARG;
+            }
+    StreamsPosesArgs a = {};
+    a.raw = raw;
+    a.raw_mirror = raw_mirror;
+    a.emit = reinterpret_cast<const long long *>(emit);
+    a.status = status;
+    a.desc = (world || reproj) ? desc : nullptr;
+    a.cam = reproj ? cam : nullptr;
+    a.x = reproj ? x : nullptr;
+    a.pred = pred;
+    a.world = world;
+    a.reproj = reproj;
+    a.quality = quality;
+    if (mirror_perm) pose_pack_perm(mirror_perm, J, a.mirror_perm);
+    a.S = S;
+    a.J = J;
+    a.RF = reproj ? RF : 1;
+    a.lag = reproj ? lag : 0;
     *args = a;
     return R3D_OK;
 }
@@ -611,6 +679,24 @@ int r3d_streams_step(void *state_dev, int32_t num_streams, int32_t receptive_fie
     const hipError_t err = r3d::launch_streams_step(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_step: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_streams_poses(const float *raw_dev, const float *raw_mirror_dev, int32_t num_streams, int32_t num_joints, const int32_t *mirror_perm,
+                      const int64_t *emit_dev, const int32_t *status_dev, const r3d_stream_pose_desc *desc_dev, const double *cam_dev,
+                      const float *x_dev, int32_t receptive_field, int32_t lag, float *pred_dev, double *world_dev, double *reproj_dev,
+                      double *quality_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsPosesArgs a;
+    const int rc = streams_poses_check_args("r3d_streams_poses", raw_dev, raw_mirror_dev, num_streams, num_joints, mirror_perm, emit_dev,
+                                            status_dev, desc_dev, cam_dev, x_dev, receptive_field, lag, pred_dev, world_dev, reproj_dev,
+                                            quality_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_poses(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_poses: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -11,6 +11,7 @@
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_poses.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
 #include "r3d_windows.hpp"
@@ -764,6 +765,25 @@ int r3d_debug_streams_step_host(void *state, int32_t num_streams, int32_t recept
         if (!stream_emits(c, a.heads[s].drained, n, a.status[s], a.lag)) continue;
         for (int i = 0; i < a.RF; ++i)
             for (int j = 0; j < a.J; ++j) stream_gather_point(a, s, n, c, i, j);
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_poses on the host - its argument rules (streams_poses_check_args), the finished-stream rule and the routines of
+// r3d_streams_poses.hpp the kernel runs: per finished stream its J points in joint order, then the quality words from their residuals.
+int r3d_debug_streams_poses_host(const float *raw, const float *raw_mirror, int32_t num_streams, int32_t num_joints,
+                                 const int32_t *mirror_perm, const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc,
+                                 const double *cam, const float *x, int32_t receptive_field, int32_t lag, float *pred, double *world,
+                                 double *reproj, double *quality) {
+    StreamsPosesArgs a;
+    const int rc = streams_poses_check_args("r3d_debug_streams_poses_host", raw, raw_mirror, num_streams, num_joints, mirror_perm, emit,
+                                            status, desc, cam, x, receptive_field, lag, pred, world, reproj, quality, &a);
+    if (rc != R3D_OK) return rc;
+    for (int s = 0; s < a.S; ++s) {
+        if (!stream_finished(a.status[s], a.emit[s])) continue;
+        double res[17];
+        for (int j = 0; j < a.J; ++j) res[j] = stream_pose_point(a, s, j);
+        if (a.quality) stream_quality(res, a.J, a.quality + 2 * s);
     }
     return R3D_OK;
 }

@@ -590,6 +590,13 @@ int streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int
                        const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror, const int32_t *mirror_perm,
                        int64_t *emit, int32_t *status, StreamsArgs *args);
 
+struct StreamsPosesArgs;     // r3d_streams_poses.hpp
+// the argument rules of r3d_streams_poses, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int32_t S, int32_t J, const int32_t *mirror_perm,
+                             const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc, const double *cam,
+                             const float *x, int32_t RF, int32_t lag, float *pred, double *world, double *reproj, double *quality,
+                             StreamsPosesArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -695,6 +702,7 @@ struct PackArgs;                                                                
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // the same kernel: r3d_finalize_dev
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream);             // the same kernel: r3d_clips_windows
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);                         // the same kernel, two launches: r3d_streams_step
+hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream);                   // the same kernel: r3d_streams_poses
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -55,11 +55,22 @@
 // workgroups reads -, and each thread copies one output point (row, joint) of the window from its ring slot through
 // stream_gather_point, the routine the host hook runs: 8 or 12 bytes read and written per thread, consecutive threads at
 // consecutive addresses of x; the ring is read in rows of J * F * 4 bytes that wrap once.
+//
+// r3d_streams_poses (a live tick's finished poses: flip average, world transform and the re-projection residual against the keypoints
+// that were fed in, include/ray3d_hip.h) is the eighth argument set, StreamsPosesArgs: one workgroup of one wavefront per stream; it
+// reads the stream's emit and status words - one address for the workgroup: scalar loads - before anything else and returns unless
+// the stream finished a frame this tick; then it reads the descriptor and the camera row (scalar loads again), thread j < J finishes
+// joint j through pose_finish / pose_world / stream_reproj - the routines the host hook runs -, writes its outputs and parks its
+// residual in LDS (17 doubles), and after a barrier thread 0 sums the J residuals in joint order and writes the two quality words.
+// S x J <= 17 threads of work per workgroup, a few hundred bytes per stream: the launch is LAUNCH-LATENCY-BOUND by construction -
+// neither bandwidth nor occupancy nor the float64 divisions show in its time; it exists to replace a string of small torch launches
+// by one.  Plain vector stores from C++ throughout, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_poses.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -211,10 +222,39 @@ __device__ __forceinline__ void streams_gather_body(const StreamsArgs &t) {
     stream_gather_point(t, s, n, c, i, pt - i * t.J);
 }
 
+// Stream blockIdx.x < S, joint threadIdx.x < J <= 17.  emit[s] and status[s] are one address for the workgroup, so the verdict is
+// uniform and an unfinished stream's workgroup leaves before the barrier as a whole: nothing of its rows is read or written.
+__device__ __forceinline__ void streams_poses_body(const StreamsPosesArgs &u) {
+    __shared__ double res[17];
+    const int s = blockIdx.x;
+    if (!stream_finished(u.status[s], u.emit[s])) return;
+    const int j = threadIdx.x;
+    if (j < u.J) {
+        const double e = stream_pose_point(u, s, j);                 // (s < S, j < J: inside rows s of every buffer)
+        if (u.quality) res[j] = e;
+    }
+    if (!u.quality) return;                  // uniform
+    __syncthreads();
+    if (j != 0) return;
+    double qw[2];
+    stream_quality(res, u.J, qw);
+    u.quality[2 * s] = qw[0];
+    u.quality[2 * s + 1] = qw[1];
+}
+
+// The eight argument sets travel in one kernel-argument segment (4 KiB on this target)
+static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
+                      sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + 8 * 8 <= 4096,
+              "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
+
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
-                                                                         const StreamsArgs sm) {
-    if (sm.heads) {                           // uniform: r3d_streams_step - the advance launch, then the gather launch
+                                                                         const StreamsArgs sm, const StreamsPosesArgs sp) {
+    if (sp.raw) {                             // uniform: r3d_streams_poses - stream blockIdx.x
+        streams_poses_body(sp);
+        return;
+    }
+    if (sm.heads) {                          // uniform: r3d_streams_step - the advance launch, then the gather launch
         if (sm.phase == 0) streams_advance_body(sm);
         else streams_gather_body(sm);
         return;
@@ -284,28 +324,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
@@ -313,14 +353,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{});
     return hipGetLastError();
 }
 
@@ -328,12 +368,19 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t);
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
+hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
+    static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args);
     return hipGetLastError();
 }
 

@@ -24,11 +24,18 @@ class OnlineLifter:
     `pad` frames of a stream that ends come out of :meth:`drain`.  `flip`: the reference's test-time flip (trainer.py:299-353) -
     the mirrored windows are gathered by the same call (`kps_left` / `kps_right`), lifted by a second forward, and the two passes
     averaged through :func:`evaluate.mirror_output` (`joints_left` / `joints_right`, default the keypoint lists).
+    `world` / `quality`: the tick's finished poses come from ONE r3d_streams_poses call instead of the torch flip finish - the same
+    float32 poses, and beside them (:meth:`step`'s third value) the poses in world coordinates (cam.normalized2world, float64) and
+    / or the re-projection residual of every joint against the keypoints that were fed in, in undistorted pixels, with its mean
+    and maximum per stream: the quality signal of a stream without ground truth.  Both read the streams' transform rows
+    (:meth:`set_cameras` ``transforms=``, :meth:`Camera.stream_pose_row`); `quality` needs a 3-feature (ray) model and the camera
+    rows - with ``encoding=None`` they are then passed to :meth:`set_cameras` as well.  Off by default: the tick is then exactly
+    what it was.
     The lifter is prepared for batches of `num_streams` windows here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), joints_left: Optional[Sequence[int]] = None,
-                 joints_right: Optional[Sequence[int]] = None, device=None):
+                 joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -45,6 +52,9 @@ class OnlineLifter:
         if nbytes == 0:
             raise ValueError("OnlineLifter: num_streams must be in 1..%d (got %d)" % (_capi.CLIPS_MAX, self.S))
         self.flip = bool(flip)
+        self.world, self.quality = bool(world), bool(quality)
+        if self.quality and self.F != 3:
+            raise ValueError("OnlineLifter: quality=True is defined for 3-feature (ray) inputs only; this pair takes %d" % self.F)
         self.perm = evaluate.mirror_permutation(self.J, kps_left, kps_right) if self.flip else None
         self.joints = (list(kps_left if joints_left is None else joints_left), list(kps_right if joints_right is None else joints_right))
         dev = self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -56,23 +66,35 @@ class OnlineLifter:
         self.status = torch.zeros((S,), dtype=torch.int32, device=dev)
         self.frame = torch.zeros((S, J, self.width), dtype=torch.float32, device=dev)
         self.action = torch.zeros((S,), dtype=torch.int32, device=dev)
-        self.cam = torch.zeros((S, 16), dtype=torch.float64, device=dev) if encoding is not None else None
+        self.cam = torch.zeros((S, 16), dtype=torch.float64, device=dev) if encoding is not None or self.quality else None
         self.param = torch.zeros((S, pos.extrinsic_dim), dtype=torch.float32, device=dev) if pos.camera_embedding else None
-        self._cameras_set = encoding is None and self.param is None
+        self.transforms = self._finish = None
+        if self.world or self.quality:  # r3d_streams_poses: the descriptors, the forwards' raw outputs and what the call writes
+            self.transforms = torch.zeros((S, 14), dtype=torch.float64, device=dev)
+            self._finish = dict(raw=torch.zeros((S, 1, J, 3), dtype=torch.float32, device=dev),
+                                raw_m=torch.zeros((S, 1, J, 3), dtype=torch.float32, device=dev) if self.flip else None,
+                                pred=torch.zeros((S, 1, J, 3), dtype=torch.float32, device=dev),
+                                world=torch.zeros((S, J, 3), dtype=torch.float64, device=dev) if self.world else None,
+                                reproj=torch.zeros((S, J), dtype=torch.float64, device=dev) if self.quality else None,
+                                quality=torch.zeros((S, 2), dtype=torch.float64, device=dev) if self.quality else None)
+        self._cameras_set = self.cam is None and self.param is None and self.transforms is None
         self._graph = None
         self._captured = None       # the captured tick's (poses, out, out_mirror) buffers
         if self.flip:               # the flip finish without host-built index tensors: what a captured tick runs
             out_perm = evaluate.mirror_permutation(J, *self.joints)
+            self._out_perm_host = [int(v) for v in out_perm]
             self._out_perm = torch.tensor(out_perm, dtype=torch.int64, device=dev)
             self._out_sign = torch.tensor([-1.0, 1.0, 1.0], dtype=torch.float32, device=dev)
         lifter.prepare([S], dev)
 
     # ---- setup -----------------------------------------------------------------------------------------------------------
-    def set_cameras(self, cam_rows=None, params=None):
+    def set_cameras(self, cam_rows=None, params=None, transforms=None):
         """The streams' cameras: `cam_rows` (S, 16) float64 - :meth:`Camera.cam_row` with distortion=True, what the pixel encodings
-        read - and `params` (S, E) float32, the forward's camera-parameter rows (models with a camera embedding).  Copied into
-        the buffers the ticks read (also the captured one's): it may be called between ticks."""
-        for given, buf, name, dtype in ((cam_rows, self.cam, "cam_rows", torch.float64), (params, self.param, "params", torch.float32)):
+        and `quality` read -, `params` (S, E) float32, the forward's camera-parameter rows (models with a camera embedding), and
+        `transforms` (S, 14) float64 - :meth:`Camera.stream_pose_row`, needed with `world` or `quality`.  Copied into the buffers
+        the ticks read (also the captured one's): it may be called between ticks."""
+        for given, buf, name, dtype in ((cam_rows, self.cam, "cam_rows", torch.float64), (params, self.param, "params", torch.float32),
+                                        (transforms, self.transforms, "transforms", torch.float64)):
             if buf is None:
                 continue
             if given is None:
@@ -97,6 +119,8 @@ class OnlineLifter:
                                self.cam.data_ptr() if self.cam is not None else None, self.action.data_ptr(), self.x.data_ptr(),
                                self.x_mirror.data_ptr() if self.flip else None, self.perm, self.emit.data_ptr(), self.status.data_ptr(),
                                torch.cuda.current_stream(dev).cuda_stream)
+        if self._finish is not None:
+            return self._finish_tick()
         if out is None:             # eager: the public forward, the reference's flip finish
             pred = lifter.forward(self.x, self.param)
             if self.flip:
@@ -108,11 +132,36 @@ class OnlineLifter:
             pred = self._mirror_finish(pred, lifter._run(_capi.R3D_INPUT_RAYS, self.x_mirror, self.rf, self.S, self.param, E, out=out_m))
         return pred
 
+    def _finish_tick(self):
+        """The forward(s) into the (S, 1, J, 3) buffers, then ONE r3d_streams_poses call: the flip average, the world transform and
+        the residuals of the streams that finished a frame this tick - eagerly and under capture alike -> poses (S, 1, J, 3)."""
+        dev, lifter, f = self.device, self.lifter, self._finish
+        E = lifter.pos.extrinsic_dim
+        lifter._run(_capi.R3D_INPUT_RAYS, self.x, self.rf, self.S, self.param, E, out=f["raw"])
+        if self.flip:
+            lifter._run(_capi.R3D_INPUT_RAYS, self.x_mirror, self.rf, self.S, self.param, E, out=f["raw_m"])
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        with torch.cuda.device(dev):
+            _capi.streams_poses(ptr(f["raw"]), ptr(f["raw_m"]), self.S, self.J, self._out_perm_host if self.flip else None,
+                                self.emit.data_ptr(), self.status.data_ptr(), self.transforms.data_ptr(), ptr(self.cam), self.x.data_ptr(),
+                                self.rf, self.lag, ptr(f["pred"]), ptr(f["world"]), ptr(f["reproj"]), ptr(f["quality"]),
+                                torch.cuda.current_stream(dev).cuda_stream, in_features=self.F)
+        return f["pred"]
+
+    def _extras(self):
+        f = self._finish
+        return {k: f[k].clone() for k in ("world", "reproj", "quality") if f[k] is not None}
+
     def step(self, frame=None, actions=None, check: bool = True):
         """One tick.  `frame` (S, J, 2) pixels or (S, J, F) model-input rows, a tensor or an array (None: no stream delivers one -
         a tick of DRAIN / IDLE actions); `actions` (S,) R3D_STREAM_* words (None: every stream PUSHes).
         -> (poses (S, J, 3), frames (S,) int64): frames[s] is the index of the frame poses[s] belongs to - the newest one for a causal
         model, `pad` frames back for a centred one - or -1: stream s has no pose this tick and poses[s] is not meaningful.
+        With `world` / `quality` -> (poses, frames, extras): a dict with "world" (S, J, 3) float64, "reproj" (S, J) float64 pixels
+        and "quality" (S, 2) float64 (mean, max of the stream's residuals) - the keys that were asked for; rows of streams without
+        a pose this tick are not meaningful (they keep what an earlier tick left).
         Raises on a refused stream (an unknown action, a PUSH after a drain began: RESTART starts the next clip) unless `check`
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
@@ -137,34 +186,44 @@ class OnlineLifter:
                 poses = self._captured[0].clone()
             else:
                 poses = self._tick()
+                if self._finish is not None:
+                    poses = poses.clone()
         frames = self.emit.clone()
+        extras = self._extras() if self._finish is not None else None
         if check:
             bad = torch.nonzero(self.status).flatten().tolist()
             if bad:
                 raise RuntimeError("r3d_streams_step refused streams %s (an unknown action, a PUSH after a drain began, or a "
                                    "corrupted head): RESTART them" % bad)
-        return poses[:, 0], frames
+        return (poses[:, 0], frames) if extras is None else (poses[:, 0], frames, extras)
 
     def drain(self, check: bool = True) -> List[tuple]:
-        """The streams have ended: `lag` ticks of DRAIN for every stream -> the list of their (poses, frames).  Nothing for a
+        """The streams have ended: `lag` ticks of DRAIN for every stream -> the list of their (poses, frames) - with `world` /
+        `quality` (poses, frames, extras), as :meth:`step` returns them.  Nothing for a
         causal model.  Afterwards a stream takes RESTART (its next clip), not PUSH."""
         act = torch.full((self.S,), DRAIN, dtype=torch.int32)
         return [self.step(None, act, check) for _ in range(self.lag)]
 
-    def lift_clips(self, clips: Sequence, cam_rows=None, params=None) -> List[torch.Tensor]:
+    def lift_clips(self, clips: Sequence, cam_rows=None, params=None, transforms=None, world: bool = False) -> list:
         """Clips of unequal length - at most S arrays (N_k, J, 2 or F) - fed side by side, one stream each: RESTART, PUSH ..., the
         drain when a clip ends, then IDLE.  -> per clip its poses (N_k, J, 3) in frame order: what the reference's evaluation
-        computes for the clip (edge padding, eval_data_prepare, the forward, the flip average)."""
+        computes for the clip (edge padding, eval_data_prepare, the forward, the flip average).
+        `world` (a lifter built with `world` and / or `quality`): -> per clip (poses, extras), `extras` the frames' rows of what
+        :meth:`step` returns third - "world" (N_k, J, 3) float64, "reproj" (N_k, J) and "quality" (N_k, 2), the keys asked for."""
         if len(clips) > self.S:
             raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
-        if cam_rows is not None or params is not None:
-            self.set_cameras(cam_rows, params)
+        if world and self._finish is None:
+            raise ValueError("lift_clips: world=True needs an OnlineLifter built with world=True or quality=True")
+        if cam_rows is not None or params is not None or transforms is not None:
+            self.set_cameras(cam_rows, params, transforms)
         clips = [np.ascontiguousarray(torch.as_tensor(c).cpu().numpy(), dtype=np.float32) for c in clips]
         lengths = [c.shape[0] for c in clips]
         if min(lengths) < 1:
             raise ValueError("lift_clips: a clip needs at least one frame")
         outs = [torch.empty((n, self.J, 3), dtype=torch.float32, device=self.device) for n in lengths]
         seen = [0] * len(clips)
+        more = [{k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in self._finish.items()
+                 if k in ("world", "reproj", "quality") and v is not None} for n in lengths] if self._finish is not None else None
         frame = np.zeros(tuple(self.frame.shape), np.float32)
         for t in range(max(lengths) + self.lag):
             act = np.full(self.S, IDLE, np.int32)
@@ -173,13 +232,15 @@ class OnlineLifter:
                     act[s], frame[s] = (RESTART if t == 0 else PUSH), c[t]
                 elif t < n + self.lag:
                     act[s] = DRAIN
-            poses, frames = self.step(frame, act)
+            poses, frames, *extras = self.step(frame, act)
             for s, n in enumerate(frames.tolist()[:len(clips)]):
                 if n >= 0:
                     outs[s][n] = poses[s]
+                    for k, v in (extras[0].items() if extras else ()):
+                        more[s][k][n] = v[s]
                     seen[s] += 1
         assert seen == lengths, (seen, lengths)
-        return outs
+        return list(zip(outs, more)) if world else outs
 
     # ---- capture ---------------------------------------------------------------------------------------------------------
     def capture(self):

@@ -961,6 +961,84 @@ int r3d_streams_poses(const float *raw_dev, const float *raw_mirror_dev,   /* (S
                       double *quality_dev,   /* (S, 2) float64: mean, max of the stream's row of reproj; NULL unless reproj_dev */
                       void *stream);
 
+/* ---- live streams that survive dropped keypoints: one call in front of a tick's r3d_streams_step ---- */
+
+/* A 2D detector does not deliver every joint of every frame.  r3d_streams_step copies or encodes whatever it is handed into the
+ * ring, and a non-finite keypoint then makes the stream's pose NaN for the next RF ticks.  r3d_streams_repair is enqueued BEFORE
+ * r3d_streams_step of the same tick, on the same stream, with the same state, shape, camera rows and action words: it reads the
+ * tick's new frames, decides per joint whether the keypoint was OBSERVED, writes a repaired frame for the step to push
+ * (frame_out_dev: the step is then given frame_out_dev as its frame_dev), rewrites the few ring entries a closing gap lets it
+ * improve, keeps a small per-stream track record, and reports which joints of the frame the step emits this tick are synthetic.
+ * A stream without gaps is left bit for bit what it is without the call.  The reference's archives are complete, so it has no
+ * behaviour to copy here; a repaired stream equals the reference's windows (np.pad 'edge' + eval_data_prepare) of the clip
+ * repaired offline by the same rules, wherever that is well defined.  Windows already emitted are never revised: a frame's window
+ * uses the best repair known at the tick it is emitted.
+ *   state_dev:   the state of r3d_streams_step.  The heads are READ, never written; ring entries may be rewritten.
+ *   track_dev:   caller-owned DEVICE memory of r3d_streams_track_bytes bytes, 8-byte aligned; all-zero is "freshly reset".  LAYOUT,
+ *                with width = 2 for the pixel encodings and in_features for R3D_ENCODE_NONE (as the frame rows of r3d_streams_step):
+ *                  int32    age[S][J]            0: the joint was never observed since the stream's last RESTART; k >= 1: it was
+ *                                                observed k - 1 frames ago; saturates at INT32_MAX; a value below 0 (a track nobody
+ *                                                zeroed) reads as 0
+ *                  float32  last[S][J][width]    the joint's last observed input, as delivered (32-bit patterns)
+ *                  uint32   missing[S][RF]       per ring slot the mask (bit j: joint j) of the joints not observed in that frame
+ *                in that order, the total rounded up to a multiple of 8 bytes.
+ *   frame_dev:   (S, J, width) float32: what the caller would have given the step; may hold non-finite entries.
+ *   conf_dev / min_conf: NULL, or (S, J) float32 detector confidences and the threshold.
+ *   max_gap:     in [0, RF - 1]: the longest gap that is interpolated when it closes (0: zero-order hold only).
+ *   frame_out_dev: (S, J, width) float32, written for the streams that PUSH or RESTART this tick.
+ *   synthetic_dev: (S) uint32: bit j set = joint j of the frame the step emits this tick was not observed - however good its repair.
+ * PER STREAM.  The head and the action word are judged by the very routine the step uses, on the head as it stands before the step.
+ *   NO PUSH (IDLE, DRAIN, a stream the step will refuse): nothing of the stream's track, ring or frame_out row is written;
+ *            synthetic[s] is the `missing` word of the frame the step will emit (a DRAIN that emits), or 0.
+ *   RESTART  the stream's track is zeroed first - whatever it held -, then the action is a PUSH with c = 0.
+ *   PUSH, joint j, c the head's count before the push:
+ *     OBSERVED means every one of the `width` input components is finite (tested on the exponent bits) and, with conf_dev,
+ *            conf >= min_conf (a NaN confidence is not observed).
+ *     not observed, age == 0   frame_out = the canonical quiet NaN (0x7FC00000) in every component; age stays 0.
+ *     not observed, age >= 1   frame_out = last[j]: zero-order hold in INPUT space (the step encodes it to the bits it encoded
+ *            before); age += 1.
+ *     observed   frame_out = the input bits, last[j] = the input bits, age = 1.  Before that, with e the joint's encoding - for a
+ *            pixel encoding the routine and bits the step will push (through the stream's camera row), for R3D_ENCODE_NONE the
+ *            row itself:
+ *            BACK-FILL  the old age was 0 and c >= 1: every frame in max(0, c - (RF - 1)) .. c - 1 gets e for joint j in the ring
+ *              (the per-joint analogue of the reference's front edge padding).
+ *            INTERPOLATION  the old age was k >= 2, g = k - 1, 1 <= g <= max_gap and g + 1 <= c: with a the ring's entry of frame
+ *              c - 1 for joint j (the held copy of the last observation), frame c - 1 - g + m, m = 1 .. g, gets per component
+ *                fl32((double)a + ((double)e - (double)a) * ((double)m / (double)(g + 1)))
+ *              every operation rounded once, no contraction; a NaN result leaves as the canonical quiet NaN.  The encodings are
+ *              affine in the (undistorted) pixel: this is linear interpolation in undistorted pixel space.
+ *            Otherwise the held values stay.
+ *     after the joints   missing[c % RF] = the mask of the joints not observed in the new frame (interpolated or back-filled
+ *            frames keep their bits); synthetic[s] = missing[(c - lag) % RF] if c - lag >= 0 - the frame the step will emit - else 0.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: S workgroups of one wavefront;
+ * thread j < J owns joint j and is the only one that writes the joint's frame_out row, age, last and ring entries; one thread
+ * forms the mask from the wavefront's ballot and writes the two mask words.  Launch-latency-bound by construction.
+ * THE WHOLE BOUNDS STORY.  Whatever the track, the state and the action words hold, the kernel reads the heads, frame_dev,
+ * conf_dev, cam_dev and action_dev within their S rows and writes the rings within r3d_streams_state_bytes, the track within
+ * r3d_streams_track_bytes, frame_out_dev within S * J * width floats and synthetic_dev within S words: ring and `missing` indices
+ * are remainders modulo RF of frames in [0, c] of a head that passed the step's head rule (rewritten ring entries: frames in
+ * [0, c - 1]); g is used only after g <= max_gap <= RF - 1 and g + 1 <= c; no index comes from `last` or `missing`, and an age only
+ * ever bounds a loop that those two comparisons have bounded first.
+ * R3D_ERR_ARG (checked on the host before any HIP call): everything r3d_streams_step refuses for the arguments the two share
+ * (state_dev, the shape, lag, encoding and in_features, frame_dev, cam_dev, action_dev); a null track_dev, frame_out_dev or
+ * synthetic_dev; max_gap outside [0, receptive_field - 1]; a non-finite min_conf; a track_dev that is not 8-byte aligned;
+ * frame_out_dev overlapping frame_dev, conf_dev, the state or the track, compared as address ranges.  r3d_streams_track_bytes
+ * returns 0 for shapes the call refuses (`width` 2 or 3, the rest as r3d_streams_state_bytes).
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+size_t r3d_streams_track_bytes(int32_t num_streams, int32_t receptive_field, int32_t num_joints, int32_t width);
+int r3d_streams_repair(void *state_dev,              /* the state of r3d_streams_step: heads READ, rings rewritten */
+                       void *track_dev,              /* r3d_streams_track_bytes, 8-byte aligned; all-zero = fresh   */
+                       int32_t num_streams, int32_t receptive_field, int32_t lag,
+                       int32_t num_joints, int32_t in_features, int32_t encoding,
+                       const float *frame_dev,       /* (S, J, width): what the caller would have given the step    */
+                       const float *conf_dev, float min_conf,   /* (S, J) or NULL: detector confidences             */
+                       const double *cam_dev,        /* (S, 16); NULL with R3D_ENCODE_NONE                          */
+                       const int32_t *action_dev,    /* (S): the words the step will read                           */
+                       int32_t max_gap,              /* 0 .. RF - 1: longest gap that is interpolated when it closes */
+                       float *frame_out_dev,         /* (S, J, width): what the step is given as frame_dev          */
+                       uint32_t *synthetic_dev,      /* (S): bit j set = joint j of the frame emitted this tick was not observed */
+                       void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -1066,6 +1144,12 @@ int r3d_debug_streams_poses_host(const float *raw, const float *raw_mirror, int3
                                  const int32_t *mirror_perm, const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc,
                                  const double *cam, const float *x, int32_t receptive_field, int32_t lag, float *pred, double *world,
                                  double *reproj, double *quality);
+/* r3d_streams_repair on the host (HOST pointers throughout, no stream): the same argument checks, the same head and action
+ * verdict, observed test, per-joint step, interpolation arithmetic and mask words, streams in order, joints in order. */
+int r3d_debug_streams_repair_host(void *state, void *track, int32_t num_streams, int32_t receptive_field, int32_t lag,
+                                  int32_t num_joints, int32_t in_features, int32_t encoding, const float *frame, const float *conf,
+                                  float min_conf, const double *cam, const int32_t *action, int32_t max_gap, float *frame_out,
+                                  uint32_t *synthetic);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

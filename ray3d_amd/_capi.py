@@ -34,14 +34,15 @@ EXPORTS = (
     "r3d_lane_stream", "r3d_lanes_join", "r3d_input_workspace_bytes", "r3d_clips_metrics", "r3d_clips_metrics_scratch_bytes",
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
-    "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses",
+    "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
-                "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host")
+                "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
+                "r3d_debug_streams_repair_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -241,9 +242,15 @@ def load():
                                      C.POINTER(C.c_int32), vp, vp, vp]
     lib.r3d_streams_poses.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, C.c_int32, C.c_int32,
                                       vp, vp, vp, vp, vp]
+    lib.r3d_streams_track_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.r3d_streams_track_bytes.restype = C.c_size_t
+    lib.r3d_streams_repair.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, vp, vp,
+                                       C.c_int32, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_repair_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                                      C.c_float, vp, vp, C.c_int32, vp, vp]
         lib.r3d_debug_streams_poses_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, C.c_int32,
                                                      C.c_int32, vp, vp, vp, vp]
         lib.r3d_debug_streams_step_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
@@ -631,6 +638,35 @@ def debug_streams_poses_host(raw_ptr: int, raw_mirror_ptr: Optional[int], num_st
     return int(load().r3d_debug_streams_poses_host(raw_ptr or None, raw_mirror_ptr or None, num_streams, num_joints, perm, emit_ptr or None,
                                                    status_ptr or None, desc_ptr or None, cam_ptr or None, x_ptr or None, receptive_field,
                                                    lag, pred_ptr or None, world_ptr or None, reproj_ptr or None, quality_ptr or None))
+
+
+def streams_track_bytes(num_streams: int, receptive_field: int, num_joints: int, width: int) -> int:
+    """r3d_streams_track_bytes: the bytes of the track r3d_streams_repair keeps for `num_streams` streams - (S, J) int32 ages,
+    (S, J, width) float32 last inputs, (S, RF) uint32 masks, in that order (0 for a shape the call refuses).  `width`: 2 for the
+    pixel encodings, in_features for R3D_ENCODE_NONE."""
+    return int(load().r3d_streams_track_bytes(num_streams, receptive_field, num_joints, width))
+
+
+def streams_repair(state_ptr: int, track_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int, in_features: int,
+                   encoding: int, frame_ptr: int, conf_ptr: Optional[int], min_conf: float, cam_ptr: Optional[int], action_ptr: int,
+                   max_gap: int, frame_out_ptr: int, synthetic_ptr: int, stream: int):
+    """r3d_streams_repair (enqueued BEFORE :func:`streams_step` of the same tick, which is then given `frame_out_ptr` as its frame):
+    every pointer is device memory; `state_ptr` the step's state; `track_ptr` :func:`streams_track_bytes` bytes, 8-byte aligned,
+    all-zero = fresh; `conf_ptr` (num_streams, num_joints) float32 or None; `cam_ptr` (num_streams, 16) float64 or None
+    (R3D_ENCODE_NONE); `synthetic_ptr` num_streams uint32."""
+    check(load().r3d_streams_repair(state_ptr, track_ptr, num_streams, receptive_field, lag, num_joints, in_features, encoding, frame_ptr,
+                                    conf_ptr or None, min_conf, cam_ptr or None, action_ptr, max_gap, frame_out_ptr, synthetic_ptr, stream),
+          "r3d_streams_repair")
+
+
+def debug_streams_repair_host(state_ptr: int, track_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int,
+                              in_features: int, encoding: int, frame_ptr: int, conf_ptr: Optional[int], min_conf: float,
+                              cam_ptr: Optional[int], action_ptr: int, max_gap: int, frame_out_ptr: int, synthetic_ptr: int) -> int:
+    """r3d_debug_streams_repair_host (hooks library only: use_hooks(True)): r3d_streams_repair on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    return int(load().r3d_debug_streams_repair_host(state_ptr or None, track_ptr or None, num_streams, receptive_field, lag, num_joints,
+                                                    in_features, encoding, frame_ptr or None, conf_ptr or None, min_conf, cam_ptr or None,
+                                                    action_ptr or None, max_gap, frame_out_ptr or None, synthetic_ptr or None))
 
 
 def _census_rows(call):

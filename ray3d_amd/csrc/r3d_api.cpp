@@ -5,6 +5,7 @@
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
 #include "r3d_streams_poses.hpp"
+#include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -237,13 +238,9 @@ static bool streams_shape_ok(int32_t S, int32_t RF, int32_t J, int32_t F) {
            S <= R3D_ENCODE_MAX_POINTS / ((int64_t)RF * J);
 }
 
-// the argument rules of r3d_streams_step, shared with its host hook; fills the kernel's argument set
-int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
-                            const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror,
-                            const int32_t *mirror_perm, int64_t *emit, int32_t *status, StreamsArgs *args) {
-    static_assert(sizeof(r3d_stream_head) == 16, "r3d_stream_head is documented as 16 bytes");
+// the rules of the arguments r3d_streams_step and r3d_streams_repair share (the pointers' null checks aside), in the step's order
+static int streams_shared_check(const char *what, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding, const double *cam) {
     static_assert(R3D_ENCODE_RAY == ENC_RAY && R3D_ENCODE_INTRINSIC == ENC_INTRINSIC && R3D_ENCODE_SCREEN == ENC_SCREEN, "encode_point_f32 takes them");
-    if (!state || !frame || !action || !x || !emit || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
     if (S < 1 || S > R3D_CLIPS_MAX) { set_error("%s: num_streams must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, S); return R3D_ERR_ARG; }
     if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
     if (RF < 1) { set_error("%s: receptive_field must be >= 1 (got %d)", what, RF); return R3D_ERR_ARG; }
@@ -255,6 +252,17 @@ int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF
         return R3D_ERR_ARG;
     }
     if (pixels && !cam) { set_error("%s: a pixel encoding needs cam_dev", what); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
+
+// the argument rules of r3d_streams_step, shared with its host hook; fills the kernel's argument set
+int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
+                            const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror,
+                            const int32_t *mirror_perm, int64_t *emit, int32_t *status, StreamsArgs *args) {
+    static_assert(sizeof(r3d_stream_head) == 16, "r3d_stream_head is documented as 16 bytes");
+    if (!state || !frame || !action || !x || !emit || !status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (const int rc = streams_shared_check(what, S, RF, lag, J, F, encoding, cam)) return rc;
+    const bool pixels = encoding != R3D_ENCODE_NONE;
     if ((x_mirror != nullptr) != (mirror_perm != nullptr)) {
         set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
         return R3D_ERR_ARG;
@@ -286,6 +294,64 @@ int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF
     a.J = J;
     a.F = F;
     a.encoding = encoding;
+    *args = a;
+    return R3D_OK;
+}
+
+// the argument rules of r3d_streams_repair, shared with its host hook; fills the kernel's argument set
+int r3d::streams_repair_check_args(const char *what, void *state, void *track, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
+                                   int32_t encoding, const float *frame, const float *conf, float min_conf, const double *cam,
+                                   const int32_t *action, int32_t max_gap, float *frame_out, uint32_t *synthetic, StreamsRepairArgs *args) {
+    if (!state || !frame || !action) { set_error("%s: null pointer (state_dev, frame_dev, action_dev)", what); return R3D_ERR_ARG; }
+    if (!track) { set_error("%s: track_dev is null", what); return R3D_ERR_ARG; }
+    if (!frame_out) { set_error("%s: frame_out_dev is null", what); return R3D_ERR_ARG; }
+    if (!synthetic) { set_error("%s: synthetic_dev is null", what); return R3D_ERR_ARG; }
+    if (const int rc = streams_shared_check(what, S, RF, lag, J, F, encoding, cam)) return rc;
+    if (!streams_shape_ok(S, RF, J, F)) {
+        set_error("%s: receptive_field * num_joints and num_streams * receptive_field * num_joints must not exceed %d", what,
+                  R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(cam) % 8) {
+        set_error("%s: the state and cam_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(track) % 8) { set_error("%s: track_dev must be 8-byte aligned", what); return R3D_ERR_ARG; }
+    if (max_gap < 0 || max_gap > RF - 1) { set_error("%s: max_gap must be in 0..receptive_field - 1 (got %d)", what, max_gap); return R3D_ERR_ARG; }
+    if ((__builtin_bit_cast(uint32_t, min_conf) & 0x7f800000u) == 0x7f800000u) { set_error("%s: min_conf must be finite", what); return R3D_ERR_ARG; }
+    // frame_out_dev may not overlap what the call reads or keeps (address ranges; the sizes fit in 64 bits)
+    const int width = encoding == R3D_ENCODE_NONE ? F : 2;
+    const uintptr_t row_bytes = (uintptr_t)S * J * width * sizeof(float), out = reinterpret_cast<uintptr_t>(frame_out);
+    const char *in_name[4] = {"frame_dev", "conf_dev", "the state", "the track"};
+    const uintptr_t ins[4] = {reinterpret_cast<uintptr_t>(frame), reinterpret_cast<uintptr_t>(conf), reinterpret_cast<uintptr_t>(state),
+                              reinterpret_cast<uintptr_t>(track)};
+    const uintptr_t in_bytes[4] = {row_bytes, (uintptr_t)S * J * sizeof(float), streams_state_bytes(S, RF, J, F), streams_track_bytes(S, RF, J, width)};
+    for (int i = 0; i < 4; ++i)
+        if (ins[i] && out < ins[i] + in_bytes[i] && ins[i] < out + row_bytes) {
+            set_error("%s: frame_out_dev overlaps %s", what, in_name[i]);
+            return R3D_ERR_ARG;
+        }
+    StreamsRepairArgs a = {};
+    a.heads = static_cast<const r3d_stream_head *>(state);
+    a.ring = reinterpret_cast<uint32_t *>(static_cast<r3d_stream_head *>(state) + S);
+    a.age = static_cast<int32_t *>(track);
+    a.last = reinterpret_cast<uint32_t *>(a.age + (size_t)S * J);
+    a.missing = a.last + (size_t)S * J * width;
+    a.frame = reinterpret_cast<const uint32_t *>(frame);
+    a.conf = conf;
+    a.cam = encoding == R3D_ENCODE_NONE ? nullptr : cam;
+    a.action = action;
+    a.frame_out = reinterpret_cast<uint32_t *>(frame_out);
+    a.synthetic = synthetic;
+    a.min_conf = min_conf;
+    a.S = S;
+    a.RF = RF;
+    a.lag = lag;
+    a.J = J;
+    a.F = F;
+    a.width = width;
+    a.encoding = encoding;
+    a.max_gap = max_gap;
     *args = a;
     return R3D_OK;
 }
@@ -697,6 +763,29 @@ int r3d_streams_poses(const float *raw_dev, const float *raw_mirror_dev, int32_t
     const hipError_t err = r3d::launch_streams_poses(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_poses: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+size_t r3d_streams_track_bytes(int32_t num_streams, int32_t receptive_field, int32_t num_joints, int32_t width) {
+    if (!streams_shape_ok(num_streams, receptive_field, num_joints, width)) return 0;
+    return r3d::streams_track_bytes(num_streams, receptive_field, num_joints, width);
+}
+
+int r3d_streams_repair(void *state_dev, void *track_dev, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                       int32_t in_features, int32_t encoding, const float *frame_dev, const float *conf_dev, float min_conf,
+                       const double *cam_dev, const int32_t *action_dev, int32_t max_gap, float *frame_out_dev, uint32_t *synthetic_dev,
+                       void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsRepairArgs a;
+    const int rc = streams_repair_check_args("r3d_streams_repair", state_dev, track_dev, num_streams, receptive_field, lag, num_joints,
+                                             in_features, encoding, frame_dev, conf_dev, min_conf, cam_dev, action_dev, max_gap,
+                                             frame_out_dev, synthetic_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_repair(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_repair: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -12,6 +12,7 @@
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
 #include "r3d_streams_poses.hpp"
+#include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_valid.hpp"
 #include "r3d_windows.hpp"
@@ -784,6 +785,32 @@ int r3d_debug_streams_poses_host(const float *raw, const float *raw_mirror, int3
         double res[17];
         for (int j = 0; j < a.J; ++j) res[j] = stream_pose_point(a, s, j);
         if (a.quality) stream_quality(res, a.J, a.quality + 2 * s);
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_repair on the host - its argument rules (streams_repair_check_args) and the routines of r3d_streams_repair.hpp
+// the kernel runs: per stream the verdict on the head and the action word, then - for a stream that takes a push - the track zeroed
+// on a RESTART, its J joints in joint order, and the two mask words from the joints that were not observed.
+int r3d_debug_streams_repair_host(void *state, void *track, int32_t num_streams, int32_t receptive_field, int32_t lag,
+                                  int32_t num_joints, int32_t in_features, int32_t encoding, const float *frame, const float *conf,
+                                  float min_conf, const double *cam, const int32_t *action, int32_t max_gap, float *frame_out,
+                                  uint32_t *synthetic) {
+    StreamsRepairArgs a;
+    const int rc = streams_repair_check_args("r3d_debug_streams_repair_host", state, track, num_streams, receptive_field, lag, num_joints,
+                                             in_features, encoding, frame, conf, min_conf, cam, action, max_gap, frame_out, synthetic, &a);
+    if (rc != R3D_OK) return rc;
+    for (int s = 0; s < a.S; ++s) {
+        const StreamRepairStep rs = stream_repair_step(a, s);
+        if (!rs.st.push) {
+            a.synthetic[s] = stream_repair_idle_word(a, s, rs.st);
+            continue;
+        }
+        for (int i = 0; rs.restart && i < stream_repair_track_words(a); ++i) stream_repair_zero(a, s, i);
+        uint32_t mask = 0;
+        for (int j = 0; j < a.J; ++j)
+            if (stream_repair_joint(a, s, j, rs.c, rs.restart)) mask |= 1u << j;
+        stream_repair_finish(a, s, rs.c, mask);
     }
     return R3D_OK;
 }

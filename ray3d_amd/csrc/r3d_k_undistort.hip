@@ -65,12 +65,24 @@
 // S x J <= 17 threads of work per workgroup, a few hundred bytes per stream: the launch is LAUNCH-LATENCY-BOUND by construction -
 // neither bandwidth nor occupancy nor the float64 divisions show in its time; it exists to replace a string of small torch launches
 // by one.  Plain vector stores from C++ throughout, no atomics.
+//
+// r3d_streams_repair (live streams that survive dropped keypoints: a repaired frame for r3d_streams_step to push, the ring entries a
+// closing gap lets it improve, a per-stream track record, include/ray3d_hip.h) is the ninth argument set, StreamsRepairArgs, enqueued
+// BEFORE the step of the same tick: one workgroup of one wavefront per stream; it reads the stream's head and action word - one
+// address for the workgroup: scalar loads - and judges them through stream_step, the step's own routine, before anything else; a
+// stream that takes no push has one thread write its word of `synthetic` and nothing more.  Otherwise thread j < J owns joint j
+// through stream_repair_joint - the routine the host hook runs: it alone writes the joint's row of frame_out, its age and last, and
+// the joint's entries of the ring, so no two threads touch the same word -, the wavefront's ballot of the joints not observed is
+// the frame's mask, and thread 0 writes it and the word of `synthetic`.  A few hundred bytes per stream and, when a gap closes, at
+// most RF - 1 ring entries of one joint: LAUNCH-LATENCY-BOUND by construction, as r3d_streams_poses is.  Plain vector stores from
+// C++ throughout, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
 #include "r3d_streams_poses.hpp"
+#include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
 #include "r3d_windows.hpp"
 
@@ -242,14 +254,38 @@ __device__ __forceinline__ void streams_poses_body(const StreamsPosesArgs &u) {
     u.quality[2 * s + 1] = qw[1];
 }
 
-// The eight argument sets travel in one kernel-argument segment (4 KiB on this target)
+// Stream blockIdx.x < S, joint threadIdx.x < J <= 17; the workgroup is ONE wavefront (launch_streams_repair).  The head and the action
+// word are one address for the workgroup, so the verdict is uniform and both barriers are reached by every thread or by none.
+__device__ __forceinline__ void streams_repair_body(const StreamsRepairArgs &r) {
+    const int s = blockIdx.x, j = threadIdx.x;
+    const StreamRepairStep rs = stream_repair_step(r, s);
+    if (!rs.st.push) {                       // uniform: IDLE, DRAIN, a refused stream - nothing of its track, ring or row is written
+        if (j == 0) r.synthetic[s] = stream_repair_idle_word(r, s, rs.st);
+        return;
+    }
+    if (rs.restart) {                        // uniform: the track is zeroed first (every word by one thread), whatever it held
+        for (int i = j; i < stream_repair_track_words(r); i += blockDim.x) stream_repair_zero(r, s, i);
+        __syncthreads();
+    }
+    bool miss = false;
+    if (j < r.J) miss = stream_repair_joint(r, s, j, rs.c, rs.restart);        // (s < S, j < J: inside rows s of every buffer)
+    const unsigned long long mask = __ballot(miss);                             // (no thread left before it; bit j: thread j < J <= 17)
+    if (j == 0) stream_repair_finish(r, s, rs.c, (uint32_t)mask);
+}
+
+// The nine argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
-                      sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + 8 * 8 <= 4096,
+                      sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) + 9 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
-                                                                         const StreamsArgs sm, const StreamsPosesArgs sp) {
+                                                                         const StreamsArgs sm, const StreamsPosesArgs sp,
+                                                                         const StreamsRepairArgs sr) {
+    if (sr.age) {                            // uniform: r3d_streams_repair - stream blockIdx.x
+        streams_repair_body(sr);
+        return;
+    }
     if (sp.raw) {                             // uniform: r3d_streams_poses - stream blockIdx.x
         streams_poses_body(sp);
         return;
@@ -324,28 +360,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
@@ -353,14 +389,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
@@ -368,19 +404,26 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
+hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
+    static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args);
     return hipGetLastError();
 }
 

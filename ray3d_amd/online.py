@@ -31,11 +31,18 @@ class OnlineLifter:
     (:meth:`set_cameras` ``transforms=``, :meth:`Camera.stream_pose_row`); `quality` needs a 3-feature (ray) model and the camera
     rows - with ``encoding=None`` they are then passed to :meth:`set_cameras` as well.  Off by default: the tick is then exactly
     what it was.
+    `repair` (an int K in 0 .. RF - 1, None: off): the streams survive dropped keypoints - r3d_streams_repair runs in front of the
+    step of every tick.  Frames may then hold non-finite entries (a joint the detector did not deliver), and :meth:`step` takes
+    detector confidences (`min_conf`: a joint below it counts as not delivered).  A missing joint is held at its last observed
+    value; when it comes back after a gap of at most K frames, the frames of the gap that are still to be emitted are interpolated
+    (K = 0: hold only); a joint missing from a stream's start is back-filled from its first observation.  :meth:`step` then
+    returns ``extras["synthetic"]``: per stream the bit mask of the joints of the emitted frame that were not observed.
     The lifter is prepared for batches of `num_streams` windows here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), joints_left: Optional[Sequence[int]] = None,
-                 joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False):
+                 joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False,
+                 repair: Optional[int] = None, min_conf: float = 0.0):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -77,6 +84,18 @@ class OnlineLifter:
                                 world=torch.zeros((S, J, 3), dtype=torch.float64, device=dev) if self.world else None,
                                 reproj=torch.zeros((S, J), dtype=torch.float64, device=dev) if self.quality else None,
                                 quality=torch.zeros((S, 2), dtype=torch.float64, device=dev) if self.quality else None)
+        self.repair, self.min_conf = None, float(min_conf)
+        if repair is not None:          # r3d_streams_repair: the track, the confidences, the repaired frame and the mask words
+            if isinstance(repair, bool) or int(repair) != repair or not 0 <= int(repair) <= rf - 1:
+                raise ValueError("OnlineLifter: repair must be an int in 0..%d (got %r)" % (rf - 1, repair))
+            if not np.isfinite(self.min_conf):
+                raise ValueError("OnlineLifter: min_conf must be finite (got %r)" % (min_conf,))
+            self.repair = int(repair)
+            self.track = torch.zeros(_capi.streams_track_bytes(S, rf, J, self.width), dtype=torch.uint8, device=dev)   # all zero: fresh
+            self.frame_out = torch.zeros((S, J, self.width), dtype=torch.float32, device=dev)
+            self.conf = torch.zeros((S, J), dtype=torch.float32, device=dev)
+            self.synthetic = torch.zeros((S,), dtype=torch.int32, device=dev)      # (uint32 words: 17 bits are used)
+            self._use_conf = False
         self._cameras_set = self.cam is None and self.param is None and self.transforms is None
         self._graph = None
         self._captured = None       # the captured tick's (poses, out, out_mirror) buffers
@@ -114,8 +133,17 @@ class OnlineLifter:
     def _tick(self, out=None, out_m=None):
         """r3d_streams_step, the forward(s), the flip finish - on the current stream -> poses (S, 1, J, 3)."""
         dev, lifter = self.device, self.lifter
+        frame = self.frame
+        if self.repair is not None:     # the repaired frame is what the step pushes
+            with torch.cuda.device(dev):
+                _capi.streams_repair(self.state.data_ptr(), self.track.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding,
+                                     self.frame.data_ptr(), self.conf.data_ptr() if self._use_conf else None, self.min_conf,
+                                     self.cam.data_ptr() if self.cam is not None and self.encoding != _capi.R3D_ENCODE_NONE else None,
+                                     self.action.data_ptr(), self.repair, self.frame_out.data_ptr(), self.synthetic.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream)
+            frame = self.frame_out
         with torch.cuda.device(dev):
-            _capi.streams_step(self.state.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding, self.frame.data_ptr(),
+            _capi.streams_step(self.state.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding, frame.data_ptr(),
                                self.cam.data_ptr() if self.cam is not None else None, self.action.data_ptr(), self.x.data_ptr(),
                                self.x_mirror.data_ptr() if self.flip else None, self.perm, self.emit.data_ptr(), self.status.data_ptr(),
                                torch.cuda.current_stream(dev).cuda_stream)
@@ -152,9 +180,12 @@ class OnlineLifter:
 
     def _extras(self):
         f = self._finish
-        return {k: f[k].clone() for k in ("world", "reproj", "quality") if f[k] is not None}
+        out = {k: f[k].clone() for k in ("world", "reproj", "quality") if f[k] is not None} if f is not None else {}
+        if self.repair is not None:
+            out["synthetic"] = self.synthetic.clone()
+        return out
 
-    def step(self, frame=None, actions=None, check: bool = True):
+    def step(self, frame=None, actions=None, check: bool = True, conf=None):
         """One tick.  `frame` (S, J, 2) pixels or (S, J, F) model-input rows, a tensor or an array (None: no stream delivers one -
         a tick of DRAIN / IDLE actions); `actions` (S,) R3D_STREAM_* words (None: every stream PUSHes).
         -> (poses (S, J, 3), frames (S,) int64): frames[s] is the index of the frame poses[s] belongs to - the newest one for a causal
@@ -162,6 +193,11 @@ class OnlineLifter:
         With `world` / `quality` -> (poses, frames, extras): a dict with "world" (S, J, 3) float64, "reproj" (S, J) float64 pixels
         and "quality" (S, 2) float64 (mean, max of the stream's residuals) - the keys that were asked for; rows of streams without
         a pose this tick are not meaningful (they keep what an earlier tick left).
+        With `repair` -> (poses, frames, extras) as well: extras["synthetic"] (S,) int32, bit j set = joint j of the frame the pose
+        belongs to was not observed (held, interpolated or back-filled); the "reproj" of such a joint compares the prediction with
+        a made-up keypoint.  `frame` may then hold non-finite entries, and `conf` (S, J) detector confidences may be given: a joint
+        below `min_conf` (or with a NaN confidence) counts as not delivered.  A lifter that was captured takes `conf` on every tick
+        or on none.
         Raises on a refused stream (an unknown action, a PUSH after a drain began: RESTART starts the next clip) unless `check`
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
@@ -173,6 +209,20 @@ class OnlineLifter:
             self.frame.copy_(t.to(torch.float32))
         elif actions is None:
             raise ValueError("step: without a frame the actions must be given")
+        if conf is not None:
+            if self.repair is None:
+                raise ValueError("step: conf needs an OnlineLifter built with repair=")
+            c = torch.as_tensor(conf)
+            if tuple(c.shape) != (self.S, self.J):
+                raise ValueError("step: conf must be %s (got %s)" % ((self.S, self.J), tuple(c.shape)))
+            if self._graph is not None and not self._use_conf:
+                raise ValueError("step: the captured tick was recorded without confidences")
+            self.conf.copy_(c.to(torch.float32))
+            self._use_conf = True
+        elif self.repair is not None:
+            if self._graph is not None and self._use_conf:
+                raise ValueError("step: the captured tick was recorded with confidences")
+            self._use_conf = False
         if actions is None:
             self.action.fill_(PUSH)
         else:
@@ -189,7 +239,7 @@ class OnlineLifter:
                 if self._finish is not None:
                     poses = poses.clone()
         frames = self.emit.clone()
-        extras = self._extras() if self._finish is not None else None
+        extras = self._extras() if self._finish is not None or self.repair is not None else None
         if check:
             bad = torch.nonzero(self.status).flatten().tolist()
             if bad:
@@ -209,11 +259,12 @@ class OnlineLifter:
         drain when a clip ends, then IDLE.  -> per clip its poses (N_k, J, 3) in frame order: what the reference's evaluation
         computes for the clip (edge padding, eval_data_prepare, the forward, the flip average).
         `world` (a lifter built with `world` and / or `quality`): -> per clip (poses, extras), `extras` the frames' rows of what
-        :meth:`step` returns third - "world" (N_k, J, 3) float64, "reproj" (N_k, J) and "quality" (N_k, 2), the keys asked for."""
+        :meth:`step` returns third - "world" (N_k, J, 3) float64, "reproj" (N_k, J) and "quality" (N_k, 2), the keys asked for, and
+        with `repair` "synthetic" (N_k,) int32.  With `repair` the clips may hold non-finite entries (joints that were not detected)."""
         if len(clips) > self.S:
             raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
-        if world and self._finish is None:
-            raise ValueError("lift_clips: world=True needs an OnlineLifter built with world=True or quality=True")
+        if world and self._finish is None and self.repair is None:
+            raise ValueError("lift_clips: world=True needs an OnlineLifter built with world=True, quality=True or repair=")
         if cam_rows is not None or params is not None or transforms is not None:
             self.set_cameras(cam_rows, params, transforms)
         clips = [np.ascontiguousarray(torch.as_tensor(c).cpu().numpy(), dtype=np.float32) for c in clips]
@@ -222,8 +273,10 @@ class OnlineLifter:
             raise ValueError("lift_clips: a clip needs at least one frame")
         outs = [torch.empty((n, self.J, 3), dtype=torch.float32, device=self.device) for n in lengths]
         seen = [0] * len(clips)
-        more = [{k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in self._finish.items()
-                 if k in ("world", "reproj", "quality") and v is not None} for n in lengths] if self._finish is not None else None
+        rows = {k: v for k, v in (self._finish or {}).items() if k in ("world", "reproj", "quality") and v is not None}
+        if self.repair is not None:
+            rows["synthetic"] = self.synthetic
+        more = [{k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in rows.items()} for n in lengths]
         frame = np.zeros(tuple(self.frame.shape), np.float32)
         for t in range(max(lengths) + self.lag):
             act = np.full(self.S, IDLE, np.int32)
@@ -244,8 +297,8 @@ class OnlineLifter:
 
     # ---- capture ---------------------------------------------------------------------------------------------------------
     def capture(self):
-        """Record one tick - r3d_streams_step, the forward or forwards, the flip finish - into a hipGraph on a side stream; from
-        then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
+        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish - into
+        a hipGraph on a side stream; from then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
         capture may come between two ticks."""
         if self._graph is not None:
             return

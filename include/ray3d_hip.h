@@ -1093,6 +1093,10 @@ int r3d_debug_forward_census(r3d_model *pos, r3d_model *trj, int64_t batch, int 
  * tile_kind empty, every kernel name a forward's launch record can carry.  Same return convention. */
 int r3d_debug_census_domain(r3d_census_row *rows, int32_t cap);
 
+/* The largest window count of every plan kind that has one, ascending (what r3d_workspace_bytes walks): a call of edge + 1
+ * windows runs the next kind's plan.  Returns their number (which may exceed `cap`: nothing is written past it). */
+int r3d_debug_plan_kind_edges(int64_t *edges, int32_t cap);
+
 /* The per-keypoint routine of the R3D_INPUT_UV_DIST pre-pass, run on the host: `row16` one camera row of 16 doubles, `uv`
  * n pixel pairs; out_uv (n, 2) the undistorted pixels, out_rays (n, 3) the float64 rays before the cast (either may be
  * NULL).  Returns 0 or R3D_ERR_ARG. */

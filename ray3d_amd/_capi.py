@@ -37,7 +37,7 @@ EXPORTS = (
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
-                "r3d_debug_forward_census", "r3d_debug_census_domain",
+                "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
                 "r3d_debug_undistort_host", "r3d_debug_encode_px_host", "r3d_debug_valid_losses_host",
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
@@ -264,6 +264,7 @@ def load():
         lib.r3d_debug_forward_census.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                                  C.POINTER(CensusRow), C.c_int32]
         lib.r3d_debug_census_domain.argtypes = [C.POINTER(CensusRow), C.c_int32]
+        lib.r3d_debug_plan_kind_edges.argtypes = [i64p, C.c_int32]
         lib.r3d_debug_clips_poses_host.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp,
                                                    C.c_int64, vp]
         lib.r3d_debug_clips_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32,
@@ -706,6 +707,16 @@ def debug_census_domain():
     lib = load()
     rows = _census_rows(lambda r, cap: lib.r3d_debug_census_domain(r, cap))
     return [k for _, k, _, kind, _ in rows if not kind], {(k, kind) for _, k, _, kind, _ in rows if kind}
+
+
+def debug_plan_kind_edges():
+    """r3d_debug_plan_kind_edges (hooks library only): the largest window count of every plan kind that has one, ascending."""
+    lib = load()
+    buf = (C.c_int64 * 8)()
+    n = lib.r3d_debug_plan_kind_edges(buf, 8)
+    if n < 0 or n > 8:
+        raise Ray3DHipError("r3d_debug_plan_kind_edges returned %d" % n)
+    return [int(v) for v in buf[:n]]
 
 
 def _parent_table(parents):

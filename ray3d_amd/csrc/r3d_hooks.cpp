@@ -520,6 +520,14 @@ int r3d_debug_census_domain(r3d_census_row *rows, int32_t cap) {
     return out.n;
 }
 
+// Test hook: where the plan kind switches with the window count (r3d_plan.cpp, plan_kind_edges).
+int r3d_debug_plan_kind_edges(int64_t *edges, int32_t cap) {
+    const std::vector<int64_t> v = plan_kind_edges();
+    for (size_t i = 0; i < v.size() && (int32_t)i < cap; ++i)
+        if (edges) edges[i] = v[i];
+    return (int)v.size();
+}
+
 // Test hook: the pre-pass's per-keypoint routine (r3d_undistort.hpp) on the host.
 int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays) {
     if (!row16 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_undistort_host: bad argument"); return R3D_ERR_ARG; }

@@ -1039,6 +1039,54 @@ int r3d_streams_repair(void *state_dev,              /* the state of r3d_streams
                        uint32_t *synthetic_dev,      /* (S): bit j set = joint j of the frame emitted this tick was not observed */
                        void *stream);
 
+/* ---- early poses for live streams of centred models: one read-only call behind a tick's r3d_streams_step ---- */
+
+/* A centred model's pose of a frame is emitted `lag` ticks after the frame arrived.  r3d_streams_peek is enqueued AFTER
+ * r3d_streams_step of the same tick, on the same stream, with the same state and shape, and writes for every look L of `looks`
+ * the window the reference builds when the clip ENDS at this tick's frame - back edge padding in place of the frames that have not
+ * arrived - for the frame L ticks old: a pose now, superseded by the stream's final pose of that frame `lag - L` ticks later.
+ * Nothing of the state is written: the streams go on as if the call had not been made.
+ *   looks:      HOST array of num_looks entries, 1 <= num_looks <= R3D_STREAMS_PEEK_MAX, strictly increasing, each in [0, lag): they
+ *               travel as a kernel argument.  A small look is early and sees little of the future (look 0: none at all, the newest
+ *               frame); a look of lag - 1 lacks one future frame only.  lag == 0 (a causal model) has no admissible look.
+ *   action_dev, status_dev: the action words this tick's step read and the status words it wrote.  action_dev NULL: every stream
+ *               counts as pushed.
+ *   x_dev / x_mirror_dev / mirror_perm: (K, S, RF, J, F) float32, K = num_looks; the mirrored copy as r3d_streams_step takes it.
+ *   emit_dev:   (K, S) int64: the frame the window of row block (k, s) belongs to, or -1.
+ *   peek_status_dev: (K, S) int32: 1 when status_dev[s] != 0 or the head is invalid (r3d_streams_step's rule), 0 otherwise.
+ * PER LOOK k AND STREAM s (integers only).  c is the head's count after the step, L = looks[k], p = c - 1 - L.  The stream PREVIEWS
+ * when status_dev[s] == 0, the action word is PUSH or RESTART (or action_dev is NULL), the head is valid, drained == 0, c >= 1 and
+ * p >= 0.  Then emit = p and row i of x_dev[k, s] is the ring's copy of frame clamp(p - (RF - 1 - lag) + i, 0, c - 1), found at slot
+ * frame % RF - r3d_streams_step's rule with p in place of n: the window a drain started now would emit at its (lag - L)-th tick, and
+ * window p of the reference's np.pad(..., 'edge') + eval_data_prepare on the stream's c frames so far.  The oldest frame it names
+ * is c - RF + lag - L > c - RF, which the ring holds.  Otherwise emit = -1 and nothing of row block (k, s) is read or written.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: (ceil(RF * J / 256), S, K)
+ * workgroups, one output point (row, joint) per thread; each workgroup reads its stream's head, action and status word uniformly and
+ * decides before anything is written; nothing the launch writes is read by another of its workgroups.
+ * THE WHOLE BOUNDS STORY.  Whatever the state and the words hold, the kernel reads the state within r3d_streams_state_bytes,
+ * action_dev and status_dev within S words, and writes x_dev and x_mirror_dev within K * S * RF * J * F floats, emit_dev and
+ * peek_status_dev within K * S words: a ring slot is a remainder modulo RF of a non-negative number, a frame index is clamped into
+ * [0, c - 1] of a head that passed the rule, and no head that fails it is followed.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (state_dev, looks, status_dev, x_dev, emit_dev,
+ * peek_status_dev), num_streams outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, receptive_field < 1, lag outside [0,
+ * receptive_field - 1], in_features other than 2 or 3, lag == 0, num_looks outside 1..R3D_STREAMS_PEEK_MAX, a look outside
+ * [0, lag), looks that are not strictly increasing, exactly one of x_mirror_dev / mirror_perm, a mirror_perm that is not a
+ * permutation, receptive_field * num_joints or num_looks * num_streams * receptive_field * num_joints above R3D_ENCODE_MAX_POINTS, a
+ * state or emit_dev pointer that is not 8-byte aligned.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+#define R3D_STREAMS_PEEK_MAX 8
+int r3d_streams_peek(const void *state_dev,           /* the state of r3d_streams_step: READ, never written     */
+                     int32_t num_streams, int32_t receptive_field, int32_t lag,
+                     int32_t num_joints, int32_t in_features,
+                     const int32_t *looks, int32_t num_looks,   /* HOST, strictly increasing, 0 <= look < lag    */
+                     const int32_t *action_dev,       /* (S) the words of this tick's step, or NULL: all pushed  */
+                     const int32_t *status_dev,       /* (S) what this tick's step wrote                         */
+                     float *x_dev,                    /* (K, S, RF, J, F): look k, stream s own row block (k, s) */
+                     float *x_mirror_dev, const int32_t *mirror_perm,   /* both NULL, or both given (HOST perm)  */
+                     int64_t *emit_dev,               /* (K, S) the preview frame of the row block, or -1        */
+                     int32_t *peek_status_dev,        /* (K, S) 0, or 1: refused by the step / invalid head      */
+                     void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -1154,6 +1202,12 @@ int r3d_debug_streams_repair_host(void *state, void *track, int32_t num_streams,
                                   int32_t num_joints, int32_t in_features, int32_t encoding, const float *frame, const float *conf,
                                   float min_conf, const double *cam, const int32_t *action, int32_t max_gap, float *frame_out,
                                   uint32_t *synthetic);
+/* r3d_streams_peek on the host (HOST pointers throughout, no stream): the same argument checks, the same verdict per look and
+ * stream and the same point routine, looks in order, streams in order. */
+int r3d_debug_streams_peek_host(const void *state, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                                int32_t in_features, const int32_t *looks, int32_t num_looks, const int32_t *action,
+                                const int32_t *status, float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit,
+                                int32_t *peek_status);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

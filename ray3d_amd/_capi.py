@@ -35,6 +35,7 @@ EXPORTS = (
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
+    "r3d_streams_peek",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
@@ -42,7 +43,7 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
-                "r3d_debug_streams_repair_host")
+                "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -119,6 +120,7 @@ def window_run_dtype():
 WINDOW_RUN_DESC_BYTES = 48                                              # sizeof(r3d_window_run_desc)
 R3D_ENCODE_NONE = 3                                                     # r3d_streams_step only: model-input rows, copied bit for bit
 R3D_STREAM_IDLE, R3D_STREAM_PUSH, R3D_STREAM_RESTART, R3D_STREAM_DRAIN = 0, 1, 2, 3   # action words of r3d_streams_step
+STREAMS_PEEK_MAX = 8                                                    # R3D_STREAMS_PEEK_MAX: looks per r3d_streams_peek call
 STREAM_HEAD_BYTES = 16                                                  # sizeof(r3d_stream_head)
 
 
@@ -246,9 +248,13 @@ def load():
     lib.r3d_streams_track_bytes.restype = C.c_size_t
     lib.r3d_streams_repair.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_float, vp, vp,
                                        C.c_int32, vp, vp, vp]
+    lib.r3d_streams_peek.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp, vp,
+                                     vp, C.POINTER(C.c_int32), vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_peek_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                    C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, vp]
         lib.r3d_debug_streams_repair_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                       C.c_float, vp, vp, C.c_int32, vp, vp]
         lib.r3d_debug_streams_poses_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, vp, vp, vp, vp, C.c_int32,
@@ -668,6 +674,39 @@ def debug_streams_repair_host(state_ptr: int, track_ptr: int, num_streams: int, 
     return int(load().r3d_debug_streams_repair_host(state_ptr or None, track_ptr or None, num_streams, receptive_field, lag, num_joints,
                                                     in_features, encoding, frame_ptr or None, conf_ptr or None, min_conf, cam_ptr or None,
                                                     action_ptr or None, max_gap, frame_out_ptr or None, synthetic_ptr or None))
+
+
+def _looks_table(looks):
+    """The host array of looks r3d_streams_peek takes (any length: the call judges it)."""
+    looks = [int(v) for v in looks]
+    return (C.c_int32 * max(len(looks), 1))(*looks), len(looks)
+
+
+def streams_peek(state_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int, in_features: int, looks,
+                 action_ptr: Optional[int], status_ptr: int, x_ptr: int, x_mirror_ptr: Optional[int], mirror_perm, emit_ptr: int,
+                 peek_status_ptr: int, stream: int):
+    """r3d_streams_peek (enqueued AFTER :func:`streams_step` of the same tick): every pointer is device memory; `state_ptr` the
+    step's state, read only; `looks` a host sequence of 1..STREAMS_PEEK_MAX strictly increasing ints in [0, lag); `action_ptr`
+    (or None: every stream counts as pushed) and `status_ptr` the step's words; `x_ptr` / `x_mirror_ptr` (len(looks), num_streams,
+    receptive_field, num_joints, in_features) float32, `x_mirror_ptr` (or None) and `mirror_perm` go together; `emit_ptr`
+    (len(looks), num_streams) int64, `peek_status_ptr` the same shape int32."""
+    perm = _mirror_table("r3d_streams_peek", mirror_perm, num_joints)
+    table, n = _looks_table(looks)
+    check(load().r3d_streams_peek(state_ptr, num_streams, receptive_field, lag, num_joints, in_features, table, n, action_ptr or None,
+                                  status_ptr, x_ptr, x_mirror_ptr or None, perm, emit_ptr, peek_status_ptr, stream), "r3d_streams_peek")
+
+
+def debug_streams_peek_host(state_ptr: int, num_streams: int, receptive_field: int, lag: int, num_joints: int, in_features: int, looks,
+                            action_ptr: Optional[int], status_ptr: int, x_ptr: int, x_mirror_ptr: Optional[int], mirror_perm,
+                            emit_ptr: int, peek_status_ptr: int, num_looks: Optional[int] = None) -> int:
+    """r3d_debug_streams_peek_host (hooks library only: use_hooks(True)): r3d_streams_peek on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for).  `looks` None: a null pointer; `num_looks` overrides the
+    sequence's length."""
+    perm = _mirror_table("r3d_debug_streams_peek_host", mirror_perm, num_joints)
+    table, n = _looks_table(looks) if looks is not None else (None, 0)
+    return int(load().r3d_debug_streams_peek_host(state_ptr or None, num_streams, receptive_field, lag, num_joints, in_features, table,
+                                                  n if num_looks is None else num_looks, action_ptr or None, status_ptr or None,
+                                                  x_ptr or None, x_mirror_ptr or None, perm, emit_ptr or None, peek_status_ptr or None))
 
 
 def _census_rows(call):

@@ -4,6 +4,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
@@ -352,6 +353,60 @@ int r3d::streams_repair_check_args(const char *what, void *state, void *track, i
     a.width = width;
     a.encoding = encoding;
     a.max_gap = max_gap;
+    *args = a;
+    return R3D_OK;
+}
+
+// the argument rules of r3d_streams_peek, shared with its host hook; fills the kernel's argument set
+int r3d::streams_peek_check_args(const char *what, const void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
+                                 const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status, float *x,
+                                 float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status, StreamsPeekArgs *args) {
+    if (!state || !looks || !status || !x || !emit || !peek_status) { set_error("%s: null pointer", what); return R3D_ERR_ARG; }
+    if (S < 1 || S > R3D_CLIPS_MAX) { set_error("%s: num_streams must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, S); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (RF < 1) { set_error("%s: receptive_field must be >= 1 (got %d)", what, RF); return R3D_ERR_ARG; }
+    if (lag < 0 || lag > RF - 1) { set_error("%s: lag must be in 0..receptive_field - 1 (got %d)", what, lag); return R3D_ERR_ARG; }
+    if (F != 2 && F != 3) { set_error("%s: in_features must be 2 or 3 (got %d)", what, F); return R3D_ERR_ARG; }
+    if (lag == 0) { set_error("%s: lag is 0 (a causal model): a look lies in 0..lag - 1, so none is admissible", what); return R3D_ERR_ARG; }
+    if (num_looks < 1 || num_looks > R3D_STREAMS_PEEK_MAX) {
+        set_error("%s: num_looks must be in 1..%d (got %d)", what, R3D_STREAMS_PEEK_MAX, num_looks);
+        return R3D_ERR_ARG;
+    }
+    for (int k = 0; k < num_looks; ++k) {
+        if (looks[k] < 0 || looks[k] >= lag) { set_error("%s: looks[%d] must be in 0..lag - 1 = %d (got %d)", what, k, lag - 1, looks[k]); return R3D_ERR_ARG; }
+        if (k && looks[k] <= looks[k - 1]) { set_error("%s: looks must be strictly increasing (looks[%d] = %d after %d)", what, k, looks[k], looks[k - 1]); return R3D_ERR_ARG; }
+    }
+    if ((x_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
+    if (!streams_shape_ok(S, RF, J, F) || (int64_t)num_looks * S > R3D_ENCODE_MAX_POINTS / ((int64_t)RF * J)) {
+        set_error("%s: receptive_field * num_joints and num_looks * num_streams * receptive_field * num_joints must not exceed %d", what,
+                  R3D_ENCODE_MAX_POINTS);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(emit) % 8) {
+        set_error("%s: the state and emit_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    StreamsPeekArgs a = {};
+    a.heads = static_cast<const r3d_stream_head *>(state);
+    a.ring = reinterpret_cast<const uint32_t *>(a.heads + S);
+    a.action = action;
+    a.status = status;
+    a.x = reinterpret_cast<uint32_t *>(x);
+    a.x_mirror = reinterpret_cast<uint32_t *>(x_mirror);
+    a.emit = reinterpret_cast<long long *>(emit);
+    a.peek_status = peek_status;
+    if (mirror_perm) window_pack_perm(mirror_perm, J, a.mirror_perm);
+    for (int k = 0; k < num_looks; ++k) a.looks[k] = looks[k];
+    a.S = S;
+    a.RF = RF;
+    a.lag = lag;
+    a.J = J;
+    a.F = F;
+    a.K = num_looks;
     *args = a;
     return R3D_OK;
 }
@@ -786,6 +841,23 @@ int r3d_streams_repair(void *state_dev, void *track_dev, int32_t num_streams, in
     const hipError_t err = r3d::launch_streams_repair(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_repair: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_streams_peek(const void *state_dev, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                     int32_t in_features, const int32_t *looks, int32_t num_looks, const int32_t *action_dev, const int32_t *status_dev,
+                     float *x_dev, float *x_mirror_dev, const int32_t *mirror_perm, int64_t *emit_dev, int32_t *peek_status_dev,
+                     void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsPeekArgs a;
+    const int rc = streams_peek_check_args("r3d_streams_peek", state_dev, num_streams, receptive_field, lag, num_joints, in_features, looks,
+                                           num_looks, action_dev, status_dev, x_dev, x_mirror_dev, mirror_perm, emit_dev, peek_status_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_peek(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_peek: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -11,6 +11,7 @@
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
@@ -820,6 +821,30 @@ int r3d_debug_streams_repair_host(void *state, void *track, int32_t num_streams,
             if (stream_repair_joint(a, s, j, rs.c, rs.restart)) mask |= 1u << j;
         stream_repair_finish(a, s, rs.c, mask);
     }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_peek on the host - its argument rules (streams_peek_check_args) and the routines of r3d_streams_peek.hpp the
+// kernel runs: per look and stream the verdict (stream_peek) and its two words, then - for a stream that previews - the window's
+// points in row and joint order (stream_peek_point).
+int r3d_debug_streams_peek_host(const void *state, int32_t num_streams, int32_t receptive_field, int32_t lag, int32_t num_joints,
+                                int32_t in_features, const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status,
+                                float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status) {
+    StreamsPeekArgs a;
+    const int rc = streams_peek_check_args("r3d_debug_streams_peek_host", state, num_streams, receptive_field, lag, num_joints, in_features,
+                                           looks, num_looks, action, status, x, x_mirror, mirror_perm, emit, peek_status, &a);
+    if (rc != R3D_OK) return rc;
+    for (int k = 0; k < a.K; ++k)
+        for (int s = 0; s < a.S; ++s) {
+            const long long c = a.heads[s].count;
+            const StreamPeek pk = stream_peek(c, a.heads[s].drained, a.action != nullptr, a.action ? a.action[s] : R3D_STREAM_PUSH,
+                                              a.status[s], stream_peek_look(a, k), a.lag);
+            a.emit[(long long)k * a.S + s] = pk.p;
+            a.peek_status[(long long)k * a.S + s] = pk.bad ? 1 : 0;
+            if (!pk.previews) continue;
+            for (int i = 0; i < a.RF; ++i)
+                for (int j = 0; j < a.J; ++j) stream_peek_point(a, k, s, pk.p, c, i, j);
+        }
     return R3D_OK;
 }
 

@@ -603,6 +603,12 @@ int streams_repair_check_args(const char *what, void *state, void *track, int32_
                               int32_t encoding, const float *frame, const float *conf, float min_conf, const double *cam,
                               const int32_t *action, int32_t max_gap, float *frame_out, uint32_t *synthetic, StreamsRepairArgs *args);
 
+struct StreamsPeekArgs;     // r3d_streams_peek.hpp
+// the argument rules of r3d_streams_peek, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_peek_check_args(const char *what, const void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
+                            const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status, float *x,
+                            float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status, StreamsPeekArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -710,6 +716,7 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);                         // the same kernel, two launches: r3d_streams_step
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream);                   // the same kernel: r3d_streams_poses
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_repair
+hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -76,11 +76,21 @@
 // the frame's mask, and thread 0 writes it and the word of `synthetic`.  A few hundred bytes per stream and, when a gap closes, at
 // most RF - 1 ring entries of one joint: LAUNCH-LATENCY-BOUND by construction, as r3d_streams_poses is.  Plain vector stores from
 // C++ throughout, no atomics.
+//
+// r3d_streams_peek (early poses for live streams of centred models: the windows a drain started now would emit, read out of the rings
+// without ending the streams, include/ray3d_hip.h) is the tenth argument set, StreamsPeekArgs, enqueued AFTER the step of the same
+// tick: blockIdx.y names a stream and blockIdx.z a look (the looks travel by value in the argument set), the workgroup reads the
+// stream's head, action and status word - one address for the workgroup: scalar loads - and decides through stream_peek of
+// r3d_streams_peek.hpp before anything is written, and each thread copies one output point (row, joint) through stream_peek_point,
+// the gather's arithmetic with the preview frame in place of the emitted one and the routine the host hook runs: 8 or 12 bytes read
+// and written per thread, consecutive threads at consecutive addresses of x.  The state is const to it.  Plain vector stores from
+// C++, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
 #include "r3d_undistort.hpp"
@@ -273,15 +283,40 @@ __device__ __forceinline__ void streams_repair_body(const StreamsRepairArgs &r) 
     if (j == 0) stream_repair_finish(r, s, rs.c, (uint32_t)mask);
 }
 
-// The nine argument sets travel in one kernel-argument segment (4 KiB on this target)
+// Stream blockIdx.y < S, look blockIdx.z < K, output point blockIdx.x * 256 + threadIdx.x of the preview window.  The head, the action
+// and the status word are one address for the workgroup, so the verdict is uniform and comes before any store; the state is only
+// read, and what the launch writes - row block (k, s) and its two words - no other workgroup of it reads.
+__device__ __forceinline__ void streams_peek_body(const StreamsPeekArgs &e) {
+    const int s = blockIdx.y, k = blockIdx.z;
+    const long long c = e.heads[s].count;
+    const StreamPeek pk = stream_peek(c, e.heads[s].drained, e.action != nullptr, e.action ? e.action[s] : R3D_STREAM_PUSH, e.status[s],
+                                      stream_peek_look(e, k), e.lag);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        e.emit[(long long)k * e.S + s] = pk.p;          // (-1 unless the stream previews)
+        e.peek_status[(long long)k * e.S + s] = pk.bad ? 1 : 0;
+    }
+    if (!pk.previews) return;                // uniform: the row block is left untouched
+    // (RF * J and K * S * RF * J fit in 31 bits - checked on the host)
+    const int pt = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= e.RF * e.J) return;
+    const int i = pt / e.J;
+    stream_peek_point(e, k, s, pk.p, c, i, pt - i * e.J);
+}
+
+// The ten argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
-                      sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) + 9 * 8 <= 4096,
+                      sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) +
+                      sizeof(StreamsPeekArgs) + 10 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
                                                                          const StreamsArgs sm, const StreamsPosesArgs sp,
-                                                                         const StreamsRepairArgs sr) {
+                                                                         const StreamsRepairArgs sr, const StreamsPeekArgs pk) {
+    if (pk.heads) {                          // uniform: r3d_streams_peek - stream blockIdx.y, look blockIdx.z
+        streams_peek_body(pk);
+        return;
+    }
     if (sr.age) {                            // uniform: r3d_streams_repair - stream blockIdx.x
         streams_repair_body(sr);
         return;
@@ -360,28 +395,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
@@ -389,14 +424,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
@@ -404,26 +439,33 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
     static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_peek: (ceil(RF * J / 256), S, K) workgroups, one launch, nothing else
+hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream) {
+    const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args);
     return hipGetLastError();
 }
 

@@ -37,12 +37,20 @@ class OnlineLifter:
     value; when it comes back after a gap of at most K frames, the frames of the gap that are still to be emitted are interpolated
     (K = 0: hold only); a joint missing from a stream's start is back-filled from its first observation.  :meth:`step` then
     returns ``extras["synthetic"]``: per stream the bit mask of the joints of the emitted frame that were not observed.
-    The lifter is prepared for batches of `num_streams` windows here, once."""
+    `previews` (a strictly increasing sequence of 1 .. 8 looks, each in 0 .. lag - 1; None: off; centred models only): early
+    poses.  A centred model's pose of a frame comes `lag` ticks after the frame; with previews every tick also enqueues
+    r3d_streams_peek behind its final forward - for every look L the window the reference builds when the clip ENDS at this tick's
+    frame, for the frame L ticks old - and lifts the K * S preview windows with ONE more forward (and the mirrored one with `flip`),
+    finished the way the final poses are.  :meth:`step` then returns ``extras["previews"]``.  A small look is early and has seen
+    little of the future (look 0: the newest frame, no future at all); look lag - 1 lacks one frame only.  A preview is superseded
+    by the final pose of its frame `lag - L` ticks later and never revised; the final poses are bit for bit what they are without
+    previews.  With `repair` the previews are lifted from the repaired ring.
+    The lifter is prepared for batches of `num_streams` windows (and of K * `num_streams` with previews) here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), joints_left: Optional[Sequence[int]] = None,
                  joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False,
-                 repair: Optional[int] = None, min_conf: float = 0.0):
+                 repair: Optional[int] = None, min_conf: float = 0.0, previews: Optional[Sequence[int]] = None):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -62,6 +70,9 @@ class OnlineLifter:
         self.world, self.quality = bool(world), bool(quality)
         if self.quality and self.F != 3:
             raise ValueError("OnlineLifter: quality=True is defined for 3-feature (ray) inputs only; this pair takes %d" % self.F)
+        self.looks = self._check_looks(previews, self.lag) if previews is not None else None
+        if self.looks and _capi.streams_state_bytes(len(self.looks) * self.S, self.rf, self.J, self.F) == 0:
+            raise ValueError("OnlineLifter: len(previews) * num_streams must be in 1..%d (got %d)" % (_capi.CLIPS_MAX, len(self.looks) * self.S))
         self.perm = evaluate.mirror_permutation(self.J, kps_left, kps_right) if self.flip else None
         self.joints = (list(kps_left if joints_left is None else joints_left), list(kps_right if joints_right is None else joints_right))
         dev = self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -96,6 +107,22 @@ class OnlineLifter:
             self.conf = torch.zeros((S, J), dtype=torch.float32, device=dev)
             self.synthetic = torch.zeros((S,), dtype=torch.int32, device=dev)      # (uint32 words: 17 bits are used)
             self._use_conf = False
+        self._pfinish = self._pv = None
+        if self.looks:                  # r3d_streams_peek: K * S preview windows, their words, and the K-fold copies of the streams' rows
+            K = len(self.looks)
+            self.px = torch.zeros((K, S, rf, J, F), dtype=torch.float32, device=dev)
+            self.px_mirror = torch.zeros((K, S, rf, J, F), dtype=torch.float32, device=dev) if self.flip else None
+            self.pemit = torch.full((K, S), -1, dtype=torch.int64, device=dev)
+            self.pstatus = torch.zeros((K, S), dtype=torch.int32, device=dev)
+            self._ptiled = {name: torch.zeros((K * S,) + tuple(buf.shape[1:]), dtype=buf.dtype, device=dev) if buf is not None else None
+                            for name, buf in (("cam_rows", self.cam), ("params", self.param), ("transforms", self.transforms))}
+            if self._finish is not None:
+                self._pfinish = dict(raw=torch.zeros((K * S, 1, J, 3), dtype=torch.float32, device=dev),
+                                     raw_m=torch.zeros((K * S, 1, J, 3), dtype=torch.float32, device=dev) if self.flip else None,
+                                     pred=torch.zeros((K * S, 1, J, 3), dtype=torch.float32, device=dev),
+                                     world=torch.zeros((K * S, J, 3), dtype=torch.float64, device=dev) if self.world else None,
+                                     reproj=torch.zeros((K * S, J), dtype=torch.float64, device=dev) if self.quality else None,
+                                     quality=torch.zeros((K * S, 2), dtype=torch.float64, device=dev) if self.quality else None)
         self._cameras_set = self.cam is None and self.param is None and self.transforms is None
         self._graph = None
         self._captured = None       # the captured tick's (poses, out, out_mirror) buffers
@@ -104,7 +131,25 @@ class OnlineLifter:
             self._out_perm_host = [int(v) for v in out_perm]
             self._out_perm = torch.tensor(out_perm, dtype=torch.int64, device=dev)
             self._out_sign = torch.tensor([-1.0, 1.0, 1.0], dtype=torch.float32, device=dev)
-        lifter.prepare([S], dev)
+        lifter.prepare([S] + ([len(self.looks) * S] if self.looks else []), dev)
+
+    @staticmethod
+    def _check_looks(previews, lag: int):
+        if lag == 0:
+            raise ValueError("OnlineLifter: previews need a centred model - this pair is causal (lag 0): a look lies in 0..lag - 1")
+        try:
+            looks = tuple(previews)
+            ok = all(not isinstance(v, bool) and int(v) == v for v in looks)
+        except (TypeError, ValueError):
+            looks, ok = (), False
+        if not ok or not 1 <= len(looks) <= _capi.STREAMS_PEEK_MAX:
+            raise ValueError("OnlineLifter: previews must be a sequence of 1..%d ints (got %r)" % (_capi.STREAMS_PEEK_MAX, previews))
+        looks = tuple(int(v) for v in looks)
+        if min(looks) < 0 or max(looks) > lag - 1:
+            raise ValueError("OnlineLifter: every look of previews must be in 0..%d = lag - 1 (got %r)" % (lag - 1, looks))
+        if any(b <= a for a, b in zip(looks, looks[1:])):
+            raise ValueError("OnlineLifter: previews must be strictly increasing (got %r)" % (looks,))
+        return looks
 
     # ---- setup -----------------------------------------------------------------------------------------------------------
     def set_cameras(self, cam_rows=None, params=None, transforms=None):
@@ -122,6 +167,8 @@ class OnlineLifter:
             if tuple(t.shape) != tuple(buf.shape):
                 raise ValueError("set_cameras: %s must be %s (got %s)" % (name, tuple(buf.shape), tuple(t.shape)))
             buf.copy_(t)
+            if self.looks:              # the preview batch's rows: look k, stream s at row k * S + s
+                self._ptiled[name].copy_(buf.repeat((len(self.looks),) + (1,) * (buf.dim() - 1)))
         self._cameras_set = True
 
     # ---- one tick --------------------------------------------------------------------------------------------------------
@@ -130,8 +177,51 @@ class OnlineLifter:
         negation and a permutation)."""
         return 0.5 * (pred + pred_m.index_select(2, self._out_perm) * self._out_sign)
 
-    def _tick(self, out=None, out_m=None):
-        """r3d_streams_step, the forward(s), the flip finish - on the current stream -> poses (S, 1, J, 3)."""
+    def _tick(self, out=None, out_m=None, pout=None, pout_m=None):
+        """r3d_streams_step, the forward(s), the flip finish - on the current stream -> poses (S, 1, J, 3).  With previews the tick
+        goes on behind them: r3d_streams_peek, the preview batch's forward(s) and finish (:meth:`_preview_tick`)."""
+        poses = self._final_tick(out, out_m)
+        if self.looks:
+            self._pv = self._preview_tick(pout, pout_m)
+        return poses
+
+    def _preview_tick(self, out=None, out_m=None):
+        """r3d_streams_peek behind the tick's final forward, ONE forward over the K * S preview windows (and the mirrored one), and
+        the finish in use - the torch flip average, or one r3d_streams_poses call over K * S pseudo-streams that reads the peek's
+        emit and status words -> preview poses (K * S, 1, J, 3), look k, stream s at row k * S + s."""
+        dev, lifter, KS = self.device, self.lifter, len(self.looks) * self.S
+        with torch.cuda.device(dev):
+            _capi.streams_peek(self.state.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.looks, self.action.data_ptr(),
+                               self.status.data_ptr(), self.px.data_ptr(), self.px_mirror.data_ptr() if self.flip else None, self.perm,
+                               self.pemit.data_ptr(), self.pstatus.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        x = self.px.view(KS, self.rf, self.J, self.F)
+        xm = self.px_mirror.view(KS, self.rf, self.J, self.F) if self.flip else None
+        param, E = self._ptiled["params"], lifter.pos.extrinsic_dim
+        f = self._pfinish
+        if f is not None:
+            lifter._run(_capi.R3D_INPUT_RAYS, x, self.rf, KS, param, E, out=f["raw"])
+            if self.flip:
+                lifter._run(_capi.R3D_INPUT_RAYS, xm, self.rf, KS, param, E, out=f["raw_m"])
+
+            def ptr(t):
+                return t.data_ptr() if t is not None else None
+            with torch.cuda.device(dev):
+                _capi.streams_poses(ptr(f["raw"]), ptr(f["raw_m"]), KS, self.J, self._out_perm_host if self.flip else None,
+                                    self.pemit.data_ptr(), self.pstatus.data_ptr(), self._ptiled["transforms"].data_ptr(),
+                                    ptr(self._ptiled["cam_rows"]), x.data_ptr(), self.rf, self.lag, ptr(f["pred"]), ptr(f["world"]),
+                                    ptr(f["reproj"]), ptr(f["quality"]), torch.cuda.current_stream(dev).cuda_stream, in_features=self.F)
+            return f["pred"]
+        if out is None:             # eager: the public forward, the reference's flip finish
+            pred = lifter.forward(x, param)
+            if self.flip:
+                pred = 0.5 * (pred + evaluate.mirror_output(lifter.forward(xm, param), *self.joints))
+            return pred
+        pred = lifter._run(_capi.R3D_INPUT_RAYS, x, self.rf, KS, param, E, out=out)
+        if self.flip:
+            pred = self._mirror_finish(pred, lifter._run(_capi.R3D_INPUT_RAYS, xm, self.rf, KS, param, E, out=out_m))
+        return pred
+
+    def _final_tick(self, out=None, out_m=None):
         dev, lifter = self.device, self.lifter
         frame = self.frame
         if self.repair is not None:     # the repaired frame is what the step pushes
@@ -183,6 +273,11 @@ class OnlineLifter:
         out = {k: f[k].clone() for k in ("world", "reproj", "quality") if f[k] is not None} if f is not None else {}
         if self.repair is not None:
             out["synthetic"] = self.synthetic.clone()
+        if self.looks:
+            K, S, p = len(self.looks), self.S, self._pfinish
+            poses, frames = self._pv.clone().view(K, S, self.J, 3), self.pemit.clone()
+            more = {k: p[k].clone().view((K, S) + tuple(p[k].shape[1:])) for k in ("world", "reproj", "quality") if p[k] is not None} if p else {}
+            out["previews"] = [dict({k: v[i] for k, v in more.items()}, look=L, poses=poses[i], frames=frames[i]) for i, L in enumerate(self.looks)]
         return out
 
     def step(self, frame=None, actions=None, check: bool = True, conf=None):
@@ -198,6 +293,11 @@ class OnlineLifter:
         a made-up keypoint.  `frame` may then hold non-finite entries, and `conf` (S, J) detector confidences may be given: a joint
         below `min_conf` (or with a NaN confidence) counts as not delivered.  A lifter that was captured takes `conf` on every tick
         or on none.
+        With `previews` -> (poses, frames, extras) as well: extras["previews"] is a list with one dict per look L, in the order
+        given: "look" L, "poses" (S, J, 3), "frames" (S,) int64 - frames[s] the frame the early pose of stream s belongs to (the
+        newest one less L), or -1: stream s has no preview this tick (it did not PUSH, or holds no more than L frames) and its
+        rows are not meaningful - and, with `world` / `quality`, "world" (S, J, 3), "reproj" (S, J) and "quality" (S, 2) of the
+        preview poses.  A preview is never revised: the final pose of that frame arrives `lag - L` ticks later in `poses`.
         Raises on a refused stream (an unknown action, a PUSH after a drain began: RESTART starts the next clip) unless `check`
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
@@ -239,7 +339,7 @@ class OnlineLifter:
                 if self._finish is not None:
                     poses = poses.clone()
         frames = self.emit.clone()
-        extras = self._extras() if self._finish is not None or self.repair is not None else None
+        extras = self._extras() if self._finish is not None or self.repair is not None or self.looks else None
         if check:
             bad = torch.nonzero(self.status).flatten().tolist()
             if bad:
@@ -254,17 +354,24 @@ class OnlineLifter:
         act = torch.full((self.S,), DRAIN, dtype=torch.int32)
         return [self.step(None, act, check) for _ in range(self.lag)]
 
-    def lift_clips(self, clips: Sequence, cam_rows=None, params=None, transforms=None, world: bool = False) -> list:
+    def lift_clips(self, clips: Sequence, cam_rows=None, params=None, transforms=None, world: bool = False, previews: bool = False) -> list:
         """Clips of unequal length - at most S arrays (N_k, J, 2 or F) - fed side by side, one stream each: RESTART, PUSH ..., the
         drain when a clip ends, then IDLE.  -> per clip its poses (N_k, J, 3) in frame order: what the reference's evaluation
         computes for the clip (edge padding, eval_data_prepare, the forward, the flip average).
         `world` (a lifter built with `world` and / or `quality`): -> per clip (poses, extras), `extras` the frames' rows of what
         :meth:`step` returns third - "world" (N_k, J, 3) float64, "reproj" (N_k, J) and "quality" (N_k, 2), the keys asked for, and
-        with `repair` "synthetic" (N_k,) int32.  With `repair` the clips may hold non-finite entries (joints that were not detected)."""
+        with `repair` "synthetic" (N_k,) int32.  With `repair` the clips may hold non-finite entries (joints that were not detected).
+        `previews` (a lifter built with `previews`): -> per clip (poses, extras) as well, and extras["previews"] is a list with one
+        dict per look L: "look" L, "poses" (max(N_k - L, 0), J, 3) - the early poses of the frames 0 .. N_k - 1 - L in frame order,
+        each lifted when the stream held L more frames than it; the clip's last L frames never get that preview, so a clip of no
+        more than L frames has none - and the frames' "world" / "reproj" / "quality" rows where the lifter was built with them.
+        Comparing these poses and `poses[:N_k - L]` with ground truth (:mod:`ray3d_amd.metrics`) is what a look costs in accuracy."""
         if len(clips) > self.S:
             raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
         if world and self._finish is None and self.repair is None:
             raise ValueError("lift_clips: world=True needs an OnlineLifter built with world=True, quality=True or repair=")
+        if previews and not self.looks:
+            raise ValueError("lift_clips: previews=True needs an OnlineLifter built with previews=")
         if cam_rows is not None or params is not None or transforms is not None:
             self.set_cameras(cam_rows, params, transforms)
         clips = [np.ascontiguousarray(torch.as_tensor(c).cpu().numpy(), dtype=np.float32) for c in clips]
@@ -277,6 +384,12 @@ class OnlineLifter:
         if self.repair is not None:
             rows["synthetic"] = self.synthetic
         more = [{k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in rows.items()} for n in lengths]
+        early = None
+        if previews:                # per clip and look: the rows of the frames 0 .. N - 1 - L
+            prow = dict({k: v for k, v in (self._pfinish or {}).items() if k in ("world", "reproj", "quality") and v is not None}, poses=torch.empty((0, self.J, 3), dtype=torch.float32))
+            early = [[dict({k: torch.empty((max(n - L, 0),) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in prow.items()},
+                           look=L) for L in self.looks] for n in lengths]
+            early_seen = [[0] * len(self.looks) for _ in lengths]
         frame = np.zeros(tuple(self.frame.shape), np.float32)
         for t in range(max(lengths) + self.lag):
             act = np.full(self.S, IDLE, np.int32)
@@ -290,14 +403,27 @@ class OnlineLifter:
                 if n >= 0:
                     outs[s][n] = poses[s]
                     for k, v in (extras[0].items() if extras else ()):
-                        more[s][k][n] = v[s]
+                        if k != "previews":
+                            more[s][k][n] = v[s]
                     seen[s] += 1
+            for i, pv in enumerate(extras[0]["previews"] if previews else ()):
+                for s, n in enumerate(pv["frames"].tolist()[:len(clips)]):
+                    if n >= 0:
+                        for k, dst in early[s][i].items():
+                            if k != "look":
+                                dst[n] = pv[k][s]
+                        early_seen[s][i] += 1
         assert seen == lengths, (seen, lengths)
-        return list(zip(outs, more)) if world else outs
+        if previews:
+            assert early_seen == [[max(n - L, 0) for L in self.looks] for n in lengths], (early_seen, lengths)
+            for s in range(len(clips)):
+                more[s]["previews"] = early[s]
+        return list(zip(outs, more)) if world or previews else outs
 
     # ---- capture ---------------------------------------------------------------------------------------------------------
     def capture(self):
-        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish - into
+        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish, and with
+        `previews` r3d_streams_peek, the preview batch's forward or forwards and their finish - into
         a hipGraph on a side stream; from then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
         capture may come between two ticks."""
         if self._graph is not None:
@@ -308,16 +434,22 @@ class OnlineLifter:
         out = torch.empty((S, 1, J, 3), dtype=torch.float32, device=dev)
         out_m = torch.empty((S, 1, J, 3), dtype=torch.float32, device=dev) if self.flip else None
         E = self.lifter.pos.extrinsic_dim
+        pout = pout_m = None
         with torch.no_grad():       # the workspace and the schedules exist before the capture: nothing allocates inside it
+            if self.looks:          # (the larger batch first: the grow-only workspace is then final)
+                KS = len(self.looks) * S
+                pout = torch.empty((KS, 1, J, 3), dtype=torch.float32, device=dev)
+                pout_m = torch.empty((KS, 1, J, 3), dtype=torch.float32, device=dev) if self.flip else None
+                self.lifter._run(_capi.R3D_INPUT_RAYS, self.px.view(KS, self.rf, J, self.F), self.rf, KS, self._ptiled["params"], E, out=pout)
             self.lifter._run(_capi.R3D_INPUT_RAYS, self.x, self.rf, S, self.param, E, out=out)
         torch.cuda.synchronize(dev)
         self.lifter.check_status(dev)
         g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream(dev)
         with torch.no_grad(), torch.cuda.stream(side):
             with torch.cuda.graph(g, stream=side):
-                poses = self._tick(out, out_m)
+                poses = self._tick(out, out_m, pout, pout_m)
         torch.cuda.synchronize(dev)
-        self._graph, self._captured = g, (poses, out, out_m)
+        self._graph, self._captured = g, (poses, out, out_m, pout, pout_m)
 
     def release(self):
         """Drop the captured graph (before the lifter's prepared schedules are released or its options change)."""

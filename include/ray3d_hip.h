@@ -1087,6 +1087,72 @@ int r3d_streams_peek(const void *state_dev,           /* the state of r3d_stream
                      int32_t *peek_status_dev,        /* (K, S) 0, or 1: refused by the step / invalid head      */
                      void *stream);
 
+/* ---- one world skeleton per person from several cameras: one call behind a tick's r3d_streams_poses ---- */
+
+/* Several cameras watch the same person; each is a live stream.  r3d_streams_poses writes, per stream and tick, the pose in WORLD
+ * coordinates and the per-joint re-projection residual: the model predicts in a camera-independent frame, so the streams' world
+ * poses are directly comparable.  r3d_streams_fuse is enqueued AFTER r3d_streams_poses of the same tick, on the same stream, and
+ * combines them: per GROUP of streams (one person) and joint a gated, weighted mean over the group's members that finished a frame
+ * this tick.  The reference is monocular and has nothing to copy here: what follows is this library's definition, held bit for bit
+ * between the device and the host hook.
+ *   world_dev:  (S, J, 3) float64, what r3d_streams_poses wrote.  Rows of streams that did not finish a frame are never read.
+ *   reproj_dev: (S, J) float64 residuals in pixels (r3d_streams_poses), or NULL: every weight is 1.
+ *   emit_dev, status_dev: (S) the words r3d_streams_step wrote this tick.
+ *   synthetic_dev: (S) the mask words of r3d_streams_repair (bit j: joint j of the emitted frame was not observed), or NULL.
+ *   member_dev: (G, M) int32 in DEVICE memory: the stream index in slot m of group g; a negative word is an empty slot.  The
+ *               table may be rewritten between ticks.  The same stream in two slots counts as two candidates.
+ *   soft_px > 0, max_px (<= 0: off), max_dist in metres (<= 0: off).
+ * THE RULE PER GROUP g AND JOINT j.  Integers decide first; after that the arithmetic is float64, no contraction, every operation
+ * rounded once, slots visited in ascending slot order, every sum started from zero.
+ *   1. CANDIDATES.  Slot m, s = member[g, m], is a candidate when 0 <= s < S (an index outside that range is not followed: nothing
+ *      of it is read); the stream finished this tick (status[s] == 0 and emit[s] >= 0, r3d_streams_poses's rule); the three
+ *      components of world[s, j] are finite (tested on the exponent bits); and, with reproj_dev, r = reproj[s, j] is finite and
+ *      r <= max_px when max_px > 0.  TIERS, with synthetic_dev: if at least one candidate has bit j of synthetic[s] clear, the
+ *      candidates with bit j set are dropped - a held or interpolated keypoint does not vote against an observed one; if all
+ *      candidates are synthetic, all stay.
+ *   2. WEIGHT.  w = 1.0 / (soft_px * soft_px + r * r); 1.0 without reproj_dev.
+ *   3. GATE, only with max_dist > 0 and at least two candidates (after the tiers).  d(a, b) = sqrt(((dx*dx) + (dy*dy)) + (dz*dz)),
+ *      the correctly rounded sqrt.  The cost of candidate m is c_m = the sum of w_t * d(x_m, x_t) over the other candidates t.  The
+ *      medoid is the first candidate, replaced by a later one only when c < c_best: ties and NaN costs keep the earlier slot.  The
+ *      inliers are the candidates with d(x_medoid, x_m) <= max_dist (the medoid is one).  Without the gate every candidate is an
+ *      inlier.  Two cameras that disagree by more than max_dist thus keep the one with the smaller residual.
+ *   4. OUTPUTS.  den = sum of w over the inliers.  fused_dev[g, j, r] = (sum of w * x[r]) / den.  spread_dev[g, j] =
+ *      sqrt((sum of w * q(fused, x)) / den), q the squared distance formed as inside d, `fused` the value just computed: the
+ *      weighted RMS distance of the inliers from the fused point, in metres.  count_dev[g, j] = the number of inliers.  Bit j of
+ *      used_dev[g, m] is set when slot m was an inlier for joint j (bits J .. 31 are 0).  No inlier: fused and spread are the
+ *      canonical quiet NaN (0x7FF8000000000000), count is 0.  Any NaN the arithmetic produces (an overflowing sum, a weight that
+ *      underflows the denominator to 0) leaves as the canonical quiet NaN.
+ * EVERY row of every output given is written on every call, also those of a group whose slots are all empty (NaN, NaN, 0, 0).
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: G workgroups of one wavefront;
+ * the workgroup reads its M member words uniformly, once; thread j < J owns joint j, stages its candidates' points and weights in
+ * LDS (at most 16 x 17 x 32 bytes per group) and runs the gate out of it; a `used` word is the wavefront's ballot for its slot,
+ * written by one thread.  Launch-latency-bound by construction.
+ * THE WHOLE BOUNDS STORY.  The only index taken from device memory is a member word, and it is used only after 0 <= s < S held.
+ * Whatever the inputs hold, the kernel reads member_dev within G * M words, emit_dev, status_dev and synthetic_dev within S words,
+ * world_dev within S * J * 3 and reproj_dev within S * J doubles, and writes fused_dev within G * J * 3 doubles, spread_dev and
+ * count_dev within G * J elements and used_dev within G * M words; the staging area is indexed by slot m < M <= 16 and joint
+ * j < J <= 17 only.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (world_dev, emit_dev, status_dev, member_dev,
+ * fused_dev), num_streams or num_groups outside 1..R3D_CLIPS_MAX, num_joints outside 1..17, max_members outside
+ * 1..R3D_FUSE_MAX_MEMBERS, a soft_px that is not finite or <= 0, a NaN max_px or max_dist, world_dev, reproj_dev, emit_dev,
+ * fused_dev or spread_dev not 8-byte aligned, an output extent (fused_dev, spread_dev, count_dev, used_dev) that overlaps an input
+ * extent (world_dev, reproj_dev, emit_dev, status_dev, synthetic_dev, member_dev), compared as address ranges.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+#define R3D_FUSE_MAX_MEMBERS 16
+int r3d_streams_fuse(const double *world_dev,          /* (S, J, 3) float64: what r3d_streams_poses wrote          */
+                     const double *reproj_dev,         /* (S, J) float64 px, or NULL: every weight is 1            */
+                     const int64_t *emit_dev, const int32_t *status_dev,   /* (S): this tick's step words            */
+                     const uint32_t *synthetic_dev,    /* (S) r3d_streams_repair's masks, or NULL                  */
+                     int32_t num_streams, int32_t num_joints,
+                     const int32_t *member_dev,        /* (G, M) stream index per slot, < 0: empty slot; DEVICE    */
+                     int32_t num_groups, int32_t max_members,              /* G in 1..R3D_CLIPS_MAX, M in 1..16     */
+                     double soft_px, double max_px, double max_dist,       /* > 0; <= 0: off; <= 0: off             */
+                     double *fused_dev,                /* (G, J, 3) float64                                        */
+                     double *spread_dev,               /* (G, J) float64 metres, may be NULL                       */
+                     int32_t *count_dev,               /* (G, J) contributors, may be NULL                         */
+                     uint32_t *used_dev,               /* (G, M): bit j = slot m contributed to joint j; may be NULL */
+                     void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -1208,6 +1274,12 @@ int r3d_debug_streams_peek_host(const void *state, int32_t num_streams, int32_t 
                                 int32_t in_features, const int32_t *looks, int32_t num_looks, const int32_t *action,
                                 const int32_t *status, float *x, float *x_mirror, const int32_t *mirror_perm, int64_t *emit,
                                 int32_t *peek_status);
+/* r3d_streams_fuse on the host (HOST pointers throughout, no stream): the same argument checks and the same per-joint routine on
+ * a staging area of its own, groups in order, joints in order; the `used` words from the joints' inlier masks. */
+int r3d_debug_streams_fuse_host(const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
+                                const uint32_t *synthetic, int32_t num_streams, int32_t num_joints, const int32_t *member,
+                                int32_t num_groups, int32_t max_members, double soft_px, double max_px, double max_dist, double *fused,
+                                double *spread, int32_t *count, uint32_t *used);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

@@ -35,7 +35,7 @@ EXPORTS = (
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
-    "r3d_streams_peek",
+    "r3d_streams_peek", "r3d_streams_fuse",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
@@ -43,7 +43,7 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
-                "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host")
+                "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -121,6 +121,7 @@ WINDOW_RUN_DESC_BYTES = 48                                              # sizeof
 R3D_ENCODE_NONE = 3                                                     # r3d_streams_step only: model-input rows, copied bit for bit
 R3D_STREAM_IDLE, R3D_STREAM_PUSH, R3D_STREAM_RESTART, R3D_STREAM_DRAIN = 0, 1, 2, 3   # action words of r3d_streams_step
 STREAMS_PEEK_MAX = 8                                                    # R3D_STREAMS_PEEK_MAX: looks per r3d_streams_peek call
+FUSE_MAX_MEMBERS = 16                                                   # R3D_FUSE_MAX_MEMBERS: slots per group of r3d_streams_fuse
 STREAM_HEAD_BYTES = 16                                                  # sizeof(r3d_stream_head)
 
 
@@ -250,9 +251,13 @@ def load():
                                        C.c_int32, vp, vp, vp]
     lib.r3d_streams_peek.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, vp, vp,
                                      vp, C.POINTER(C.c_int32), vp, vp, vp]
+    lib.r3d_streams_fuse.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                     vp, vp, vp, vp, vp]
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_fuse_host.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                    C.c_double, vp, vp, vp, vp]
         lib.r3d_debug_streams_peek_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                     C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, vp]
         lib.r3d_debug_streams_repair_host.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
@@ -707,6 +712,32 @@ def debug_streams_peek_host(state_ptr: int, num_streams: int, receptive_field: i
     return int(load().r3d_debug_streams_peek_host(state_ptr or None, num_streams, receptive_field, lag, num_joints, in_features, table,
                                                   n if num_looks is None else num_looks, action_ptr or None, status_ptr or None,
                                                   x_ptr or None, x_mirror_ptr or None, perm, emit_ptr or None, peek_status_ptr or None))
+
+
+def streams_fuse(world_ptr: int, reproj_ptr: Optional[int], emit_ptr: int, status_ptr: int, synthetic_ptr: Optional[int], num_streams: int,
+                 num_joints: int, member_ptr: int, num_groups: int, max_members: int, soft_px: float, max_px: float, max_dist: float,
+                 fused_ptr: int, spread_ptr: Optional[int], count_ptr: Optional[int], used_ptr: Optional[int], stream: int):
+    """r3d_streams_fuse (enqueued AFTER :func:`streams_poses` of the same tick): every pointer is device memory; `world_ptr`
+    (num_streams, num_joints, 3) float64 and `reproj_ptr` (num_streams, num_joints) float64 or None what r3d_streams_poses wrote;
+    `emit_ptr` / `status_ptr` the step's words; `synthetic_ptr` r3d_streams_repair's mask words or None; `member_ptr` (num_groups,
+    max_members) int32 stream indices, negative: an empty slot, max_members <= FUSE_MAX_MEMBERS; `fused_ptr` (num_groups,
+    num_joints, 3) float64; `spread_ptr` (num_groups, num_joints) float64, `count_ptr` the same shape int32 and `used_ptr`
+    (num_groups, max_members) uint32, each or None."""
+    check(load().r3d_streams_fuse(world_ptr, reproj_ptr or None, emit_ptr, status_ptr, synthetic_ptr or None, num_streams, num_joints,
+                                  member_ptr, num_groups, max_members, soft_px, max_px, max_dist, fused_ptr, spread_ptr or None,
+                                  count_ptr or None, used_ptr or None, stream), "r3d_streams_fuse")
+
+
+def debug_streams_fuse_host(world_ptr: int, reproj_ptr: Optional[int], emit_ptr: int, status_ptr: int, synthetic_ptr: Optional[int],
+                            num_streams: int, num_joints: int, member_ptr: int, num_groups: int, max_members: int, soft_px: float,
+                            max_px: float, max_dist: float, fused_ptr: int, spread_ptr: Optional[int], count_ptr: Optional[int],
+                            used_ptr: Optional[int]) -> int:
+    """r3d_debug_streams_fuse_host (hooks library only: use_hooks(True)): r3d_streams_fuse on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    return int(load().r3d_debug_streams_fuse_host(world_ptr or None, reproj_ptr or None, emit_ptr or None, status_ptr or None,
+                                                  synthetic_ptr or None, num_streams, num_joints, member_ptr or None, num_groups,
+                                                  max_members, soft_px, max_px, max_dist, fused_ptr or None, spread_ptr or None,
+                                                  count_ptr or None, used_ptr or None))
 
 
 def _census_rows(call):

@@ -4,6 +4,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -478,6 +479,65 @@ int r3d::streams_poses_check_args(const char *what, const float *raw, const floa
     return R3D_OK;
 }
 
+// the argument rules of r3d_streams_fuse, shared with its host hook; fills the kernel's argument set
+int r3d::streams_fuse_check_args(const char *what, const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
+                                 const uint32_t *synthetic, int32_t S, int32_t J, const int32_t *member, int32_t G, int32_t M,
+                                 double soft_px, double max_px, double max_dist, double *fused, double *spread, int32_t *count,
+                                 uint32_t *used, StreamsFuseArgs *args) {
+    if (!world || !emit || !status || !member || !fused) {
+        set_error("%s: null pointer (world_dev, emit_dev, status_dev, member_dev, fused_dev)", what);
+        return R3D_ERR_ARG;
+    }
+    if (S < 1 || S > R3D_CLIPS_MAX) { set_error("%s: num_streams must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, S); return R3D_ERR_ARG; }
+    if (G < 1 || G > R3D_CLIPS_MAX) { set_error("%s: num_groups must be in 1..%d (got %d)", what, R3D_CLIPS_MAX, G); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (M < 1 || M > R3D_FUSE_MAX_MEMBERS) { set_error("%s: max_members must be in 1..%d (got %d)", what, R3D_FUSE_MAX_MEMBERS, M); return R3D_ERR_ARG; }
+    if (!stream_finite_bits64(soft_px) || !(soft_px > 0.0)) { set_error("%s: soft_px must be finite and > 0", what); return R3D_ERR_ARG; }
+    if (max_px != max_px || max_dist != max_dist) { set_error("%s: max_px and max_dist must not be NaN (<= 0 switches them off)", what); return R3D_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(world) % 8 || reinterpret_cast<uintptr_t>(reproj) % 8 || reinterpret_cast<uintptr_t>(emit) % 8 ||
+        reinterpret_cast<uintptr_t>(fused) % 8 || reinterpret_cast<uintptr_t>(spread) % 8) {
+        set_error("%s: world_dev, reproj_dev, emit_dev, fused_dev and spread_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    // an output extent may not overlap an input extent (address ranges; the sizes fit in 64 bits)
+    const uintptr_t sj = (uintptr_t)S * J, gj = (uintptr_t)G * J, gm = (uintptr_t)G * M;
+    const char *out_name[4] = {"fused_dev", "spread_dev", "count_dev", "used_dev"};
+    const char *in_name[6] = {"world_dev", "reproj_dev", "emit_dev", "status_dev", "synthetic_dev", "member_dev"};
+    const uintptr_t outs[4] = {reinterpret_cast<uintptr_t>(fused), reinterpret_cast<uintptr_t>(spread), reinterpret_cast<uintptr_t>(count),
+                               reinterpret_cast<uintptr_t>(used)};
+    const uintptr_t out_bytes[4] = {gj * 3 * sizeof(double), gj * sizeof(double), gj * sizeof(int32_t), gm * sizeof(uint32_t)};
+    const uintptr_t ins[6] = {reinterpret_cast<uintptr_t>(world), reinterpret_cast<uintptr_t>(reproj), reinterpret_cast<uintptr_t>(emit),
+                              reinterpret_cast<uintptr_t>(status), reinterpret_cast<uintptr_t>(synthetic), reinterpret_cast<uintptr_t>(member)};
+    const uintptr_t in_bytes[6] = {sj * 3 * sizeof(double), sj * sizeof(double), (uintptr_t)S * sizeof(int64_t), (uintptr_t)S * sizeof(int32_t),
+                                   (uintptr_t)S * sizeof(uint32_t), gm * sizeof(int32_t)};
+    for (int o = 0; o < 4; ++o)
+        for (int i = 0; i < 6; ++i)
+            if (outs[o] && ins[i] && outs[o] < ins[i] + in_bytes[i] && ins[i] < outs[o] + out_bytes[o]) {
+                set_error("%s: %s overlaps %s: the call does not work in place", what, out_name[o], in_name[i]);
+                return R3D_ERR_ARG;
+            }
+    StreamsFuseArgs a = {};
+    a.world = world;
+    a.reproj = reproj;
+    a.emit = reinterpret_cast<const long long *>(emit);
+    a.status = status;
+    a.synthetic = synthetic;
+    a.member = member;
+    a.fused = fused;
+    a.spread = spread;
+    a.count = count;
+    a.used = used;
+    a.soft_px = soft_px;
+    a.max_px = max_px;
+    a.max_dist = max_dist;
+    a.S = S;
+    a.J = J;
+    a.G = G;
+    a.M = M;
+    *args = a;
+    return R3D_OK;
+}
+
 extern "C" {
 
 int r3d_create(const r3d_config *cfg, r3d_model **out) {
@@ -858,6 +918,24 @@ int r3d_streams_peek(const void *state_dev, int32_t num_streams, int32_t recepti
     const hipError_t err = r3d::launch_streams_peek(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_peek: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_streams_fuse(const double *world_dev, const double *reproj_dev, const int64_t *emit_dev, const int32_t *status_dev,
+                     const uint32_t *synthetic_dev, int32_t num_streams, int32_t num_joints, const int32_t *member_dev, int32_t num_groups,
+                     int32_t max_members, double soft_px, double max_px, double max_dist, double *fused_dev, double *spread_dev,
+                     int32_t *count_dev, uint32_t *used_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsFuseArgs a;
+    const int rc = streams_fuse_check_args("r3d_streams_fuse", world_dev, reproj_dev, emit_dev, status_dev, synthetic_dev, num_streams,
+                                           num_joints, member_dev, num_groups, max_members, soft_px, max_px, max_dist, fused_dev,
+                                           spread_dev, count_dev, used_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_fuse(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_fuse: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -11,6 +11,7 @@
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -845,6 +846,29 @@ int r3d_debug_streams_peek_host(const void *state, int32_t num_streams, int32_t 
             for (int i = 0; i < a.RF; ++i)
                 for (int j = 0; j < a.J; ++j) stream_peek_point(a, k, s, pk.p, c, i, j);
         }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_fuse on the host - its argument rules (streams_fuse_check_args) and the routine of r3d_streams_fuse.hpp the
+// kernel runs: per group its J joints in joint order through stream_fuse_joint on a staging area of stride 1, then the `used` words
+// from the joints' inlier masks, as the wavefront's ballots form them.
+int r3d_debug_streams_fuse_host(const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
+                                const uint32_t *synthetic, int32_t num_streams, int32_t num_joints, const int32_t *member,
+                                int32_t num_groups, int32_t max_members, double soft_px, double max_px, double max_dist, double *fused,
+                                double *spread, int32_t *count, uint32_t *used) {
+    StreamsFuseArgs a;
+    const int rc = streams_fuse_check_args("r3d_debug_streams_fuse_host", world, reproj, emit, status, synthetic, num_streams, num_joints,
+                                           member, num_groups, max_members, soft_px, max_px, max_dist, fused, spread, count, used, &a);
+    if (rc != R3D_OK) return rc;
+    for (int g = 0; g < a.G; ++g) {
+        uint32_t words[R3D_FUSE_MAX_MEMBERS] = {};
+        for (int j = 0; j < a.J; ++j) {
+            double stage[STREAMS_FUSE_STAGE];
+            const uint32_t inl = stream_fuse_joint(a, g, j, stage, 1);
+            for (int m = 0; m < a.M; ++m) words[m] |= ((inl >> m) & 1u) << j;
+        }
+        for (int m = 0; a.used && m < a.M; ++m) a.used[(long long)g * a.M + m] = words[m];
+    }
     return R3D_OK;
 }
 

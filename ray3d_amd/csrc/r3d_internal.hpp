@@ -609,6 +609,13 @@ int streams_peek_check_args(const char *what, const void *state, int32_t S, int3
                             const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status, float *x,
                             float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status, StreamsPeekArgs *args);
 
+struct StreamsFuseArgs;     // r3d_streams_fuse.hpp
+// the argument rules of r3d_streams_fuse, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_fuse_check_args(const char *what, const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
+                            const uint32_t *synthetic, int32_t S, int32_t J, const int32_t *member, int32_t G, int32_t M, double soft_px,
+                            double max_px, double max_dist, double *fused, double *spread, int32_t *count, uint32_t *used,
+                            StreamsFuseArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -717,6 +724,7 @@ hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);    
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream);                   // the same kernel: r3d_streams_poses
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_repair
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
+hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_fuse
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

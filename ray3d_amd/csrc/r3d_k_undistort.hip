@@ -85,11 +85,22 @@
 // the gather's arithmetic with the preview frame in place of the emitted one and the routine the host hook runs: 8 or 12 bytes read
 // and written per thread, consecutive threads at consecutive addresses of x.  The state is const to it.  Plain vector stores from
 // C++, no atomics.
+//
+// r3d_streams_fuse (one world skeleton per person from several cameras: per group of streams and joint the gated, weighted mean of the
+// world poses r3d_streams_poses wrote this tick, include/ray3d_hip.h) is the eleventh argument set, StreamsFuseArgs, enqueued AFTER
+// the r3d_streams_poses of the same tick: one workgroup of one wavefront per group; its M member words are one address per slot for
+// the workgroup - scalar loads, read once, range-checked before they index anything -, thread j < J owns joint j through
+// stream_fuse_joint - the routine the host hook runs -, which stages the candidates' points and weights in LDS (4 * 16 * 17 doubles,
+// component-major so that the wavefront's threads touch consecutive doubles; each thread reads back only what it wrote itself: no
+// barrier), runs the O(M^2) gate out of LDS and writes the joint's fused point, spread and count; the `used` word of slot m is the
+// wavefront's ballot of "slot m was an inlier of my joint", written by thread 0, as r3d_streams_repair forms its mask.  At most
+// 16 x 17 points per group: LAUNCH-LATENCY-BOUND by construction, as r3d_streams_poses is.  Plain vector stores from C++, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -303,16 +314,35 @@ __device__ __forceinline__ void streams_peek_body(const StreamsPeekArgs &e) {
     stream_peek_point(e, k, s, pk.p, c, i, pt - i * e.J);
 }
 
-// The ten argument sets travel in one kernel-argument segment (4 KiB on this target)
+// Group blockIdx.x < G, joint threadIdx.x < J <= 17; the workgroup is ONE wavefront (launch_streams_fuse).  No thread leaves before the
+// ballots; `used` and M are the same for every thread, so the loop around them is uniform.
+__device__ __forceinline__ void streams_fuse_body(const StreamsFuseArgs &f) {
+    __shared__ double stage[STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS];
+    const int g = blockIdx.x, j = threadIdx.x;
+    uint32_t inl = 0;
+    if (j < f.J) inl = stream_fuse_joint(f, g, j, stage + j, STREAMS_FUSE_JOINTS);     // (g < G, j < J <= 17: column j of the staging area)
+    if (!f.used) return;                     // uniform
+    for (int m = 0; m < f.M; ++m) {
+        const unsigned long long mask = __ballot((inl >> m) & 1u);                     // (bit j: thread j < J <= 17)
+        if (j == 0) f.used[(long long)g * f.M + m] = (uint32_t)mask;
+    }
+}
+
+// The eleven argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
                       sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) +
-                      sizeof(StreamsPeekArgs) + 10 * 8 <= 4096,
+                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + 11 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
                                                                          const StreamsArgs sm, const StreamsPosesArgs sp,
-                                                                         const StreamsRepairArgs sr, const StreamsPeekArgs pk) {
+                                                                         const StreamsRepairArgs sr, const StreamsPeekArgs pk,
+                                                                         const StreamsFuseArgs fz) {
+    if (fz.member) {                         // uniform: r3d_streams_fuse - group blockIdx.x
+        streams_fuse_body(fz);
+        return;
+    }
     if (pk.heads) {                          // uniform: r3d_streams_peek - stream blockIdx.y, look blockIdx.z
         streams_peek_body(pk);
         return;
@@ -395,28 +425,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
@@ -424,14 +454,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
@@ -439,33 +469,40 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
     static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_peek: (ceil(RF * J / 256), S, K) workgroups, one launch, nothing else
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_fuse: G workgroups of one wavefront, one launch, nothing else
+hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream) {
+    static_assert(STREAMS_FUSE_THREADS == 64 && STREAMS_FUSE_THREADS >= STREAMS_FUSE_JOINTS, "one wavefront holds a group's joints: its ballots are the used words");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args);
     return hipGetLastError();
 }
 

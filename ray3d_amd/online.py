@@ -45,12 +45,24 @@ class OnlineLifter:
     little of the future (look 0: the newest frame, no future at all); look lag - 1 lacks one frame only.  A preview is superseded
     by the final pose of its frame `lag - L` ticks later and never revised; the final poses are bit for bit what they are without
     previews.  With `repair` the previews are lifted from the repaired ring.
+    `groups` (a list of lists of stream indices, e.g. ``[[0, 3], [1, 2, 4]]``; None: off; needs `world`): several cameras watch the
+    same person - every tick also enqueues ONE r3d_streams_fuse call behind r3d_streams_poses, and :meth:`step` returns one world
+    skeleton per group: per joint the weighted mean of the world poses of the group's streams that finished a frame this tick.
+    With `quality` the weight of a joint is 1 / (`fuse_soft_px`^2 + residual^2) and a residual above `fuse_max_px` (> 0) drops
+    the joint of that stream; without it every weight is 1.  With `repair` a held or interpolated keypoint does not vote against
+    an observed one.  `fuse_max_dist` (metres, > 0): of cameras that disagree, only those within that distance of the weighted
+    medoid are kept - of two, the one with the smaller residual.  A group has 1 .. 16 members (or none: its rows are NaN); the
+    table lives on the device, has room for 16 members per group and is rewritten by :meth:`set_groups`.  The final poses, world
+    poses and quality outputs are bit for bit what they are without groups.  Previews are NOT fused: extras["previews"] stay
+    per stream.
     The lifter is prepared for batches of `num_streams` windows (and of K * `num_streams` with previews) here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
                  kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), joints_left: Optional[Sequence[int]] = None,
                  joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False,
-                 repair: Optional[int] = None, min_conf: float = 0.0, previews: Optional[Sequence[int]] = None):
+                 repair: Optional[int] = None, min_conf: float = 0.0, previews: Optional[Sequence[int]] = None,
+                 groups: Optional[Sequence[Sequence[int]]] = None, fuse_soft_px: float = 2.0, fuse_max_px: float = 0.0,
+                 fuse_max_dist: float = 0.0):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -71,6 +83,17 @@ class OnlineLifter:
         if self.quality and self.F != 3:
             raise ValueError("OnlineLifter: quality=True is defined for 3-feature (ray) inputs only; this pair takes %d" % self.F)
         self.looks = self._check_looks(previews, self.lag) if previews is not None else None
+        self.G, table = 0, None
+        if groups is not None:
+            if not self.world:
+                raise ValueError("OnlineLifter: groups need world=True (the streams' world poses are what is fused)")
+            table = self._member_table(groups, None, self.S)
+            self.G = table.shape[0]
+            self.fuse_soft_px, self.fuse_max_px, self.fuse_max_dist = float(fuse_soft_px), float(fuse_max_px), float(fuse_max_dist)
+            if not np.isfinite(self.fuse_soft_px) or self.fuse_soft_px <= 0:
+                raise ValueError("OnlineLifter: fuse_soft_px must be finite and > 0 (got %r)" % (fuse_soft_px,))
+            if np.isnan(self.fuse_max_px) or np.isnan(self.fuse_max_dist):
+                raise ValueError("OnlineLifter: fuse_max_px and fuse_max_dist must not be NaN (<= 0 switches them off)")
         if self.looks and _capi.streams_state_bytes(len(self.looks) * self.S, self.rf, self.J, self.F) == 0:
             raise ValueError("OnlineLifter: len(previews) * num_streams must be in 1..%d (got %d)" % (_capi.CLIPS_MAX, len(self.looks) * self.S))
         self.perm = evaluate.mirror_permutation(self.J, kps_left, kps_right) if self.flip else None
@@ -107,6 +130,14 @@ class OnlineLifter:
             self.conf = torch.zeros((S, J), dtype=torch.float32, device=dev)
             self.synthetic = torch.zeros((S,), dtype=torch.int32, device=dev)      # (uint32 words: 17 bits are used)
             self._use_conf = False
+        self._fuse = None
+        if self.G:                      # r3d_streams_fuse: the member table and what the call writes
+            M = _capi.FUSE_MAX_MEMBERS
+            self.member = torch.from_numpy(table).to(dev)
+            self._fuse = dict(fused=torch.zeros((self.G, J, 3), dtype=torch.float64, device=dev),
+                              fused_spread=torch.zeros((self.G, J), dtype=torch.float64, device=dev),
+                              fused_count=torch.zeros((self.G, J), dtype=torch.int32, device=dev),
+                              fused_used=torch.zeros((self.G, M), dtype=torch.int32, device=dev))      # (uint32 words: 17 bits are used)
         self._pfinish = self._pv = None
         if self.looks:                  # r3d_streams_peek: K * S preview windows, their words, and the K-fold copies of the streams' rows
             K = len(self.looks)
@@ -151,7 +182,37 @@ class OnlineLifter:
             raise ValueError("OnlineLifter: previews must be strictly increasing (got %r)" % (looks,))
         return looks
 
+    @staticmethod
+    def _member_table(groups, num_groups, num_streams):
+        """The (G, FUSE_MAX_MEMBERS) int32 member table of `groups`, empty slots -1; `num_groups`: the number it must have."""
+        M = _capi.FUSE_MAX_MEMBERS
+        try:
+            rows = [[v for v in g] for g in groups]
+            ok = all(not isinstance(v, bool) and int(v) == v for g in rows for v in g)
+        except (TypeError, ValueError):
+            rows, ok = [], False
+        if not ok or not 1 <= len(rows) <= _capi.CLIPS_MAX:
+            raise ValueError("OnlineLifter: groups must be a list of 1..%d lists of stream indices (got %r)" % (_capi.CLIPS_MAX, groups))
+        if num_groups is not None and len(rows) != num_groups:
+            raise ValueError("set_groups: the lifter was built for %d groups (got %d)" % (num_groups, len(rows)))
+        table = np.full((len(rows), M), -1, np.int32)
+        for g, row in enumerate(rows):
+            if len(row) > M:
+                raise ValueError("OnlineLifter: group %d has %d members; r3d_streams_fuse takes at most %d" % (g, len(row), M))
+            if any(not 0 <= int(v) < num_streams for v in row):
+                raise ValueError("OnlineLifter: group %d names a stream outside 0..%d (got %r)" % (g, num_streams - 1, row))
+            table[g, :len(row)] = [int(v) for v in row]
+        return table
+
     # ---- setup -----------------------------------------------------------------------------------------------------------
+    def set_groups(self, groups):
+        """Who watches whom has changed: rewrites the member table on the device - the buffer the ticks read, also the captured
+        one - so that the NEXT tick fuses the new groups.  The number of groups stays what the lifter was built with; a group may
+        be empty."""
+        if not self.G:
+            raise ValueError("set_groups: needs an OnlineLifter built with groups=")
+        self.member.copy_(torch.from_numpy(self._member_table(groups, self.G, self.S)))
+
     def set_cameras(self, cam_rows=None, params=None, transforms=None):
         """The streams' cameras: `cam_rows` (S, 16) float64 - :meth:`Camera.cam_row` with distortion=True, what the pixel encodings
         and `quality` read -, `params` (S, E) float32, the forward's camera-parameter rows (models with a camera embedding), and
@@ -266,6 +327,13 @@ class OnlineLifter:
                                 self.emit.data_ptr(), self.status.data_ptr(), self.transforms.data_ptr(), ptr(self.cam), self.x.data_ptr(),
                                 self.rf, self.lag, ptr(f["pred"]), ptr(f["world"]), ptr(f["reproj"]), ptr(f["quality"]),
                                 torch.cuda.current_stream(dev).cuda_stream, in_features=self.F)
+            if self._fuse is not None:      # one more launch: the groups' skeletons from what the call above just wrote
+                z = self._fuse
+                _capi.streams_fuse(ptr(f["world"]), ptr(f["reproj"]), self.emit.data_ptr(), self.status.data_ptr(),
+                                   self.synthetic.data_ptr() if self.repair is not None else None, self.S, self.J, self.member.data_ptr(),
+                                   self.G, _capi.FUSE_MAX_MEMBERS, self.fuse_soft_px, self.fuse_max_px, self.fuse_max_dist,
+                                   ptr(z["fused"]), ptr(z["fused_spread"]), ptr(z["fused_count"]), ptr(z["fused_used"]),
+                                   torch.cuda.current_stream(dev).cuda_stream)
         return f["pred"]
 
     def _extras(self):
@@ -273,6 +341,8 @@ class OnlineLifter:
         out = {k: f[k].clone() for k in ("world", "reproj", "quality") if f[k] is not None} if f is not None else {}
         if self.repair is not None:
             out["synthetic"] = self.synthetic.clone()
+        if self._fuse is not None:
+            out.update({k: v.clone() for k, v in self._fuse.items()})
         if self.looks:
             K, S, p = len(self.looks), self.S, self._pfinish
             poses, frames = self._pv.clone().view(K, S, self.J, 3), self.pemit.clone()
@@ -298,6 +368,11 @@ class OnlineLifter:
         newest one less L), or -1: stream s has no preview this tick (it did not PUSH, or holds no more than L frames) and its
         rows are not meaningful - and, with `world` / `quality`, "world" (S, J, 3), "reproj" (S, J) and "quality" (S, 2) of the
         preview poses.  A preview is never revised: the final pose of that frame arrives `lag - L` ticks later in `poses`.
+        With `groups` -> extras["fused"] (G, J, 3) float64, one world skeleton per group; extras["fused_spread"] (G, J) float64,
+        the weighted RMS distance in metres of the contributing cameras from the fused joint; extras["fused_count"] (G, J) int32,
+        how many cameras contributed (0: no member of the group delivered the joint this tick - "fused" and "fused_spread" are
+        NaN there); extras["fused_used"] (G, 16) int32, bit j of word (g, m) set = the m-th member of group g contributed to
+        joint j.  Previews are not fused.
         Raises on a refused stream (an unknown action, a PUSH after a drain began: RESTART starts the next clip) unless `check`
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
@@ -365,7 +440,11 @@ class OnlineLifter:
         dict per look L: "look" L, "poses" (max(N_k - L, 0), J, 3) - the early poses of the frames 0 .. N_k - 1 - L in frame order,
         each lifted when the stream held L more frames than it; the clip's last L frames never get that preview, so a clip of no
         more than L frames has none - and the frames' "world" / "reproj" / "quality" rows where the lifter was built with them.
-        Comparing these poses and `poses[:N_k - L]` with ground truth (:mod:`ray3d_amd.metrics`) is what a look costs in accuracy."""
+        Comparing these poses and `poses[:N_k - L]` with ground truth (:mod:`ray3d_amd.metrics`) is what a look costs in accuracy.
+        With `groups` and `world`: -> (the per-clip list, fused): `fused` has one dict per group - "fused" (T_g, J, 3), "fused_spread"
+        (T_g, J), "fused_count" (T_g, J) and "fused_used" (T_g, 16), row n the group's skeleton of frame n.  The clips start together,
+        so frame n of every clip is emitted by the same tick; T_g is the length of the longest clip among the group's members
+        (0 when no member carries a clip)."""
         if len(clips) > self.S:
             raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
         if world and self._finish is None and self.repair is None:
@@ -390,6 +469,10 @@ class OnlineLifter:
             early = [[dict({k: torch.empty((max(n - L, 0),) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in prow.items()},
                            look=L) for L in self.looks] for n in lengths]
             early_seen = [[0] * len(self.looks) for _ in lengths]
+        fused = None
+        if world and self._fuse is not None:
+            spans = [max([lengths[s] for s in row if 0 <= s < len(clips)], default=0) for row in self.member.cpu().tolist()]
+            fused = [{k: torch.empty((n,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device) for k, v in self._fuse.items()} for n in spans]
         frame = np.zeros(tuple(self.frame.shape), np.float32)
         for t in range(max(lengths) + self.lag):
             act = np.full(self.S, IDLE, np.int32)
@@ -403,9 +486,13 @@ class OnlineLifter:
                 if n >= 0:
                     outs[s][n] = poses[s]
                     for k, v in (extras[0].items() if extras else ()):
-                        if k != "previews":
+                        if k != "previews" and not k.startswith("fused"):
                             more[s][k][n] = v[s]
                     seen[s] += 1
+            for g, rows_g in enumerate(fused or ()):       # (every clip began at tick 0: this tick emits frame t - lag)
+                if 0 <= t - self.lag < rows_g["fused"].shape[0]:
+                    for k, dst in rows_g.items():
+                        dst[t - self.lag] = extras[0][k][g]
             for i, pv in enumerate(extras[0]["previews"] if previews else ()):
                 for s, n in enumerate(pv["frames"].tolist()[:len(clips)]):
                     if n >= 0:
@@ -418,11 +505,13 @@ class OnlineLifter:
             assert early_seen == [[max(n - L, 0) for L in self.looks] for n in lengths], (early_seen, lengths)
             for s in range(len(clips)):
                 more[s]["previews"] = early[s]
-        return list(zip(outs, more)) if world or previews else outs
+        per_clip = list(zip(outs, more)) if world or previews else outs
+        return (per_clip, fused) if fused is not None else per_clip
 
     # ---- capture ---------------------------------------------------------------------------------------------------------
     def capture(self):
-        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish, and with
+        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish
+        (with `groups` r3d_streams_fuse behind it), and with
         `previews` r3d_streams_peek, the preview batch's forward or forwards and their finish - into
         a hipGraph on a side stream; from then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
         capture may come between two ticks."""

@@ -1153,6 +1153,102 @@ int r3d_streams_fuse(const double *world_dev,          /* (S, J, 3) float64: wha
                      uint32_t *used_dev,               /* (G, M): bit j = slot m contributed to joint j; may be NULL */
                      void *stream);
 
+/* ---- detections to live streams: one call in front of a tick's r3d_streams_repair / r3d_streams_step ---- */
+
+/* r3d_streams_step expects row s of its frame to be the same person on every tick, and its caller to know when to RESTART and when
+ * to DRAIN a stream.  A 2D detector delivers neither: per camera and tick an unordered list of 0 .. D skeletons with joints
+ * missing; people enter, are missed for a few frames, and leave.  r3d_streams_assign is enqueued BEFORE r3d_streams_repair /
+ * r3d_streams_step of the same tick, on the same stream.  Per camera it associates the tick's detections with that camera's P
+ * stream slots (stream s = c * P + p), starts new tracks, ends lost ones and writes exactly what repair and step read: the action
+ * words, the frame rows and the confidence rows.  The reference works on complete, pre-associated archives and has nothing to copy
+ * here: what follows is this library's definition, held bit for bit between the device and the host hook.
+ *   det_dev:       (C, D, J, width) float32 keypoints, width 2 or 3 as the frame rows of r3d_streams_step; components 0 and 1 are
+ *                  what the rule measures with.  Detections d >= det_count[c] are never read.
+ *   det_conf_dev:  (C, D, J) float32 detector confidences, or NULL.
+ *   det_count_dev: (C) int32, read clamped into [0, D].
+ * THE STATE.  assign_dev is caller-owned DEVICE memory of r3d_streams_assign_bytes bytes, 8-byte aligned; all-zero means "no
+ * tracks".  In this order, the total rounded up to 8 bytes: int64 next_id[C], int64 id[S], int32 phase[S] (0 free, 1 live, 2
+ * draining; any other value - and 2 when lag == 0 - reads as 0), int32 missed[S] (a value below 0 reads as 0), int32 left[S] (read
+ * clamped into [1, lag]), uint32 seen[S] (bit j set: ref[j] holds an observation; bits J .. 31 are not read), float32
+ * ref[S][J][width] (the per-joint last observation).
+ * THE RULE PER CAMERA c.  Integers decide first; the arithmetic is float64, no contraction, every operation rounded once, joints
+ * visited in ascending order, every sum started from zero, sqrt and / the correctly rounded ones.
+ *   1. DETECTIONS.  n = clamp(det_count[c], 0, D).  Joint j of detection d < n is OBSERVED when all `width` components are finite
+ *      (tested on the exponent bits) and - with det_conf_dev - conf >= min_conf (a NaN confidence is not observed).  size(d) =
+ *      max(max x - min x, max y - min y) over the observed joints, components 0 and 1 widened to float64.  The detection is VALID
+ *      when it has at least min_joints observed joints and size > 0.
+ *   2. COST.  For a live slot p (phase 1 at entry) and a valid detection d the COMMON joints are those observed in d and set in
+ *      seen[p].  Fewer than min_common: the pair is inadmissible.  Otherwise cost = (sum over the common joints of
+ *      sqrt((dx*dx) + (dy*dy)) / their number) / size(d), dx and dy components 0 and 1 of det - ref[p].  The pair is admissible
+ *      when cost <= max_cost; a NaN cost fails.
+ *   3. GREEDY MATCHING.  Repeatedly the admissible pair with the smallest cost among the unmatched slots and the unmatched
+ *      detections is matched; ties go to the smaller p, then the smaller d.  It stops when no admissible pair is left.
+ *   4. LIVE SLOTS.  MATCHED with d: action PUSH; the frame_out row is the detection's bits (unobserved joints included: they are
+ *      what r3d_streams_repair repairs); the conf_out row its confidences, or 1.0 without det_conf_dev; missed = 0; per observed
+ *      joint ref[j] takes the detection's bits and bit j of seen is set; match = d.  UNMATCHED with missed + 1 <= max_missed:
+ *      action PUSH; the frame row is the canonical quiet NaN (0x7FC00000) with R3D_ASSIGN_FILL_NAN - r3d_streams_repair holds or
+ *      interpolates it - and with R3D_ASSIGN_FILL_HOLD ref[j] where seen, else the canonical NaN; the conf_out row is 0.0;
+ *      missed += 1.  UNMATCHED BEYOND max_missed: the track ends.  lag > 0: action DRAIN, left = lag - 1, the slot goes to phase 2,
+ *      or to 0 when left == 0.  lag == 0: action IDLE, phase 0.
+ *   5. DRAINING SLOTS.  action DRAIN; left -= 1; phase 0 when left reaches 0.  An ended track thus gets exactly `lag` DRAIN ticks.
+ *   6. BIRTHS.  The valid unmatched detections, in ascending d, take the slots that were FREE AT ENTRY, in ascending p (a slot
+ *      freed in this call is not reused in it).  A born slot: action RESTART; id = next_id[c], then next_id[c] += 1; phase 1;
+ *      missed = 0; seen and ref from the detection's observed joints; the frame_out and conf_out rows as for a match; match = d.
+ *      A detection that finds no free slot is counted in stats[c][3] and otherwise ignored.
+ *   7. REMAINING FREE SLOTS.  action IDLE.
+ * OUTPUTS.  EVERY element of every output given is written on every call.  The frame_out rows of slots that neither PUSH nor
+ * RESTART are the canonical NaN, their conf_out rows 0.0, their match -1.  id_dev[s] is the track's identity on every tick the
+ * slot is live or draining - the tick the track ends included -, -1 for a slot that is free and stays free.  Identities count from
+ * the state's next_id[c] per camera: (c, id) names a track.  stats_dev[c] = the valid detections, the matched ones, the births
+ * and the valid detections that found no slot.  Copied keypoints and confidences travel as 32-bit patterns.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: C workgroups of one wavefront.
+ * Lanes own detections for step 1; the P x D pairs are dealt over the lanes for step 2, the cost keys in LDS; step 3 is at most
+ * min(P, D) rounds of a wavefront-wide arg-min over (cost, p * D + d) with taken-row and taken-column masks; ballots and
+ * popcounts rank step 6's detections and slots; then lanes own slots.  Launch-latency-bound by construction.
+ * THE WHOLE BOUNDS STORY.  Nothing in the state is ever used as an index: phase, missed, left and seen are compared and masked,
+ * ref is subtracted and copied, the identities are copied and counted.  The only value taken from device memory that bounds a
+ * loop or forms an index is det_count[c], after its clamp into [0, D]: a matched or born slot copies detection d < n <= D.
+ * Whatever the inputs and the state hold, the kernel reads det_dev within C * D * J * width floats, det_conf_dev within C * D * J,
+ * det_count_dev within C words, reads and writes the state within r3d_streams_assign_bytes bytes, and writes action_dev, match_dev
+ * and id_dev within S elements, frame_out_dev within S * J * width, conf_out_dev within S * J and stats_dev within C * 4; the LDS
+ * keys are indexed by p * D + d < P * D <= 1024 only.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (assign_dev, prm, det_dev, det_count_dev,
+ * action_dev, frame_out_dev, match_dev, id_dev), a struct_size other than sizeof(r3d_assign_params), num_cameras < 1, slots outside
+ * 1..R3D_ASSIGN_MAX_SLOTS, max_detections outside 1..R3D_ASSIGN_MAX_DETECTIONS, num_cameras * slots > R3D_CLIPS_MAX, num_joints
+ * outside 1..17, a width other than 2 or 3, lag < 0, min_joints or min_common outside 1..num_joints, max_missed < 0, an unknown
+ * fill, a non-finite min_conf, a max_cost that is not finite and > 0, assign_dev or id_dev not 8-byte aligned, an output extent
+ * (action_dev, frame_out_dev, conf_out_dev, match_dev, id_dev, stats_dev) that overlaps an input extent (det_dev, det_conf_dev,
+ * det_count_dev), the state or another output, compared as address ranges.  r3d_streams_assign_bytes returns 0 for shapes the
+ * call refuses.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+#define R3D_ASSIGN_MAX_SLOTS 32        /* P: stream slots per camera      */
+#define R3D_ASSIGN_MAX_DETECTIONS 32   /* D: detections per camera & tick */
+#define R3D_ASSIGN_FILL_NAN  0         /* an unmatched live slot pushes canonical NaNs (for r3d_streams_repair) */
+#define R3D_ASSIGN_FILL_HOLD 1         /* ... pushes the per-joint last observation (a caller without repair)   */
+typedef struct {
+    int32_t struct_size;               /* sizeof of the CALLER's struct; any other size is R3D_ERR_ARG */
+    int32_t num_cameras, slots, max_detections;   /* C, P, D: stream s = c * P + p; S = C * P <= R3D_CLIPS_MAX */
+    int32_t num_joints, width;         /* J in 1..17; width 2 or 3: the frame rows of r3d_streams_step */
+    int32_t lag;                       /* the step's lag: how many DRAIN ticks an ended track gets */
+    int32_t min_joints, min_common;    /* 1..J each */
+    int32_t max_missed;                /* >= 0: consecutive unmatched ticks a track survives */
+    int32_t fill;                      /* R3D_ASSIGN_FILL_* */
+    float   min_conf;                  /* finite; used only with det_conf_dev */
+    double  max_cost;                  /* finite, > 0 */
+} r3d_assign_params;
+size_t r3d_streams_assign_bytes(int32_t num_cameras, int32_t slots, int32_t num_joints, int32_t width);
+int r3d_streams_assign(void *assign_dev, const r3d_assign_params *prm /* HOST */,
+                       const float *det_dev,        /* (C, D, J, width) */
+                       const float *det_conf_dev,   /* (C, D, J) or NULL */
+                       const int32_t *det_count_dev,/* (C): read clamped into [0, D] */
+                       int32_t *action_dev,         /* (S) R3D_STREAM_* for this tick's repair / step */
+                       float *frame_out_dev,        /* (S, J, width): what repair / step get as frame_dev */
+                       float *conf_out_dev,         /* (S, J) or NULL */
+                       int32_t *match_dev,          /* (S): detection index matched or born from, or -1 */
+                       int64_t *id_dev,             /* (S): the slot's track identity this tick, or -1 */
+                       int32_t *stats_dev,          /* (C, 4) or NULL: valid, matched, born, dropped */
+                       void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -1280,6 +1376,12 @@ int r3d_debug_streams_fuse_host(const double *world, const double *reproj, const
                                 const uint32_t *synthetic, int32_t num_streams, int32_t num_joints, const int32_t *member,
                                 int32_t num_groups, int32_t max_members, double soft_px, double max_px, double max_dist, double *fused,
                                 double *spread, int32_t *count, uint32_t *used);
+/* r3d_streams_assign on the host (HOST pointers throughout, no stream): the same argument checks and the same per-detection,
+ * per-pair, per-slot and per-camera routines, cameras in order; the greedy matching as plain loops over the same keys in the
+ * same order. */
+int r3d_debug_streams_assign_host(void *assign, const r3d_assign_params *prm, const float *det, const float *det_conf,
+                                  const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match,
+                                  int64_t *id, int32_t *stats);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

@@ -35,7 +35,7 @@ EXPORTS = (
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
-    "r3d_streams_peek", "r3d_streams_fuse",
+    "r3d_streams_peek", "r3d_streams_fuse", "r3d_streams_assign_bytes", "r3d_streams_assign",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
@@ -43,7 +43,8 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_encode_host", "r3d_debug_clips_valid_losses_host", "r3d_debug_clips_poses_host",
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
-                "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host")
+                "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host",
+                "r3d_debug_streams_assign_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -122,6 +123,8 @@ R3D_ENCODE_NONE = 3                                                     # r3d_st
 R3D_STREAM_IDLE, R3D_STREAM_PUSH, R3D_STREAM_RESTART, R3D_STREAM_DRAIN = 0, 1, 2, 3   # action words of r3d_streams_step
 STREAMS_PEEK_MAX = 8                                                    # R3D_STREAMS_PEEK_MAX: looks per r3d_streams_peek call
 FUSE_MAX_MEMBERS = 16                                                   # R3D_FUSE_MAX_MEMBERS: slots per group of r3d_streams_fuse
+ASSIGN_MAX_SLOTS, ASSIGN_MAX_DETECTIONS = 32, 32                        # R3D_ASSIGN_MAX_SLOTS, R3D_ASSIGN_MAX_DETECTIONS
+R3D_ASSIGN_FILL_NAN, R3D_ASSIGN_FILL_HOLD = 0, 1                        # what an unmatched live slot of r3d_streams_assign pushes
 STREAM_HEAD_BYTES = 16                                                  # sizeof(r3d_stream_head)
 
 
@@ -253,9 +256,13 @@ def load():
                                      vp, C.POINTER(C.c_int32), vp, vp, vp]
     lib.r3d_streams_fuse.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                      vp, vp, vp, vp, vp]
+    lib.r3d_streams_assign_bytes.restype = C.c_size_t
+    lib.r3d_streams_assign_bytes.argtypes = [C.c_int32] * 4
+    lib.r3d_streams_assign.argtypes = [vp] * 12
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_streams_assign_host.argtypes = [vp] * 11
         lib.r3d_debug_streams_fuse_host.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                                     C.c_double, vp, vp, vp, vp]
         lib.r3d_debug_streams_peek_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
@@ -738,6 +745,45 @@ def debug_streams_fuse_host(world_ptr: int, reproj_ptr: Optional[int], emit_ptr:
                                                   synthetic_ptr or None, num_streams, num_joints, member_ptr or None, num_groups,
                                                   max_members, soft_px, max_px, max_dist, fused_ptr or None, spread_ptr or None,
                                                   count_ptr or None, used_ptr or None))
+
+
+class AssignParams(C.Structure):
+    """r3d_assign_params (include/ray3d_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("num_cameras", C.c_int32), ("slots", C.c_int32), ("max_detections", C.c_int32),
+                ("num_joints", C.c_int32), ("width", C.c_int32), ("lag", C.c_int32), ("min_joints", C.c_int32), ("min_common", C.c_int32),
+                ("max_missed", C.c_int32), ("fill", C.c_int32), ("min_conf", C.c_float), ("max_cost", C.c_double)]
+
+
+def assign_params(num_cameras: int, slots: int, max_detections: int, num_joints: int, width: int, lag: int, min_joints: int,
+                  min_common: int, max_missed: int, fill: int, min_conf: float, max_cost: float) -> AssignParams:
+    """An r3d_assign_params with its struct_size set."""
+    return AssignParams(C.sizeof(AssignParams), num_cameras, slots, max_detections, num_joints, width, lag, min_joints, min_common,
+                        max_missed, fill, min_conf, max_cost)
+
+
+def streams_assign_bytes(num_cameras: int, slots: int, num_joints: int, width: int) -> int:
+    """r3d_streams_assign_bytes: bytes of the state of r3d_streams_assign (all zero = no tracks); 0 for shapes the call refuses."""
+    return int(load().r3d_streams_assign_bytes(num_cameras, slots, num_joints, width))
+
+
+def streams_assign(state_ptr: int, prm: AssignParams, det_ptr: int, det_conf_ptr: Optional[int], det_count_ptr: int, action_ptr: int,
+                   frame_out_ptr: int, conf_out_ptr: Optional[int], match_ptr: int, id_ptr: int, stats_ptr: Optional[int], stream: int):
+    """r3d_streams_assign (enqueued BEFORE :func:`streams_repair` / :func:`streams_step` of the same tick): every pointer is device
+    memory but `prm` (:func:`assign_params`); `det_ptr` (C, D, J, width) float32, `det_conf_ptr` (C, D, J) float32 or None,
+    `det_count_ptr` (C,) int32; written: `action_ptr` (S,) int32, `frame_out_ptr` (S, J, width) float32, `conf_out_ptr` (S, J) float32
+    or None, `match_ptr` (S,) int32, `id_ptr` (S,) int64, `stats_ptr` (C, 4) int32 or None, S = C * P."""
+    check(load().r3d_streams_assign(state_ptr, C.byref(prm), det_ptr, det_conf_ptr or None, det_count_ptr, action_ptr, frame_out_ptr,
+                                    conf_out_ptr or None, match_ptr, id_ptr, stats_ptr or None, stream), "r3d_streams_assign")
+
+
+def debug_streams_assign_host(state_ptr: Optional[int], prm: Optional[AssignParams], det_ptr: Optional[int], det_conf_ptr: Optional[int],
+                              det_count_ptr: Optional[int], action_ptr: Optional[int], frame_out_ptr: Optional[int],
+                              conf_out_ptr: Optional[int], match_ptr: Optional[int], id_ptr: Optional[int], stats_ptr: Optional[int]) -> int:
+    """r3d_debug_streams_assign_host (hooks library only: use_hooks(True)): r3d_streams_assign on HOST pointers; returns the status
+    code instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    return int(load().r3d_debug_streams_assign_host(state_ptr or None, C.byref(prm) if prm is not None else None, det_ptr or None,
+                                                    det_conf_ptr or None, det_count_ptr or None, action_ptr or None, frame_out_ptr or None,
+                                                    conf_out_ptr or None, match_ptr or None, id_ptr or None, stats_ptr or None))
 
 
 def _census_rows(call):

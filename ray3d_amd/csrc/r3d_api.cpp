@@ -4,6 +4,7 @@
 #include "r3d_internal.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
@@ -538,6 +539,87 @@ int r3d::streams_fuse_check_args(const char *what, const double *world, const do
     return R3D_OK;
 }
 
+// the shapes r3d_streams_assign takes: what r3d_streams_assign_bytes and the argument rules share
+static bool streams_assign_shape_ok(int32_t C, int32_t P, int32_t J, int32_t width) {
+    return C >= 1 && P >= 1 && P <= R3D_ASSIGN_MAX_SLOTS && (long long)C * P <= R3D_CLIPS_MAX && J >= 1 && J <= 17 && (width == 2 || width == 3);
+}
+
+// the argument rules of r3d_streams_assign, shared with its host hook; fills the kernel's argument set
+int r3d::streams_assign_check_args(const char *what, void *state, const r3d_assign_params *prm, const float *det, const float *det_conf,
+                                   const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match,
+                                   int64_t *id, int32_t *stats, StreamsAssignArgs *args) {
+    if (!state || !prm || !det || !det_count || !action || !frame_out || !match || !id) {
+        set_error("%s: null pointer (assign_dev, prm, det_dev, det_count_dev, action_dev, frame_out_dev, match_dev, id_dev)", what);
+        return R3D_ERR_ARG;
+    }
+    if (prm->struct_size != (int32_t)sizeof(r3d_assign_params)) {
+        set_error("%s: prm->struct_size is %d, this library's r3d_assign_params has %d bytes", what, prm->struct_size, (int)sizeof(r3d_assign_params));
+        return R3D_ERR_ARG;
+    }
+    const int32_t C = prm->num_cameras, P = prm->slots, D = prm->max_detections, J = prm->num_joints, width = prm->width;
+    if (C < 1) { set_error("%s: num_cameras must be >= 1 (got %d)", what, C); return R3D_ERR_ARG; }
+    if (P < 1 || P > R3D_ASSIGN_MAX_SLOTS) { set_error("%s: slots must be in 1..%d (got %d)", what, R3D_ASSIGN_MAX_SLOTS, P); return R3D_ERR_ARG; }
+    if (D < 1 || D > R3D_ASSIGN_MAX_DETECTIONS) { set_error("%s: max_detections must be in 1..%d (got %d)", what, R3D_ASSIGN_MAX_DETECTIONS, D); return R3D_ERR_ARG; }
+    if ((long long)C * P > R3D_CLIPS_MAX) { set_error("%s: num_cameras * slots must be <= %d (got %d * %d)", what, R3D_CLIPS_MAX, C, P); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (width != 2 && width != 3) { set_error("%s: width must be 2 or 3 (got %d)", what, width); return R3D_ERR_ARG; }
+    if (prm->lag < 0) { set_error("%s: lag must be >= 0 (got %d)", what, prm->lag); return R3D_ERR_ARG; }
+    if (prm->min_joints < 1 || prm->min_joints > J || prm->min_common < 1 || prm->min_common > J) {
+        set_error("%s: min_joints and min_common must be in 1..num_joints = %d (got %d, %d)", what, J, prm->min_joints, prm->min_common);
+        return R3D_ERR_ARG;
+    }
+    if (prm->max_missed < 0) { set_error("%s: max_missed must be >= 0 (got %d)", what, prm->max_missed); return R3D_ERR_ARG; }
+    if (prm->fill != R3D_ASSIGN_FILL_NAN && prm->fill != R3D_ASSIGN_FILL_HOLD) { set_error("%s: unknown fill %d", what, prm->fill); return R3D_ERR_ARG; }
+    if (!stream_finite_bits(__builtin_bit_cast(uint32_t, prm->min_conf))) { set_error("%s: min_conf must be finite", what); return R3D_ERR_ARG; }
+    if (!stream_finite_bits64(prm->max_cost) || !(prm->max_cost > 0.0)) { set_error("%s: max_cost must be finite and > 0", what); return R3D_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(id) % 8) {
+        set_error("%s: assign_dev and id_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    // an output extent may not overlap an input extent, the state or another output (address ranges; the sizes fit in 64 bits)
+    const uintptr_t S = (uintptr_t)C * P, cdj = (uintptr_t)C * D * J, sj = S * J;
+    const char *name[10] = {"action_dev", "frame_out_dev", "conf_out_dev", "match_dev", "id_dev", "stats_dev",
+                            "det_dev", "det_conf_dev", "det_count_dev", "assign_dev"};
+    const uintptr_t ptr[10] = {reinterpret_cast<uintptr_t>(action), reinterpret_cast<uintptr_t>(frame_out), reinterpret_cast<uintptr_t>(conf_out),
+                               reinterpret_cast<uintptr_t>(match), reinterpret_cast<uintptr_t>(id), reinterpret_cast<uintptr_t>(stats),
+                               reinterpret_cast<uintptr_t>(det), reinterpret_cast<uintptr_t>(det_conf), reinterpret_cast<uintptr_t>(det_count),
+                               reinterpret_cast<uintptr_t>(state)};
+    const uintptr_t bytes[10] = {S * sizeof(int32_t), sj * width * sizeof(float), sj * sizeof(float), S * sizeof(int32_t), S * sizeof(int64_t),
+                                 (uintptr_t)C * 4 * sizeof(int32_t), cdj * width * sizeof(float), cdj * sizeof(float), (uintptr_t)C * sizeof(int32_t),
+                                 (uintptr_t)streams_assign_bytes(C, P, J, width)};
+    for (int o = 0; o < 6; ++o)              // (the outputs come first)
+        for (int i = o + 1; i < 10; ++i)
+            if (ptr[o] && ptr[i] && ptr[o] < ptr[i] + bytes[i] && ptr[i] < ptr[o] + bytes[o]) {
+                set_error("%s: %s overlaps %s: the call does not work in place", what, name[o], name[i]);
+                return R3D_ERR_ARG;
+            }
+    StreamsAssignArgs a = {};
+    a.state = state;
+    a.det = reinterpret_cast<const uint32_t *>(det);
+    a.det_conf = det_conf;
+    a.det_count = det_count;
+    a.action = action;
+    a.frame_out = reinterpret_cast<uint32_t *>(frame_out);
+    a.conf_out = reinterpret_cast<uint32_t *>(conf_out);
+    a.match = match;
+    a.id_out = reinterpret_cast<long long *>(id);
+    a.stats = stats;
+    a.max_cost = prm->max_cost;
+    a.min_conf = prm->min_conf;
+    a.C = C;
+    a.P = P;
+    a.D = D;
+    a.J = J;
+    a.width = width;
+    a.lag = prm->lag;
+    a.min_joints = prm->min_joints;
+    a.min_common = prm->min_common;
+    a.max_missed = prm->max_missed;
+    a.fill = prm->fill;
+    *args = a;
+    return R3D_OK;
+}
+
 extern "C" {
 
 int r3d_create(const r3d_config *cfg, r3d_model **out) {
@@ -936,6 +1018,27 @@ int r3d_streams_fuse(const double *world_dev, const double *reproj_dev, const in
     const hipError_t err = r3d::launch_streams_fuse(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_fuse: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+size_t r3d_streams_assign_bytes(int32_t num_cameras, int32_t slots, int32_t num_joints, int32_t width) {
+    if (!streams_assign_shape_ok(num_cameras, slots, num_joints, width)) return 0;
+    return r3d::streams_assign_bytes(num_cameras, slots, num_joints, width);
+}
+
+int r3d_streams_assign(void *assign_dev, const r3d_assign_params *prm, const float *det_dev, const float *det_conf_dev,
+                       const int32_t *det_count_dev, int32_t *action_dev, float *frame_out_dev, float *conf_out_dev, int32_t *match_dev,
+                       int64_t *id_dev, int32_t *stats_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsAssignArgs a;
+    const int rc = streams_assign_check_args("r3d_streams_assign", assign_dev, prm, det_dev, det_conf_dev, det_count_dev, action_dev,
+                                             frame_out_dev, conf_out_dev, match_dev, id_dev, stats_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_assign(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_assign: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

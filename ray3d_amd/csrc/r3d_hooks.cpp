@@ -11,6 +11,7 @@
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
@@ -868,6 +869,59 @@ int r3d_debug_streams_fuse_host(const double *world, const double *reproj, const
             for (int m = 0; m < a.M; ++m) words[m] |= ((inl >> m) & 1u) << j;
         }
         for (int m = 0; a.used && m < a.M; ++m) a.used[(long long)g * a.M + m] = words[m];
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_assign on the host - its argument rules (streams_assign_check_args) and the routines of
+// r3d_streams_assign.hpp the kernel runs: per camera the detections' summaries, the P x D cost keys, the greedy matching as plain
+// loops over the same keys in the kernel's order (stream_assign_better), the free-slot and leftover masks the kernel forms with
+// ballots, then the slots in order and the camera's finish.
+int r3d_debug_streams_assign_host(void *assign, const r3d_assign_params *prm, const float *det, const float *det_conf,
+                                  const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match,
+                                  int64_t *id, int32_t *stats) {
+    StreamsAssignArgs a;
+    const int rc = streams_assign_check_args("r3d_debug_streams_assign_host", assign, prm, det, det_conf, det_count, action, frame_out,
+                                             conf_out, match, id, stats, &a);
+    if (rc != R3D_OK) return rc;
+    const StreamAssignState st = stream_assign_state(a);
+    unsigned long long key[R3D_ASSIGN_MAX_SLOTS * R3D_ASSIGN_MAX_DETECTIONS];      // [p * D + d]
+    for (int c = 0; c < a.C; ++c) {
+        const int n = stream_assign_count(a.det_count[c], a.D);
+        StreamAssignDet dets[R3D_ASSIGN_MAX_DETECTIONS];
+        uint32_t valid = 0;
+        for (int d = 0; d < a.D; ++d) {
+            dets[d] = d < n ? stream_assign_detection(a, c, d) : StreamAssignDet{0u, 0.0, false};
+            if (dets[d].valid) valid |= 1u << d;
+        }
+        for (int p = 0; p < a.P; ++p)
+            for (int d = 0; d < a.D; ++d) key[p * a.D + d] = stream_assign_pair(a, st, c, p, d, dets[d]);
+        uint32_t rows = 0, cols = 0, free_mask = 0;
+        int matched[R3D_ASSIGN_MAX_SLOTS];
+        for (int p = 0; p < a.P; ++p) matched[p] = -1;
+        for (;;) {
+            unsigned long long best = STREAM_ASSIGN_NONE;
+            int at = a.P * a.D;
+            for (int i = 0; i < a.P * a.D; ++i) {
+                const int p = i / a.D, d = i - p * a.D;
+                if (((rows >> p) | (cols >> d)) & 1u) continue;
+                if (stream_assign_better(key[i], i, best, at)) {
+                    best = key[i];
+                    at = i;
+                }
+            }
+            if (best == STREAM_ASSIGN_NONE) break;
+            const int p = at / a.D, d = at - p * a.D;
+            rows |= 1u << p;
+            cols |= 1u << d;
+            matched[p] = d;
+        }
+        for (int p = 0; p < a.P; ++p)
+            if (stream_assign_phase(st.phase[(long long)c * a.P + p], a.lag) == 0) free_mask |= 1u << p;
+        const uint32_t unmatched = valid & ~cols;
+        const long long next = st.next_id[c];
+        for (int p = 0; p < a.P; ++p) stream_assign_slot(a, st, c, p, matched[p], free_mask, unmatched, next);
+        stream_assign_finish(a, st, c, valid, cols, free_mask, unmatched, next);
     }
     return R3D_OK;
 }

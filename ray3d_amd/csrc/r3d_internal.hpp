@@ -616,6 +616,12 @@ int streams_fuse_check_args(const char *what, const double *world, const double 
                             double max_px, double max_dist, double *fused, double *spread, int32_t *count, uint32_t *used,
                             StreamsFuseArgs *args);
 
+struct StreamsAssignArgs;   // r3d_streams_assign.hpp
+// the argument rules of r3d_streams_assign, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_assign_check_args(const char *what, void *state, const r3d_assign_params *prm, const float *det, const float *det_conf,
+                              const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match, int64_t *id,
+                              int32_t *stats, StreamsAssignArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -725,6 +731,7 @@ hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_repair
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_fuse
+hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_assign
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

@@ -95,11 +95,25 @@
 // barrier), runs the O(M^2) gate out of LDS and writes the joint's fused point, spread and count; the `used` word of slot m is the
 // wavefront's ballot of "slot m was an inlier of my joint", written by thread 0, as r3d_streams_repair forms its mask.  At most
 // 16 x 17 points per group: LAUNCH-LATENCY-BOUND by construction, as r3d_streams_poses is.  Plain vector stores from C++, no atomics.
+//
+// r3d_streams_assign (detections to live streams: per camera the association of a tick's unordered detections with the camera's
+// stream slots, births and ends of tracks, and the action / frame / confidence rows r3d_streams_repair and r3d_streams_step read,
+// include/ray3d_hip.h) is the twelfth argument set, StreamsAssignArgs, enqueued BEFORE the repair / step of the same tick: one
+// workgroup of one wavefront per camera.  Lane d owns detection d for the per-detection summary (its size and observed mask go to
+// LDS, the valid bits are a ballot); the P x D pairs are dealt over the lanes, their cost keys - the bits of a non-negative double,
+// which order as integers - go to LDS (at most 32 x 32 x 8 bytes; lane (d, half) owns column d's pairs with the slots of its parity: no division, one reference row per
+// half wavefront and step); the greedy matching is at most min(P, D) rounds of a lane-local
+// scan of the untaken pairs and a six-step xor butterfly over (key, pair index), every lane ending with the same winner; the free
+// slots are a ballot, and a free slot's popcount rank picks its detection; then lane p owns slot p: its state words and its row of
+// every output through stream_assign_slot - the routine the host hook runs.  The keys share the LDS block of r3d_streams_fuse's
+// staging area (one raw block, handed to both bodies): the kernel's static LDS does not grow.  The state is read before the
+// barrier in front of the matching and written after it, each slot's words by its own lane.  Plain vector stores from C++, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
+#include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
@@ -316,8 +330,7 @@ __device__ __forceinline__ void streams_peek_body(const StreamsPeekArgs &e) {
 
 // Group blockIdx.x < G, joint threadIdx.x < J <= 17; the workgroup is ONE wavefront (launch_streams_fuse).  No thread leaves before the
 // ballots; `used` and M are the same for every thread, so the loop around them is uniform.
-__device__ __forceinline__ void streams_fuse_body(const StreamsFuseArgs &f) {
-    __shared__ double stage[STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS];
+__device__ __forceinline__ void streams_fuse_body(const StreamsFuseArgs &f, double *stage) {
     const int g = blockIdx.x, j = threadIdx.x;
     uint32_t inl = 0;
     if (j < f.J) inl = stream_fuse_joint(f, g, j, stage + j, STREAMS_FUSE_JOINTS);     // (g < G, j < J <= 17: column j of the staging area)
@@ -328,19 +341,94 @@ __device__ __forceinline__ void streams_fuse_body(const StreamsFuseArgs &f) {
     }
 }
 
-// The eleven argument sets travel in one kernel-argument segment (4 KiB on this target)
+// Camera blockIdx.x < C; the workgroup is ONE wavefront (launch_streams_assign) and no lane leaves before the last ballot: every
+// loop bound and every branch around a barrier, a shuffle or a ballot is the same for all 64 lanes.  `lds`: STREAMS_ASSIGN_LDS_BYTES.
+__device__ __forceinline__ void streams_assign_body(const StreamsAssignArgs &a, unsigned char *lds) {
+    unsigned long long *key = reinterpret_cast<unsigned long long *>(lds + STREAMS_ASSIGN_LDS_KEYS);       // [p * D + d], p < P, d < D
+    double *size = reinterpret_cast<double *>(lds + STREAMS_ASSIGN_LDS_SIZE);                              // [d], d < D <= 32
+    uint32_t *obs = reinterpret_cast<uint32_t *>(lds + STREAMS_ASSIGN_LDS_OBS);                            // [d], d < D <= 32
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const StreamAssignState st = stream_assign_state(a);
+    const int n = stream_assign_count(a.det_count[c], a.D);         // (one address for the workgroup; the clamp: n <= D)
+    // step 1: lane d < n <= D owns detection d
+    StreamAssignDet det = {0u, 0.0, false};
+    if (lane < n) det = stream_assign_detection(a, c, lane);
+    if (lane < a.D) {
+        size[lane] = det.size;
+        obs[lane] = det.obs;
+    }
+    const uint32_t valid = (uint32_t)__ballot(det.valid);           // (bit d: lane d < n <= 32)
+    __syncthreads();
+    // step 2: lane (d, half) = (lane % 32, lane / 32) owns the pairs (p, d) with p = half, half + 2, ... < P of its column d < D:
+    // no division, one reference row per half wavefront and step
+    const int d = lane & 31, half = lane >> 5, pairs = a.P * a.D;
+    if (d < a.D) {
+        const StreamAssignDet dd = {obs[d], size[d], ((valid >> d) & 1u) != 0};
+        for (int p = half; p < a.P; p += 2) key[p * a.D + d] = stream_assign_pair(a, st, c, p, d, dd);      // (p < P, d < D)
+    }
+    __syncthreads();
+    // step 3: the greedy matching; `rows`, `cols` and the winner are the same in every lane
+    uint32_t rows = 0, cols = 0;
+    int matched = -1;
+    const int rounds = a.P < a.D ? a.P : a.D;
+    for (int r = 0; r < rounds; ++r) {
+        unsigned long long best = STREAM_ASSIGN_NONE;
+        int at = pairs;
+        if (d < a.D && !((cols >> d) & 1u))                         // (a lane whose column is taken has nothing left to offer)
+            for (int p = half; p < a.P; p += 2) {
+                if ((rows >> p) & 1u) continue;
+                const int i = p * a.D + d;
+                const unsigned long long k = key[i];
+                if (stream_assign_better(k, i, best, at)) {
+                    best = k;
+                    at = i;
+                }
+            }
+        for (int off = STREAMS_ASSIGN_THREADS / 2; off > 0; off >>= 1) {
+            const unsigned long long k = __shfl_xor(best, off);
+            const int i = __shfl_xor(at, off);
+            if (stream_assign_better(k, i, best, at)) {
+                best = k;
+                at = i;
+            }
+        }
+        if (best == STREAM_ASSIGN_NONE) break;                      // uniform: no admissible pair is left
+        const int wp = at / a.D, wd = at - wp * a.D;                // (at < pairs: an admissible key came from a real pair)
+        rows |= 1u << wp;
+        cols |= 1u << wd;
+        if (lane == wp) matched = wd;
+    }
+    // steps 4 to 7: lane p < P owns slot p
+    const int phase = lane < a.P ? stream_assign_phase(st.phase[(long long)c * a.P + lane], a.lag) : -1;
+    const uint32_t free_mask = (uint32_t)__ballot(phase == 0);      // (bit p: lane p < P <= 32)
+    const uint32_t unmatched = valid & ~cols;
+    const long long next = st.next_id[c];                           // (every lane reads it before lane 0 replaces it below)
+    if (lane < a.P) stream_assign_slot(a, st, c, lane, matched, free_mask, unmatched, next);
+    if (lane == 0) stream_assign_finish(a, st, c, valid, cols, free_mask, unmatched, next);
+}
+
+// The block of LDS the fuse mode's staging area and the assign mode's keys share
+constexpr int STREAMS_SHARED_LDS_BYTES = (int)sizeof(double) * STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS;
+static_assert(STREAMS_ASSIGN_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_streams_assign lives inside the staging area of r3d_streams_fuse");
+
+// The twelve argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
                       sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) +
-                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + 11 * 8 <= 4096,
+                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + sizeof(StreamsAssignArgs) + 12 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
                                                                          const StreamsArgs sm, const StreamsPosesArgs sp,
                                                                          const StreamsRepairArgs sr, const StreamsPeekArgs pk,
-                                                                         const StreamsFuseArgs fz) {
+                                                                         const StreamsFuseArgs fz, const StreamsAssignArgs as) {
+    __shared__ __attribute__((aligned(16))) unsigned char shared_lds[STREAMS_SHARED_LDS_BYTES];    // one block: the two modes below
+    if (as.state) {                          // uniform: r3d_streams_assign - camera blockIdx.x
+        streams_assign_body(as, shared_lds);
+        return;
+    }
     if (fz.member) {                         // uniform: r3d_streams_fuse - group blockIdx.x
-        streams_fuse_body(fz);
+        streams_fuse_body(fz, reinterpret_cast<double *>(shared_lds));
         return;
     }
     if (pk.heads) {                          // uniform: r3d_streams_peek - stream blockIdx.y, look blockIdx.z
@@ -425,28 +513,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
@@ -454,14 +542,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
@@ -469,40 +557,47 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
     static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_peek: (ceil(RF * J / 256), S, K) workgroups, one launch, nothing else
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{}, StreamsAssignArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_assign: C workgroups of one wavefront, one launch, nothing else
+hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream) {
+    static_assert(STREAMS_ASSIGN_THREADS == 64, "one wavefront holds a camera's detections and slots: its ballots are their masks");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.C), dim3(STREAMS_ASSIGN_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, args);
     return hipGetLastError();
 }
 
 // r3d_streams_fuse: G workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream) {
     static_assert(STREAMS_FUSE_THREADS == 64 && STREAMS_FUSE_THREADS >= STREAMS_FUSE_JOINTS, "one wavefront holds a group's joints: its ballots are the used words");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args, StreamsAssignArgs{});
     return hipGetLastError();
 }
 

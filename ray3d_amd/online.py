@@ -55,6 +55,18 @@ class OnlineLifter:
     table lives on the device, has room for 16 members per group and is rewritten by :meth:`set_groups`.  The final poses, world
     poses and quality outputs are bit for bit what they are without groups.  Previews are NOT fused: extras["previews"] stay
     per stream.
+    `cameras` (an int C; None: off; with `max_detections` D): the streams are C cameras x P = `num_streams` / C slots (stream
+    s = c * P + p, P <= 32) and :meth:`track` takes what a 2D detector delivers - per camera and tick an unordered list of up to
+    D <= 32 skeletons with joints missing - instead of :meth:`step`'s per-stream rows: ONE r3d_streams_assign call in front of the
+    tick associates each camera's detections with its slots (greedy, by the mean joint distance to the slot's last observation
+    over the detection's size, at most `assign_max_cost`), starts a track on a free slot for a detection nobody claims (at least
+    `assign_min_joints` observed joints, default min(4, J); a match needs `assign_min_common` joints in common, default
+    min(3, J)), keeps a track alive through `assign_max_missed` unmatched ticks and then ends it (the slot drains and is free
+    again), and writes the tick's actions, frame rows and confidences on the device.  `assign_fill`: what an unmatched live slot
+    pushes - "nan" (needs `repair`, which then holds or interpolates the joints) or "hold" (the per-joint last observation).
+    Identities are per camera; grouping the cameras' tracks into people stays the caller's job through :meth:`set_groups`, and
+    extras["track_id"] is what they need to drive it.  :meth:`set_cameras` is unchanged: a camera's row is repeated over its P
+    slots.  Without `cameras` nothing of the class changes.
     The lifter is prepared for batches of `num_streams` windows (and of K * `num_streams` with previews) here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
@@ -62,7 +74,9 @@ class OnlineLifter:
                  joints_right: Optional[Sequence[int]] = None, device=None, world: bool = False, quality: bool = False,
                  repair: Optional[int] = None, min_conf: float = 0.0, previews: Optional[Sequence[int]] = None,
                  groups: Optional[Sequence[Sequence[int]]] = None, fuse_soft_px: float = 2.0, fuse_max_px: float = 0.0,
-                 fuse_max_dist: float = 0.0):
+                 fuse_max_dist: float = 0.0, cameras: Optional[int] = None, max_detections: Optional[int] = None,
+                 assign_max_cost: float = 0.5, assign_max_missed: int = 5, assign_min_joints: Optional[int] = None,
+                 assign_min_common: Optional[int] = None, assign_fill: str = "nan"):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -125,7 +139,7 @@ class OnlineLifter:
             if not np.isfinite(self.min_conf):
                 raise ValueError("OnlineLifter: min_conf must be finite (got %r)" % (min_conf,))
             self.repair = int(repair)
-            self.track = torch.zeros(_capi.streams_track_bytes(S, rf, J, self.width), dtype=torch.uint8, device=dev)   # all zero: fresh
+            self.repair_track = torch.zeros(_capi.streams_track_bytes(S, rf, J, self.width), dtype=torch.uint8, device=dev)   # all zero: fresh
             self.frame_out = torch.zeros((S, J, self.width), dtype=torch.float32, device=dev)
             self.conf = torch.zeros((S, J), dtype=torch.float32, device=dev)
             self.synthetic = torch.zeros((S,), dtype=torch.int32, device=dev)      # (uint32 words: 17 bits are used)
@@ -138,6 +152,12 @@ class OnlineLifter:
                               fused_spread=torch.zeros((self.G, J), dtype=torch.float64, device=dev),
                               fused_count=torch.zeros((self.G, J), dtype=torch.int32, device=dev),
                               fused_used=torch.zeros((self.G, M), dtype=torch.int32, device=dev))      # (uint32 words: 17 bits are used)
+        self._assign, self._tracking, self._use_det_conf = None, False, False
+        if cameras is not None:         # r3d_streams_assign: its state, the detections and what the call writes beside action / frame / conf
+            self._assign = self._assign_setup(cameras, max_detections, assign_max_cost, assign_max_missed, assign_min_joints,
+                                              assign_min_common, assign_fill)
+        elif max_detections is not None:
+            raise ValueError("OnlineLifter: max_detections needs cameras=")
         self._pfinish = self._pv = None
         if self.looks:                  # r3d_streams_peek: K * S preview windows, their words, and the K-fold copies of the streams' rows
             K = len(self.looks)
@@ -163,6 +183,44 @@ class OnlineLifter:
             self._out_perm = torch.tensor(out_perm, dtype=torch.int64, device=dev)
             self._out_sign = torch.tensor([-1.0, 1.0, 1.0], dtype=torch.float32, device=dev)
         lifter.prepare([S] + ([len(self.looks) * S] if self.looks else []), dev)
+
+    def _assign_setup(self, cameras, max_detections, max_cost, max_missed, min_joints, min_common, fill):
+        """The arguments of `cameras=` checked -> dict of r3d_streams_assign's parameter block and buffers."""
+        S, J, dev = self.S, self.J, self.device
+
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not integer(cameras) or cameras < 1 or S % int(cameras) or not 1 <= S // int(cameras) <= _capi.ASSIGN_MAX_SLOTS:
+            raise ValueError("OnlineLifter: num_streams must be cameras * P with P in 1..%d slots per camera (got num_streams=%d, "
+                             "cameras=%r)" % (_capi.ASSIGN_MAX_SLOTS, S, cameras))
+        if not integer(max_detections) or not 1 <= max_detections <= _capi.ASSIGN_MAX_DETECTIONS:
+            raise ValueError("OnlineLifter: cameras= needs max_detections in 1..%d (got %r)" % (_capi.ASSIGN_MAX_DETECTIONS, max_detections))
+        C, D = int(cameras), int(max_detections)
+        min_joints = min(4, J) if min_joints is None else min_joints
+        min_common = min(3, J) if min_common is None else min_common
+        if not integer(min_joints) or not integer(min_common) or not 1 <= min_joints <= J or not 1 <= min_common <= J:
+            raise ValueError("OnlineLifter: assign_min_joints and assign_min_common must be in 1..%d (got %r, %r)" % (J, min_joints, min_common))
+        if not integer(max_missed) or max_missed < 0:
+            raise ValueError("OnlineLifter: assign_max_missed must be an int >= 0 (got %r)" % (max_missed,))
+        if not np.isfinite(float(max_cost)) or float(max_cost) <= 0:
+            raise ValueError("OnlineLifter: assign_max_cost must be finite and > 0 (got %r)" % (max_cost,))
+        if fill not in ("nan", "hold"):
+            raise ValueError("OnlineLifter: assign_fill must be 'nan' or 'hold' (got %r)" % (fill,))
+        if fill == "nan" and self.repair is None:
+            raise ValueError("OnlineLifter: assign_fill='nan' needs repair= (r3d_streams_repair holds or interpolates the missing "
+                             "frames); assign_fill='hold' pushes the last observation instead")
+        if not np.isfinite(self.min_conf):
+            raise ValueError("OnlineLifter: min_conf must be finite (got %r)" % (self.min_conf,))
+        prm = _capi.assign_params(C, S // C, D, J, self.width, self.lag, int(min_joints), int(min_common), int(max_missed),
+                                  _capi.R3D_ASSIGN_FILL_NAN if fill == "nan" else _capi.R3D_ASSIGN_FILL_HOLD, self.min_conf, float(max_cost))
+        return dict(prm=prm, C=C, D=D,
+                    state=torch.zeros(_capi.streams_assign_bytes(C, S // C, J, self.width), dtype=torch.uint8, device=dev),   # all zero: no tracks
+                    det=torch.zeros((C, D, J, self.width), dtype=torch.float32, device=dev),
+                    det_conf=torch.zeros((C, D, J), dtype=torch.float32, device=dev),
+                    det_count=torch.zeros((C,), dtype=torch.int32, device=dev),
+                    track_id=torch.full((S,), -1, dtype=torch.int64, device=dev),
+                    match=torch.full((S,), -1, dtype=torch.int32, device=dev),
+                    assign_stats=torch.zeros((C, 4), dtype=torch.int32, device=dev))
 
     @staticmethod
     def _check_looks(previews, lag: int):
@@ -284,10 +342,18 @@ class OnlineLifter:
 
     def _final_tick(self, out=None, out_m=None):
         dev, lifter = self.device, self.lifter
+        if self._tracking:              # the tick's actions, frame rows and confidences come from the detections
+            z = self._assign
+            with torch.cuda.device(dev):
+                _capi.streams_assign(z["state"].data_ptr(), z["prm"], z["det"].data_ptr(),
+                                     z["det_conf"].data_ptr() if self._use_det_conf else None, z["det_count"].data_ptr(),
+                                     self.action.data_ptr(), self.frame.data_ptr(), self.conf.data_ptr() if self.repair is not None else None,
+                                     z["match"].data_ptr(), z["track_id"].data_ptr(), z["assign_stats"].data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream)
         frame = self.frame
         if self.repair is not None:     # the repaired frame is what the step pushes
             with torch.cuda.device(dev):
-                _capi.streams_repair(self.state.data_ptr(), self.track.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding,
+                _capi.streams_repair(self.state.data_ptr(), self.repair_track.data_ptr(), self.S, self.rf, self.lag, self.J, self.F, self.encoding,
                                      self.frame.data_ptr(), self.conf.data_ptr() if self._use_conf else None, self.min_conf,
                                      self.cam.data_ptr() if self.cam is not None and self.encoding != _capi.R3D_ENCODE_NONE else None,
                                      self.action.data_ptr(), self.repair, self.frame_out.data_ptr(), self.synthetic.data_ptr(),
@@ -343,6 +409,8 @@ class OnlineLifter:
             out["synthetic"] = self.synthetic.clone()
         if self._fuse is not None:
             out.update({k: v.clone() for k, v in self._fuse.items()})
+        if self._tracking:
+            out.update({k: self._assign[k].clone() for k in ("track_id", "match", "assign_stats")})
         if self.looks:
             K, S, p = len(self.looks), self.S, self._pfinish
             poses, frames = self._pv.clone().view(K, S, self.J, 3), self.pemit.clone()
@@ -377,6 +445,9 @@ class OnlineLifter:
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
             raise RuntimeError("OnlineLifter: call set_cameras first (this configuration reads camera rows / parameter rows)")
+        if self._assign is not None and self._graph is not None:
+            raise ValueError("step: the captured tick of a lifter built with cameras= starts with r3d_streams_assign: use track()")
+        self._tracking = False
         if frame is not None:
             t = torch.as_tensor(frame)
             if tuple(t.shape) != tuple(self.frame.shape):
@@ -405,6 +476,54 @@ class OnlineLifter:
             if tuple(a.shape) != (self.S,):
                 raise ValueError("step: actions must be (%d,) (got %s)" % (self.S, tuple(a.shape)))
             self.action.copy_(a.to(torch.int32))
+        return self._run_tick(check)
+
+    def track(self, detections, counts, conf=None, check: bool = True):
+        """One tick from a detector's output (a lifter built with `cameras=`): `detections` (C, D, J, 2) pixels or (C, D, J, F)
+        model-input rows, a tensor or an array - per camera up to D skeletons in any order, a joint that was not detected
+        non-finite; `counts` (C,) how many of each camera's rows are filled (read clamped into 0..D; the rows behind it are not
+        looked at); `conf` (C, D, J) detector confidences (a joint below `min_conf`, or with a NaN confidence, counts as not
+        detected).  The inputs are copied into persistent device buffers, then r3d_streams_assign, r3d_streams_repair (with
+        `repair`), r3d_streams_step and the rest of the tick are enqueued exactly as :meth:`step` does with the actions, frame
+        rows and confidences the assign call wrote - nothing comes back to the host in between, and a captured lifter replays
+        all of it.  -> (poses, frames, extras) as :meth:`step` returns them, and extras["track_id"] (S,) int64 - the identity of
+        the track in slot s this tick, counted per camera from 0, -1 for a free slot; a track keeps its identity and its slot
+        from its first tick to the last pose of its drain -, extras["match"] (S,) int32 - the detection row the slot took this
+        tick (matched or born from), -1 for none: the slot pushed a synthetic frame, drains or is free - and
+        extras["assign_stats"] (C, 4) int32: the camera's valid detections, the matched ones, the births and the valid
+        detections that found no free slot.  A track's last `assign_max_missed` frames before its end are synthetic (nobody was
+        matched): with `repair` extras["synthetic"] marks their joints.  Cross-camera grouping is the caller's: map
+        (camera, track_id) to people and call :meth:`set_groups`.  A lifter that was captured takes `conf` on every tick or on
+        none."""
+        z = self._assign
+        if z is None:
+            raise ValueError("track: needs an OnlineLifter built with cameras=")
+        if not self._cameras_set:
+            raise RuntimeError("OnlineLifter: call set_cameras first (this configuration reads camera rows / parameter rows)")
+        t = torch.as_tensor(detections)
+        if tuple(t.shape) != tuple(z["det"].shape):
+            raise ValueError("track: detections must be %s (got %s)" % (tuple(z["det"].shape), tuple(t.shape)))
+        n = torch.as_tensor(counts)
+        if tuple(n.shape) != (z["C"],):
+            raise ValueError("track: counts must be (%d,) (got %s)" % (z["C"], tuple(n.shape)))
+        if conf is not None:
+            c = torch.as_tensor(conf)
+            if tuple(c.shape) != tuple(z["det_conf"].shape):
+                raise ValueError("track: conf must be %s (got %s)" % (tuple(z["det_conf"].shape), tuple(c.shape)))
+        if self._graph is not None and self._use_det_conf != (conf is not None):
+            raise ValueError("track: the captured tick was recorded %s confidences" % ("with" if self._use_det_conf else "without"))
+        z["det"].copy_(t.to(torch.float32))
+        z["det_count"].copy_(n.to(torch.int32))
+        if conf is not None:
+            z["det_conf"].copy_(c.to(torch.float32))
+        self._use_det_conf = conf is not None
+        self._tracking = True
+        if self.repair is not None:     # the repair reads the confidences the assign call writes (1.0 without a detector's)
+            self._use_conf = True
+        return self._run_tick(check)
+
+    def _run_tick(self, check: bool):
+        """The tick on the buffers as they stand - replayed when captured - and what :meth:`step` returns."""
         with torch.no_grad():
             if self._graph is not None:
                 self._graph.replay()
@@ -414,7 +533,7 @@ class OnlineLifter:
                 if self._finish is not None:
                     poses = poses.clone()
         frames = self.emit.clone()
-        extras = self._extras() if self._finish is not None or self.repair is not None or self.looks else None
+        extras = self._extras() if self._finish is not None or self.repair is not None or self.looks or self._tracking else None
         if check:
             bad = torch.nonzero(self.status).flatten().tolist()
             if bad:
@@ -510,7 +629,8 @@ class OnlineLifter:
 
     # ---- capture ---------------------------------------------------------------------------------------------------------
     def capture(self):
-        """Record one tick - r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish
+        """Record one tick - r3d_streams_assign (with `cameras`: the captured lifter then takes :meth:`track`, not :meth:`step`),
+        r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish
         (with `groups` r3d_streams_fuse behind it), and with
         `previews` r3d_streams_peek, the preview batch's forward or forwards and their finish - into
         a hipGraph on a side stream; from then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
@@ -533,6 +653,10 @@ class OnlineLifter:
             self.lifter._run(_capi.R3D_INPUT_RAYS, self.x, self.rf, S, self.param, E, out=out)
         torch.cuda.synchronize(dev)
         self.lifter.check_status(dev)
+        if self._assign is not None:    # the recorded tick starts with r3d_streams_assign; its repair reads the confidences it writes
+            self._tracking = True
+            if self.repair is not None:
+                self._use_conf = True
         g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream(dev)
         with torch.no_grad(), torch.cuda.stream(side):
             with torch.cuda.graph(g, stream=side):

@@ -79,7 +79,7 @@ def one(lifter, name, S, ticks, reps, drop, dev):
         ol.frame.copy_(gapped[0])
 
         def repair_alone():
-            _capi.streams_repair(ol.state.data_ptr(), ol.track.data_ptr(), S, rf, ol.lag, J, 3, ol.encoding, ol.frame.data_ptr(), None, 0.0,
+            _capi.streams_repair(ol.state.data_ptr(), ol.repair_track.data_ptr(), S, rf, ol.lag, J, 3, ol.encoding, ol.frame.data_ptr(), None, 0.0,
                                  ol.cam.data_ptr(), ol.action.data_ptr(), K, ol.frame_out.data_ptr(), ol.synthetic.data_ptr(), stream)
         (alone,) = timed([repair_alone], ticks, reps, dev)
     lifter.check_status(dev)

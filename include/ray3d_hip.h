@@ -1249,6 +1249,105 @@ int r3d_streams_assign(void *assign_dev, const r3d_assign_params *prm /* HOST */
                        int32_t *stats_dev,          /* (C, 4) or NULL: valid, matched, born, dropped */
                        void *stream);
 
+/* ---- one person across cameras: one call between a tick's r3d_streams_poses and its r3d_streams_fuse ---- */
+
+/* r3d_streams_assign keeps tracks per camera and r3d_streams_fuse combines the streams a (G, M) member table names; which camera's
+ * track is which person is what r3d_streams_link decides, on the device: it keeps a table of people, G slots per scene, in
+ * caller-owned device memory, links each camera's tracks to people by the distance of their world poses, starts and ends people and
+ * writes the member table r3d_streams_fuse reads.  It is enqueued AFTER r3d_streams_poses and BEFORE r3d_streams_fuse of the same
+ * tick, on the same stream.  The reference is monocular and pre-associated and has nothing to copy here: what follows is this
+ * library's definition, held bit for bit between the device and the host hook.
+ * SHAPES.  N scenes (a scene is a room whose cameras see the same people), C cameras per scene, P slots per camera, G people per
+ * scene.  Stream s = (n * C + c) * P + p - as r3d_streams_assign numbers them with num_cameras = N * C -, S = N * C * P; person
+ * n * G + g.  M = max_members is the member table's row length, C <= M <= R3D_FUSE_MAX_MEMBERS.
+ *   world_dev:             (S, J, 3) float64, what r3d_streams_poses wrote this tick.
+ *   emit_dev, status_dev:  (S) this tick's words of r3d_streams_step.  A stream FINISHED when status == 0 and emit >= 0, as for
+ *                          r3d_streams_poses.
+ *   id_dev:                (S) int64 track identities: what r3d_streams_assign wrote this tick (a caller without it supplies its
+ *                          own); < 0: no track.
+ * THE STATE.  link_dev is caller-owned DEVICE memory of r3d_streams_link_bytes bytes, 8-byte aligned; all-zero means "no people".
+ * In this order, the total rounded up to 8 bytes: int64 next_id[N], int64 pid[N*G], int64 link_id[N*G][C], double ref[N*G][J][3],
+ * int32 phase[N*G] (0 free, 1 live; any other value reads as 0), int32 missed[N*G] (a value below 0 reads as 0), int32 link[N*G][C]
+ * (the slot PLUS ONE; 0: none; a value outside 0..P reads as 0), uint32 seen[N*G] (bit j set: ref[j] holds a point; bits J .. 31
+ * are not read).
+ * THE RULE PER SCENE n.  Integers decide first; the arithmetic is float64, no contraction, every operation rounded once, joints
+ * visited in ascending order, every sum started from zero, sqrt and / the correctly rounded ones.  Joint j of a finished stream is
+ * PRESENT when its three world components are finite (tested on the exponent bits).  cost(g, s), over the COMMON joints - present
+ * in s and set in seen[g] -, is (sum of sqrt(((dx*dx) + (dy*dy)) + (dz*dz))) / their number, d = world[s][j] - ref[g][j]; it is
+ * defined with at least one common joint.
+ *   A. VALIDATE, people in ascending g, cameras in ascending c.  The link p of live person g in camera c, s its stream, is DROPPED
+ *      when id_dev[s] < 0 or id_dev[s] != link_id[g][c] (the track ended or the slot was reused; a draining track keeps its
+ *      identity and stays linked through its drain); when, with break_dist > 0, the stream finished, has a common joint and
+ *      cost(g, s) > break_dist (a NaN cost keeps the link); when a smaller g holds the same stream after its own tests (only a
+ *      state nobody zeroed has that).
+ *   B. PER CAMERA, ascending c, strictly in that order.  CANDIDATES are the slots p with id >= 0, finished this tick, held by no
+ *      person, with at least min_joints present joints.  ELIGIBLE are the live people - those born earlier in this call included -
+ *      without a link in camera c and with a non-empty seen.  A pair is ADMISSIBLE with at least min_common common joints and
+ *      cost <= max_dist (a NaN cost fails).  GREEDY MATCHING: repeatedly the admissible pair with the smallest cost among the
+ *      unmatched people and candidates is matched; ties go to the smaller g, then the smaller p; it stops when no admissible pair
+ *      is left.  A matched pair sets link = p + 1 and link_id = id_dev[s].  BIRTHS: the unmatched candidates, in ascending p, take
+ *      the people that are free now, in ascending g: pid = next_id[n], then next_id[n] += 1; phase 1; missed 0; seen is the
+ *      stream's present mask and ref[j] its point for every present joint (the other joints' ref stays); camera c's link is set
+ *      as for a match, the person's other links are none.  A candidate that finds no free person is counted in stats[n][3] and
+ *      stays unlinked: it is a candidate again on the next tick.  During B the ref of a person alive at entry is its value at
+ *      entry; camera c + 1 sees the people camera c bore.
+ *   C. PER LIVE PERSON.  Per joint, over the linked members that finished and have the joint present, cameras in ascending order:
+ *      ref[j] = (sum of their points, per component) / their number, and bit j of seen is set; with no such member the joint's
+ *      ref and bit stay.  With at least one link missed = 0.  With none: when missed + 1 > max_missed the person is FREED - phase
+ *      0, not reused within this call -, else missed += 1; until then it keeps its ref, so a track re-born after an occlusion,
+ *      with a new track identity, re-joins the same pid.
+ * Every link word of the state is written on every call, 0 for a person that is not live after step B; link_id only where a link is
+ * made; the other words of a person only where the rule changes them.
+ * OUTPUTS.  EVERY element of every output given is written on every call.  member_dev[g][c] = the absolute stream index of the
+ * person's link in camera c, or -1; slots C .. M - 1 hold -1: r3d_streams_fuse takes the table as it is, with num_groups = N * G.
+ * person_dev[g] = the pid of a person live after the call, else -1.  group_dev[s] = the absolute person index that holds stream
+ * s, or -1.  stats_dev[n] = the people live after the call, the links step B's matching made, the births and the candidates that
+ * found no free person.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: N workgroups of one wavefront.
+ * Lane g owns person g in step A and for the words of step C, whose joint means are dealt over the lanes by joint; in step B lane p
+ * summarises slot p, the G x P pairs are dealt over the lanes, their cost keys in LDS, the matching at most min(G, P) rounds of a
+ * wavefront-wide arg-min, births ranked by ballots and popcounts.  The cameras are visited one after the other: the launch's time
+ * grows with C.
+ * THE WHOLE BOUNDS STORY.  ONE state word becomes an index: a link word, and only after its range check - a value outside 1..P
+ * reads as "none", so the slot p = link - 1 < P and the stream (n * C + c) * P + p < S.  Everything else in the state is compared
+ * and masked (phase, missed, seen), subtracted, averaged and copied (ref) or copied and counted (the identities).  The inputs
+ * form no index at all.  Whatever the inputs and the state hold, the kernel reads world_dev within S * J * 3 doubles and emit_dev,
+ * status_dev and id_dev within S words, reads and writes the state within r3d_streams_link_bytes bytes, and writes member_dev
+ * within N * G * M words, person_dev within N * G, group_dev within S and stats_dev within N * 4; the LDS keys are indexed by
+ * g * P + p < G * P <= 1024 only, step C's member rows by g * C + c < G * C <= 512.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (link_dev, prm, world_dev, emit_dev, status_dev,
+ * id_dev, member_dev, person_dev), a struct_size other than sizeof(r3d_link_params), num_scenes < 1, num_cameras outside
+ * 1..R3D_FUSE_MAX_MEMBERS, slots outside 1..R3D_ASSIGN_MAX_SLOTS, people outside 1..R3D_LINK_MAX_PEOPLE, num_joints outside 1..17,
+ * max_members outside num_cameras..R3D_FUSE_MAX_MEMBERS, num_scenes * num_cameras * slots or num_scenes * people above
+ * R3D_CLIPS_MAX, min_joints or min_common outside 1..num_joints, max_missed < 0, a max_dist that is not finite and > 0, a
+ * break_dist that is NaN or - when > 0 - not finite or below max_dist, link_dev, world_dev, emit_dev, id_dev or person_dev not
+ * 8-byte aligned, an output extent (member_dev, person_dev, group_dev, stats_dev) that overlaps an input extent (world_dev,
+ * emit_dev, status_dev, id_dev), the state or another output, compared as address ranges.  r3d_streams_link_bytes returns 0 for
+ * shapes the call refuses.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+#define R3D_LINK_MAX_PEOPLE 32         /* G: people per scene */
+typedef struct {
+    int32_t struct_size;               /* sizeof of the CALLER's struct; any other size is R3D_ERR_ARG */
+    int32_t num_scenes, num_cameras, slots;       /* N, C, P: stream s = (n * C + c) * P + p; S = N * C * P <= R3D_CLIPS_MAX */
+    int32_t people, max_members;       /* G in 1..R3D_LINK_MAX_PEOPLE; M in C..R3D_FUSE_MAX_MEMBERS: the member table is (N * G, M) */
+    int32_t num_joints;                /* J in 1..17 */
+    int32_t min_joints, min_common;    /* 1..J each */
+    int32_t max_missed;                /* >= 0: consecutive ticks without a link a person survives */
+    double  max_dist;                  /* metres; finite, > 0 */
+    double  break_dist;                /* metres; <= 0: off; else finite and >= max_dist */
+} r3d_link_params;
+size_t r3d_streams_link_bytes(int32_t num_scenes, int32_t num_cameras, int32_t people, int32_t num_joints);
+int r3d_streams_link(void *link_dev, const r3d_link_params *prm /* HOST */,
+                     const double *world_dev,     /* (S, J, 3) float64: what r3d_streams_poses wrote */
+                     const int64_t *emit_dev,     /* (S) */
+                     const int32_t *status_dev,   /* (S) */
+                     const int64_t *id_dev,       /* (S): the track identities of this tick, < 0: no track */
+                     int32_t *member_dev,         /* (N * G, M): what r3d_streams_fuse gets as member_dev */
+                     int64_t *person_dev,         /* (N * G): the pid of a live person, or -1 */
+                     int32_t *group_dev,          /* (S) or NULL: the person index that holds the stream, or -1 */
+                     int32_t *stats_dev,          /* (N, 4) or NULL: live, linked, born, dropped */
+                     void *stream);
+
 const char *r3d_last_error(void);
 const char *r3d_version(void);
 int r3d_abi_version(void);                 /* R3D_ABI_VERSION the library was built with */
@@ -1382,6 +1481,11 @@ int r3d_debug_streams_fuse_host(const double *world, const double *reproj, const
 int r3d_debug_streams_assign_host(void *assign, const r3d_assign_params *prm, const float *det, const float *det_conf,
                                   const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match,
                                   int64_t *id, int32_t *stats);
+/* r3d_streams_link on the host (HOST pointers throughout, no stream): the same argument checks and the same per-link, per-slot,
+ * per-pair and per-person routines, scenes, cameras and people in order; the greedy matching as plain loops over the same keys in
+ * the same order. */
+int r3d_debug_streams_link_host(void *link, const r3d_link_params *prm, const double *world, const int64_t *emit, const int32_t *status,
+                                const int64_t *id, int32_t *member, int64_t *person, int32_t *group, int32_t *stats);
 /* The device path's tables and per-element routines run on the CPU: packs the handle's host weights (every r3d_set_weight done) the
  * way r3d_finalize does, then once more through the descriptor / inverse / segment tables of r3d_finalize_dev and the routines its
  * kernel runs, work item by work item, and compares the two images as 32-bit patterns: *mismatches differing floats, *first_index

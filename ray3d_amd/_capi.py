@@ -35,7 +35,8 @@ EXPORTS = (
     "r3d_clips_encode", "r3d_clips_valid_losses", "r3d_clips_valid_scratch_bytes", "r3d_clips_poses",
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
-    "r3d_streams_peek", "r3d_streams_fuse", "r3d_streams_assign_bytes", "r3d_streams_assign",
+    "r3d_streams_peek", "r3d_streams_fuse", "r3d_streams_assign_bytes", "r3d_streams_assign", "r3d_streams_link_bytes",
+    "r3d_streams_link",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
@@ -44,7 +45,7 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
                 "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host",
-                "r3d_debug_streams_assign_host")
+                "r3d_debug_streams_assign_host", "r3d_debug_streams_link_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -124,6 +125,7 @@ R3D_STREAM_IDLE, R3D_STREAM_PUSH, R3D_STREAM_RESTART, R3D_STREAM_DRAIN = 0, 1, 2
 STREAMS_PEEK_MAX = 8                                                    # R3D_STREAMS_PEEK_MAX: looks per r3d_streams_peek call
 FUSE_MAX_MEMBERS = 16                                                   # R3D_FUSE_MAX_MEMBERS: slots per group of r3d_streams_fuse
 ASSIGN_MAX_SLOTS, ASSIGN_MAX_DETECTIONS = 32, 32                        # R3D_ASSIGN_MAX_SLOTS, R3D_ASSIGN_MAX_DETECTIONS
+LINK_MAX_PEOPLE = 32                                                    # R3D_LINK_MAX_PEOPLE: people per scene of r3d_streams_link
 R3D_ASSIGN_FILL_NAN, R3D_ASSIGN_FILL_HOLD = 0, 1                        # what an unmatched live slot of r3d_streams_assign pushes
 STREAM_HEAD_BYTES = 16                                                  # sizeof(r3d_stream_head)
 
@@ -259,10 +261,14 @@ def load():
     lib.r3d_streams_assign_bytes.restype = C.c_size_t
     lib.r3d_streams_assign_bytes.argtypes = [C.c_int32] * 4
     lib.r3d_streams_assign.argtypes = [vp] * 12
+    lib.r3d_streams_link_bytes.restype = C.c_size_t
+    lib.r3d_streams_link_bytes.argtypes = [C.c_int32] * 4
+    lib.r3d_streams_link.argtypes = [vp] * 11
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
         lib.r3d_debug_streams_assign_host.argtypes = [vp] * 11
+        lib.r3d_debug_streams_link_host.argtypes = [vp] * 10
         lib.r3d_debug_streams_fuse_host.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                                     C.c_double, vp, vp, vp, vp]
         lib.r3d_debug_streams_peek_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
@@ -784,6 +790,45 @@ def debug_streams_assign_host(state_ptr: Optional[int], prm: Optional[AssignPara
     return int(load().r3d_debug_streams_assign_host(state_ptr or None, C.byref(prm) if prm is not None else None, det_ptr or None,
                                                     det_conf_ptr or None, det_count_ptr or None, action_ptr or None, frame_out_ptr or None,
                                                     conf_out_ptr or None, match_ptr or None, id_ptr or None, stats_ptr or None))
+
+
+class LinkParams(C.Structure):
+    """r3d_link_params (include/ray3d_hip.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("num_scenes", C.c_int32), ("num_cameras", C.c_int32), ("slots", C.c_int32),
+                ("people", C.c_int32), ("max_members", C.c_int32), ("num_joints", C.c_int32), ("min_joints", C.c_int32),
+                ("min_common", C.c_int32), ("max_missed", C.c_int32), ("max_dist", C.c_double), ("break_dist", C.c_double)]
+
+
+def link_params(num_scenes: int, num_cameras: int, slots: int, people: int, max_members: int, num_joints: int, min_joints: int,
+                min_common: int, max_missed: int, max_dist: float, break_dist: float = 0.0) -> LinkParams:
+    """An r3d_link_params with its struct_size set."""
+    return LinkParams(C.sizeof(LinkParams), num_scenes, num_cameras, slots, people, max_members, num_joints, min_joints, min_common,
+                      max_missed, max_dist, break_dist)
+
+
+def streams_link_bytes(num_scenes: int, num_cameras: int, people: int, num_joints: int) -> int:
+    """r3d_streams_link_bytes: bytes of the state of r3d_streams_link (all zero = no people); 0 for shapes the call refuses."""
+    return int(load().r3d_streams_link_bytes(num_scenes, num_cameras, people, num_joints))
+
+
+def streams_link(state_ptr: int, prm: LinkParams, world_ptr: int, emit_ptr: int, status_ptr: int, id_ptr: int, member_ptr: int,
+                 person_ptr: int, group_ptr: Optional[int], stats_ptr: Optional[int], stream: int):
+    """r3d_streams_link (enqueued BEHIND :func:`streams_poses` and BEFORE :func:`streams_fuse` of the same tick): every pointer is
+    device memory but `prm` (:func:`link_params`); `world_ptr` (S, J, 3) float64, `emit_ptr` (S,) int64, `status_ptr` (S,) int32,
+    `id_ptr` (S,) int64 track identities; written: `member_ptr` (N * G, M) int32 - the member table of :func:`streams_fuse` -,
+    `person_ptr` (N * G,) int64, `group_ptr` (S,) int32 or None, `stats_ptr` (N, 4) int32 or None, S = N * C * P."""
+    check(load().r3d_streams_link(state_ptr, C.byref(prm), world_ptr, emit_ptr, status_ptr, id_ptr, member_ptr, person_ptr,
+                                  group_ptr or None, stats_ptr or None, stream), "r3d_streams_link")
+
+
+def debug_streams_link_host(state_ptr: Optional[int], prm: Optional[LinkParams], world_ptr: Optional[int], emit_ptr: Optional[int],
+                            status_ptr: Optional[int], id_ptr: Optional[int], member_ptr: Optional[int], person_ptr: Optional[int],
+                            group_ptr: Optional[int], stats_ptr: Optional[int]) -> int:
+    """r3d_debug_streams_link_host (hooks library only: use_hooks(True)): r3d_streams_link on HOST pointers; returns the status code
+    instead of raising (R3D_ERR_ARG is what the tests ask for)."""
+    return int(load().r3d_debug_streams_link_host(state_ptr or None, C.byref(prm) if prm is not None else None, world_ptr or None,
+                                                  emit_ptr or None, status_ptr or None, id_ptr or None, member_ptr or None,
+                                                  person_ptr or None, group_ptr or None, stats_ptr or None))
 
 
 def _census_rows(call):

@@ -6,6 +6,7 @@
 #include "r3d_streams.hpp"
 #include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
+#include "r3d_streams_link.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -620,6 +621,90 @@ int r3d::streams_assign_check_args(const char *what, void *state, const r3d_assi
     return R3D_OK;
 }
 
+// the shapes r3d_streams_link's state takes: what r3d_streams_link_bytes and the argument rules share
+static bool streams_link_shape_ok(int32_t N, int32_t C, int32_t G, int32_t J) {
+    return N >= 1 && C >= 1 && C <= R3D_FUSE_MAX_MEMBERS && G >= 1 && G <= R3D_LINK_MAX_PEOPLE && (long long)N * C <= R3D_CLIPS_MAX &&
+           (long long)N * G <= R3D_CLIPS_MAX && J >= 1 && J <= 17;
+}
+
+// the argument rules of r3d_streams_link, shared with its host hook; fills the kernel's argument set
+int r3d::streams_link_check_args(const char *what, void *state, const r3d_link_params *prm, const double *world, const int64_t *emit,
+                                 const int32_t *status, const int64_t *id, int32_t *member, int64_t *person, int32_t *group,
+                                 int32_t *stats, StreamsLinkArgs *args) {
+    if (!state || !prm || !world || !emit || !status || !id || !member || !person) {
+        set_error("%s: null pointer (link_dev, prm, world_dev, emit_dev, status_dev, id_dev, member_dev, person_dev)", what);
+        return R3D_ERR_ARG;
+    }
+    if (prm->struct_size != (int32_t)sizeof(r3d_link_params)) {
+        set_error("%s: prm->struct_size is %d, this library's r3d_link_params has %d bytes", what, prm->struct_size, (int)sizeof(r3d_link_params));
+        return R3D_ERR_ARG;
+    }
+    const int32_t N = prm->num_scenes, C = prm->num_cameras, P = prm->slots, G = prm->people, M = prm->max_members, J = prm->num_joints;
+    if (N < 1) { set_error("%s: num_scenes must be >= 1 (got %d)", what, N); return R3D_ERR_ARG; }
+    if (C < 1 || C > R3D_FUSE_MAX_MEMBERS) { set_error("%s: num_cameras must be in 1..%d (got %d)", what, R3D_FUSE_MAX_MEMBERS, C); return R3D_ERR_ARG; }
+    if (P < 1 || P > R3D_ASSIGN_MAX_SLOTS) { set_error("%s: slots must be in 1..%d (got %d)", what, R3D_ASSIGN_MAX_SLOTS, P); return R3D_ERR_ARG; }
+    if (G < 1 || G > R3D_LINK_MAX_PEOPLE) { set_error("%s: people must be in 1..%d (got %d)", what, R3D_LINK_MAX_PEOPLE, G); return R3D_ERR_ARG; }
+    if (J < 1 || J > 17) { set_error("%s: num_joints must be in 1..17 (got %d)", what, J); return R3D_ERR_ARG; }
+    if (M < C || M > R3D_FUSE_MAX_MEMBERS) { set_error("%s: max_members must be in num_cameras..%d (got %d)", what, R3D_FUSE_MAX_MEMBERS, M); return R3D_ERR_ARG; }
+    if ((long long)N * C * P > R3D_CLIPS_MAX || (long long)N * G > R3D_CLIPS_MAX) {
+        set_error("%s: num_scenes * num_cameras * slots and num_scenes * people must be <= %d (got %d * %d * %d, %d * %d)", what, R3D_CLIPS_MAX, N, C, P, N, G);
+        return R3D_ERR_ARG;
+    }
+    if (prm->min_joints < 1 || prm->min_joints > J || prm->min_common < 1 || prm->min_common > J) {
+        set_error("%s: min_joints and min_common must be in 1..num_joints = %d (got %d, %d)", what, J, prm->min_joints, prm->min_common);
+        return R3D_ERR_ARG;
+    }
+    if (prm->max_missed < 0) { set_error("%s: max_missed must be >= 0 (got %d)", what, prm->max_missed); return R3D_ERR_ARG; }
+    if (!stream_finite_bits64(prm->max_dist) || !(prm->max_dist > 0.0)) { set_error("%s: max_dist must be finite and > 0", what); return R3D_ERR_ARG; }
+    if (prm->break_dist != prm->break_dist || (prm->break_dist > 0.0 && (!stream_finite_bits64(prm->break_dist) || prm->break_dist < prm->max_dist))) {
+        set_error("%s: break_dist must be <= 0 (off) or finite and >= max_dist", what);
+        return R3D_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(state) % 8 || reinterpret_cast<uintptr_t>(world) % 8 || reinterpret_cast<uintptr_t>(emit) % 8 ||
+        reinterpret_cast<uintptr_t>(id) % 8 || reinterpret_cast<uintptr_t>(person) % 8) {
+        set_error("%s: link_dev, world_dev, emit_dev, id_dev and person_dev must be 8-byte aligned", what);
+        return R3D_ERR_ARG;
+    }
+    // an output extent may not overlap an input extent, the state or another output (address ranges; the sizes fit in 64 bits)
+    const uintptr_t S = (uintptr_t)N * C * P, NG = (uintptr_t)N * G;
+    const char *name[9] = {"member_dev", "person_dev", "group_dev", "stats_dev", "world_dev", "emit_dev", "status_dev", "id_dev", "link_dev"};
+    const uintptr_t ptr[9] = {reinterpret_cast<uintptr_t>(member), reinterpret_cast<uintptr_t>(person), reinterpret_cast<uintptr_t>(group),
+                              reinterpret_cast<uintptr_t>(stats), reinterpret_cast<uintptr_t>(world), reinterpret_cast<uintptr_t>(emit),
+                              reinterpret_cast<uintptr_t>(status), reinterpret_cast<uintptr_t>(id), reinterpret_cast<uintptr_t>(state)};
+    const uintptr_t bytes[9] = {NG * M * sizeof(int32_t), NG * sizeof(int64_t), S * sizeof(int32_t), (uintptr_t)N * 4 * sizeof(int32_t),
+                                S * J * 3 * sizeof(double), S * sizeof(int64_t), S * sizeof(int32_t), S * sizeof(int64_t),
+                                (uintptr_t)streams_link_bytes(N, C, G, J)};
+    for (int o = 0; o < 4; ++o)              // (the outputs come first)
+        for (int i = o + 1; i < 9; ++i)
+            if (ptr[o] && ptr[i] && ptr[o] < ptr[i] + bytes[i] && ptr[i] < ptr[o] + bytes[o]) {
+                set_error("%s: %s overlaps %s: the call does not work in place", what, name[o], name[i]);
+                return R3D_ERR_ARG;
+            }
+    StreamsLinkArgs a = {};
+    a.state = state;
+    a.world = world;
+    a.emit = reinterpret_cast<const long long *>(emit);
+    a.status = status;
+    a.id = reinterpret_cast<const long long *>(id);
+    a.member = member;
+    a.person = reinterpret_cast<long long *>(person);
+    a.group = group;
+    a.stats = stats;
+    a.max_dist = prm->max_dist;
+    a.break_dist = prm->break_dist;
+    a.N = N;
+    a.C = C;
+    a.P = P;
+    a.G = G;
+    a.M = M;
+    a.J = J;
+    a.min_joints = prm->min_joints;
+    a.min_common = prm->min_common;
+    a.max_missed = prm->max_missed;
+    *args = a;
+    return R3D_OK;
+}
+
 extern "C" {
 
 int r3d_create(const r3d_config *cfg, r3d_model **out) {
@@ -1039,6 +1124,26 @@ int r3d_streams_assign(void *assign_dev, const r3d_assign_params *prm, const flo
     const hipError_t err = r3d::launch_streams_assign(a, (hipStream_t)stream);
     if (err != hipSuccess) {
         set_error("r3d_streams_assign: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+size_t r3d_streams_link_bytes(int32_t num_scenes, int32_t num_cameras, int32_t people, int32_t num_joints) {
+    if (!streams_link_shape_ok(num_scenes, num_cameras, people, num_joints)) return 0;
+    return r3d::streams_link_bytes(num_scenes, num_cameras, people, num_joints);
+}
+
+int r3d_streams_link(void *link_dev, const r3d_link_params *prm, const double *world_dev, const int64_t *emit_dev, const int32_t *status_dev,
+                     const int64_t *id_dev, int32_t *member_dev, int64_t *person_dev, int32_t *group_dev, int32_t *stats_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::StreamsLinkArgs a;
+    const int rc = streams_link_check_args("r3d_streams_link", link_dev, prm, world_dev, emit_dev, status_dev, id_dev, member_dev, person_dev,
+                                           group_dev, stats_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_streams_link(a, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_streams_link: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

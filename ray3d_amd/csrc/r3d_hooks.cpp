@@ -13,6 +13,7 @@
 #include "r3d_streams.hpp"
 #include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
+#include "r3d_streams_link.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -922,6 +923,114 @@ int r3d_debug_streams_assign_host(void *assign, const r3d_assign_params *prm, co
         const long long next = st.next_id[c];
         for (int p = 0; p < a.P; ++p) stream_assign_slot(a, st, c, p, matched[p], free_mask, unmatched, next);
         stream_assign_finish(a, st, c, valid, cols, free_mask, unmatched, next);
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_streams_link on the host - its argument rules (streams_link_check_args) and the routines of r3d_streams_link.hpp
+// the kernel runs: per scene and camera the links' tests in ascending g (a stream a smaller g holds is dropped), the slots'
+// summaries, the G x P cost keys, the greedy matching as plain loops over the same keys in the kernel's order
+// (stream_assign_better), the births by the ranks the kernel forms with ballots, then the people in order and the scene's finish.
+int r3d_debug_streams_link_host(void *link, const r3d_link_params *prm, const double *world, const int64_t *emit, const int32_t *status,
+                                const int64_t *id, int32_t *member, int64_t *person, int32_t *group, int32_t *stats) {
+    StreamsLinkArgs a;
+    const int rc = streams_link_check_args("r3d_debug_streams_link_host", link, prm, world, emit, status, id, member, person, group, stats, &a);
+    if (rc != R3D_OK) return rc;
+    const StreamLinkState st = stream_link_state(a);
+    unsigned long long key[R3D_LINK_MAX_PEOPLE * R3D_ASSIGN_MAX_SLOTS];            // [g * P + p]
+    for (int n = 0; n < a.N; ++n) {
+        bool entry[R3D_LINK_MAX_PEOPLE], alive[R3D_LINK_MAX_PEOPLE];
+        for (int g = 0; g < a.G; ++g) {
+            entry[g] = alive[g] = st.phase[n * a.G + g] == 1;
+        }
+        long long next = st.next_id[n];
+        int links = 0, births = 0, dropped = 0;
+        for (int c = 0; c < a.C; ++c) {
+            int p1[R3D_LINK_MAX_PEOPLE];
+            bool made[R3D_LINK_MAX_PEOPLE];
+            uint32_t held = 0, cand = 0, elig = 0, free_mask = 0, pres[R3D_ASSIGN_MAX_SLOTS];
+            for (int g = 0; g < a.G; ++g) {
+                made[g] = false;
+                p1[g] = entry[g] ? stream_link_validate(a, st, n, (uint32_t)(n * a.G + g), c) : 0;
+                if (p1[g] == 0) continue;
+                if ((held >> (p1[g] - 1)) & 1u) p1[g] = 0;          // a smaller g holds the stream
+                else held |= 1u << (p1[g] - 1);
+            }
+            for (int p = 0; p < a.P; ++p)
+                if (stream_link_candidate(a, n, c, p, held, &pres[p])) cand |= 1u << p;
+            for (int g = 0; g < a.G; ++g)
+                if (alive[g] && p1[g] == 0 && stream_link_seen(st.seen[n * a.G + g], a.J) != 0u) elig |= 1u << g;
+            uint32_t rows = 0, cols = 0;
+            if (cand && elig) {
+                for (int g = 0; g < a.G; ++g)
+                    for (int p = 0; p < a.P; ++p)
+                        key[g * a.P + p] = ((cand >> p) & (elig >> g) & 1u) ? stream_link_pair(a, st, n, g, c, p, pres[p]) : STREAM_ASSIGN_NONE;
+                for (;;) {
+                    unsigned long long best = STREAM_ASSIGN_NONE;
+                    int at = a.G * a.P;
+                    for (int i = 0; i < a.G * a.P; ++i) {
+                        const int g = i / a.P, p = i - g * a.P;
+                        if (((rows >> g) | (cols >> p)) & 1u) continue;
+                        if (stream_assign_better(key[i], i, best, at)) {
+                            best = key[i];
+                            at = i;
+                        }
+                    }
+                    if (best == STREAM_ASSIGN_NONE) break;
+                    const int g = at / a.P, p = at - g * a.P;
+                    rows |= 1u << g;
+                    cols |= 1u << p;
+                    p1[g] = p + 1;
+                    made[g] = true;
+                }
+            }
+            const uint32_t unmatched = cand & ~cols;
+            for (int g = 0; g < a.G; ++g)
+                if (!alive[g]) free_mask |= 1u << g;
+            const int want = __builtin_popcount(unmatched), room = __builtin_popcount(free_mask);
+            const int born = want < room ? want : room;
+            for (int g = 0; g < a.G; ++g) {
+                if (!((free_mask >> g) & 1u)) continue;
+                const int rank = __builtin_popcount(free_mask & ((1u << g) - 1u));
+                if (rank >= want) continue;
+                const int p = stream_assign_nth_bit(unmatched, rank);
+                stream_link_birth(a, st, (uint32_t)(n * a.G + g), stream_link_stream(a, n, c, p),
+                                            (long long)((unsigned long long)next + (unsigned long long)rank));
+                alive[g] = true;
+                p1[g] = p + 1;
+                made[g] = true;
+            }
+            next = (long long)((unsigned long long)next + (unsigned long long)born);
+            links += __builtin_popcount(cols);
+            births += born;
+            dropped += want - born;
+            for (int g = 0; g < a.G; ++g) stream_link_store(a, st, n, (uint32_t)(n * a.G + g), c, p1[g], made[g]);
+            if (a.group)
+                for (int p = 0; p < a.P; ++p) {
+                    int32_t who = -1;
+                    for (int g = a.G - 1; g >= 0; --g)
+                        if (p1[g] == p + 1) who = n * a.G + g;
+                    a.group[stream_link_stream(a, n, c, p)] = who;
+                }
+        }
+        int lives = 0;
+        for (int g = 0; g < a.G; ++g) {
+            const uint32_t gi = (uint32_t)(n * a.G + g);
+            int32_t tbl[R3D_FUSE_MAX_MEMBERS];
+            uint32_t add = 0;
+            const bool linked = alive[g] && stream_link_members(a, st, n, gi, tbl);
+            if (alive[g])
+                for (int j = 0; j < a.J; ++j)
+                    if (stream_link_joint(a, st, gi, j, tbl)) add |= 1u << j;
+            lives += stream_link_person(a, st, gi, alive[g], linked, add) ? 1 : 0;
+        }
+        st.next_id[n] = next;
+        if (a.stats) {
+            a.stats[4 * n] = lives;
+            a.stats[4 * n + 1] = links;
+            a.stats[4 * n + 2] = births;
+            a.stats[4 * n + 3] = dropped;
+        }
     }
     return R3D_OK;
 }

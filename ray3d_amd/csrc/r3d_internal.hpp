@@ -622,6 +622,12 @@ int streams_assign_check_args(const char *what, void *state, const r3d_assign_pa
                               const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match, int64_t *id,
                               int32_t *stats, StreamsAssignArgs *args);
 
+struct StreamsLinkArgs;     // r3d_streams_link.hpp
+// the argument rules of r3d_streams_link, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int streams_link_check_args(const char *what, void *state, const r3d_link_params *prm, const double *world, const int64_t *emit,
+                            const int32_t *status, const int64_t *id, int32_t *member, int64_t *person, int32_t *group, int32_t *stats,
+                            StreamsLinkArgs *args);
+
 #ifdef R3D_TIMING      // r3d_timing.cpp
 void timing_arm_forward(const Schedule::Fwd &fw, FwdArgs &fa, hipStream_t stream);
 void timing_report_forward(const Plan *pl, const Schedule::Fwd &fw, const FwdArgs &fa, int64_t B, hipStream_t stream);
@@ -732,6 +738,7 @@ hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stre
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_fuse
 hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_assign
+hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_link
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

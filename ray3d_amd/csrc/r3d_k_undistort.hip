@@ -108,6 +108,21 @@
 // every output through stream_assign_slot - the routine the host hook runs.  The keys share the LDS block of r3d_streams_fuse's
 // staging area (one raw block, handed to both bodies): the kernel's static LDS does not grow.  The state is read before the
 // barrier in front of the matching and written after it, each slot's words by its own lane.  Plain vector stores from C++, no atomics.
+//
+// r3d_streams_link (one person across cameras: per scene the association of the cameras' tracks with a table of people by the
+// distance of their world poses, births and ends of people, and the member table r3d_streams_fuse reads, include/ray3d_hip.h) is
+// the thirteenth argument set, StreamsLinkArgs, enqueued between r3d_streams_poses and r3d_streams_fuse of the same tick: one
+// workgroup of one wavefront per scene.  Lane g owns person g: its state words, its links and its row of the member table.  The
+// cameras are visited in order, one uniform loop: lane g tests its link (stream_link_validate), P ballots find the held slots and
+// drop a link a smaller g holds; lane p summarises slot p (its present mask goes to LDS, the candidate bits are a ballot); the
+// G x P pairs are dealt over the lanes - lane (p, half) owns column p's pairs with the people of its parity -, their cost keys
+// go to LDS at [g * P + p]; the greedy matching is r3d_streams_assign's: a lane-local scan of the untaken pairs and a six-step xor
+// butterfly over (key, pair index); the free people are a ballot, and a free person's popcount rank picks its candidate.  A person
+// born in camera c writes its reference pose to the state; the barrier that ends the camera's turn makes it visible to the lanes
+// that form camera c + 1's keys.  Step C: lane g lists person g's finished members in LDS, lane (j, half) forms joint j of the
+// people of its parity (stream_link_joint; the ballot is the person's new seen bits), then lane g finishes person g
+// (stream_link_person).  Keys and masks live inside the LDS block of r3d_streams_fuse's staging area: the kernel's static LDS
+// does not grow.  Plain vector stores from C++, no atomics.
 #include "r3d_internal.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
@@ -115,6 +130,7 @@
 #include "r3d_streams.hpp"
 #include "r3d_streams_assign.hpp"
 #include "r3d_streams_fuse.hpp"
+#include "r3d_streams_link.hpp"
 #include "r3d_streams_peek.hpp"
 #include "r3d_streams_poses.hpp"
 #include "r3d_streams_repair.hpp"
@@ -407,22 +423,156 @@ __device__ __forceinline__ void streams_assign_body(const StreamsAssignArgs &a, 
     if (lane == 0) stream_assign_finish(a, st, c, valid, cols, free_mask, unmatched, next);
 }
 
-// The block of LDS the fuse mode's staging area and the assign mode's keys share
+// Scene blockIdx.x < N; the workgroup is ONE wavefront (launch_streams_link) and no lane leaves before the last ballot: the camera
+// loop, every other loop bound and every branch around a barrier, a shuffle or a ballot is the same for all 64 lanes.  Lanes G .. 63
+// own no person and lanes P .. 63 no slot: they take part in the ballots with `false`.  `lds`: STREAMS_LINK_LDS_BYTES.
+__device__ __forceinline__ void streams_link_body(const StreamsLinkArgs &a, unsigned char *lds) {
+    unsigned long long *key = reinterpret_cast<unsigned long long *>(lds + STREAMS_LINK_LDS_KEYS);         // [g * P + p], g < G, p < P
+    uint32_t *pres = reinterpret_cast<uint32_t *>(lds + STREAMS_LINK_LDS_PRES);                            // [p], p < P <= 32
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const StreamLinkState st = stream_link_state(a);
+    const bool mine = lane < a.G;                                   // lane g < G owns person g
+    const uint32_t gi = (uint32_t)(n * a.G + (mine ? lane : 0));    // (gi < N * G <= R3D_CLIPS_MAX in every lane)
+    const uint32_t below = (1u << (lane & 31)) - 1u;                // the people / slots in front of this lane's
+    const bool entry = mine && st.phase[gi] == 1;                   // live at entry
+    bool alive = entry;                                             // ... or born in this call
+    long long next = st.next_id[n];                                 // (lane 0 replaces it after the last camera)
+    int links = 0, births = 0, dropped = 0;
+    const int pl = lane & 31, half = lane >> 5, pairs = a.G * a.P;
+    const int rounds = a.G < a.P ? a.G : a.P;
+    for (int c = 0; c < a.C; ++c) {
+        // step A: lane g tests its link; of several people on one stream the smallest g keeps it
+        int p1 = entry ? stream_link_validate(a, st, n, gi, c) : 0;
+        uint32_t held = 0;
+        for (int p = 0; p < a.P; ++p) {
+            const uint32_t m = (uint32_t)__ballot(p1 == p + 1);     // (bit g: lane g < G <= 32)
+            if (m) held |= 1u << p;
+            if (p1 == p + 1 && (m & below)) p1 = 0;
+        }
+        // step B: lane p < P summarises slot p
+        uint32_t present = 0;
+        const bool candidate = lane < a.P && stream_link_candidate(a, n, c, lane, held, &present);
+        if (lane < a.P) pres[lane] = present;
+        const uint32_t cand = (uint32_t)__ballot(candidate);        // (bit p: lane p < P <= 32)
+        // (a person's seen word in memory is current: nobody writes it before step C but its own birth, by this lane)
+        const uint32_t elig = (uint32_t)__ballot(alive && p1 == 0 && stream_link_seen(st.seen[gi], a.J) != 0u);
+        uint32_t rows = 0, cols = 0;
+        bool made = false;
+        if (cand && elig) {                                         // uniform
+            __syncthreads();
+            // lane (p, half) = (lane % 32, lane / 32) owns the pairs (g, p) with g = half, half + 2, ... < G of its column p < P
+            if (pl < a.P)
+                for (int g = half; g < a.G; g += 2)
+                    key[g * a.P + pl] = ((cand >> pl) & (elig >> g) & 1u) ? stream_link_pair(a, st, n, g, c, pl, pres[pl]) : STREAM_ASSIGN_NONE;
+            __syncthreads();
+            // the greedy matching; `rows`, `cols` and the winner are the same in every lane
+            for (int r = 0; r < rounds; ++r) {
+                unsigned long long best = STREAM_ASSIGN_NONE;
+                int at = pairs;
+                if (pl < a.P && !((cols >> pl) & 1u))
+                    for (int g = half; g < a.G; g += 2) {
+                        if ((rows >> g) & 1u) continue;
+                        const int i = g * a.P + pl;
+                        const unsigned long long k = key[i];
+                        if (stream_assign_better(k, i, best, at)) {
+                            best = k;
+                            at = i;
+                        }
+                    }
+                for (int off = STREAMS_LINK_THREADS / 2; off > 0; off >>= 1) {
+                    const unsigned long long k = __shfl_xor(best, off);
+                    const int i = __shfl_xor(at, off);
+                    if (stream_assign_better(k, i, best, at)) {
+                        best = k;
+                        at = i;
+                    }
+                }
+                if (best == STREAM_ASSIGN_NONE) break;              // uniform: no admissible pair is left
+                const int wg = at / a.P, wp = at - wg * a.P;        // (at < pairs: an admissible key came from a real pair)
+                rows |= 1u << wg;
+                cols |= 1u << wp;
+                if (lane == wg) {
+                    p1 = wp + 1;
+                    made = true;
+                }
+            }
+        }
+        // births: the rank-th unmatched candidate takes the rank-th free person
+        const uint32_t unmatched = cand & ~cols;
+        const uint32_t free_mask = (uint32_t)__ballot(mine && !alive);
+        const int want = __builtin_popcount(unmatched), room = __builtin_popcount(free_mask);
+        const int born = want < room ? want : room;
+        if (mine && !alive) {
+            const int rank = __builtin_popcount(free_mask & below);
+            if (rank < want) {
+                const int p = stream_assign_nth_bit(unmatched, rank);      // (a bit of cand: p < P)
+                stream_link_birth(a, st, gi, stream_link_stream(a, n, c, p), (long long)((unsigned long long)next + (unsigned long long)rank));
+                alive = true;
+                p1 = p + 1;
+                made = true;
+            }
+        }
+        next = (long long)((unsigned long long)next + (unsigned long long)born);
+        links += __builtin_popcount(cols);
+        births += born;
+        dropped += want - born;
+        if (mine) stream_link_store(a, st, n, gi, c, p1, made);
+        if (a.group)                                                // uniform
+            for (int p = 0; p < a.P; ++p) {
+                const uint32_t m = (uint32_t)__ballot(p1 == p + 1);     // (at most one bit)
+                if (lane == p) a.group[stream_link_stream(a, n, c, p)] = m ? n * a.G + __builtin_ctz(m) : -1;
+            }
+        __syncthreads();        // a born person's words are in memory before camera c + 1's keys are formed; the LDS is free again
+    }
+    // step C: lane g lists person g's finished members in LDS (the keys' block is free now); then lane (j, half) forms joint j of the
+    // people of its parity - consecutive lanes read consecutive points -, the ballot of "got a point" is the person's new seen bits;
+    // then lane g finishes person g
+    int32_t *tbl = reinterpret_cast<int32_t *>(lds + STREAMS_LINK_LDS_KEYS);           // [g * C + c], g < G, c < C <= 16
+    const bool linked = alive && stream_link_members(a, st, n, gi, tbl + lane * a.C);  // (alive: lane < G)
+    const uint32_t alive_mask = (uint32_t)__ballot(alive);
+    __syncthreads();
+    for (int g0 = 0; g0 < a.G; g0 += 2) {                               // uniform: both halves make every turn
+        const int g = g0 + half;
+        const bool got = g < a.G && pl < a.J && ((alive_mask >> g) & 1u) && stream_link_joint(a, st, (uint32_t)(n * a.G + g), pl, tbl + g * a.C);
+        const unsigned long long m = __ballot(got);
+        if (pl == 0 && g < a.G) pres[g] = (uint32_t)(half ? m >> 32 : m);           // (bit j: lane j of the half; pres is free as well)
+    }
+    __syncthreads();
+    const bool live = mine && stream_link_person(a, st, gi, alive, linked, pres[lane & 31]);
+    const uint32_t lives = (uint32_t)__ballot(live);
+    if (lane == 0) {
+        st.next_id[n] = next;
+        if (a.stats) {
+            a.stats[4 * n] = __builtin_popcount(lives);
+            a.stats[4 * n + 1] = links;
+            a.stats[4 * n + 2] = births;
+            a.stats[4 * n + 3] = dropped;
+        }
+    }
+}
+
+// The block of LDS the fuse mode's staging area, the assign mode's keys and the link mode's keys share
 constexpr int STREAMS_SHARED_LDS_BYTES = (int)sizeof(double) * STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS;
 static_assert(STREAMS_ASSIGN_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_streams_assign lives inside the staging area of r3d_streams_fuse");
+static_assert(STREAMS_LINK_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_streams_link lives inside the staging area of r3d_streams_fuse");
 
-// The twelve argument sets travel in one kernel-argument segment (4 KiB on this target)
+// The thirteen argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
                       sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) +
-                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + sizeof(StreamsAssignArgs) + 12 * 8 <= 4096,
+                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + sizeof(StreamsAssignArgs) + sizeof(StreamsLinkArgs) + 13 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
                                                                          const ClipsProjectArgs g, const PackArgs k, const WindowsArgs wn,
                                                                          const StreamsArgs sm, const StreamsPosesArgs sp,
                                                                          const StreamsRepairArgs sr, const StreamsPeekArgs pk,
-                                                                         const StreamsFuseArgs fz, const StreamsAssignArgs as) {
-    __shared__ __attribute__((aligned(16))) unsigned char shared_lds[STREAMS_SHARED_LDS_BYTES];    // one block: the two modes below
+                                                                         const StreamsFuseArgs fz, const StreamsAssignArgs as,
+                                                                         const StreamsLinkArgs lk) {
+    __shared__ __attribute__((aligned(16))) unsigned char shared_lds[STREAMS_SHARED_LDS_BYTES];    // one block: the three modes below
+    if (lk.state) {                          // uniform: r3d_streams_link - scene blockIdx.x
+        streams_link_body(lk, shared_lds);
+        return;
+    }
     if (as.state) {                          // uniform: r3d_streams_assign - camera blockIdx.x
         streams_assign_body(as, shared_lds);
         return;
@@ -513,28 +663,28 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
@@ -542,14 +692,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
@@ -557,47 +707,54 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
     static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_peek: (ceil(RF * J / 256), S, K) workgroups, one launch, nothing else
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{}, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_assign: C workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream) {
     static_assert(STREAMS_ASSIGN_THREADS == 64, "one wavefront holds a camera's detections and slots: its ballots are their masks");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.C), dim3(STREAMS_ASSIGN_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.C), dim3(STREAMS_ASSIGN_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, args, StreamsLinkArgs{});
+    return hipGetLastError();
+}
+
+// r3d_streams_link: N workgroups of one wavefront, one launch, nothing else
+hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream) {
+    static_assert(STREAMS_LINK_THREADS == 64, "one wavefront holds a scene's people and a camera's slots: its ballots are their masks");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.N), dim3(STREAMS_LINK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, args);
     return hipGetLastError();
 }
 
 // r3d_streams_fuse: G workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream) {
     static_assert(STREAMS_FUSE_THREADS == 64 && STREAMS_FUSE_THREADS >= STREAMS_FUSE_JOINTS, "one wavefront holds a group's joints: its ballots are the used words");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args, StreamsAssignArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args, StreamsAssignArgs{}, StreamsLinkArgs{});
     return hipGetLastError();
 }
 

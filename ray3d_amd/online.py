@@ -64,9 +64,20 @@ class OnlineLifter:
     min(3, J)), keeps a track alive through `assign_max_missed` unmatched ticks and then ends it (the slot drains and is free
     again), and writes the tick's actions, frame rows and confidences on the device.  `assign_fill`: what an unmatched live slot
     pushes - "nan" (needs `repair`, which then holds or interpolates the joints) or "hold" (the per-joint last observation).
-    Identities are per camera; grouping the cameras' tracks into people stays the caller's job through :meth:`set_groups`, and
-    extras["track_id"] is what they need to drive it.  :meth:`set_cameras` is unchanged: a camera's row is repeated over its P
-    slots.  Without `cameras` nothing of the class changes.
+    Identities are per camera: (camera, extras["track_id"]) names a track.  Which camera's track is which person is decided on the
+    device with `people=` (below); without it a caller maps the tracks to people and drives :meth:`set_groups`.
+    :meth:`set_cameras` is unchanged: a camera's row is repeated over its P slots.  Without `cameras` nothing of the class changes.
+    `people` (an int G in 1..32; None: off; needs `cameras` and `world`, excludes `groups`): the cameras are `scenes` rooms of
+    `cameras` / `scenes` <= 16 cameras each that see the same people, and every :meth:`track` tick also enqueues ONE
+    r3d_streams_link call between r3d_streams_poses and r3d_streams_fuse: it keeps G people per scene in device memory, links each
+    camera's finished tracks to the person whose reference pose is nearest (the mean joint distance of the world poses, at most
+    `link_max_dist` metres, over at least `link_min_common` common joints, default min(3, J)), starts a person for a track nobody
+    claims (at least `link_min_joints` finite joints, default min(4, J)), unlinks a track whose identity changed or ended - with
+    `link_break_dist` (metres, > 0, >= `link_max_dist`) also one that moved that far from its person -, frees a person that had
+    no link for more than `link_max_missed` ticks, and writes the member table the fuse call of the same tick reads: the fuse
+    buffers have `scenes` * G rows, person n * G + g in row n * G + g, and :meth:`set_groups` raises.  Nothing comes back to the
+    host in between, so :meth:`capture` records the whole tick from detections to one fused skeleton per person.  Such a lifter
+    takes :meth:`track` only: :meth:`step` and :meth:`lift_clips` refuse it.  Without `people` nothing of the class changes.
     The lifter is prepared for batches of `num_streams` windows (and of K * `num_streams` with previews) here, once."""
 
     def __init__(self, lifter, num_streams: int, encoding: Optional[str] = None, flip: bool = False,
@@ -76,7 +87,9 @@ class OnlineLifter:
                  groups: Optional[Sequence[Sequence[int]]] = None, fuse_soft_px: float = 2.0, fuse_max_px: float = 0.0,
                  fuse_max_dist: float = 0.0, cameras: Optional[int] = None, max_detections: Optional[int] = None,
                  assign_max_cost: float = 0.5, assign_max_missed: int = 5, assign_min_joints: Optional[int] = None,
-                 assign_min_common: Optional[int] = None, assign_fill: str = "nan"):
+                 assign_min_common: Optional[int] = None, assign_fill: str = "nan", people: Optional[int] = None, scenes: int = 1,
+                 link_max_dist: float = 0.5, link_break_dist: float = 0.0, link_max_missed: int = 25,
+                 link_min_joints: Optional[int] = None, link_min_common: Optional[int] = None):
         pos = lifter.pos
         if lifter.num_lanes():
             raise ValueError("OnlineLifter: a lifter with lanes is not supported (set_lanes(0) first)")
@@ -98,11 +111,19 @@ class OnlineLifter:
             raise ValueError("OnlineLifter: quality=True is defined for 3-feature (ray) inputs only; this pair takes %d" % self.F)
         self.looks = self._check_looks(previews, self.lag) if previews is not None else None
         self.G, table = 0, None
+        if people is not None:          # the member table is r3d_streams_link's output: scenes * people rows, empty until the first tick
+            if groups is not None:
+                raise ValueError("OnlineLifter: people= writes the member table itself; it excludes groups=")
+            if cameras is None or not self.world:
+                raise ValueError("OnlineLifter: people= needs cameras= (the tracks it links) and world=True (the poses it compares)")
+            self.G = self._link_shape(people, scenes, cameras)
+            table = np.full((self.G, _capi.FUSE_MAX_MEMBERS), -1, np.int32)
         if groups is not None:
             if not self.world:
                 raise ValueError("OnlineLifter: groups need world=True (the streams' world poses are what is fused)")
             table = self._member_table(groups, None, self.S)
             self.G = table.shape[0]
+        if self.G:
             self.fuse_soft_px, self.fuse_max_px, self.fuse_max_dist = float(fuse_soft_px), float(fuse_max_px), float(fuse_max_dist)
             if not np.isfinite(self.fuse_soft_px) or self.fuse_soft_px <= 0:
                 raise ValueError("OnlineLifter: fuse_soft_px must be finite and > 0 (got %r)" % (fuse_soft_px,))
@@ -158,6 +179,9 @@ class OnlineLifter:
                                               assign_min_common, assign_fill)
         elif max_detections is not None:
             raise ValueError("OnlineLifter: max_detections needs cameras=")
+        self._link = None
+        if people is not None:          # r3d_streams_link: its state and what the call writes beside the member table
+            self._link = self._link_setup(people, scenes, link_max_dist, link_break_dist, link_max_missed, link_min_joints, link_min_common)
         self._pfinish = self._pv = None
         if self.looks:                  # r3d_streams_peek: K * S preview windows, their words, and the K-fold copies of the streams' rows
             K = len(self.looks)
@@ -222,6 +246,47 @@ class OnlineLifter:
                     match=torch.full((S,), -1, dtype=torch.int32, device=dev),
                     assign_stats=torch.zeros((C, 4), dtype=torch.int32, device=dev))
 
+    def _link_shape(self, people, scenes, cameras) -> int:
+        """`people=`, `scenes=` and the cameras checked -> the number of people, scenes * people."""
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not integer(people) or not 1 <= people <= _capi.LINK_MAX_PEOPLE:
+            raise ValueError("OnlineLifter: people must be an int in 1..%d (got %r)" % (_capi.LINK_MAX_PEOPLE, people))
+        if not integer(scenes) or scenes < 1 or not integer(cameras) or cameras < 1 or cameras % int(scenes) \
+                or cameras // int(scenes) > _capi.FUSE_MAX_MEMBERS:
+            raise ValueError("OnlineLifter: cameras must be scenes * C with C in 1..%d cameras per scene (got cameras=%r, scenes=%r)"
+                             % (_capi.FUSE_MAX_MEMBERS, cameras, scenes))
+        if int(scenes) * int(people) > _capi.CLIPS_MAX:
+            raise ValueError("OnlineLifter: scenes * people must be in 1..%d (got %d)" % (_capi.CLIPS_MAX, int(scenes) * int(people)))
+        return int(scenes) * int(people)
+
+    def _link_setup(self, people, scenes, max_dist, break_dist, max_missed, min_joints, min_common):
+        """The arguments of `people=` checked -> dict of r3d_streams_link's parameter block and buffers."""
+        S, J, dev, z = self.S, self.J, self.device, self._assign
+        N, G = int(scenes), int(people)
+
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        min_joints = min(4, J) if min_joints is None else min_joints
+        min_common = min(3, J) if min_common is None else min_common
+        if not integer(min_joints) or not integer(min_common) or not 1 <= min_joints <= J or not 1 <= min_common <= J:
+            raise ValueError("OnlineLifter: link_min_joints and link_min_common must be in 1..%d (got %r, %r)" % (J, min_joints, min_common))
+        if not integer(max_missed) or max_missed < 0:
+            raise ValueError("OnlineLifter: link_max_missed must be an int >= 0 (got %r)" % (max_missed,))
+        max_dist, break_dist = float(max_dist), float(break_dist)
+        if not np.isfinite(max_dist) or max_dist <= 0:
+            raise ValueError("OnlineLifter: link_max_dist must be finite and > 0 (got %r)" % (max_dist,))
+        if np.isnan(break_dist) or (break_dist > 0 and (not np.isfinite(break_dist) or break_dist < max_dist)):
+            raise ValueError("OnlineLifter: link_break_dist must be <= 0 (off) or finite and >= link_max_dist (got %r)" % (break_dist,))
+        C = z["C"] // N
+        prm = _capi.link_params(N, C, S // z["C"], G, _capi.FUSE_MAX_MEMBERS, J, int(min_joints), int(min_common), int(max_missed),
+                                max_dist, break_dist)
+        return dict(prm=prm, N=N, G=G,
+                    state=torch.zeros(_capi.streams_link_bytes(N, C, G, J), dtype=torch.uint8, device=dev),      # all zero: no people
+                    person_id=torch.full((N * G,), -1, dtype=torch.int64, device=dev),
+                    stream_person=torch.full((S,), -1, dtype=torch.int32, device=dev),
+                    link_stats=torch.zeros((N, 4), dtype=torch.int32, device=dev))
+
     @staticmethod
     def _check_looks(previews, lag: int):
         if lag == 0:
@@ -267,6 +332,8 @@ class OnlineLifter:
         """Who watches whom has changed: rewrites the member table on the device - the buffer the ticks read, also the captured
         one - so that the NEXT tick fuses the new groups.  The number of groups stays what the lifter was built with; a group may
         be empty."""
+        if self._link is not None:
+            raise ValueError("set_groups: a lifter built with people= writes its member table on the device (r3d_streams_link)")
         if not self.G:
             raise ValueError("set_groups: needs an OnlineLifter built with groups=")
         self.member.copy_(torch.from_numpy(self._member_table(groups, self.G, self.S)))
@@ -393,6 +460,11 @@ class OnlineLifter:
                                 self.emit.data_ptr(), self.status.data_ptr(), self.transforms.data_ptr(), ptr(self.cam), self.x.data_ptr(),
                                 self.rf, self.lag, ptr(f["pred"]), ptr(f["world"]), ptr(f["reproj"]), ptr(f["quality"]),
                                 torch.cuda.current_stream(dev).cuda_stream, in_features=self.F)
+            if self._link is not None:      # the member table of this tick: the cameras' tracks linked to people
+                k, t = self._link, self._assign
+                _capi.streams_link(k["state"].data_ptr(), k["prm"], ptr(f["world"]), self.emit.data_ptr(), self.status.data_ptr(),
+                                   t["track_id"].data_ptr(), self.member.data_ptr(), k["person_id"].data_ptr(),
+                                   k["stream_person"].data_ptr(), k["link_stats"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             if self._fuse is not None:      # one more launch: the groups' skeletons from what the call above just wrote
                 z = self._fuse
                 _capi.streams_fuse(ptr(f["world"]), ptr(f["reproj"]), self.emit.data_ptr(), self.status.data_ptr(),
@@ -411,6 +483,8 @@ class OnlineLifter:
             out.update({k: v.clone() for k, v in self._fuse.items()})
         if self._tracking:
             out.update({k: self._assign[k].clone() for k in ("track_id", "match", "assign_stats")})
+        if self._link is not None:
+            out.update({k: self._link[k].clone() for k in ("person_id", "stream_person", "link_stats")})
         if self.looks:
             K, S, p = len(self.looks), self.S, self._pfinish
             poses, frames = self._pv.clone().view(K, S, self.J, 3), self.pemit.clone()
@@ -445,6 +519,8 @@ class OnlineLifter:
         is off - the check reads the status words back, the tick's one synchronisation."""
         if not self._cameras_set:
             raise RuntimeError("OnlineLifter: call set_cameras first (this configuration reads camera rows / parameter rows)")
+        if self._link is not None:
+            raise ValueError("step: a lifter built with people= links the tracks r3d_streams_assign keeps: it takes track() only")
         if self._assign is not None and self._graph is not None:
             raise ValueError("step: the captured tick of a lifter built with cameras= starts with r3d_streams_assign: use track()")
         self._tracking = False
@@ -492,9 +568,13 @@ class OnlineLifter:
         tick (matched or born from), -1 for none: the slot pushed a synthetic frame, drains or is free - and
         extras["assign_stats"] (C, 4) int32: the camera's valid detections, the matched ones, the births and the valid
         detections that found no free slot.  A track's last `assign_max_missed` frames before its end are synthetic (nobody was
-        matched): with `repair` extras["synthetic"] marks their joints.  Cross-camera grouping is the caller's: map
-        (camera, track_id) to people and call :meth:`set_groups`.  A lifter that was captured takes `conf` on every tick or on
-        none."""
+        matched): with `repair` extras["synthetic"] marks their joints.  Cross-camera grouping: with `people=` the tick links
+        the cameras' tracks to people itself - extras["person_id"] (scenes * G,) int64, the identity of the person in row g of the
+        fused outputs, counted per scene from 0, -1 for a free row; extras["stream_person"] (S,) int32, the row of the person
+        that holds stream s, or -1; extras["link_stats"] (scenes, 4) int32: the scene's live people, the links made by matching,
+        the births and the tracks that found no free person; the extras["fused*"] rows are those people's skeletons -; without
+        it a caller maps (camera, track_id) to people and calls :meth:`set_groups`.  A lifter that was captured takes `conf` on
+        every tick or on none."""
         z = self._assign
         if z is None:
             raise ValueError("track: needs an OnlineLifter built with cameras=")
@@ -564,6 +644,8 @@ class OnlineLifter:
         (T_g, J), "fused_count" (T_g, J) and "fused_used" (T_g, 16), row n the group's skeleton of frame n.  The clips start together,
         so frame n of every clip is emitted by the same tick; T_g is the length of the longest clip among the group's members
         (0 when no member carries a clip)."""
+        if self._link is not None:
+            raise ValueError("lift_clips: a lifter built with people= links the tracks r3d_streams_assign keeps: it takes track() only")
         if len(clips) > self.S:
             raise ValueError("lift_clips: %d clips on %d streams" % (len(clips), self.S))
         if world and self._finish is None and self.repair is None:
@@ -631,7 +713,7 @@ class OnlineLifter:
     def capture(self):
         """Record one tick - r3d_streams_assign (with `cameras`: the captured lifter then takes :meth:`track`, not :meth:`step`),
         r3d_streams_repair (with `repair`), r3d_streams_step, the forward or forwards, the flip finish
-        (with `groups` r3d_streams_fuse behind it), and with
+        (with `people` r3d_streams_link and with `groups` or `people` r3d_streams_fuse behind it), and with
         `previews` r3d_streams_peek, the preview batch's forward or forwards and their finish - into
         a hipGraph on a side stream; from then on :meth:`step` copies its inputs into the captured buffers and replays it.  The streams' state is not touched:
         capture may come between two ticks."""

@@ -237,7 +237,19 @@ int r3d_release(r3d_model *pos, r3d_model *trj, int64_t B);   /* un-pins the siz
  * mode and for r3d_forward_pair alike: an element of x_dev, param_dev or a pixel coordinate that is NaN or +-Inf makes every
  * output of the windows that read it NaN (non-finite at least) - as the reference's forward does - and leaves every other
  * window's output bits exactly what they are without it.  It is not an error: nothing is reported through r3d_status, and
- * the call takes no longer than on finite input (tests/test_gpu_nonfinite.py). */
+ * the call takes no longer than on finite input (tests/test_gpu_nonfinite.py).
+ * Size limits of one forward (r3d_forward, r3d_forward_pair, r3d_forward_pair_split; every input mode).  With
+ * frames = (B - 1) * window_stride + RF and J = num_joints, a call is refused with R3D_ERR_ARG ("B too large for one call"),
+ * before any HIP call, unless all of
+ *   frames * J * 3 * 4 < 2^31 - 1   the raw input, counted at three floats per keypoint whatever the mode: the first-level
+ *                                   gathers address it through one buffer descriptor with 32-bit byte offsets;
+ *   B * (RF / 3)       < 2^31 - 1   the rows of the first level (a problem's row count is an int);
+ *   B * RF * J * 3 * 4 < 2^31 - 1   R3D_INPUT_UV_DIST / PX_* with cam_stride != 0 and window_stride < RF only: the windows
+ *                                   the pre-pass materialises
+ * hold ("the 2 GiB limits").  Workspace buffers may be of any size: they are addressed from 64-bit tile bases.  One buffer is
+ * not: the per-frame buffer of a clip call (window_stride 1, one camera) is read with 32-bit byte offsets, so a
+ * call whose frames * (floats per frame of that buffer) * 4 reaches 2^32 - 1 bytes runs the gathered first levels instead -
+ * the same poses to rounding, more arithmetic; nothing is refused. */
 int r3d_forward(r3d_model *m, const r3d_input *in, int64_t B, float *out_dev,
                 void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
@@ -1405,6 +1417,32 @@ int r3d_debug_census_domain(r3d_census_row *rows, int32_t cap);
 /* The largest window count of every plan kind that has one, ascending (what r3d_workspace_bytes walks): a call of edge + 1
  * windows runs the next kind's plan.  Returns their number (which may exceed `cap`: nothing is written past it). */
 int r3d_debug_plan_kind_edges(int64_t *edges, int32_t cap);
+
+/* The workspace layout of a call of `batch` windows: one row per buffer of the plan that call runs, in workspace order, then
+ * "(tail)" (the slack behind the last buffer, up to the next multiple of 256 bytes) and "(control)" (the single-launch
+ * forward's ready counters and problem table).  Offsets and sizes are in bytes from workspace_dev; a buffer's bytes are
+ * batch * floats_per_window * 4.  The per-frame buffer of clip calls (per_frame = 1; floats_per_window is then its floats
+ * per input FRAME) is the last buffer: a clip call uses (batch - 1) * window_stride + RF rows of it, the ones beyond `batch`
+ * lying in the tail.  *workspace_bytes (optional) = the sum of the rows' bytes = what this plan needs; r3d_workspace_bytes is
+ * the maximum of that over the plans of smaller calls.  No device call.  Returns the number of rows (which may exceed `cap`:
+ * nothing is written past it), or a negative code. */
+typedef struct r3d_plan_buffer_row {
+    char name[48];
+    int64_t floats_per_window;
+    uint64_t offset_bytes;
+    uint64_t bytes;
+    int32_t per_frame;
+    int32_t reserved;
+} r3d_plan_buffer_row;
+int r3d_debug_plan_buffers(r3d_model *pos, r3d_model *trj, int64_t batch, r3d_plan_buffer_row *rows, int32_t cap,
+                           uint64_t *workspace_bytes);
+
+/* What a forward decides from the SHAPE of its call, with no pointer and on handles in any state: the size limits (above,
+ * "Size limits of one forward": the functions the forward itself asks) - 0, or R3D_ERR_ARG with r3d_last_error set - and, in
+ * *per_frame (optional), whether a call of this shape runs the per-frame first layers.  `mode`, `window_stride` and
+ * `cam_stride` as in r3d_input.  No device call. */
+int r3d_debug_call_check(r3d_model *pos, r3d_model *trj, int32_t mode, int64_t window_stride, int64_t cam_stride,
+                         int64_t batch, int32_t *per_frame);
 
 /* The per-keypoint routine of the R3D_INPUT_UV_DIST pre-pass, run on the host: `row16` one camera row of 16 doubles, `uv`
  * n pixel pairs; out_uv (n, 2) the undistorted pixels, out_rays (n, 3) the float64 rays before the cast (either may be

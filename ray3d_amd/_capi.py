@@ -45,7 +45,7 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
                 "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host",
-                "r3d_debug_streams_assign_host", "r3d_debug_streams_link_host")
+                "r3d_debug_streams_assign_host", "r3d_debug_streams_link_host", "r3d_debug_plan_buffers", "r3d_debug_call_check")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -158,6 +158,12 @@ class CensusRow(C.Structure):
     """r3d_census_row: one (launch, tile kind) of r3d_debug_forward_census."""
     _fields_ = [("launch", C.c_int32), ("blocks", C.c_int32), ("tiles", C.c_int32), ("kernel", C.c_char * 48),
                 ("tile_kind", C.c_char * 48)]
+
+
+class PlanBufferRow(C.Structure):
+    """r3d_plan_buffer_row: one workspace buffer of r3d_debug_plan_buffers."""
+    _fields_ = [("name", C.c_char * 48), ("floats_per_window", C.c_int64), ("offset_bytes", C.c_uint64), ("bytes", C.c_uint64),
+                ("per_frame", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Ray3DHipError(RuntimeError):
@@ -289,6 +295,8 @@ def load():
                                                  C.POINTER(CensusRow), C.c_int32]
         lib.r3d_debug_census_domain.argtypes = [C.POINTER(CensusRow), C.c_int32]
         lib.r3d_debug_plan_kind_edges.argtypes = [i64p, C.c_int32]
+        lib.r3d_debug_plan_buffers.argtypes = [vp, vp, C.c_int64, C.POINTER(PlanBufferRow), C.c_int32, C.POINTER(C.c_uint64)]
+        lib.r3d_debug_call_check.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]
         lib.r3d_debug_clips_poses_host.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.c_int32, C.c_int64, vp, vp,
                                                    C.c_int64, vp]
         lib.r3d_debug_clips_valid_losses_host.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32,
@@ -878,6 +886,34 @@ def debug_plan_kind_edges():
     if n < 0 or n > 8:
         raise Ray3DHipError("r3d_debug_plan_kind_edges returned %d" % n)
     return [int(v) for v in buf[:n]]
+
+
+def debug_plan_buffers(pos: Optional[Handle], trj: Optional[Handle], batch: int):
+    """r3d_debug_plan_buffers (hooks library only: use_hooks(True)): ``(rows, workspace_bytes)`` of a call of `batch` windows - rows
+    ``(name, floats_per_window, offset_bytes, bytes, per_frame)`` in workspace order, the plan's buffers then "(tail)" and
+    "(control)"; `workspace_bytes` their sum.  Host only."""
+    lib = _lib_of(pos, trj)
+    cap = 128
+    while True:
+        rows = (PlanBufferRow * cap)()
+        total = C.c_uint64()
+        n = lib.r3d_debug_plan_buffers(pos.ptr if pos else None, trj.ptr if trj else None, int(batch), rows, cap, C.byref(total))
+        if n < 0:
+            raise Ray3DHipError("r3d_debug_plan_buffers returned %d" % n)
+        if n <= cap:
+            return [(r.name.decode(), int(r.floats_per_window), int(r.offset_bytes), int(r.bytes), bool(r.per_frame)) for r in rows[:n]], int(total.value)
+        cap = n
+
+
+def debug_call_check(pos: Optional[Handle], trj: Optional[Handle], batch: int, window_stride: int, mode: int = R3D_INPUT_RAYS,
+                     cam_stride: int = 0):
+    """r3d_debug_call_check (hooks library only: use_hooks(True)): ``(code, message, per_frame)`` - what a forward of this shape
+    answers to its size limits (0 and "" when it is accepted) and whether it would run the per-frame first layers.  Host only."""
+    lib = _lib_of(pos, trj)
+    pf = C.c_int32()
+    rc = int(lib.r3d_debug_call_check(pos.ptr if pos else None, trj.ptr if trj else None, int(mode), int(window_stride), int(cam_stride),
+                                      int(batch), C.byref(pf)))
+    return rc, (lib.r3d_last_error().decode() if rc != 0 else ""), bool(pf.value)
 
 
 def _parent_table(parents):

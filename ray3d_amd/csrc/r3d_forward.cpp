@@ -49,7 +49,7 @@ bool same_input_shape(const Model *a, const Model *b) {
 
 // activations (the input is read in place in both modes: UV mode encodes the rays inside the gather), then - 256-byte
 // aligned - the single-launch forward's control region: ready counters + abort flag, the call's problem table
-static size_t workspace_act_bytes(const Plan *pl, int64_t B) {
+size_t workspace_act_bytes(const Plan *pl, int64_t B) {
     const size_t act = ((size_t)pl->floats_per_window * (size_t)B + (size_t)pl->tail_floats + 64) * sizeof(float);
     return (act + 255) / 256 * 256;
 }
@@ -93,6 +93,25 @@ int dist_check(const Model *a, const r3d_input *in, bool need_cam) {
         return R3D_ERR_ARG;
     }
     if (in->window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
+    return R3D_OK;
+}
+
+// The size limits of one call (include/ray3d_hip.h, "Size limits of one forward"), judged on shapes alone - check_call and
+// redirect_px ask here, and so does r3d_debug_call_check.  The first-level gathers address the whole raw input through one
+// buffer descriptor with 32-bit byte offsets, and a problem's row count is an int.
+int call_size_check(const Model *a, int64_t window_stride, int64_t B) {
+    if (((B - 1) * window_stride + a->RF) * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL || B * (int64_t)(a->RF / 3) >= 0x7fffffffLL) {
+        set_error("B too large for one call (the raw input must stay below 2 GiB)");
+        return R3D_ERR_ARG;
+    }
+    return R3D_OK;
+}
+// ... of the pixel modes: the windows the pre-pass materialises (overlapping windows with a camera row each)
+int px_size_check(const Model *a, int64_t window_stride, int64_t cam_stride, int64_t B) {
+    if (cam_stride != 0 && window_stride < a->RF && B * (int64_t)a->RF * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL) {
+        set_error("B too large for one call (the materialised rays of overlapping windows must stay below 2 GiB)");
+        return R3D_ERR_ARG;
+    }
     return R3D_OK;
 }
 
@@ -369,11 +388,7 @@ int check_call(const Call &c) {
     const bool needs_param = a->cfg.embed_dim > 0 || (b && b->cfg.embed_dim > 0);
     if (needs_param && !in->param_dev) { set_error("param_dev is required when the camera embedding is on"); return R3D_ERR_ARG; }
     if (in->window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
-    if (((c.B - 1) * in->window_stride + a->RF) * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL || c.B * (int64_t)(a->RF / 3) >= 0x7fffffffLL) {
-        set_error("B too large for one call (the raw input must stay below 2 GiB)");
-        return R3D_ERR_ARG;
-    }
-    return R3D_OK;
+    return call_size_check(a, in->window_stride, c.B);
 }
 
 // ---- 2. the pixel modes: the forward is the R3D_INPUT_RAYS one, on the input the pre-pass writes into the workspace's tail
@@ -381,10 +396,7 @@ int redirect_px(Call &c) {
     const Model *a = c.a;
     const r3d_input *in = c.in;
     if (!px_mode(in->mode)) return R3D_OK;
-    if (dist_materialised(a, in) && c.B * (int64_t)a->RF * (int64_t)(a->cfg.num_joints * 3) * 4 >= 0x7fffffffLL) {
-        set_error("B too large for one call (the materialised rays of overlapping windows must stay below 2 GiB)");
-        return R3D_ERR_ARG;
-    }
+    if (const int rc = px_size_check(a, in->window_stride, in->cam_stride, c.B); rc != R3D_OK) return rc;
     c.ws_need = workspace_bytes_pair(c.a, c.b, c.B);
     const size_t dist_off = (c.ws_need + 255) / 256 * 256;
     const size_t need = dist_off + dist_ray_bytes(a, in, c.B);

@@ -532,6 +532,68 @@ int r3d_debug_plan_kind_edges(int64_t *edges, int32_t cap) {
     return (int)v.size();
 }
 
+// Test hook: the workspace layout of a call of `batch` windows (include/ray3d_hip.h): the buffers of the plan the driver picks
+// (plan_get(plan_kind(batch))) at the offsets fill_prob / frame_stage / decoder_tail give them, then the tail and the control region.
+int r3d_debug_plan_buffers(r3d_model *pos, r3d_model *trj, int64_t batch, r3d_plan_buffer_row *rows, int32_t cap, uint64_t *workspace_bytes) {
+    const ModelPair mp = model_pair(pos, trj);
+    Model *a = mp.a, *b = mp.b;
+    if (!a || batch <= 0 || (!rows && cap > 0)) return -1;
+    if (b && !same_input_shape(a, b)) return -1;
+    const Plan *pl = plan_get(a, b, plan_kind(batch));
+    if (!pl) return -2;
+    int n = 0;
+    auto row = [&](const char *name, int64_t fpw, int per_frame, uint64_t offset, uint64_t bytes) {
+        if (n < cap) {
+            r3d_plan_buffer_row &r = rows[n];
+            memset(&r, 0, sizeof r);
+            strncpy(r.name, name, sizeof r.name - 1);
+            r.floats_per_window = fpw;
+            r.per_frame = per_frame;
+            r.offset_bytes = offset;
+            r.bytes = bytes;
+        }
+        ++n;
+    };
+    for (size_t i = 0; i < pl->buffers.size(); ++i) {
+        const BufferSpec &bf = pl->buffers[i];
+        if (bf.external != 0) continue;                        // (the caller's camera-parameter rows: no workspace)
+        row(bf.name.c_str(), bf.floats_per_window, (int)i == pl->frame_buf ? 1 : 0, (uint64_t)bf.offset_per_window * (uint64_t)batch * sizeof(float),
+            (uint64_t)bf.floats_per_window * (uint64_t)batch * sizeof(float));
+    }
+    const uint64_t used = (uint64_t)pl->floats_per_window * (uint64_t)batch * sizeof(float), act = workspace_act_bytes(pl, batch);
+    row("(tail)", pl->tail_floats + 64, 0, used, act - used);
+    row("(control)", 0, 0, act, fwd_ctrl_bytes(pl, batch));
+    if (workspace_bytes) *workspace_bytes = act + fwd_ctrl_bytes(pl, batch);
+    return n;
+}
+
+// Test hook: what the forward driver decides from the SHAPE of a call, without a pointer: the size limits (call_size_check,
+// px_size_check - check_call and redirect_px ask the same functions) and whether a clip call's first levels read the per-frame
+// buffer (call_shares_first_layers, with the tile lists a plan with such a buffer always gets).
+int r3d_debug_call_check(r3d_model *pos, r3d_model *trj, int32_t mode, int64_t window_stride, int64_t cam_stride, int64_t batch,
+                         int32_t *per_frame) {
+    const ModelPair mp = model_pair(pos, trj);
+    Model *a = mp.a, *b = mp.b;
+    if (per_frame) *per_frame = 0;
+    if (!a) { set_error("forward: no model given"); return R3D_ERR_ARG; }
+    if (batch <= 0) { set_error("forward: null input/output or B <= 0"); return R3D_ERR_ARG; }
+    if (b && !same_input_shape(a, b)) { set_error("pos and trj models disagree on J / F / levels / extrinsic_dim"); return R3D_ERR_ARG; }
+    if (mode < R3D_INPUT_RAYS || mode > R3D_INPUT_PX_SCREEN) { set_error("bad input mode %d", mode); return R3D_ERR_ARG; }
+    if (window_stride <= 0) { set_error("window_stride must be positive"); return R3D_ERR_ARG; }
+    if (const int rc = call_size_check(a, window_stride, batch); rc != R3D_OK) return rc;
+    const bool px = mode != R3D_INPUT_RAYS && mode != R3D_INPUT_UV;
+    if (px)
+        if (const int rc = px_size_check(a, window_stride, cam_stride, batch); rc != R3D_OK) return rc;
+    if (per_frame) {
+        // (a pixel mode's forward is the R3D_INPUT_RAYS one on what the pre-pass wrote: redirect_px)
+        const bool materialised = px && cam_stride != 0 && window_stride < a->RF;
+        const int64_t ws = materialised ? a->RF : window_stride;
+        const Plan *pl = plan_get(a, b, plan_kind(batch));
+        *per_frame = call_shares_first_layers(pl, a, batch, mode == R3D_INPUT_UV, ws, px ? 0 : cam_stride, (batch - 1) * ws + a->RF, pl->frame_buf >= 0) ? 1 : 0;
+    }
+    return R3D_OK;
+}
+
 // Test hook: the pre-pass's per-keypoint routine (r3d_undistort.hpp) on the host.
 int r3d_debug_undistort_host(const double *row16, const double *uv, int64_t n, double *out_uv, double *out_rays) {
     if (!row16 || (!uv && n > 0) || n < 0) { set_error("r3d_debug_undistort_host: bad argument"); return R3D_ERR_ARG; }

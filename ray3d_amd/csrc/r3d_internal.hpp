@@ -527,6 +527,9 @@ int fill_prob(const Plan *pl, const ProbSpec &q, int64_t B, const Model *a, cons
               unsigned char *tags);
 bool same_input_shape(const Model *a, const Model *b);
 size_t workspace_bytes_pair(Model *a, Model *b, int64_t B);                    // r3d_workspace_bytes of a pair
+size_t workspace_act_bytes(const Plan *pl, int64_t B);                         // ... its activations: the plan's buffers, the tail, rounded to 256
+int call_size_check(const Model *a, int64_t window_stride, int64_t B);         // the size limits of one call, on shapes alone
+int px_size_check(const Model *a, int64_t window_stride, int64_t cam_stride, int64_t B);
 int dist_check(const Model *a, const r3d_input *in, bool need_cam);           // the pixel modes: argument rules, bytes of the pre-pass's output
 size_t dist_ray_bytes(const Model *a, const r3d_input *in, int64_t B);
 struct FwdKeys { int cu_limit, nwg, lane_key0, nlanes; };                      // lane keys lane_key0 .. lane_key0 + nlanes - 1 (schedule_key)

@@ -523,6 +523,74 @@ int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_join
                      float *x_mirror_dev, const int32_t *mirror_perm,   /* both NULL: no mirrored copy */
                      int32_t *status_dev, void *stream);
 
+/* ---- a shard's model inputs repaired: dropped keypoints held, back-filled and interpolated before the first forward ---- */
+
+/* The archive-side counterpart of r3d_streams_repair.  One NaN keypoint in a shard's pixel archive makes r3d_clips_encode write a
+ * non-finite input row, and by the non-finite contract every window that reads it comes out NaN.  This call repairs x_dev
+ * (out_rows, J, F), F = 2 | 3, IN PLACE, enqueued behind r3d_clips_encode on the same stream with the same table, out_rows and
+ * max_rows, before the first forward reads the buffer.  The reference's archives are complete, so the rule is this library's; an
+ * archive knows both ends of every gap, so - unlike the live rule, which never revises an emitted window - every gap of at most
+ * max_gap rows is interpolated from both sides and a late first observation is back-filled over the whole clip.
+ * A clip's rows are its local rows r in [0, R), R = pad_front + n_frames + pad_back, starting at out_first; local row r belongs
+ * to source frame first_frame + clamp(r - pad_front, 0, n_frames - 1), as in r3d_clips_encode.  The descriptors' `cam` is not read.
+ * OBSERVED(r, j): every one of the F components of x_dev[out_first + r, j] is finite (judged on the exponent bits), and - with
+ * conf_dev, (total_frames, J) float32 over SOURCE frames - conf[source frame, j] >= min_conf; a NaN confidence is not observed.
+ * Only x_dev is judged, never the mirrored copy.
+ * THE RULE per clip and joint, decided on the contents at entry.  O: the observed local rows of (clip, j).  A missing row r gets
+ * (all F components):
+ *   O empty:                                    the canonical quiet NaN 0x7FC00000                                   state 4
+ *   r < min O:                                  the bits of row min O - the back-fill, the per-joint analogue of
+ *                                               the front edge padding                                              state 3
+ *   p = max{o in O, o < r}, q = min{o in O, o > r} exists and g = q - p - 1 <= max_gap:
+ *                                               per component fl32(a + (e - a) * ((r - p) / (g + 1))) in float64,
+ *                                               a = x[p], e = x[q], every operation rounded once, a NaN result the
+ *                                               canonical quiet NaN: the routine, and the bits, of r3d_streams_repair  state 1
+ *   otherwise:                                  the bits of row p - the hold                                        state 2
+ * Observed points have state 0 and are NEVER written; a missing point's value depends on observed points only: the call is in
+ * place and its result does not depend on any order of execution.
+ *   x_mirror_dev / mirror_perm: both NULL, or both given (HOST perm), as in r3d_clips_encode: x_mirror_dev[row, dest(j)] of every
+ *               REWRITTEN point gets the new value with the sign bit of component 0 turned (also of the canonical NaN), the
+ *               other components bit for bit; points that were observed keep what r3d_clips_encode wrote.
+ *   state_dev:  (out_rows, J) uint8 or NULL: the state of every point of every row of a followed clip.
+ *   stats_dev:  (num_clips, J, 4) int32 or NULL: {interpolated, held, back-filled, never-observed} point counts over the clip's
+ *               OWN frames only (pad_front <= r < pad_front + n_frames), exact integers; written whole for a followed clip -
+ *               nothing needs to be zeroed beforehand.
+ *   status_dev: num_clips int32 words, required: 0 for a clip that was followed, 1 for an invalid descriptor.
+ * WHAT FOLLOWS.  A clip without a missing point is not written at all.  Padding rows repeat an edge frame, so the repair of a
+ * padded clip is the padding of the repaired clip, bit for bit, whatever the pads (the surplus rows of a rounded-up batch
+ * included).  If every joint of a clip was observed at least once, every value of the clip is finite afterwards - with ONE
+ * exception: an interpolation between endpoints near FLT_MAX may round to an infinity.
+ * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: (num_joints, num_clips)
+ * workgroups of 256 threads.  A workgroup builds the bitmap of its clip-joint's observed rows in LDS (R3D_REPAIR_MAX_ROWS bits),
+ * then every missing point finds p and q in it; the work per point is bounded by max_gap / 64 + 2 bitmap words whatever the
+ * pattern.  No atomics.
+ * INVALID DESCRIPTORS - THE WHOLE BOUNDS STORY.  A descriptor is invalid when n_frames < 1, a pad is < 0, R > max_rows, R >
+ * R3D_REPAIR_MAX_ROWS, the output rows are not inside [0, out_rows), or - with conf_dev, the only thing read by source frame -
+ * [first_frame, first_frame + n_frames) is not inside [0, total_frames) (without conf_dev first_frame is not read).  The kernel
+ * never follows an invalid descriptor: status_dev[c] = 1 and nothing else of that clip is read or written.  No index comes from a
+ * float: p and q are bit positions of a bitmap indexed by r < R <= R3D_REPAIR_MAX_ROWS, so rows p and q lie inside the clip; a
+ * source frame is a clamped index of a descriptor that passed the rule.  Beyond the descriptors the call reads the table within
+ * num_clips descriptors and conf_dev within total_frames * num_joints floats, and touches x_dev / x_mirror_dev within out_rows *
+ * num_joints * F floats, state_dev within out_rows * num_joints bytes, stats_dev within num_clips * num_joints * 4 words and
+ * status_dev within num_clips words: no input can make it touch memory outside these extents.  Overlapping OUTPUT ranges of two
+ * valid clips are the caller's error, as in r3d_clips_encode.
+ * R3D_ERR_ARG (checked on the host before any HIP call): a null required pointer (x_dev, clips_dev, status_dev), in_features
+ * other than 2 or 3, num_joints outside 1..17, num_clips outside 1..R3D_CLIPS_MAX, max_rows outside 1..R3D_REPAIR_MAX_ROWS,
+ * out_rows outside 1..R3D_ENCODE_MAX_POINTS, max_gap outside 0..R3D_REPAIR_MAX_ROWS, a min_conf that is not finite, conf_dev with
+ * total_frames outside 1..R3D_ENCODE_MAX_POINTS, exactly one of x_mirror_dev / mirror_perm, a mirror_perm that is not a
+ * permutation, a table pointer that is not 8-byte aligned, state_dev / stats_dev / status_dev / conf_dev / the table overlapping
+ * x_dev or x_mirror_dev (address ranges), x_dev overlapping x_mirror_dev.
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph). */
+#define R3D_REPAIR_MAX_ROWS 65536   /* rows (pad_front + n_frames + pad_back) of one clip */
+int r3d_clips_repair(float *x_dev, int64_t out_rows, int32_t num_joints, int32_t in_features,   /* (out_rows, J, F), F = 2 | 3: IN PLACE */
+                     float *x_mirror_dev, const int32_t *mirror_perm,    /* both NULL, or both given (HOST perm), as r3d_clips_encode */
+                     const r3d_clip_input_desc *clips_dev, int32_t num_clips, int64_t max_rows,   /* the table r3d_clips_encode read */
+                     const float *conf_dev, int64_t total_frames, float min_conf,   /* (total_frames, J) over SOURCE frames, or NULL */
+                     int32_t max_gap,                                    /* 0 .. R3D_REPAIR_MAX_ROWS: longest gap that is interpolated */
+                     uint8_t *state_dev,                                 /* (out_rows, J), may be NULL */
+                     int32_t *stats_dev,                                 /* (num_clips, J, 4), may be NULL */
+                     int32_t *status_dev, void *stream);                 /* (num_clips): 0 followed, 1 invalid descriptor */
+
 /* ---- per-clip validation losses: Trainer.test after the forwards ---- */
 
 /* lib/train_val/trainer.py:187-223 for one clip of n_frames frames, in the NORMALISED frame (no world transform): the
@@ -1462,6 +1530,12 @@ int r3d_debug_valid_losses_host(const float *pos, const float *trj, const float 
 int r3d_debug_clips_encode_host(const float *px, int64_t total_frames, int32_t num_joints, int32_t encoding,
                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, float *x, int64_t out_rows,
                                 float *x_mirror, const int32_t *mirror_perm, int32_t *status);
+/* r3d_clips_repair on the host (HOST pointers throughout, no stream): the same argument checks and return codes, the same
+ * descriptor rule, observed test, bitmap searches and per-point routine, clips in table order, joints in order. */
+int r3d_debug_clips_repair_host(float *x, int64_t out_rows, int32_t num_joints, int32_t in_features, float *x_mirror,
+                                const int32_t *mirror_perm, const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows,
+                                const float *conf, int64_t total_frames, float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats,
+                                int32_t *status);
 /* r3d_clips_valid_losses on the host (HOST pointers throughout, no scratch): the same argument checks, the same descriptor rule,
  * per valid clip exactly r3d_debug_valid_losses_host on the clip's slice; an invalid clip's row is NaN, its frame rows stay. */
 int r3d_debug_clips_valid_losses_host(const float *pos, const float *trj, const float *gt, int64_t total_frames, int32_t num_joints,

@@ -36,7 +36,7 @@ EXPORTS = (
     "r3d_clips_project", "r3d_forward_pair_split", "r3d_finalize_dev", "r3d_clips_windows",
     "r3d_streams_state_bytes", "r3d_streams_step", "r3d_streams_poses", "r3d_streams_track_bytes", "r3d_streams_repair",
     "r3d_streams_peek", "r3d_streams_fuse", "r3d_streams_assign_bytes", "r3d_streams_assign", "r3d_streams_link_bytes",
-    "r3d_streams_link",
+    "r3d_streams_link", "r3d_clips_repair",
 )
 HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_forward_check",   # libray3d_hip_hooks.so only
                 "r3d_debug_forward_census", "r3d_debug_census_domain", "r3d_debug_plan_kind_edges",
@@ -45,7 +45,8 @@ HOOK_EXPORTS = ("r3d_debug_schedule_check", "r3d_debug_plan_check", "r3d_debug_f
                 "r3d_debug_clips_project_host", "r3d_debug_pack_replay_host", "r3d_debug_weights_image",
                 "r3d_debug_clips_windows_host", "r3d_debug_streams_step_host", "r3d_debug_streams_poses_host",
                 "r3d_debug_streams_repair_host", "r3d_debug_streams_peek_host", "r3d_debug_streams_fuse_host",
-                "r3d_debug_streams_assign_host", "r3d_debug_streams_link_host", "r3d_debug_plan_buffers", "r3d_debug_call_check")
+                "r3d_debug_streams_assign_host", "r3d_debug_streams_link_host", "r3d_debug_plan_buffers", "r3d_debug_call_check",
+                "r3d_debug_clips_repair_host")
 ABI_VERSION = 6                                                          # R3D_ABI_VERSION of the header this binding follows
 METRIC_NAMES = ("mpjpe", "p_mpjpe", "n_mpjpe", "velocity", "root")     # R3D_METRIC_* order
 METRIC_OUT_DOUBLES = 5 * (1 + 128)                                      # R3D_METRIC_OUT_DOUBLES
@@ -63,6 +64,8 @@ R3D_ENCODE_RAY, R3D_ENCODE_INTRINSIC, R3D_ENCODE_SCREEN = 0, 1, 2       # `encod
 ENCODE_FLOATS = {R3D_ENCODE_RAY: 3, R3D_ENCODE_INTRINSIC: 2, R3D_ENCODE_SCREEN: 2}   # floats per encoded keypoint
 ENCODE_MAX_POINTS = 2 ** 31 - 257                                       # R3D_ENCODE_MAX_POINTS
 CLIP_INPUT_DESC_BYTES = 160                                             # sizeof(r3d_clip_input_desc)
+REPAIR_MAX_ROWS = 65536                                                 # R3D_REPAIR_MAX_ROWS
+REPAIR_STATE_NAMES = ("observed", "interpolated", "held", "back_filled", "never_observed")   # `state` of r3d_clips_repair, 0..4
 
 
 class Config(C.Structure):
@@ -240,6 +243,8 @@ def load():
     lib.r3d_clips_metrics.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.r3d_clips_encode.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int64, vp, C.c_int64, vp,
                                      C.POINTER(C.c_int32), vp, vp]
+    lib.r3d_clips_repair.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), vp, C.c_int32, C.c_int64, vp, C.c_int64,
+                                     C.c_float, C.c_int32, vp, vp, vp, vp]
     lib.r3d_clips_valid_scratch_bytes.argtypes = [C.c_int32, C.c_int64]
     lib.r3d_clips_valid_scratch_bytes.restype = C.c_size_t
     lib.r3d_clips_valid_losses.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, vp, C.c_int32, C.c_int64,
@@ -273,6 +278,8 @@ def load():
     lib.r3d_last_error.restype = C.c_char_p
     lib.r3d_version.restype = C.c_char_p
     if _hooks:
+        lib.r3d_debug_clips_repair_host.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32), vp, C.c_int32, C.c_int64, vp,
+                                                    C.c_int64, C.c_float, C.c_int32, vp, vp, vp]
         lib.r3d_debug_streams_assign_host.argtypes = [vp] * 11
         lib.r3d_debug_streams_link_host.argtypes = [vp] * 10
         lib.r3d_debug_streams_fuse_host.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double,
@@ -536,6 +543,32 @@ def _mirror_table(what: str, mirror_perm, num_joints: int):
     if len(mirror_perm) != num_joints:
         raise Ray3DHipError("%s: mirror_perm has %d entries, num_joints is %d" % (what, len(mirror_perm), num_joints))
     return (C.c_int32 * len(mirror_perm))(*[int(v) for v in mirror_perm])
+
+
+def clips_repair(x_ptr: int, out_rows: int, num_joints: int, in_features: int, x_mirror_ptr: Optional[int], mirror_perm, table_ptr: int,
+                 num_clips: int, max_rows: int, conf_ptr: Optional[int], total_frames: int, min_conf: float, max_gap: int,
+                 state_ptr: Optional[int], stats_ptr: Optional[int], status_ptr: int, stream: int):
+    """r3d_clips_repair (enqueued BEHIND :func:`clips_encode`, with its table, `out_rows` and `max_rows`): every pointer is device
+    memory; `x_ptr` (out_rows, num_joints, in_features) float32, repaired in place; `x_mirror_ptr` (or None) and `mirror_perm` (a
+    host sequence of num_joints ints, or None) go together; `conf_ptr` (total_frames, num_joints) float32 over source frames or None;
+    `state_ptr` (out_rows, num_joints) uint8 or None; `stats_ptr` (num_clips, num_joints, 4) int32 or None; `status_ptr` num_clips
+    int32."""
+    perm = _mirror_table("r3d_clips_repair", mirror_perm, num_joints)
+    check(load().r3d_clips_repair(x_ptr, out_rows, num_joints, in_features, x_mirror_ptr or None, perm, table_ptr, num_clips, max_rows,
+                                  conf_ptr or None, total_frames, min_conf, max_gap, state_ptr or None, stats_ptr or None, status_ptr, stream),
+          "r3d_clips_repair")
+
+
+def debug_clips_repair_host(x_ptr: int, out_rows: int, num_joints: int, in_features: int, x_mirror_ptr: Optional[int], mirror_perm,
+                            table_ptr: int, num_clips: int, max_rows: int, conf_ptr: Optional[int], total_frames: int, min_conf: float,
+                            max_gap: int, state_ptr: Optional[int], stats_ptr: Optional[int], status_ptr: int) -> int:
+    """r3d_debug_clips_repair_host (hooks library only: use_hooks(True)): r3d_clips_repair on HOST pointers; `mirror_perm` a host
+    sequence of ints of any length (the call judges it) or None; returns the status code instead of raising (R3D_ERR_ARG is what the
+    tests ask for)."""
+    perm = (C.c_int32 * max(len(mirror_perm), 1))(*[int(v) for v in mirror_perm]) if mirror_perm is not None else None
+    return int(load().r3d_debug_clips_repair_host(x_ptr or None, out_rows, num_joints, in_features, x_mirror_ptr or None, perm,
+                                                  table_ptr or None, num_clips, max_rows, conf_ptr or None, total_frames, min_conf, max_gap,
+                                                  state_ptr or None, stats_ptr or None, status_ptr or None))
 
 
 def clips_poses(raw_ptr: int, raw_mirror_ptr: Optional[int], raw_rows: int, num_joints: int, mirror_perm, table_ptr: int,

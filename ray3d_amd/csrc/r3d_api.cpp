@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "r3d_internal.hpp"
+#include "r3d_clips_repair.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_streams.hpp"
 #include "r3d_streams_assign.hpp"
@@ -131,6 +132,70 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
                                  const float *x_mirror, const int32_t *mirror_perm, const int32_t *status) {
     static_assert(sizeof(r3d_clip_input_desc) == 160, "r3d_clip_input_desc is documented as 160 bytes");
     return clips_input_check(what, px, total_frames, J, encoding, clips, num_clips, max_rows, x, out_rows, x_mirror, mirror_perm, status);
+}
+
+// the argument rules of r3d_clips_repair, shared with its host hook; fills the kernel's argument set
+int r3d::clips_repair_check_args(const char *what, float *x, int64_t out_rows, int32_t J, int32_t F, float *x_mirror, const int32_t *mirror_perm,
+                                 const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *conf, int64_t total_frames,
+                                 float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats, int32_t *status, ClipsRepairArgs *args) {
+    if (!x || !clips || !status) { set_error("%s: null pointer (x_dev, clips_dev, status_dev)", what); return R3D_ERR_ARG; }
+    if (F != 2 && F != 3) { set_error("%s: in_features must be 2 or 3 (got %d)", what, F); return R3D_ERR_ARG; }
+    if (const int rc = clips_range_check(what, num_clips, J)) return rc;
+    if (max_rows < 1 || max_rows > R3D_REPAIR_MAX_ROWS) {
+        set_error("%s: max_rows must be in 1..%d (got %lld)", what, R3D_REPAIR_MAX_ROWS, (long long)max_rows);
+        return R3D_ERR_ARG;
+    }
+    if (out_rows < 1 || out_rows > R3D_ENCODE_MAX_POINTS) {
+        set_error("%s: out_rows must be in 1..%d (got %lld)", what, R3D_ENCODE_MAX_POINTS, (long long)out_rows);
+        return R3D_ERR_ARG;
+    }
+    if (max_gap < 0 || max_gap > R3D_REPAIR_MAX_ROWS) { set_error("%s: max_gap must be in 0..%d (got %d)", what, R3D_REPAIR_MAX_ROWS, max_gap); return R3D_ERR_ARG; }
+    if ((__builtin_bit_cast(uint32_t, min_conf) & 0x7f800000u) == 0x7f800000u) { set_error("%s: min_conf must be finite", what); return R3D_ERR_ARG; }
+    if (conf && (total_frames < 1 || total_frames > R3D_ENCODE_MAX_POINTS)) {
+        set_error("%s: total_frames must be in 1..%d with conf_dev (got %lld)", what, R3D_ENCODE_MAX_POINTS, (long long)total_frames);
+        return R3D_ERR_ARG;
+    }
+    if ((x_mirror != nullptr) != (mirror_perm != nullptr)) {
+        set_error("%s: x_mirror_dev and mirror_perm go together (both or neither)", what);
+        return R3D_ERR_ARG;
+    }
+    if (const int rc = mirror_perm_check(what, mirror_perm, J)) return rc;
+    if (reinterpret_cast<uintptr_t>(clips) % 8) { set_error("%s: the clip table must be 8-byte aligned", what); return R3D_ERR_ARG; }
+    // the call works in place on x_dev / x_mirror_dev, and on nothing else: no other extent may overlap them, nor they each other
+    // (address ranges; the sizes fit in 64 bits)
+    const uintptr_t x_bytes = (uintptr_t)out_rows * J * F * sizeof(float);
+    const char *io_name[2] = {"x_dev", "x_mirror_dev"};
+    const uintptr_t io[2] = {reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(x_mirror)};
+    if (io[1] && io[0] < io[1] + x_bytes && io[1] < io[0] + x_bytes) { set_error("%s: x_dev overlaps x_mirror_dev", what); return R3D_ERR_ARG; }
+    const char *name[5] = {"state_dev", "stats_dev", "status_dev", "conf_dev", "the clip table"};
+    const uintptr_t at[5] = {reinterpret_cast<uintptr_t>(state), reinterpret_cast<uintptr_t>(stats), reinterpret_cast<uintptr_t>(status),
+                             reinterpret_cast<uintptr_t>(conf), reinterpret_cast<uintptr_t>(clips)};
+    const uintptr_t bytes[5] = {(uintptr_t)out_rows * J, (uintptr_t)num_clips * J * 4 * sizeof(int32_t), (uintptr_t)num_clips * sizeof(int32_t),
+                                conf ? (uintptr_t)total_frames * J * sizeof(float) : 0, (uintptr_t)num_clips * sizeof(r3d_clip_input_desc)};
+    for (int o = 0; o < 5; ++o)
+        for (int i = 0; i < 2; ++i)
+            if (at[o] && io[i] && at[o] < io[i] + x_bytes && io[i] < at[o] + bytes[o]) {
+                set_error("%s: %s overlaps %s", what, name[o], io_name[i]);
+                return R3D_ERR_ARG;
+            }
+    ClipsRepairArgs a = {};
+    a.table = clips;
+    a.x = reinterpret_cast<uint32_t *>(x);
+    a.x_mirror = reinterpret_cast<uint32_t *>(x_mirror);
+    a.conf = conf;
+    a.state = state;
+    a.stats = stats;
+    a.status = status;
+    a.out_rows = out_rows;
+    a.max_rows = max_rows;
+    a.total_frames = conf ? total_frames : 0;
+    if (mirror_perm) mirror_pack_inverse(mirror_perm, J, a.mirror_inv);
+    a.min_conf = min_conf;
+    a.J = J;
+    a.F = F;
+    a.max_gap = max_gap;
+    *args = a;
+    return R3D_OK;
 }
 
 // the argument rules of r3d_clips_project, shared with its host hook: r3d_clips_encode's on the source, the table and the inputs it
@@ -929,6 +994,22 @@ int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_join
     const hipError_t err = r3d::launch_clips_encode(a, num_clips, (hipStream_t)stream);   // (the launcher consumed the error: print what it returned)
     if (err != hipSuccess) {
         set_error("r3d_clips_encode: launch failed: %s", hipGetErrorString(err));
+        return R3D_ERR_HIP;
+    }
+    return 0;
+}
+
+int r3d_clips_repair(float *x_dev, int64_t out_rows, int32_t num_joints, int32_t in_features, float *x_mirror_dev, const int32_t *mirror_perm,
+                     const r3d_clip_input_desc *clips_dev, int32_t num_clips, int64_t max_rows, const float *conf_dev, int64_t total_frames,
+                     float min_conf, int32_t max_gap, uint8_t *state_dev, int32_t *stats_dev, int32_t *status_dev, void *stream) {
+    // (every check on the host, before any HIP call)
+    r3d::ClipsRepairArgs a;
+    const int rc = clips_repair_check_args("r3d_clips_repair", x_dev, out_rows, num_joints, in_features, x_mirror_dev, mirror_perm, clips_dev,
+                                           num_clips, max_rows, conf_dev, total_frames, min_conf, max_gap, state_dev, stats_dev, status_dev, &a);
+    if (rc != R3D_OK) return rc;
+    const hipError_t err = r3d::launch_clips_repair(a, num_clips, (hipStream_t)stream);
+    if (err != hipSuccess) {
+        set_error("r3d_clips_repair: launch failed: %s", hipGetErrorString(err));
         return R3D_ERR_HIP;
     }
     return 0;

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "r3d_internal.hpp"
+#include "r3d_clips_repair.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
 #include "r3d_streams.hpp"
@@ -885,6 +886,47 @@ int r3d_debug_streams_repair_host(void *state, void *track, int32_t num_streams,
         for (int j = 0; j < a.J; ++j)
             if (stream_repair_joint(a, s, j, rs.c, rs.restart)) mask |= 1u << j;
         stream_repair_finish(a, s, rs.c, mask);
+    }
+    return R3D_OK;
+}
+
+// Test hook: r3d_clips_repair on the host - its argument rules (clips_repair_check_args) and the routines of r3d_clips_repair.hpp the
+// kernel runs: per clip the verdict on the descriptor, then per joint the bitmap of observed rows built from the contents at entry
+// and, in the kernel's steps of 256 rows with its carry, every missing point through clip_repair_point.
+int r3d_debug_clips_repair_host(float *x, int64_t out_rows, int32_t num_joints, int32_t in_features, float *x_mirror,
+                                const int32_t *mirror_perm, const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows,
+                                const float *conf, int64_t total_frames, float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats,
+                                int32_t *status) {
+    ClipsRepairArgs a;
+    const int rc = clips_repair_check_args("r3d_debug_clips_repair_host", x, out_rows, num_joints, in_features, x_mirror, mirror_perm, clips,
+                                           num_clips, max_rows, conf, total_frames, min_conf, max_gap, state, stats, status, &a);
+    if (rc != R3D_OK) return rc;
+    std::vector<unsigned long long> bits(CLIPS_REPAIR_WORDS);
+    for (int32_t ci = 0; ci < num_clips; ++ci) {
+        const ClipRepairClip c = clip_repair_clip(a, clips + ci);
+        status[ci] = c.ok ? 0 : 1;
+        if (!c.ok) continue;
+        const int steps = (c.R + CLIPS_REPAIR_THREADS - 1) / CLIPS_REPAIR_THREADS;
+        for (int j = 0; j < a.J; ++j) {
+            int first = -1;
+            for (int w = 0; w < steps * CLIPS_REPAIR_WAVES; ++w) bits[w] = 0ull;
+            for (int r = 0; r < c.R; ++r)
+                if (clip_repair_observed(a, c, r, j)) {
+                    bits[r >> 6] |= 1ull << (r & 63);
+                    if (first < 0) first = r;
+                }
+            int carry = -1, cnt[5] = {0, 0, 0, 0, 0};
+            for (int base = 0; base < c.R; base += CLIPS_REPAIR_THREADS) {
+                for (int r = base; r < c.R && r < base + CLIPS_REPAIR_THREADS; ++r) {
+                    int st = CLIP_REPAIR_OBSERVED;
+                    if (!((bits[r >> 6] >> (r & 63)) & 1ull)) st = clip_repair_point(a, c, bits.data(), first, clip_repair_prev(bits.data(), r, carry), r, j);
+                    if (state) state[(c.out_first + r) * a.J + j] = (uint8_t)st;
+                    if (r >= c.pad_front && r < c.pad_front + c.n) ++cnt[st];
+                }
+                carry = clip_repair_carry(bits.data(), base >> 6, carry);
+            }
+            for (int k = 0; stats && k < 4; ++k) stats[((long long)ci * a.J + j) * 4 + k] = cnt[k + 1];
+        }
     }
     return R3D_OK;
 }

@@ -625,6 +625,12 @@ int streams_assign_check_args(const char *what, void *state, const r3d_assign_pa
                               const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match, int64_t *id,
                               int32_t *stats, StreamsAssignArgs *args);
 
+struct ClipsRepairArgs;     // r3d_clips_repair.hpp
+// the argument rules of r3d_clips_repair, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+int clips_repair_check_args(const char *what, float *x, int64_t out_rows, int32_t J, int32_t F, float *x_mirror, const int32_t *mirror_perm,
+                            const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *conf, int64_t total_frames,
+                            float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats, int32_t *status, ClipsRepairArgs *args);
+
 struct StreamsLinkArgs;     // r3d_streams_link.hpp
 // the argument rules of r3d_streams_link, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
 int streams_link_check_args(const char *what, void *state, const r3d_link_params *prm, const double *world, const int64_t *emit,
@@ -741,6 +747,7 @@ hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stre
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_fuse
 hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_assign
+hipError_t launch_clips_repair(const ClipsRepairArgs &args, int num_clips, hipStream_t stream);     // the same kernel: r3d_clips_repair
 hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_link
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table

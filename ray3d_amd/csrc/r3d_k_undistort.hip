@@ -123,7 +123,23 @@
 // people of its parity (stream_link_joint; the ballot is the person's new seen bits), then lane g finishes person g
 // (stream_link_person).  Keys and masks live inside the LDS block of r3d_streams_fuse's staging area: the kernel's static LDS
 // does not grow.  Plain vector stores from C++, no atomics.
+//
+// r3d_clips_repair (shard evaluation that survives dropped keypoints: the inputs r3d_clips_encode wrote, repaired in place before the
+// first forward reads them, include/ray3d_hip.h) is the fourteenth argument set, ClipsRepairArgs, enqueued BEHIND r3d_clips_encode
+// with the same table: one workgroup of 256 threads per (joint blockIdx.x, clip blockIdx.y).  It reads its descriptor by scalar loads
+// and decides on it before anything else (clip_repair_clip of r3d_clips_repair.hpp).  Pass 1: the clip's rows in steps of 256, each
+// thread judges one point (clip_repair_observed), each wavefront's ballot is one word of the clip-joint's bitmap of observed rows in
+// LDS, stored by one lane; a barrier.  Pass 2, the same steps: a thread whose point is MISSING finds p - in the step's four words, else
+// the running "last observed row in front of this step" every thread carries along, the same value in all of them - and q - in no more
+// than max_gap / 64 + 2 words - with count-leading / trailing-zero operations and writes its own point of x, x_mirror and state through
+// clip_repair_point, the routine the host hook runs.  Work per point is bounded whatever the pattern: no scan.  The counters are ballot
+// popcounts, summed per wavefront, reduced through LDS and stored by one thread.  The bitmap (8 192 bytes) and the per-wavefront words
+// live inside the LDS block of r3d_streams_fuse's staging area: the kernel's static LDS does not grow.  Observed points are never
+// written and a missing point reads observed points only: in place, whatever the order.  Rows of one joint are J * F * 4 bytes apart:
+// a wavefront's 64 points are 64 short accesses, served from the cache lines the other joints' workgroups of the clip read as well.
+// Plain vector stores from C++, no atomics; nothing is pre-zeroed by the caller.
 #include "r3d_internal.hpp"
+#include "r3d_clips_repair.hpp"
 #include "r3d_pack.hpp"
 #include "r3d_poses.hpp"
 #include "r3d_project.hpp"
@@ -551,15 +567,68 @@ __device__ __forceinline__ void streams_link_body(const StreamsLinkArgs &a, unsi
     }
 }
 
-// The block of LDS the fuse mode's staging area, the assign mode's keys and the link mode's keys share
+// Joint blockIdx.x < J of clip blockIdx.y: 256 threads, four wavefronts.  The descriptor is one address for the workgroup, so the
+// verdict is uniform and a refused clip's workgroup leaves as a whole before any barrier; every loop bound is uniform, and no thread
+// leaves before the last ballot or barrier: a thread past the clip's rows takes part with `false`.  `lds`: CLIPS_REPAIR_LDS_BYTES.
+__device__ __forceinline__ void clips_repair_body(const ClipsRepairArgs &a, unsigned char *lds) {
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(lds + CLIPS_REPAIR_LDS_BITS);   // [r / 64], r < R <= 65 536
+    int32_t *wfirst = reinterpret_cast<int32_t *>(lds + CLIPS_REPAIR_LDS_FIRST);                      // [wave]
+    int32_t *wcount = reinterpret_cast<int32_t *>(lds + CLIPS_REPAIR_LDS_COUNT);                      // [wave * 4 + counter]
+    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const ClipRepairClip c = clip_repair_clip(a, a.table + blockIdx.y);
+    if (j == 0 && tid == 0) a.status[blockIdx.y] = c.ok ? 0 : 1;
+    if (!c.ok) return;                       // an invalid descriptor is not followed: nothing else of the clip is read or written
+    // pass 1: the bitmap of observed rows; a step's four words are written whole, so rows R .. read as not observed
+    int first = -1;                          // the first row this wavefront saw observed (the same in its 64 lanes)
+    for (int base = 0; base < c.R; base += CLIPS_REPAIR_THREADS) {
+        const int r = base + tid;
+        const unsigned long long m = __ballot(r < c.R && clip_repair_observed(a, c, r, j));
+        if (lane == 0) bits[(base >> 6) + wave] = m;            // (base + 255 < R + 255 <= 65 536 + 255, base a multiple of 256: word < 1 024)
+        if (first < 0 && m) first = base + wave * 64 + __builtin_ctzll(m);
+    }
+    if (lane == 0) wfirst[wave] = first;
+    __syncthreads();                         // the bitmap is whole, and every point was judged before any is rewritten
+    first = -1;                              // min O
+    for (int w = 0; w < CLIPS_REPAIR_WAVES; ++w) {
+        const int f = wfirst[w];
+        if (f >= 0 && (first < 0 || f < first)) first = f;
+    }
+    // pass 2: the missing points
+    const int own0 = c.pad_front, own1 = c.pad_front + (int)c.n;    // the clip's own frames: what the counters count
+    int carry = -1, cnt[4] = {0, 0, 0, 0};
+    for (int base = 0; base < c.R; base += CLIPS_REPAIR_THREADS) {
+        const int r = base + tid;
+        int state = CLIP_REPAIR_OBSERVED;
+        if (r < c.R) {
+            if (!((bits[r >> 6] >> (r & 63)) & 1ull)) state = clip_repair_point(a, c, bits, first, clip_repair_prev(bits, r, carry), r, j);
+            if (a.state) a.state[(c.out_first + r) * a.J + j] = (uint8_t)state;
+        }
+        if (a.stats) {                       // uniform
+            const int mine = r >= own0 && r < own1 ? state : CLIP_REPAIR_OBSERVED;
+            for (int k = 0; k < 4; ++k) cnt[k] += (int)__popcll(__ballot(mine == k + 1));
+        }
+        carry = clip_repair_carry(bits, base >> 6, carry);
+    }
+    if (!a.stats) return;                    // uniform
+    if (lane == 0)
+        for (int k = 0; k < 4; ++k) wcount[wave * 4 + k] = cnt[k];
+    __syncthreads();
+    if (tid != 0) return;
+    int32_t *out = a.stats + ((long long)blockIdx.y * a.J + j) * 4;
+    for (int k = 0; k < 4; ++k) out[k] = wcount[k] + wcount[4 + k] + wcount[8 + k] + wcount[12 + k];
+}
+
+// The block of LDS the fuse mode's staging area, the assign mode's keys and the link mode's keys and the clip repair's bitmap share
 constexpr int STREAMS_SHARED_LDS_BYTES = (int)sizeof(double) * STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS;
 static_assert(STREAMS_ASSIGN_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_streams_assign lives inside the staging area of r3d_streams_fuse");
 static_assert(STREAMS_LINK_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_streams_link lives inside the staging area of r3d_streams_fuse");
+static_assert(CLIPS_REPAIR_LDS_BYTES <= STREAMS_SHARED_LDS_BYTES, "r3d_clips_repair lives inside the staging area of r3d_streams_fuse");
 
-// The thirteen argument sets travel in one kernel-argument segment (4 KiB on this target)
+// The fourteen argument sets travel in one kernel-argument segment (4 KiB on this target)
 static_assert(sizeof(UndistArgs) + sizeof(ClipsEncArgs) + sizeof(ClipsPosesArgs) + sizeof(ClipsProjectArgs) + sizeof(PackArgs) +
                       sizeof(WindowsArgs) + sizeof(StreamsArgs) + sizeof(StreamsPosesArgs) + sizeof(StreamsRepairArgs) +
-                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + sizeof(StreamsAssignArgs) + sizeof(StreamsLinkArgs) + 13 * 8 <= 4096,
+                      sizeof(StreamsPeekArgs) + sizeof(StreamsFuseArgs) + sizeof(StreamsAssignArgs) + sizeof(StreamsLinkArgs) +
+                      sizeof(ClipsRepairArgs) + 14 * 8 <= 4096,
               "the argument sets of r3d_undistort_rays_f64 (with 8 bytes of alignment slack each) must fit the kernel-argument segment");
 
 extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const UndistArgs a, const ClipsEncArgs c, const ClipsPosesArgs q,
@@ -567,8 +636,12 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
                                                                          const StreamsArgs sm, const StreamsPosesArgs sp,
                                                                          const StreamsRepairArgs sr, const StreamsPeekArgs pk,
                                                                          const StreamsFuseArgs fz, const StreamsAssignArgs as,
-                                                                         const StreamsLinkArgs lk) {
-    __shared__ __attribute__((aligned(16))) unsigned char shared_lds[STREAMS_SHARED_LDS_BYTES];    // one block: the three modes below
+                                                                         const StreamsLinkArgs lk, const ClipsRepairArgs rp) {
+    __shared__ __attribute__((aligned(16))) unsigned char shared_lds[STREAMS_SHARED_LDS_BYTES];    // one block: the four modes below
+    if (rp.x) {                              // uniform: r3d_clips_repair - joint blockIdx.x of clip blockIdx.y
+        clips_repair_body(rp, shared_lds);
+        return;
+    }
     if (lk.state) {                          // uniform: r3d_streams_link - scene blockIdx.x
         streams_link_body(lk, shared_lds);
         return;
@@ -663,28 +736,35 @@ extern "C" __global__ __launch_bounds__(256) void r3d_undistort_rays_f64(const U
 
 hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream) {
     if (args.npts <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((args.npts + 255) / 256), dim3(256), 0, stream>>>(args, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_encode: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, args, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
+    return hipGetLastError();
+}
+
+// r3d_clips_repair: (J, num_clips) workgroups of 256 threads, one launch, nothing else
+hipError_t launch_clips_repair(const ClipsRepairArgs &args, int num_clips, hipStream_t stream) {
+    static_assert(CLIPS_REPAIR_THREADS == 256, "the kernel's workgroups are 256 threads: a step is four bitmap words");
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.J, (unsigned)num_clips), dim3(CLIPS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, args);
     return hipGetLastError();
 }
 
 // r3d_clips_poses: (ceil(max_frames * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_frames * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, args, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_project: (ceil(max_rows * J / 256), num_clips) workgroups, one launch, nothing else
 hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.max_rows * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)num_clips), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, args, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
@@ -692,14 +772,14 @@ hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hip
 hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream) {
     static_assert(PACK_THREADS == 256, "the kernel's workgroups are 256 threads");
     if (nblk <= 0) return hipSuccess;
-    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)nblk), dim3(PACK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, args, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_clips_windows: (ceil(RF * J / 256), batch) workgroups, one launch, nothing else
 hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)batch), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, args, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
@@ -707,54 +787,54 @@ hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t 
 hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream) {
     StreamsArgs t = args;
     t.phase = 0;
-    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)t.S), dim3(64), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     t.phase = 1;
     const unsigned gx = (unsigned)((t.RF * t.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)t.S), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, t, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_poses: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream) {
     static_assert(STREAMS_POSES_THREADS == 64 && STREAMS_POSES_THREADS >= 17, "one wavefront holds a stream's joints");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_POSES_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, args, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_repair: S workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream) {
     static_assert(STREAMS_REPAIR_THREADS == 64 && STREAMS_REPAIR_THREADS >= 17, "one wavefront holds a stream's joints: its ballot is the mask");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.S), dim3(STREAMS_REPAIR_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, args, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_peek: (ceil(RF * J / 256), S, K) workgroups, one launch, nothing else
 hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream) {
     const unsigned gx = (unsigned)((args.RF * args.J + 255) / 256);
-    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3(gx, (unsigned)args.S, (unsigned)args.K), dim3(256), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, args, StreamsFuseArgs{}, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_assign: C workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream) {
     static_assert(STREAMS_ASSIGN_THREADS == 64, "one wavefront holds a camera's detections and slots: its ballots are their masks");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.C), dim3(STREAMS_ASSIGN_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, args, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.C), dim3(STREAMS_ASSIGN_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, args, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_link: N workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream) {
     static_assert(STREAMS_LINK_THREADS == 64, "one wavefront holds a scene's people and a camera's slots: its ballots are their masks");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.N), dim3(STREAMS_LINK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, args);
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.N), dim3(STREAMS_LINK_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, StreamsFuseArgs{}, StreamsAssignArgs{}, args, ClipsRepairArgs{});
     return hipGetLastError();
 }
 
 // r3d_streams_fuse: G workgroups of one wavefront, one launch, nothing else
 hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream) {
     static_assert(STREAMS_FUSE_THREADS == 64 && STREAMS_FUSE_THREADS >= STREAMS_FUSE_JOINTS, "one wavefront holds a group's joints: its ballots are the used words");
-    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args, StreamsAssignArgs{}, StreamsLinkArgs{});
+    r3d_undistort_rays_f64<<<dim3((unsigned)args.G), dim3(STREAMS_FUSE_THREADS), 0, stream>>>(UndistArgs{}, ClipsEncArgs{}, ClipsPosesArgs{}, ClipsProjectArgs{}, PackArgs{}, WindowsArgs{}, StreamsArgs{}, StreamsPosesArgs{}, StreamsRepairArgs{}, StreamsPeekArgs{}, args, StreamsAssignArgs{}, StreamsLinkArgs{}, ClipsRepairArgs{});
     return hipGetLastError();
 }
 

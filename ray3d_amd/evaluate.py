@@ -42,6 +42,7 @@ class Clip:
     action: str = ""
     clip_id: int = 0
     frame: str = "normalized"   # the frame of gt_norm and of the predictions: "normalized" | "camera"
+    conf: Optional[np.ndarray] = None   # (N, J) float32 keypoint confidences, read by ``repair=`` only (None: every keypoint +inf)
 
 
 _IDENTITY_R, _IDENTITY_T = np.eye(3, dtype=np.float64), np.zeros((3, 1), dtype=np.float64)
@@ -545,6 +546,17 @@ def _encoding_id(encoding, arg: str = "encode") -> int:
     return ENCODINGS[encoding]
 
 
+def _repair_needs_encode(repair, encode):
+    """``repair=`` works on the encode call's buffer: a ValueError without ``encode=``, or for a K outside 0..REPAIR_MAX_ROWS."""
+    if repair is None:
+        return
+    from . import _capi
+    if encode is None:
+        raise ValueError("repair=: the repair works on the encode call's buffer (r3d_clips_encode's output); give encode= and raw pixels")
+    if isinstance(repair, bool) or int(repair) != repair or not 0 <= int(repair) <= _capi.REPAIR_MAX_ROWS:
+        raise ValueError("repair= must be an integer in 0..%d, the longest gap that is interpolated (got %r)" % (_capi.REPAIR_MAX_ROWS, repair))
+
+
 class _ShardInputs:
     """What the clips `mine` of a shard are lifted from.  ``inputs(k)`` -> (input of clip k, its mirrored input or None without
     `flip`, the clip's camera parameter row on `dev`, extra keywords of ``lift_clip``):
@@ -555,10 +567,15 @@ class _ShardInputs:
       uploaded, ONE :func:`shard_encode_hip` call on the current stream pads, encodes and - with `flip` - mirrors every clip and
       its status is read (a refused descriptor raises); a clip's inputs are its slices of the two buffers, lifted with
       ``n_windows=``.  `lifter`'s ``clip_batch_sizes`` size the slices.  Clips of fewer than `pool_below` frames (0: none) are
-      encoded without padding: they are not lifted from slices but gathered from the buffer (:class:`_Pool`)."""
+      encoded without padding: they are not lifted from slices but gathered from the buffer (:class:`_Pool`).
+      `repair` (None: off - no code path, buffer or launch differs): ONE :func:`shard_repair_hip` call right behind the encode call,
+      on its two buffers and its table (with `pool_below` the re-laid-out one), with ``max_gap=repair``; keypoints of confidence
+      (``Clip.conf``; clips without one count as +inf) below `min_conf` are not observed; `repair_out` (a dict) receives "state",
+      "stats" and "status"; a refused descriptor raises."""
 
     def __init__(self, mine: Sequence[Clip], rf: int, dev, causal: bool, encode: Optional[str], lifter, flip: bool = False,
-                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None, pool_below: int = 0):
+                 kps_left: Sequence[int] = (), kps_right: Sequence[int] = (), mirror: Optional[Callable] = None, pool_below: int = 0,
+                 repair: Optional[int] = None, min_conf: float = 0.0, repair_out: Optional[dict] = None):
         self.mine, self.dev, self.flip, self.encode = mine, dev, flip, encode
         self.lengths = [int(c.rays.shape[0]) for c in mine]
         self.pad, self.shift = (rf - 1) // 2, ((rf - 1) // 2 if causal else 0)
@@ -580,8 +597,28 @@ class _ShardInputs:
         self.rows = [int(d["pad_front"]) + int(d["n_frames"]) + int(d["pad_back"]) for d in itable]
         px_all = torch.from_numpy(np.concatenate([np.ascontiguousarray(c.rays, dtype=np.float32) for c in mine], axis=0)).to(dev)
         perm = mirror_permutation(px_all.shape[1], kps_left, kps_right) if flip else None
-        self.x_all, self.xm_all, status = shard_encode_hip(px_all, _to_device_bytes(itable, dev), len(mine), out_rows, max_rows, encode, perm)
+        if repair is not None:
+            from . import _capi
+            for k, rows in enumerate(self.rows):
+                if rows > _capi.REPAIR_MAX_ROWS:
+                    raise ValueError("repair=: clip %d of this rank's shard (clip_id %s, %d frames) has %d padded rows; r3d_clips_repair takes "
+                                     "at most %d" % (k, mine[k].clip_id, self.lengths[k], rows, _capi.REPAIR_MAX_ROWS))
+        table_dev = _to_device_bytes(itable, dev)
+        self.x_all, self.xm_all, status = shard_encode_hip(px_all, table_dev, len(mine), out_rows, max_rows, encode, perm)
+        if repair is not None:
+            conf_all = None
+            if any(c.conf is not None for c in mine):
+                J = px_all.shape[1]
+                conf_all = torch.from_numpy(np.concatenate(
+                    [np.ascontiguousarray(c.conf, dtype=np.float32).reshape(n, J) if c.conf is not None else np.full((n, J), np.inf, np.float32)
+                     for c, n in zip(mine, self.lengths)], axis=0)).to(dev)
+            rstate, rstats, rstatus = shard_repair_hip(self.x_all, table_dev, len(mine), out_rows, max_rows, int(repair), self.xm_all, perm,
+                                                       conf_all, min_conf)
         _raise_if_refused(status, "r3d_clips_encode")
+        if repair is not None:
+            _raise_if_refused(rstatus, "r3d_clips_repair")
+            if repair_out is not None:
+                repair_out.update(state=rstate, stats=rstats, status=rstatus)
 
     def __call__(self, k: int):
         c = self.mine[k]
@@ -728,6 +765,49 @@ def shard_encode_hip(px_all: torch.Tensor, table_dev: torch.Tensor, num_clips: i
                            [int(v) for v in mirror_perm] if mirror_perm is not None else None,
                            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return x_all, x_mirror_all, status
+
+
+def shard_repair_hip(x_all: torch.Tensor, table_dev: torch.Tensor, num_clips: int, out_rows: int, max_rows: int, max_gap: int,
+                     x_mirror_all: Optional[torch.Tensor] = None, mirror_perm: Optional[Sequence[int]] = None,
+                     conf_all: Optional[torch.Tensor] = None, min_conf: float = 0.0, state: Optional[torch.Tensor] = None,
+                     stats: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """ONE r3d_clips_repair call on the current stream, right behind the :func:`shard_encode_hip` call whose `x_all` (out_rows, J,
+    F) / `x_mirror_all`, `table_dev`, `out_rows` and `max_rows` it is given: every keypoint that is not observed - a non-finite
+    component, or with `conf_all` ((total_frames, J) float32 over the SOURCE frames) a confidence below `min_conf` - is repaired IN
+    PLACE in both buffers: gaps of at most `max_gap` rows interpolated from both sides, longer ones held, a late first observation
+    back-filled, a joint never observed the canonical NaN (include/ray3d_hip.h has the rule).  Returns (state (out_rows, J) uint8:
+    0 observed, 1 interpolated, 2 held, 3 back-filled, 4 never observed; stats (num_clips, J, 4) int32: those four counts over each
+    clip's own frames; status (num_clips,) int32: 0 = followed, 1 = invalid descriptor).  `state` / `stats` / `status`: tensors to
+    write into (contiguous, of exactly these shapes) instead of new ones - needed under hipGraph capture; a new `state` is NOT
+    zeroed: rows no clip covers keep what they held.  No copy and no synchronisation: the caller reads `status` when it wants to."""
+    from . import _capi
+    dev = x_all.device
+    if not x_all.is_cuda or x_all.dim() != 3 or x_all.shape[-1] not in (2, 3):
+        raise ValueError("x_all: a contiguous float32 (out_rows, J, 2 | 3) tensor on a GPU is needed")
+    J, F = int(x_all.shape[1]), int(x_all.shape[2])
+    _need(x_all, "x_all", torch.float32, dev, shape=(out_rows, J, F))
+    _need_table(table_dev, num_clips, _capi.CLIP_INPUT_DESC_BYTES, dev)
+    if (x_mirror_all is None) != (mirror_perm is None):
+        raise ValueError("x_mirror_all and mirror_perm go together (both or neither)")
+    if x_mirror_all is not None:
+        _need(x_mirror_all, "x_mirror_all", torch.float32, dev, shape=(out_rows, J, F))
+    if max_rows > _capi.REPAIR_MAX_ROWS:
+        raise ValueError("max_rows is %d: r3d_clips_repair takes clips of at most %d rows" % (max_rows, _capi.REPAIR_MAX_ROWS))
+    total = 0
+    if conf_all is not None:
+        if conf_all.dim() != 2 or conf_all.shape[0] < 1:
+            raise ValueError("conf_all: a contiguous float32 (total_frames, J) tensor is needed")
+        _need(conf_all, "conf_all", torch.float32, dev, last=J)
+        total = int(conf_all.shape[0])
+    state = _out_buffer(state, "state", True, torch.uint8, dev, (out_rows, J))
+    stats = _out_buffer(stats, "stats", True, torch.int32, dev, (num_clips, J, 4))
+    status = _status_buffer(status, num_clips, dev)
+    with torch.cuda.device(dev):
+        _capi.clips_repair(x_all.data_ptr(), out_rows, J, F, x_mirror_all.data_ptr() if x_mirror_all is not None else None,
+                           [int(v) for v in mirror_perm] if mirror_perm is not None else None, table_dev.data_ptr(), num_clips, max_rows,
+                           conf_all.data_ptr() if conf_all is not None else None, total, float(min_conf), int(max_gap),
+                           state.data_ptr(), stats.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return state, stats, status
 
 
 # ------------------------------------------------------------------------------------ a whole shard's finished poses in one call
@@ -947,7 +1027,8 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
                           kps_left: Sequence[int] = (), kps_right: Sequence[int] = (),
                           joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
                           causal: bool = False, encode: Optional[str] = None, world: bool = True, root_relative: bool = False,
-                          pool_below: Optional[int] = None):
+                          pool_below: Optional[int] = None, repair: Optional[int] = None, min_conf: float = 0.0,
+                          repair_out: Optional[dict] = None):
     """:func:`predict_clip` for many clips, with the poses in world coordinates on top - the numerical core of the reference's
     Trainer.render (lib/train_val/trainer.py:505-526: cam.normalized2world / cam.camera2world on the flip-averaged poses) without
     its height rebase and its animation.  Every clip is lifted with ``raw_out=`` into one raw buffer and ONE r3d_clips_poses call
@@ -955,7 +1036,7 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     (poses (N, J, 3) float32 - the bits of :func:`predict_clip` - , world (N, J, 3) float64 or None without `world`): views of the
     two shard buffers.  The transform is :func:`clip_world_transform`'s: a ``frame="camera"`` clip goes through Rc2w / Tc2w,
     `root_relative` is the identity.  `lift_clip` must be the bound ``forward_clip`` of a lifter; `encode` as in
-    :func:`evaluate_clips_batched`, and so is `pool_below`.  Single rank, GPU only.  No ground truth is needed: ``Clip.gt_norm``
+    :func:`evaluate_clips_batched`, and so are `pool_below` and `repair` / `min_conf` / `repair_out`.  Single rank, GPU only.  No ground truth is needed: ``Clip.gt_norm``
     may be an empty array."""
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -963,12 +1044,14 @@ def predict_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, d
     lifter = _lifter_of(lift_clip, need="predict_clips_batched", by_name=True)
     if encode is not None:
         _encoding_id(encode)
+    _repair_needs_encode(repair, encode)
     if not clips:
         return []
     table, first, total, longest = clip_table(clips, root_relative)
     table_dev = _to_device_bytes(table, dev)
     below = int(pool_below or 0)
-    inputs = _ShardInputs(clips, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, pool_below=below)
+    inputs = _ShardInputs(clips, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, pool_below=below, repair=repair,
+                          min_conf=min_conf, repair_out=repair_out)
     jl = kps_left if joints_left is None else joints_left
     jr = kps_right if joints_right is None else joints_right
     pool = _Pool(clips, inputs, rf, causal, flip, lifter, below, kps_left, kps_right) if below else None
@@ -984,7 +1067,8 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
                            joints_left: Optional[Sequence[int]] = None, joints_right: Optional[Sequence[int]] = None,
                            root_relative: bool = False, mirror: Optional[Callable] = None, detail: bool = False,
                            include_root: bool = False, encode: Optional[str] = None, finish: bool = False,
-                           pool_below: Optional[int] = None):
+                           pool_below: Optional[int] = None, repair: Optional[int] = None, min_conf: float = 0.0,
+                           repair_out: Optional[dict] = None):
     """:func:`evaluate_clips` (with `detail`: :func:`evaluate_clips_detail`, `include_root` as there) with the measuring side in
     ONE call per shard: the rank's clip table and ground truth are uploaded once, every clip is lifted into its slice of one
     prediction buffer (``lift_clip(padded, param_row, out=slice)``: ``Ray3DLifter.forward_clip``; the flip average is written
@@ -1020,7 +1104,16 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     Recommended: ``pool_below=1024``.  Measured at RF 243, flip on (profiles/clips_windows_ab.json): pooling 2 000
     clips of 40 - 400 frames takes 0.62 of the per-clip path's time (run-to-run spread 3.6 % / 0.3 %); thresholds of 512, 1 024
     and 2 048 on a mixed shard cannot be told apart; pooling clips of 1 000 - 6 000 frames is 5 % SLOWER than lifting them per
-    clip (the clip kernels' per-frame first level), so the crossover lies between 400 and about 2 000 frames."""
+    clip (the clip kernels' per-frame first level), so the crossover lies between 400 and about 2 000 frames.
+
+    `repair` (None: off - no code path, buffer or launch differs; needs `encode`): pixel archives with dropped keypoints.  A NaN
+    keypoint makes the encode call write a non-finite input row, and every window that reads it comes out NaN.  With ``repair=K``
+    ONE r3d_clips_repair call (:func:`shard_repair_hip`) runs right behind the shard's encode call, on its buffers and its table
+    (with `pool_below` the re-laid-out one): per clip and joint, gaps of at most K frames are interpolated from both sides, longer
+    ones held, a late first observation back-filled over the clip's start; a joint never observed stays NaN.  With ``Clip.conf``
+    ((N, J) confidences; a clip without one counts as +inf) a keypoint below `min_conf` is not observed either.  `repair_out` (a
+    dict) receives this rank's "state" (out_rows, J) uint8, "stats" (clips, J, 4) int32 and "status"; a refused descriptor raises,
+    and so does a clip of more than ``_capi.REPAIR_MAX_ROWS`` padded rows.  A clip without a missing keypoint keeps its bits."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("evaluate_clips_batched measures on the GPU (r3d_clips_metrics); on CPU tensors use evaluate_clips")
@@ -1030,6 +1123,7 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         if mirror is not None:
             raise ValueError("encode=: the flip pass mirrors the encoded input on the device; `mirror` must be None")
         _lifter_of(lift_clip, need="encode=")
+    _repair_needs_encode(repair, encode)
     below = int(pool_below or 0)
     if below:
         if mirror is not None:
@@ -1045,7 +1139,8 @@ def evaluate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         table_dev = _to_device_bytes(table, dev)
         gt_all = _ground_truth(mine, dev, root_relative)
         pred_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
-        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, mirror, pool_below=below)
+        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, flip, kps_left, kps_right, mirror, pool_below=below, repair=repair,
+                              min_conf=min_conf, repair_out=repair_out)
         jl = kps_left if joints_left is None else joints_left
         jr = kps_right if joints_right is None else joints_right
         if finish:
@@ -1447,7 +1542,8 @@ def clip_frame_table(lengths: Sequence[int]):
 
 def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, device, parents=H36M_17_PARENTS, group=None,
                            pos_is_sum: bool = True, gt_root_relative: bool = False, causal: bool = False,
-                           bone_pairs: Optional[Sequence[tuple]] = None, encode: Optional[str] = None):
+                           bone_pairs: Optional[Sequence[tuple]] = None, encode: Optional[str] = None, repair: Optional[int] = None,
+                           min_conf: float = 0.0, repair_out: Optional[dict] = None):
     """:func:`validate_clips` with the measuring side in ONE call per shard: the rank's clip table and ground truth are uploaded
     once, every clip is lifted into its slice of one pose buffer and one trajectory buffer
     (``lift_clip(padded, param_row, out=pose_slice, trj_out=trj_slice)``), and one :func:`shard_valid_hip` call fills the sums
@@ -1461,7 +1557,7 @@ def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     `encode` ("ray" | "intrinsic" | "screen"): ``Clip.rays`` holds RAW PIXELS (N, J, 2) and the input side is one call per
     shard as well, exactly as in :func:`evaluate_clips_batched` (no mirror): the rank's pixels are uploaded once, ONE
     r3d_clips_encode call pads and encodes every clip, each clip is lifted from its slice with ``n_windows=``; a descriptor
-    the encode call refuses raises."""
+    the encode call refuses raises.  `repair` / `min_conf` / `repair_out`: as in :func:`evaluate_clips_batched`."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("validate_clips_batched measures on the GPU (r3d_clips_valid_losses); on CPU tensors use validate_clips")
@@ -1469,6 +1565,7 @@ def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
     if encode is not None:        # (decided before the shards are cut: every rank raises alike, also one with an empty shard)
         _encoding_id(encode)
         _lifter_of(lift_clip, partial_ok=True, need="encode=")
+    _repair_needs_encode(repair, encode)
     shards, mine, local = _valid_plan(clips, group, dev)
     if mine:
         table, first, total, longest = clip_frame_table([c.rays.shape[0] for c in mine])
@@ -1476,7 +1573,7 @@ def validate_clips_batched(lift_clip: Callable, clips: Sequence[Clip], rf: int, 
         gt_all = _ground_truth(mine, dev)
         pos_all = torch.empty((total, 1, gt_all.shape[1], 3), dtype=torch.float32, device=dev)
         trj_all = torch.empty((total, 1, 1, 3), dtype=torch.float32, device=dev)
-        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter)
+        inputs = _ShardInputs(mine, rf, dev, causal, encode, lifter, repair=repair, min_conf=min_conf, repair_out=repair_out)
 
         def lift(k):
             rows = slice(first[k], first[k] + mine[k].rays.shape[0])

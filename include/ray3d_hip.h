@@ -111,7 +111,7 @@ int r3d_finalize(r3d_model *m);
  * parameters live in device memory and change (a validation pass after every epoch).  `weights_dev` and `numel` are HOST arrays
  * of `count` entries: entry i is the device pointer and the element count of tensor r3d_weight_key(m, i), contiguous float32 in
  * torch layout, on the current HIP device.  No weight is copied to the host, nothing waits for the device, and the number of
- * launches (two, of r3d_undistort_rays_f64's pack argument set, behind one small copy of the pointer table) does not depend on
+ * launches (two, of the kernel r3d_k_pack, behind one small copy of the pointer table) does not depend on
  * the number of layers.  The packed image is BIT FOR BIT what r3d_finalize produces from the same values (the same float64
  * arithmetic, per element, without contraction); non-finite inputs are outside that promise (NaN payloads may differ).
  * Checked on the host before any device call: count != r3d_num_weights, a null argument or a null entry -> R3D_ERR_ARG; a numel[i]
@@ -560,7 +560,7 @@ int r3d_clips_encode(const float *px_dev, int64_t total_frames, int32_t num_join
  * padded clip is the padding of the repaired clip, bit for bit, whatever the pads (the surplus rows of a rounded-up batch
  * included).  If every joint of a clip was observed at least once, every value of the clip is finite afterwards - with ONE
  * exception: an interpolation between endpoints near FLT_MAX may round to an infinity.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: (num_joints, num_clips)
+ * ONE LAUNCH of the call's own kernel, r3d_k_clips_repair: (num_joints, num_clips)
  * workgroups of 256 threads.  A workgroup builds the bitmap of its clip-joint's observed rows in LDS (R3D_REPAIR_MAX_ROWS bits),
  * then every missing point finds p and q in it; the work per point is bounded by max_gap / 64 + 2 bitmap words whatever the
  * pattern.  No atomics.
@@ -741,8 +741,8 @@ int r3d_clips_valid_losses(const float *pos_dev, const float *trj_dev, const flo
  * num_joints, total_frames or raw_rows above R3D_ENCODE_MAX_POINTS (index arithmetic), a table, raw_first_dev or world_dev
  * pointer that is not 8-byte aligned, an output extent (pred_dev, world_dev) that overlaps the extent of raw_dev or
  * raw_mirror_dev - compared as address ranges: in-place use is refused rather than given rules.
- * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
- * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch is of the
+ * call's own kernel, r3d_k_clips_poses. */
 int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t raw_rows, int32_t num_joints,
                     const int32_t *mirror_perm,                 /* HOST, J entries; given exactly when raw_mirror_dev is */
                     const r3d_clip_desc *clips_dev, const int64_t *raw_first_dev, int32_t num_clips, int64_t max_frames,
@@ -811,8 +811,8 @@ int r3d_clips_poses(const float *raw_dev, const float *raw_mirror_dev, int64_t r
  * total_frames or out_rows < 1, max_rows * num_joints, total_frames or out_rows above R3D_ENCODE_MAX_POINTS (index arithmetic),
  * exactly one of x_mirror_dev / mirror_perm, a mirror_perm that is not a permutation, a table pointer that is not 8-byte aligned -
  * and, with gt_dev or px_dev given, gt_rows < 1 or above R3D_ENCODE_MAX_POINTS; a px_dev that is not 8-byte aligned.
- * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
- * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch is of the
+ * call's own kernel, r3d_k_clips_project. */
 typedef struct {
     int64_t first_frame;  /* row of the clip's first frame in world_dev (many descriptors may name the same frames)        */
     int64_t n_frames;
@@ -874,8 +874,8 @@ int r3d_clips_project(const float *world_dev, int64_t total_frames, int32_t num_
  * outside 1..65535 (the grid's second dimension), window0 outside [0, 2^62], receptive_field * num_joints, total_frames or batch *
  * receptive_field * num_joints above R3D_ENCODE_MAX_POINTS (index arithmetic), exactly one of run_param_dev / param_dev,
  * extrinsic_dim < 1 with run_param_dev given, a mirror_perm that is not a permutation, a table pointer that is not 8-byte aligned.
- * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch runs on the
- * elementwise kernel r3d_clips_encode runs on, with an argument set of its own. */
+ * Enqueued on `stream`: no copy, no allocation, no synchronisation (it can be captured into a hipGraph).  The launch is of the
+ * call's own kernel, r3d_k_clips_windows. */
 typedef struct {
     int64_t first_frame;  /* row of the run's source clip in src_dev                                  */
     int64_t n_frames;     /* frames of that clip (>= 1)                                               */
@@ -934,7 +934,7 @@ int r3d_clips_windows(const float *src_dev, int64_t total_frames, int32_t num_jo
  * the action word is unknown; when a PUSH comes after a drain began (drained > 0: RESTART starts the next clip); when the head a
  * PUSH or DRAIN meets is invalid: count < 0, count > 2^62, drained < 0 or drained > lag; when a PUSH meets count == 2^62 (the
  * counter is full).
- * TWO LAUNCHES on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own.  Advance: S workgroups; each
+ * TWO LAUNCHES, of the call's own kernels r3d_k_streams_advance and r3d_k_streams_gather.  Advance: S workgroups; each
  * reads and judges its stream's head and action uniformly, puts the J points of the new frame into the ring slot, and one thread
  * writes the head, emit and status.  Gather: (ceil(RF * J / 256), S) workgroups, one output point (row, joint) per thread, from the
  * head, emit and status words the advance launch wrote: no head is written by the launch other workgroups read it in.
@@ -1007,7 +1007,7 @@ int r3d_streams_step(void *state_dev, int32_t num_streams, int32_t receptive_fie
  * without a mirrored pass) keep their payload.  A point behind the camera or in its plane (Zc <= 0) is simply followed, as
  * r3d_clips_project does: a mirrored, infinite or NaN residual, not an error.  A non-finite raw element touches its own point's
  * outputs and its stream's quality words, nothing else.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: S workgroups of one wavefront;
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_poses: S workgroups of one wavefront;
  * each reads its stream's emit and status words uniformly before anything else; thread j < J finishes joint j; one thread sums the
  * residuals it finds parked in LDS.  Launch-latency-bound by construction.
  * THE WHOLE BOUNDS STORY.  Whatever emit_dev, status_dev, the descriptors and the inputs hold, the kernel reads emit_dev and
@@ -1090,7 +1090,7 @@ int r3d_streams_poses(const float *raw_dev, const float *raw_mirror_dev,   /* (S
  *            Otherwise the held values stay.
  *     after the joints   missing[c % RF] = the mask of the joints not observed in the new frame (interpolated or back-filled
  *            frames keep their bits); synthetic[s] = missing[(c - lag) % RF] if c - lag >= 0 - the frame the step will emit - else 0.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: S workgroups of one wavefront;
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_repair: S workgroups of one wavefront;
  * thread j < J owns joint j and is the only one that writes the joint's frame_out row, age, last and ring entries; one thread
  * forms the mask from the wavefront's ballot and writes the two mask words.  Launch-latency-bound by construction.
  * THE WHOLE BOUNDS STORY.  Whatever the track, the state and the action words hold, the kernel reads the heads, frame_dev,
@@ -1140,7 +1140,7 @@ int r3d_streams_repair(void *state_dev,              /* the state of r3d_streams
  * frame % RF - r3d_streams_step's rule with p in place of n: the window a drain started now would emit at its (lag - L)-th tick, and
  * window p of the reference's np.pad(..., 'edge') + eval_data_prepare on the stream's c frames so far.  The oldest frame it names
  * is c - RF + lag - L > c - RF, which the ring holds.  Otherwise emit = -1 and nothing of row block (k, s) is read or written.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: (ceil(RF * J / 256), S, K)
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_peek: (ceil(RF * J / 256), S, K)
  * workgroups, one output point (row, joint) per thread; each workgroup reads its stream's head, action and status word uniformly and
  * decides before anything is written; nothing the launch writes is read by another of its workgroups.
  * THE WHOLE BOUNDS STORY.  Whatever the state and the words hold, the kernel reads the state within r3d_streams_state_bytes,
@@ -1203,7 +1203,7 @@ int r3d_streams_peek(const void *state_dev,           /* the state of r3d_stream
  *      canonical quiet NaN (0x7FF8000000000000), count is 0.  Any NaN the arithmetic produces (an overflowing sum, a weight that
  *      underflows the denominator to 0) leaves as the canonical quiet NaN.
  * EVERY row of every output given is written on every call, also those of a group whose slots are all empty (NaN, NaN, 0, 0).
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: G workgroups of one wavefront;
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_fuse: G workgroups of one wavefront;
  * the workgroup reads its M member words uniformly, once; thread j < J owns joint j, stages its candidates' points and weights in
  * LDS (at most 16 x 17 x 32 bytes per group) and runs the gate out of it; a `used` word is the wavefront's ballot for its slot,
  * written by one thread.  Launch-latency-bound by construction.
@@ -1281,7 +1281,7 @@ int r3d_streams_fuse(const double *world_dev,          /* (S, J, 3) float64: wha
  * slot is live or draining - the tick the track ends included -, -1 for a slot that is free and stays free.  Identities count from
  * the state's next_id[c] per camera: (c, id) names a track.  stats_dev[c] = the valid detections, the matched ones, the births
  * and the valid detections that found no slot.  Copied keypoints and confidences travel as 32-bit patterns.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: C workgroups of one wavefront.
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_assign: C workgroups of one wavefront.
  * Lanes own detections for step 1; the P x D pairs are dealt over the lanes for step 2, the cost keys in LDS; step 3 is at most
  * min(P, D) rounds of a wavefront-wide arg-min over (cost, p * D + d) with taken-row and taken-column masks; ballots and
  * popcounts rank step 6's detections and slots; then lanes own slots.  Launch-latency-bound by construction.
@@ -1383,7 +1383,7 @@ int r3d_streams_assign(void *assign_dev, const r3d_assign_params *prm /* HOST */
  * person_dev[g] = the pid of a person live after the call, else -1.  group_dev[s] = the absolute person index that holds stream
  * s, or -1.  stats_dev[n] = the people live after the call, the links step B's matching made, the births and the candidates that
  * found no free person.
- * ONE LAUNCH on the elementwise kernel r3d_clips_encode runs on, with an argument set of its own: N workgroups of one wavefront.
+ * ONE LAUNCH of the call's own kernel, r3d_k_streams_link: N workgroups of one wavefront.
  * Lane g owns person g in step A and for the words of step C, whose joint means are dealt over the lanes by joint; in step B lane p
  * summarises slot p, the G x P pairs are dealt over the lanes, their cost keys in LDS, the matching at most min(G, P) rounds of a
  * wavefront-wide arg-min, births ranked by ballots and popcounts.  The cameras are visited one after the other: the launch's time

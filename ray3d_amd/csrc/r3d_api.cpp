@@ -134,7 +134,7 @@ int r3d::clips_encode_check_args(const char *what, const float *px, int64_t tota
     return clips_input_check(what, px, total_frames, J, encoding, clips, num_clips, max_rows, x, out_rows, x_mirror, mirror_perm, status);
 }
 
-// the argument rules of r3d_clips_repair, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_clips_repair, shared with its host hook; fills the kernel's arguments
 int r3d::clips_repair_check_args(const char *what, float *x, int64_t out_rows, int32_t J, int32_t F, float *x_mirror, const int32_t *mirror_perm,
                                  const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *conf, int64_t total_frames,
                                  float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats, int32_t *status, ClipsRepairArgs *args) {
@@ -255,7 +255,7 @@ int r3d::clips_poses_check_args(const char *what, const float *raw, const float 
     return R3D_OK;
 }
 
-// the argument rules of r3d_clips_windows, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_clips_windows, shared with its host hook; fills the kernel's arguments
 int r3d::clips_windows_check_args(const char *what, const float *src, int64_t total_frames, int32_t J, int32_t F, int32_t RF,
                                   const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t E, int64_t window0,
                                   int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status, WindowsArgs *args) {
@@ -324,7 +324,7 @@ static int streams_shared_check(const char *what, int32_t S, int32_t RF, int32_t
     return R3D_OK;
 }
 
-// the argument rules of r3d_streams_step, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_step, shared with its host hook; fills the kernel's arguments
 int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
                             const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror,
                             const int32_t *mirror_perm, int64_t *emit, int32_t *status, StreamsArgs *args) {
@@ -367,7 +367,7 @@ int r3d::streams_check_args(const char *what, void *state, int32_t S, int32_t RF
     return R3D_OK;
 }
 
-// the argument rules of r3d_streams_repair, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_repair, shared with its host hook; fills the kernel's arguments
 int r3d::streams_repair_check_args(const char *what, void *state, void *track, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
                                    int32_t encoding, const float *frame, const float *conf, float min_conf, const double *cam,
                                    const int32_t *action, int32_t max_gap, float *frame_out, uint32_t *synthetic, StreamsRepairArgs *args) {
@@ -425,7 +425,7 @@ int r3d::streams_repair_check_args(const char *what, void *state, void *track, i
     return R3D_OK;
 }
 
-// the argument rules of r3d_streams_peek, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_peek, shared with its host hook; fills the kernel's arguments
 int r3d::streams_peek_check_args(const char *what, const void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
                                  const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status, float *x,
                                  float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status, StreamsPeekArgs *args) {
@@ -479,7 +479,7 @@ int r3d::streams_peek_check_args(const char *what, const void *state, int32_t S,
     return R3D_OK;
 }
 
-// the argument rules of r3d_streams_poses, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_poses, shared with its host hook; fills the kernel's arguments
 int r3d::streams_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int32_t S, int32_t J,
                                   const int32_t *mirror_perm, const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc,
                                   const double *cam, const float *x, int32_t RF, int32_t lag, float *pred, double *world, double *reproj,
@@ -546,7 +546,7 @@ int r3d::streams_poses_check_args(const char *what, const float *raw, const floa
     return R3D_OK;
 }
 
-// the argument rules of r3d_streams_fuse, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_fuse, shared with its host hook; fills the kernel's arguments
 int r3d::streams_fuse_check_args(const char *what, const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
                                  const uint32_t *synthetic, int32_t S, int32_t J, const int32_t *member, int32_t G, int32_t M,
                                  double soft_px, double max_px, double max_dist, double *fused, double *spread, int32_t *count,
@@ -610,7 +610,7 @@ static bool streams_assign_shape_ok(int32_t C, int32_t P, int32_t J, int32_t wid
     return C >= 1 && P >= 1 && P <= R3D_ASSIGN_MAX_SLOTS && (long long)C * P <= R3D_CLIPS_MAX && J >= 1 && J <= 17 && (width == 2 || width == 3);
 }
 
-// the argument rules of r3d_streams_assign, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_assign, shared with its host hook; fills the kernel's arguments
 int r3d::streams_assign_check_args(const char *what, void *state, const r3d_assign_params *prm, const float *det, const float *det_conf,
                                    const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match,
                                    int64_t *id, int32_t *stats, StreamsAssignArgs *args) {
@@ -692,7 +692,7 @@ static bool streams_link_shape_ok(int32_t N, int32_t C, int32_t G, int32_t J) {
            (long long)N * G <= R3D_CLIPS_MAX && J >= 1 && J <= 17;
 }
 
-// the argument rules of r3d_streams_link, shared with its host hook; fills the kernel's argument set
+// the argument rules of r3d_streams_link, shared with its host hook; fills the kernel's arguments
 int r3d::streams_link_check_args(const char *what, void *state, const r3d_link_params *prm, const double *world, const int64_t *emit,
                                  const int32_t *status, const int64_t *id, int32_t *member, int64_t *person, int32_t *group,
                                  int32_t *stats, StreamsLinkArgs *args) {

@@ -1,6 +1,6 @@
-// r3d_clips_repair: shard evaluation that survives dropped keypoints - the routines the kernel (r3d_k_undistort.hip, the fourteenth
-// argument set) and the host hook (r3d_debug_clips_repair_host) share, __host__ __device__ so that the hooks build runs the very same
-// ones on the CPU: the descriptor rule, the observed test, the searches in a clip-joint's bitmap of observed rows and the per-point
+// r3d_clips_repair: shard evaluation that survives dropped keypoints - the routines the kernel (r3d_k_elementwise.hip) and the host
+// hook (r3d_debug_clips_repair_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU: the
+// descriptor rule, the observed test, the searches in a clip-joint's bitmap of observed rows and the per-point
 // routine that applies the rule of include/ray3d_hip.h.  The call runs BEHIND r3d_clips_encode, in place on its output: observed
 // points are never written and a missing point's value depends on observed points only, so the result does not depend on the order
 // in which the points are visited.  The interpolation is r3d_streams_repair's own routine (stream_interp_bits): the same bits.
@@ -17,7 +17,7 @@
 
 namespace r3d {
 
-// r3d_clips_repair: the fourteenth argument set of r3d_undistort_rays_f64 (x == nullptr: not that mode).  blockIdx.y names a clip of
+// r3d_clips_repair: the arguments of r3d_k_clips_repair.  blockIdx.y names a clip of
 // the device-side table, blockIdx.x a joint: one workgroup of 256 threads per (clip, joint).
 struct ClipsRepairArgs {
     const r3d_clip_input_desc *table;   // num_clips (= gridDim.y) descriptors in device memory: the table r3d_clips_encode read

@@ -132,7 +132,7 @@ struct BindArgs {
     long long arm_vec4;
 };
 
-// The pixel pre-pass (r3d_k_undistort.hip) of R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: raw pixel
+// The pixel pre-pass (r3d_undistort_rays_f64, r3d_k_elementwise.hip) of R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: raw pixel
 // keypoints -> the model's float32 input (3-float rays, or one of the two 2-float encodings) in the workspace
 struct UndistArgs {
     const float *uv;               // (frames, J, 2) raw pixels, the caller's input
@@ -147,8 +147,7 @@ struct UndistArgs {
     int encoding;                  // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN (r3d_undistort.hpp), the same for every point
 };
 
-// r3d_clips_encode: the second argument set of r3d_undistort_rays_f64 (table == nullptr: the forwards' pre-pass, UndistArgs).
-// blockIdx.y names a clip of the device-side table; one output point (row, joint) per thread.
+// r3d_clips_encode: the arguments of r3d_k_clips_encode.  blockIdx.y names a clip of the device-side table; one output point (row, joint) per thread.
 struct ClipsEncArgs {
     const r3d_clip_input_desc *table;   // num_clips (= gridDim.y) descriptors in device memory
     const float *px;                    // (total_frames, J, 2) raw pixels
@@ -161,8 +160,8 @@ struct ClipsEncArgs {
     int encoding;                       // ENC_RAY / ENC_INTRINSIC / ENC_SCREEN
 };
 
-// r3d_clips_poses: the third argument set of r3d_undistort_rays_f64 (table == nullptr: not that mode).  blockIdx.y names a clip of
-// the device-side table; one output point (frame, joint) per thread (r3d_poses.hpp).
+// r3d_clips_poses: the arguments of r3d_k_clips_poses.  blockIdx.y names a clip of the device-side table; one output point
+// (frame, joint) per thread (r3d_poses.hpp).
 struct ClipsPosesArgs {
     const r3d_clip_desc *table;         // num_clips (= gridDim.y) descriptors in device memory
     const long long *raw_first;         // num_clips: the clip's first row in raw / raw_mirror
@@ -175,8 +174,8 @@ struct ClipsPosesArgs {
     int J;
 };
 
-// r3d_clips_project: the fourth argument set of r3d_undistort_rays_f64 (table == nullptr: not that mode).  blockIdx.y names a
-// (clip, camera) descriptor of the device-side table; one output point (row, joint) per thread (r3d_project.hpp).
+// r3d_clips_project: the arguments of r3d_k_clips_project.  blockIdx.y names a (clip, camera) descriptor of the device-side
+// table; one output point (row, joint) per thread (r3d_project.hpp).
 struct ClipsProjectArgs {
     const r3d_clip_project_desc *table; // num_clips (= gridDim.y) descriptors in device memory
     const float *world;                 // (total_frames, J, 3) world poses
@@ -582,57 +581,57 @@ int clips_project_check_args(const char *what, const float *world, int64_t total
                              const int32_t *status);
 
 struct WindowsArgs;     // r3d_windows.hpp
-// the argument rules of r3d_clips_windows, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_clips_windows, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int clips_windows_check_args(const char *what, const float *src, int64_t total_frames, int32_t J, int32_t F, int32_t RF,
                              const r3d_window_run_desc *runs, int32_t num_runs, const float *run_param, int32_t E, int64_t window0,
                              int64_t batch, float *x, float *param, const int32_t *mirror_perm, int32_t *status, WindowsArgs *args);
 
 struct StreamsArgs;     // r3d_streams.hpp
-// the argument rules of r3d_streams_step, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_step, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_check_args(const char *what, void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F, int32_t encoding,
                        const float *frame, const double *cam, const int32_t *action, float *x, float *x_mirror, const int32_t *mirror_perm,
                        int64_t *emit, int32_t *status, StreamsArgs *args);
 
 struct StreamsPosesArgs;     // r3d_streams_poses.hpp
-// the argument rules of r3d_streams_poses, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_poses, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_poses_check_args(const char *what, const float *raw, const float *raw_mirror, int32_t S, int32_t J, const int32_t *mirror_perm,
                              const int64_t *emit, const int32_t *status, const r3d_stream_pose_desc *desc, const double *cam,
                              const float *x, int32_t RF, int32_t lag, float *pred, double *world, double *reproj, double *quality,
                              StreamsPosesArgs *args);
 
 struct StreamsRepairArgs;     // r3d_streams_repair.hpp
-// the argument rules of r3d_streams_repair, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_repair, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_repair_check_args(const char *what, void *state, void *track, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
                               int32_t encoding, const float *frame, const float *conf, float min_conf, const double *cam,
                               const int32_t *action, int32_t max_gap, float *frame_out, uint32_t *synthetic, StreamsRepairArgs *args);
 
 struct StreamsPeekArgs;     // r3d_streams_peek.hpp
-// the argument rules of r3d_streams_peek, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_peek, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_peek_check_args(const char *what, const void *state, int32_t S, int32_t RF, int32_t lag, int32_t J, int32_t F,
                             const int32_t *looks, int32_t num_looks, const int32_t *action, const int32_t *status, float *x,
                             float *x_mirror, const int32_t *mirror_perm, int64_t *emit, int32_t *peek_status, StreamsPeekArgs *args);
 
 struct StreamsFuseArgs;     // r3d_streams_fuse.hpp
-// the argument rules of r3d_streams_fuse, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_fuse, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_fuse_check_args(const char *what, const double *world, const double *reproj, const int64_t *emit, const int32_t *status,
                             const uint32_t *synthetic, int32_t S, int32_t J, const int32_t *member, int32_t G, int32_t M, double soft_px,
                             double max_px, double max_dist, double *fused, double *spread, int32_t *count, uint32_t *used,
                             StreamsFuseArgs *args);
 
 struct StreamsAssignArgs;   // r3d_streams_assign.hpp
-// the argument rules of r3d_streams_assign, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_assign, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_assign_check_args(const char *what, void *state, const r3d_assign_params *prm, const float *det, const float *det_conf,
                               const int32_t *det_count, int32_t *action, float *frame_out, float *conf_out, int32_t *match, int64_t *id,
                               int32_t *stats, StreamsAssignArgs *args);
 
 struct ClipsRepairArgs;     // r3d_clips_repair.hpp
-// the argument rules of r3d_clips_repair, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_clips_repair, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int clips_repair_check_args(const char *what, float *x, int64_t out_rows, int32_t J, int32_t F, float *x_mirror, const int32_t *mirror_perm,
                             const r3d_clip_input_desc *clips, int32_t num_clips, int64_t max_rows, const float *conf, int64_t total_frames,
                             float min_conf, int32_t max_gap, uint8_t *state, int32_t *stats, int32_t *status, ClipsRepairArgs *args);
 
 struct StreamsLinkArgs;     // r3d_streams_link.hpp
-// the argument rules of r3d_streams_link, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's argument set
+// the argument rules of r3d_streams_link, shared with its host hook (r3d_api.cpp); on success `args` is the kernel's arguments
 int streams_link_check_args(const char *what, void *state, const r3d_link_params *prm, const double *world, const int64_t *emit,
                             const int32_t *status, const int64_t *id, int32_t *member, int64_t *person, int32_t *group, int32_t *stats,
                             StreamsLinkArgs *args);
@@ -734,21 +733,21 @@ hipError_t launch_forward(const FwdArgs &args, int nwg, int kind, bool uv, hipSt
 const char *forward_kernel_name(int kind, bool uv);
 int forward_resident_capacity(int kind, bool uv);      // workgroups of that kernel the current device holds at once (0: unknown)
 hipError_t launch_bind(const BindArgs &args, hipStream_t stream);
-hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_undistort.hip): every encoding
-hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // the same kernel, one grid row per clip
-hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_poses
-hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream);   // the same kernel: r3d_clips_project
+hipError_t launch_undistort(const UndistArgs &args, hipStream_t stream);   // r3d_undistort_rays_f64 (r3d_k_elementwise.hip): every encoding
+hipError_t launch_clips_encode(const ClipsEncArgs &args, int num_clips, hipStream_t stream);   // r3d_k_clips_encode, one grid row per clip
+hipError_t launch_clips_poses(const ClipsPosesArgs &args, int num_clips, hipStream_t stream);   // r3d_k_clips_poses
+hipError_t launch_clips_project(const ClipsProjectArgs &args, int num_clips, hipStream_t stream);   // r3d_k_clips_project
 struct PackArgs;                                                                                     // r3d_pack.hpp
-hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // the same kernel: r3d_finalize_dev
-hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream);             // the same kernel: r3d_clips_windows
-hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);                         // the same kernel, two launches: r3d_streams_step
-hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream);                   // the same kernel: r3d_streams_poses
-hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_repair
-hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_peek
-hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_fuse
-hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream);                 // the same kernel: r3d_streams_assign
-hipError_t launch_clips_repair(const ClipsRepairArgs &args, int num_clips, hipStream_t stream);     // the same kernel: r3d_clips_repair
-hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream);                     // the same kernel: r3d_streams_link
+hipError_t launch_pack(const PackArgs &args, int nblk, hipStream_t stream);                          // r3d_k_pack: r3d_finalize_dev
+hipError_t launch_clips_windows(const WindowsArgs &args, int batch, hipStream_t stream);             // r3d_k_clips_windows
+hipError_t launch_streams_step(const StreamsArgs &args, hipStream_t stream);                         // r3d_k_streams_advance, then r3d_k_streams_gather
+hipError_t launch_streams_poses(const StreamsPosesArgs &args, hipStream_t stream);                   // r3d_k_streams_poses
+hipError_t launch_streams_repair(const StreamsRepairArgs &args, hipStream_t stream);                 // r3d_k_streams_repair
+hipError_t launch_streams_peek(const StreamsPeekArgs &args, hipStream_t stream);                     // r3d_k_streams_peek
+hipError_t launch_streams_fuse(const StreamsFuseArgs &args, hipStream_t stream);                     // r3d_k_streams_fuse
+hipError_t launch_streams_assign(const StreamsAssignArgs &args, hipStream_t stream);                 // r3d_k_streams_assign
+hipError_t launch_clips_repair(const ClipsRepairArgs &args, int num_clips, hipStream_t stream);     // r3d_k_clips_repair
+hipError_t launch_streams_link(const StreamsLinkArgs &args, hipStream_t stream);                     // r3d_k_streams_link
 bool forward_single_launch();   // the single-launch form is in use (R3D_STAGED=1 turns it off)
 size_t fwd_ctrl_bytes(const Plan *pl, int64_t B);   // workspace bytes behind the activations: counters + problem table
 

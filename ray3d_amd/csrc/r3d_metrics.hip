@@ -25,8 +25,8 @@
 // runs metrics_block - the one workgroup body of the five-sum / detail mode, which the per-clip launch enters with
 // (blockIdx.x, gridDim.x) and this one with blockIdx.x and the clip's OWN workgroup count - on the clip's slice of the scratch.
 // The frame loop, the wave-of-64 detail sums and both reduction trees are therefore the same instructions for both calls: a
-// clip's results have the bits of the per-clip call by construction.  (A mode of the two documented kernels, as the detail and
-// the validation losses are: the library's kernel set stays what tests/test_host.py pins.)
+// clip's results have the bits of the per-clip call by construction.  (A mode of the two kernels, as the detail and the
+// validation losses are: the modes share the reduction trees.)
 //
 // r3d_clips_valid_losses (a shard's validation losses in one launch pair) is the two modes combined: ValidArgs AND ClipsArgs set.
 // The validation-loss branch then takes its clip from the table by the rule of r3d_clips_metrics - descriptor read once, decided

@@ -742,7 +742,7 @@ int model_finalize_dev(Model *m, const float *const *weights_dev, const int64_t 
     if ((e = hipEventRecord(ps->staged, stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(pointer table)");
     for (int phase = 0; phase < 2; ++phase)
         if ((e = launch_pack(pack_args(ps, phase, ps->d_tables, d_ptrs, m->d_arena), ps->nblk[phase], stream)) != hipSuccess)
-            return hip_fail(e, "launch r3d_undistort_rays_f64 (pack)");
+            return hip_fail(e, "launch r3d_k_pack");
     m->finalized = true;
     m->dirty = false;
     return R3D_OK;

@@ -1,5 +1,5 @@
 // r3d_finalize_dev: the BatchNorm-folding repack of model_finalize (r3d_model.cpp) per destination element, __host__ __device__ so
-// that the kernel (the pack argument set of r3d_undistort_rays_f64, r3d_k_undistort.hip) and the hooks build's host replay
+// that the kernel (r3d_k_pack, r3d_k_elementwise.hip) and the hooks build's host replay
 // (r3d_debug_pack_replay_host) run the very same routines.  The promise of include/ray3d_hip.h is an image that is bit for bit what
 // r3d_finalize uploads, so every routine replays model_finalize's float64 arithmetic in its order:
 //   * each host accumulator (rowacc[k], extra) is a chain of its own - one work item replays one chain, serially;
@@ -45,7 +45,7 @@ struct PackLayer {
 enum { PACK_BIAS = 0, PACK_WEIGHT = 1, PACK_SHARED_W = 2, PACK_SHARED_B = 3, PACK_BF3 = 4 };
 struct PackSeg { int layer, kind, blk0, nblk; };
 
-// argument set of one launch (segs == nullptr: not this mode)
+// the arguments of one launch of r3d_k_pack
 struct PackArgs {
     const PackSeg *segs;
     int nseg;

@@ -1,4 +1,4 @@
-// r3d_streams_step: live streams lifted a frame at a time - the routines the kernel (r3d_k_undistort.hip, the seventh argument set)
+// r3d_streams_step: live streams lifted a frame at a time - the routines the kernels (r3d_k_elementwise.hip)
 // and the host hook (r3d_debug_streams_step_host) share, __host__ __device__ so that the hooks build runs the very same ones on the
 // CPU: the head's validity test, the action step, the frame-to-slot index and the point copy.  The head arithmetic is integers
 // only; values are 32-bit copies, or - for the pixel encodings - encode_point_f32 of r3d_undistort.hpp.
@@ -15,9 +15,9 @@ namespace r3d {
 
 constexpr long long STREAM_COUNT_MAX = 1ll << 62;    // a head's count lies in [0, 2^62]: c - 1 - lag + k and c % RF cannot overflow
 
-// r3d_streams_step: the seventh argument set of r3d_undistort_rays_f64 (heads == nullptr: not that mode).  Two launches per call:
-// phase 0 advances the heads (blockIdx.x names a stream, one new point per thread), phase 1 gathers the windows (blockIdx.y names a
-// stream, one output point (row, joint) per thread) from the heads, emit and status words phase 0 wrote.
+// r3d_streams_step: the arguments of its two kernels.  r3d_k_streams_advance advances the heads (blockIdx.x names a stream, one new
+// point per thread), r3d_k_streams_gather gathers the windows (blockIdx.y names a stream, one output point (row, joint) per thread)
+// from the heads, emit and status words the advance launch wrote.
 struct StreamsArgs {
     r3d_stream_head *heads;             // S heads: the front of the state
     uint32_t *ring;                     // S rings of (RF, J, F) 32-bit patterns, behind the heads
@@ -30,7 +30,6 @@ struct StreamsArgs {
     unsigned long long mirror_perm[2];  // window_pack_perm (r3d_windows.hpp)
     int S, RF, lag, J, F;
     int encoding;                       // R3D_ENCODE_RAY / INTRINSIC / SCREEN (= ENC_* of r3d_undistort.hpp) or R3D_ENCODE_NONE
-    int phase;                          // 0 advance, 1 gather
 };
 
 // bytes of the state: S heads, then S rings (the arguments passed the checks of streams_check_args: no overflow)

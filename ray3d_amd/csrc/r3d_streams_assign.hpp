@@ -1,8 +1,8 @@
 // r3d_streams_assign: detections to live streams - per camera the association of a tick's unordered 2D detections with that
 // camera's stream slots, the births and the ends of tracks, and the action words, frame rows and confidence rows that
-// r3d_streams_repair / r3d_streams_step of the same tick read.  The routines the kernel (r3d_k_undistort.hip, the twelfth argument
-// set) and the host hook (r3d_debug_streams_assign_host) share, __host__ __device__ so that the hooks build runs the very same ones
-// on the CPU: the observed test, the per-detection summary, the per-pair cost, the order of the greedy matching's keys, the per-slot
+// r3d_streams_repair / r3d_streams_step of the same tick read.  The routines the kernel (r3d_k_elementwise.hip) and the host hook
+// (r3d_debug_streams_assign_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU: the
+// observed test, the per-detection summary, the per-pair cost, the order of the greedy matching's keys, the per-slot
 // step (state and outputs) and the per-camera finish.  Integers decide first; the arithmetic is float64 with floating-point
 // contraction OFF: every operation rounds once, joints are visited in ascending order and sums start from zero, the divisions and
 // the square roots are the correctly rounded ones on both sides.  The reference works on pre-associated archives and has no
@@ -18,7 +18,7 @@
 
 namespace r3d {
 
-// r3d_streams_assign: the twelfth argument set of r3d_undistort_rays_f64 (state == nullptr: not that mode).  blockIdx.x names a
+// r3d_streams_assign: the arguments of r3d_k_streams_assign.  blockIdx.x names a
 // camera; the workgroup is one wavefront.
 struct StreamsAssignArgs {
     void *state;                        // next_id[C], id[S], phase[S], missed[S], left[S], seen[S], ref[S][J][width] (assign_state)
@@ -168,6 +168,44 @@ __host__ __device__ inline unsigned long long stream_assign_pair(const StreamsAs
 // Step 3's order: (key, pair index p * D + d) is better than the best so far - the smaller cost, then the smaller p, then the smaller d
 __host__ __device__ inline bool stream_assign_better(unsigned long long key, int index, unsigned long long best_key, int best_index) {
     return key < best_key || (key == best_key && index < best_index);
+}
+
+// Step 3 on the device, for one wavefront of STREAMS_ASSIGN_THREADS lanes: the greedy matching over the R x C keys key[r * C + c] in
+// LDS (R, C <= 32).  Lane (c, half) = (lane % 32, lane / 32) scans the untaken pairs of its column c with the rows of its parity,
+// a six-step xor butterfly over (key, pair index) leaves every lane with the same winner, `won(row, column)` hears of it, and its
+// row and column are taken: at most min(R, C) rounds, ended by the first without an admissible pair.  R, C, `rows` and `cols` are
+// the same in every lane, so every loop bound and the break are uniform; no lane may have left.
+template <class Won>
+__device__ __forceinline__ void stream_assign_greedy(const unsigned long long *key, int R, int C, uint32_t &rows, uint32_t &cols, Won won) {
+    const int c = threadIdx.x & 31, half = threadIdx.x >> 5;
+    const int rounds = R < C ? R : C;
+    for (int round = 0; round < rounds; ++round) {
+        unsigned long long best = STREAM_ASSIGN_NONE;
+        int at = R * C;
+        if (c < C && !((cols >> c) & 1u))                           // (a lane whose column is taken has nothing left to offer)
+            for (int r = half; r < R; r += 2) {
+                if ((rows >> r) & 1u) continue;
+                const int i = r * C + c;
+                const unsigned long long k = key[i];
+                if (stream_assign_better(k, i, best, at)) {
+                    best = k;
+                    at = i;
+                }
+            }
+        for (int off = STREAMS_ASSIGN_THREADS / 2; off > 0; off >>= 1) {
+            const unsigned long long k = __shfl_xor(best, off);
+            const int i = __shfl_xor(at, off);
+            if (stream_assign_better(k, i, best, at)) {
+                best = k;
+                at = i;
+            }
+        }
+        if (best == STREAM_ASSIGN_NONE) break;                      // uniform: no admissible pair is left
+        const int wr = at / C, wc = at - wr * C;                    // (at < R * C: an admissible key came from a real pair)
+        rows |= 1u << wr;
+        cols |= 1u << wc;
+        won(wr, wc);
+    }
 }
 
 // The position of the r-th (from 0) set bit of `mask`; r < popcount(mask)

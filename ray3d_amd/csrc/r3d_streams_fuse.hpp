@@ -1,6 +1,6 @@
 // r3d_streams_fuse: one world skeleton per person from several cameras - per group of streams and joint the gated, weighted mean of
 // the world poses r3d_streams_poses wrote this tick, weighted by the re-projection residuals it wrote beside them.  The routines the
-// kernel (r3d_k_undistort.hip, the eleventh argument set) and the host hook (r3d_debug_streams_fuse_host) share, __host__ __device__
+// kernel (r3d_k_elementwise.hip) and the host hook (r3d_debug_streams_fuse_host) share, __host__ __device__
 // so that the hooks build runs the very same ones on the CPU.  Integers decide first (which slots are candidates); after that the
 // arithmetic is float64 with floating-point contraction OFF: every operation rounds once, slots are visited in ascending order and
 // sums start from zero, the divisions and the square roots are the correctly rounded ones on both sides - the two are held to the
@@ -16,7 +16,7 @@
 
 namespace r3d {
 
-// r3d_streams_fuse: the eleventh argument set of r3d_undistort_rays_f64 (member == nullptr: not that mode).  blockIdx.x names a group,
+// r3d_streams_fuse: the arguments of r3d_k_streams_fuse.  blockIdx.x names a group,
 // thread j < J one joint of it.
 struct StreamsFuseArgs {
     const double *world;                // (S, J, 3): what r3d_streams_poses wrote

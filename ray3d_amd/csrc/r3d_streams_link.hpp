@@ -1,6 +1,6 @@
 // r3d_streams_link: one person across cameras - per scene the association of the cameras' tracks (the streams r3d_streams_assign
 // keeps per camera) with a table of people by the distance of their world poses, the births and the ends of people, and the member
-// table r3d_streams_fuse reads.  The routines the kernel (r3d_k_undistort.hip, the thirteenth argument set) and the host hook
+// table r3d_streams_fuse reads.  The routines the kernel (r3d_k_elementwise.hip) and the host hook
 // (r3d_debug_streams_link_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU: the state's
 // words as the rule reads them, a stream's present joints, the cost of a person and a stream, step A's test of one link, step B's
 // candidate test, pair key and birth, step C's member row, per-joint mean and per-person finish.  Integers decide first; the
@@ -15,7 +15,7 @@
 #include <stdint.h>
 
 #include "ray3d_hip.h"
-#include "r3d_streams_assign.hpp"      // STREAM_ASSIGN_NONE, stream_assign_better, stream_assign_nth_bit
+#include "r3d_streams_assign.hpp"      // STREAM_ASSIGN_NONE, stream_assign_better, stream_assign_greedy, stream_assign_nth_bit
 #include "r3d_streams_fuse.hpp"        // stream_fuse_q, stream_finite_bits64, stream_finished
 
 // On the device: the instruction scheduler does not move anything across this point - one float64 division's temporaries at a time
@@ -28,7 +28,7 @@
 
 namespace r3d {
 
-// r3d_streams_link: the thirteenth argument set of r3d_undistort_rays_f64 (state == nullptr: not that mode).  blockIdx.x names a
+// r3d_streams_link: the arguments of r3d_k_streams_link.  blockIdx.x names a
 // scene; the workgroup is one wavefront.
 struct StreamsLinkArgs {
     void *state;                        // next_id[N], pid[NG], link_id[NG][C], ref[NG][J][3], phase, missed, link[NG][C], seen
@@ -51,6 +51,7 @@ constexpr int STREAMS_LINK_LDS_PRES = 8 * R3D_LINK_MAX_PEOPLE * R3D_ASSIGN_MAX_S
 constexpr int STREAMS_LINK_LDS_BYTES = STREAMS_LINK_LDS_PRES + 4 * R3D_ASSIGN_MAX_SLOTS;
 static_assert(R3D_LINK_MAX_PEOPLE <= 32 && R3D_ASSIGN_MAX_SLOTS <= 32, "people and slots are bits of 32-bit masks");
 static_assert(R3D_LINK_MAX_PEOPLE <= STREAMS_LINK_THREADS && R3D_ASSIGN_MAX_SLOTS <= STREAMS_LINK_THREADS, "one lane per person, one lane per slot");
+static_assert(STREAMS_LINK_THREADS == STREAMS_ASSIGN_THREADS, "stream_assign_greedy's butterfly spans the wavefront of either kernel");
 
 // bytes of the state (the arguments passed the shape rules: no overflow), rounded up to 8
 inline size_t streams_link_bytes(long long N, long long C, long long G, long long J) {

@@ -1,6 +1,6 @@
-// r3d_streams_peek: early poses for live streams of centred models - the routines the kernel (r3d_k_undistort.hip, the tenth argument
-// set) and the host hook (r3d_debug_streams_peek_host) share, __host__ __device__ so that the hooks build runs the very same ones on
-// the CPU: the verdict on a stream and a look, and the point copy.  Integers only; values are 32-bit copies.  The head rule, the
+// r3d_streams_peek: early poses for live streams of centred models - the routines the kernel (r3d_k_elementwise.hip) and the host
+// hook (r3d_debug_streams_peek_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU: the
+// verdict on a stream and a look, and the point copy.  Integers only; values are 32-bit copies.  The head rule, the
 // frame clamp and the slot index are those of r3d_streams.hpp: the window of preview frame p = c - 1 - look is the one a drain
 // started now would emit at its (lag - look)-th tick.
 #pragma once
@@ -14,7 +14,7 @@
 
 namespace r3d {
 
-// r3d_streams_peek: the tenth argument set of r3d_undistort_rays_f64 (heads == nullptr: not that mode).  One launch: blockIdx.y
+// r3d_streams_peek: the arguments of r3d_k_streams_peek.  One launch: blockIdx.y
 // names a stream, blockIdx.z a look, one output point (row, joint) per thread.  Nothing of the state is written: it is const here.
 struct StreamsPeekArgs {
     const r3d_stream_head *heads;       // S heads: the front of the state
@@ -49,7 +49,7 @@ __host__ __device__ inline StreamPeek stream_peek(long long count, long long dra
     return r;
 }
 
-// the look of blockIdx.z / of the hook's loop, without indexing the by-value argument set with a runtime index (k < K <= 8)
+// the look of blockIdx.z / of the hook's loop, without indexing the by-value arguments with a runtime index (k < K <= 8)
 __host__ __device__ inline int stream_peek_look(const StreamsPeekArgs &a, int k) {
     int look = a.looks[0];
 #pragma unroll

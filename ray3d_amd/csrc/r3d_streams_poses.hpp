@@ -2,9 +2,9 @@
 // emit / status) the flip average and the world transform of r3d_poses.hpp, and the one quality signal a stream without ground truth
 // has: the distance, in undistorted pixels, between the projection of the predicted absolute pose (normalized2camera,
 // lib/camera/camera.py:379-388, then the pinhole division) and the keypoints that were fed in (get_uv_given_cam_ray,
-// camera.py:473-483; the overlay of lib/train_val/trainer.py:535-537).  The routines the kernel (r3d_k_undistort.hip, the eighth
-// argument set) and the host hook (r3d_debug_streams_poses_host) share, __host__ __device__ so that the hooks build runs the very
-// same ones on the CPU.  Floating-point contraction is OFF (r3d_poses.hpp says why); the divisions and the square root are the
+// camera.py:473-483; the overlay of lib/train_val/trainer.py:535-537).  The routines the kernel (r3d_k_elementwise.hip) and the
+// host hook (r3d_debug_streams_poses_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU. 
+// Floating-point contraction is OFF (r3d_poses.hpp says why); the divisions and the square root are the
 // correctly rounded float64 ones on both sides, so the two are held to the same bits.
 #pragma once
 
@@ -18,7 +18,7 @@
 
 namespace r3d {
 
-// r3d_streams_poses: the eighth argument set of r3d_undistort_rays_f64 (raw == nullptr: not that mode).  blockIdx.x names a stream,
+// r3d_streams_poses: the arguments of r3d_k_streams_poses.  blockIdx.x names a stream,
 // thread j < J one joint of it.
 struct StreamsPosesArgs {
     const float *raw, *raw_mirror;      // (S, J, 3): what the forwards wrote; raw_mirror nullptr: no flip pass

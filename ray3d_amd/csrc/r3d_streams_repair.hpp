@@ -1,6 +1,6 @@
-// r3d_streams_repair: live streams that survive dropped keypoints - the routines the kernel (r3d_k_undistort.hip, the ninth argument
-// set) and the host hook (r3d_debug_streams_repair_host) share, __host__ __device__ so that the hooks build runs the very same ones
-// on the CPU: the observed test, the track's layout, the per-joint step with its two ring rewrites, the interpolation arithmetic and
+// r3d_streams_repair: live streams that survive dropped keypoints - the routines the kernel (r3d_k_elementwise.hip) and the host
+// hook (r3d_debug_streams_repair_host) share, __host__ __device__ so that the hooks build runs the very same ones on the CPU: the
+// observed test, the track's layout, the per-joint step with its two ring rewrites, the interpolation arithmetic and
 // the mask words.  The call runs BEFORE r3d_streams_step of the same tick and judges the head and the action word with that call's
 // own stream_step (r3d_streams.hpp), on the head as it stands: it never writes a head.  Floating-point contraction is OFF in the
 // interpolation: every operation rounds once, on the host and on the device alike.
@@ -15,7 +15,7 @@
 
 namespace r3d {
 
-// r3d_streams_repair: the ninth argument set of r3d_undistort_rays_f64 (age == nullptr: not that mode).  blockIdx.x names a stream,
+// r3d_streams_repair: the arguments of r3d_k_streams_repair.  blockIdx.x names a stream,
 // thread j < J one joint of it.
 struct StreamsRepairArgs {
     const r3d_stream_head *heads;       // S heads: the front of the state, READ only

@@ -1,5 +1,5 @@
 // R3D_INPUT_UV_DIST / R3D_INPUT_PX_INTRINSIC / R3D_INPUT_PX_SCREEN: the per-keypoint arithmetic of the pixel pre-pass
-// (r3d_k_undistort.hip), __host__ __device__ so that the hooks build runs the very same routines on the CPU
+// (r3d_k_elementwise.hip), __host__ __device__ so that the hooks build runs the very same routines on the CPU
 // (r3d_debug_undistort_host, r3d_debug_encode_px_host, r3d_debug_clips_encode_host).  float64 throughout, in the reference's order
 // (lib/camera/camera.py:412-441): cv2.undistortPoints(uv, K, dist, P=K) - five fixed-point iterations of OpenCV's
 // documented algorithm for the 5-coefficient Brown-Conrady model, then re-projection with K - followed by one of three
@@ -99,9 +99,9 @@ __host__ __device__ inline void encode_pixel_2d(const double *row, int encoding,
 }
 
 // One keypoint through the encoding `encoding` from its 16-double camera row, cast ONCE to float32 (z: ENC_RAY only, 0
-// otherwise): what r3d_undistort_rays_f64 writes per point, for both of its argument sets (the forwards' pre-pass and
-// r3d_clips_encode), and what the hooks' r3d_debug_clips_encode_host writes on the CPU.  `encoding` is uniform over a launch:
-// scalar branches.  (Values, not an output array: nothing of it lives in scratch memory.)
+// otherwise): what r3d_undistort_rays_f64 (the forwards' pre-pass) and r3d_k_clips_encode (r3d_clips_encode) write per point, and
+// what the hooks' r3d_debug_clips_encode_host writes on the CPU.  `encoding` is uniform over a launch: scalar branches.  (Values,
+// not an output array: nothing of it lives in scratch memory.)
 struct EncodedPoint { float x, y, z; };
 // The one cast.  A NaN (a bad pixel coordinate) leaves as THE canonical quiet NaN: which operand's sign and payload a NaN result
 // carries differs between the GPU and a host CPU, and the kernel and the host hook are held to the same bits.

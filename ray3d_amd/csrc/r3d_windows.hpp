@@ -1,5 +1,5 @@
 // r3d_clips_windows: a batch of (RF, J, F) windows gathered from a pool of windows drawn from many clips - the routines the kernel
-// (r3d_k_undistort.hip, the sixth argument set) and the host hook (r3d_debug_clips_windows_host) share, __host__ __device__ so
+// (r3d_k_elementwise.hip) and the host hook (r3d_debug_clips_windows_host) share, __host__ __device__ so
 // that the hooks build runs the very same ones on the CPU.  Integer arithmetic and 32-bit copies only: nothing here rounds.
 #pragma once
 
@@ -10,7 +10,7 @@
 
 namespace r3d {
 
-// r3d_clips_windows: the sixth argument set of r3d_undistort_rays_f64 (runs == nullptr: not that mode).  blockIdx.y names a window
+// r3d_clips_windows: the arguments of r3d_k_clips_windows.  blockIdx.y names a window
 // of the batch; one output point (row, joint) per thread.
 struct WindowsArgs {
     const r3d_window_run_desc *runs;    // num_runs descriptors in device memory

@@ -44,23 +44,37 @@ def test_library_exports_every_declared_symbol():
         assert name not in blob, name
 
 
+# one kernel per elementwise entry point (ray3d_amd/csrc/r3d_k_elementwise.hip) -> the bytes of static LDS it declares.  The sizes are
+# the kernels' own constants, restated from the limits of include/ray3d_hip.h that size them:
+#   res[17] doubles                                     (streams_poses_body)
+#   STREAMS_FUSE_STAGE * STREAMS_FUSE_JOINTS doubles    (r3d_streams_fuse.hpp)
+#   STREAMS_ASSIGN_LDS_BYTES                            (r3d_streams_assign.hpp)
+#   STREAMS_LINK_LDS_BYTES                              (r3d_streams_link.hpp)
+#   CLIPS_REPAIR_LDS_BYTES                              (r3d_clips_repair.hpp)
+ELEMENTWISE_KERNELS = {
+    "r3d_undistort_rays_f64": 0, "r3d_k_clips_encode": 0, "r3d_k_clips_poses": 0, "r3d_k_clips_project": 0, "r3d_k_clips_windows": 0,
+    "r3d_k_pack": 0, "r3d_k_streams_advance": 0, "r3d_k_streams_gather": 0, "r3d_k_streams_repair": 0, "r3d_k_streams_peek": 0,
+    "r3d_k_streams_poses": 136, "r3d_k_streams_fuse": 8704, "r3d_k_streams_assign": 8576, "r3d_k_streams_link": 8320,
+    "r3d_k_clips_repair": 8272,
+}
+
 PRODUCT_KERNELS = {
-    "r3d_bind_f32", "r3d_decode_f32", "r3d_decode_w4_f32", "r3d_clip_metrics_f64", "r3d_clip_metrics_sum_f64", "r3d_undistort_rays_f64",
+    "r3d_bind_f32", "r3d_decode_f32", "r3d_decode_w4_f32", "r3d_clip_metrics_f64", "r3d_clip_metrics_sum_f64",
     "r3d_gemm_f32", "r3d_gemm_uv_f32", "r3d_gemm_b3", "r3d_gemm_uv_b3", "r3d_gemm_enc_f32", "r3d_gemm_enc_uv_f32",
     "r3d_forward_f32", "r3d_forward_uv_f32", "r3d_forward_b3", "r3d_forward_uv_b3", "r3d_forward_lat", "r3d_forward_uv_lat",
     "r3d_forward_clip_f32", "r3d_forward_clip_uv_f32",
-}
+} | set(ELEMENTWISE_KERNELS)
 
 
 def _gfx950_kernels(path, tmp_path):
-    """Names of the kernels in the gfx950 code object(s) of a shared library: the offload bundle's entries of that target,
-    their metadata notes read with the ROCm LLVM's llvm-readelf (the toolchain build() compiles with)."""
+    """(name, metadata record) of the kernels in the gfx950 code object(s) of a shared library: the offload bundle's entries of
+    that target, their metadata notes read with the ROCm LLVM's llvm-readelf (the toolchain build() compiles with)."""
     import struct
     import subprocess
     readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     assert os.path.exists(readelf), readelf
     data = open(path, "rb").read()
-    magic, names, pos, k = b"__CLANG_OFFLOAD_BUNDLE__", [], 0, 0
+    magic, kernels, pos, k = b"__CLANG_OFFLOAD_BUNDLE__", [], 0, 0
     while (i := data.find(magic, pos)) >= 0:
         n, = struct.unpack_from("<Q", data, i + 24)
         p = i + 32
@@ -73,27 +87,48 @@ def _gfx950_kernels(path, tmp_path):
                 k += 1
                 co.write_bytes(data[i + off:i + off + size])
                 txt = subprocess.run([readelf, "--notes", str(co)], capture_output=True, text=True, check=True).stdout
-                for sym in re.findall(r"^\s+-?\s*\.symbol:\s+'?([\w.$]+?)\.kd'?\s*$", txt, flags=re.M):
+                rec = {}
+                for key, val in re.findall(r"^\s+-?\s*\.(\w+):\s+'?([\w.$]+?)'?\s*$", txt, flags=re.M):
+                    rec[key] = val
+                    if key != "wavefront_size" or "symbol" not in rec:      # .wavefront_size ends a kernel's record
+                        continue
+                    assert rec["symbol"].endswith(".kd"), rec["symbol"]
+                    sym = rec["symbol"][:-3]
                     # extern "C" kernels carry their own name; the metrics kernels sit in an anonymous namespace: the last
                     # <length><identifier> of the Itanium nested name _ZN...E
                     rest = sym[3:] if sym.startswith("_ZN") else ""
                     while (m := re.match(r"\d+", rest)):
                         sym, rest = rest[m.end():m.end() + int(m.group())], rest[m.end() + int(m.group()):]
-                    names.append(sym)
+                    kernels.append((sym, rec))
+                    rec = {}
         pos = i + 24
-    return names
+    return kernels
 
 
 def test_libraries_hold_exactly_the_documented_kernels(tmp_path):
     """The gfx950 code object of the product library holds the documented kernels and nothing else - no experiment's kernel
     rides along (one did: a rejected first-level tile was linked in and had its LDS attribute set in every process) - and the
-    hooks library, which links the same kernel objects, holds the same set.
-    (No assertion on scratch: r3d_forward_lat, the r3d_gemm_* kernels of the level-by-level form and r3d_clip_metrics_f64 do
-    use a few bytes of it - tools/kernel_resources.py prints the figures.)"""
+    hooks library, which links the same kernel objects, holds the same set.  Each elementwise kernel takes what its own body
+    needs: no scratch, no spilled register, and exactly the LDS it declares.
+    (No assertion on scratch for the others: r3d_forward_lat, the r3d_gemm_* kernels of the level-by-level form and
+    r3d_clip_metrics_f64 do use a few bytes of it - tools/kernel_resources.py prints the figures.)"""
+    hdr = open(os.path.join(ROOT, "include", "ray3d_hip.h")).read()
+    lim = {n: int(v) for n, v in re.findall(r"#define R3D_(ASSIGN_MAX_SLOTS|ASSIGN_MAX_DETECTIONS|LINK_MAX_PEOPLE|FUSE_MAX_MEMBERS|REPAIR_MAX_ROWS) (\d+)", hdr)}
+    slots, dets, people = lim["ASSIGN_MAX_SLOTS"], lim["ASSIGN_MAX_DETECTIONS"], lim["LINK_MAX_PEOPLE"]
+    assert ELEMENTWISE_KERNELS["r3d_k_streams_fuse"] == 8 * 4 * lim["FUSE_MAX_MEMBERS"] * 17
+    assert ELEMENTWISE_KERNELS["r3d_k_streams_assign"] == 8 * slots * dets + 8 * dets + 4 * dets
+    assert ELEMENTWISE_KERNELS["r3d_k_streams_link"] == 8 * people * slots + 4 * slots
+    assert ELEMENTWISE_KERNELS["r3d_k_clips_repair"] == lim["REPAIR_MAX_ROWS"] // 8 + 4 * 4 + 4 * 4 * 4
     for path in (_capi.LIB_PATH, _capi.HOOKS_LIB_PATH):
-        names = _gfx950_kernels(path, tmp_path)
+        kernels = _gfx950_kernels(path, tmp_path)
+        names = [name for name, _ in kernels]
         assert len(names) == len(set(names)), (path, sorted(names))
         assert set(names) == PRODUCT_KERNELS, (path, set(names) ^ PRODUCT_KERNELS)
+        for name, rec in kernels:
+            if name in ELEMENTWISE_KERNELS:
+                assert int(rec["private_segment_fixed_size"]) == 0, (path, name, rec["private_segment_fixed_size"])
+                assert int(rec["vgpr_spill_count"]) == 0, (path, name, rec["vgpr_spill_count"])
+                assert int(rec["group_segment_fixed_size"]) == ELEMENTWISE_KERNELS[name], (path, name, rec["group_segment_fixed_size"])
 
 
 @pytest.mark.parametrize("name", MODEL_CASES)

@@ -32,7 +32,7 @@ from clips_ab_common import H36M_LEFT, H36M_RIGHT, alternate, make_set, ranges_o
 
 TOOL = "clips_poses_ab"
 STEPS = (("finish", 300), ("pass", 560))      # (step, its time limit in seconds)
-KERNEL = "r3d_undistort_rays_f64"             # the elementwise kernel whose third argument set r3d_clips_poses is
+KERNEL = "r3d_k_clips_poses"                  # the kernel r3d_clips_poses launches
 
 
 def compare(a, b, equal, what):
@@ -134,8 +134,8 @@ def read_remarks(path):
 
 def resources(after, before):
     a = read_remarks(after)
-    res = {"kernel": KERNEL, "what": "compiler resource remarks (-Rpass-analysis=kernel-resource-usage, gfx950); r3d_clips_poses is the "
-                                     "third argument set of this kernel", "after": a.get(KERNEL)}
+    res = {"kernel": KERNEL, "what": "compiler resource remarks (-Rpass-analysis=kernel-resource-usage, gfx950) of the kernel "
+                                     "r3d_clips_poses launches", "after": a.get(KERNEL)}
     if before:
         b = read_remarks(before)
         res["before"] = b.get(KERNEL)

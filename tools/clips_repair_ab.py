@@ -3,8 +3,8 @@
 seed 0, raw pixels of four distorted cameras, RF 243, flip on; weights from ray3d_amd.synth):
 
   1. NO COST WHEN OFF.  `off`: wall time of evaluate_clips_batched(encode="ray", flip=True) WITHOUT repair=; `live`: one tick of
-     tools/online_ab.py's smallest (RF 9, 1 stream) and largest (RF 243, 1 024 streams) configuration - the shared elementwise
-     kernel grew an argument set.  With --parent DIR (a checkout of the parent commit, built on the same box) both steps run in
+     tools/online_ab.py's smallest (RF 9, 1 stream) and largest (RF 243, 1 024 streams) configuration - the live calls' kernels
+     come from the same file, r3d_k_elementwise.hip.  With --parent DIR (a checkout of the parent commit, built on the same box) both steps run in
      DIR as well, the two trees alternating, ROUNDS times each: this tree's means must lie inside the range the parent's own
      repetitions span in the same session.
   2. COST WHEN ON.  `on`: device-event time of the ONE r3d_clips_repair launch on the shard at 0 %, 1 % and 10 % dropped points
